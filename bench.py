@@ -14,6 +14,12 @@ quenched Schwinger model, 1024 x 1024, beta = 1.  One "step" is one pass of the 
 Chains are sharded over ranks by global chain index (weak scaling: fixed chains per GPU); the only collective is
 the packed statistics all-reduce after the timed region.  `--gpus N` without a launcher starts the N ranks itself.
 One JSON line is printed by rank 0.
+
+A plain run sets up, thermalises, warms up, times the K steps and prints the line.  --full adds what takes runs of its
+own: the CPU baseline, the C++ driver's loop, the HBM-bound kernel probes and the side measurements of the default
+workload (single chain, 128 chains, fast-path cliff, random order).  --dump-outputs DIR writes what the last timed step
+handed its caller (rank 0's chains) as DIR/<name>.npy, float64: the QoI per chain, the accumulated moments and the state,
+or, for a state of more than 2^21 entries, those at a fixed seeded set of at most 2^21 indices (state_sample*.npy).
 """
 import argparse
 import hashlib
@@ -70,6 +76,10 @@ def parse():
     ap.add_argument("--allow-variant", action="store_true",
                     help="tools only (tools/ab.sh): accept MLMCPI_LIB_VARIANT and mark the line as not a record")
     ap.add_argument("--t-final", type=float, default=0.0, help="quartic_mlmc_hier: T_final (default size / 8, i.e. a = 0.125 on the finest level)")
+    ap.add_argument("--full", action="store_true",
+                    help="also the CPU baseline, the C++ driver's loop and the side measurements of the default workload")
+    ap.add_argument("--dump-outputs", metavar="DIR", default="",
+                    help="write the outputs of the last timed step (rank 0) to DIR/<name>.npy")
     return ap.parse_args()
 
 
@@ -467,16 +477,17 @@ class SweepWorkload:
             d = self.or_heat_depth  # > 0: that launch also holds the last d overrelaxation sweeps (same launches as one call)
             # ... and the launch that finishes the QoI records the sample too (mlmcpi_lattice_sweep_draw_qoi_record, the call
             # the C++ sampler's draw_with_qoi makes when it is handed the moments): no launch of its own for record_sample
-            self.x, self.scratch, q = ops.lattice_sweep_draw_qoi(self.act, cur, oth, cur, d, a.n_heatbath, a.seed, self.chain0,
-                                                                 s + a.n_overrelax - d, 1 if self.kind == "schwinger" else 3,
-                                                                 0 if self.whole else (d or self.fuse), acc=self.acc)
+            self.x, self.scratch, self.q = ops.lattice_sweep_draw_qoi(self.act, cur, oth, cur, d, a.n_heatbath, a.seed, self.chain0,
+                                                                      s + a.n_overrelax - d, 1 if self.kind == "schwinger" else 3,
+                                                                      0 if self.whole else (d or self.fuse), acc=self.acc)
         else:
             self.x, self.scratch = ops.lattice_sweep_draw_pingpong(self.act, cur, oth, 0, a.n_heatbath, a.seed, self.chain0,
                                                                    s + a.n_overrelax, self.fuse)
         if record:
             e[3].record()
         if not self.fused:
-            ops.stats_accumulate(self.acc, self.qoi())  # qoi->evaluate + record_sample
+            self.q = self.qoi()
+            ops.stats_accumulate(self.acc, self.q)  # qoi->evaluate + record_sample
         if record:
             e[4].record()
             self.ev["or"].append((e[0], e[1]))
@@ -504,6 +515,24 @@ def or_plan(n_overrelax, fuse, blocks):
             plan.append((d, 1))
     assert len(plan) <= 2, plan
     return plan
+
+
+DUMP_SAMPLE = 1 << 21   # entries of an output larger than this are sampled (16 MiB in float64; 64 MB for all outputs)
+
+
+def dump_outputs(torch, out_dir, outputs):
+    """DIR/<name>.npy (float64) of each output of the last timed step.  An output with more than DUMP_SAMPLE entries is
+    written as <name>_sample.npy: its flat entries at fixed seeded indices (the same for every run of the same shape),
+    listed in <name>_sample_index.npy."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    for name, t in outputs.items():
+        t = t.detach()
+        if t.numel() > DUMP_SAMPLE:
+            idx = np.unique(np.random.default_rng(20241016).integers(0, t.numel(), DUMP_SAMPLE))
+            np.save(os.path.join(out_dir, f"{name}_sample_index.npy"), idx.astype(np.float64))
+            t, name = t.reshape(-1)[torch.from_numpy(idx).to(t.device)], f"{name}_sample"
+        np.save(os.path.join(out_dir, f"{name}.npy"), t.double().cpu().numpy())
 
 
 def time_steps(torch, dist, world, step, steps, warmup):
@@ -550,10 +579,10 @@ def main():
     # would be inherited by the children and mix their kernels into the same output directory) no child process is started.
     profiled = under_profiler()
     cpu = None
-    if world == 1 and not a.no_cpu_baseline and not profiled:
+    if world == 1 and a.full and not a.no_cpu_baseline and not profiled:
         cpu = cpu_baseline(a, size)
     cxx = None
-    if world == 1 and a.workload == "schwinger" and not a.no_extra_points and a.chains == 0 and not profiled:
+    if world == 1 and a.full and a.workload == "schwinger" and not a.no_extra_points and a.chains == 0 and not profiled:
         cxx = cxx_path(a, size)  # child processes; this one has not touched the GPU yet
 
     import torch
@@ -619,6 +648,7 @@ def main():
         units_per_step = W.sites * (a.n_overrelax + a.n_heatbath) * B
         step, fuse = W.step, W.fuse
         acc_of = lambda: W.acc
+        outputs = lambda: {"qoi": W.q, "moments": W.acc, "state": W.x}
     elif a.workload == "rotor_sweep":
         # OverrelaxedHeatBathSampler::draw on the rotor action, M_lat = 65536, a = 0.125
         act = abi.path_action(abi.ROTOR, size, size / 8.0, 0.25)
@@ -637,8 +667,8 @@ def main():
             if record:
                 e0, e1 = ev(), ev()
                 e0.record()
-            state["x"], state["w"], _ = ops.path_sweep_draw_qoi(act, state["x"], state["w"], state["x"], a.n_overrelax, a.n_heatbath,
-                                                                 a.seed, chain0, state["sweep"], acc=acc)
+            state["x"], state["w"], state["q"] = ops.path_sweep_draw_qoi(act, state["x"], state["w"], state["x"], a.n_overrelax,
+                                                                          a.n_heatbath, a.seed, chain0, state["sweep"], acc=acc)
             state["sweep"] += a.n_overrelax + a.n_heatbath
             if record:
                 e1.record()
@@ -646,6 +676,7 @@ def main():
         for _ in range(a.thermalise):
             step(False)
         acc_of = lambda: acc
+        outputs = lambda: {"qoi": state["q"], "moments": acc, "state": state["x"]}
     elif a.workload == "quartic_mlmc":
         # BASELINE configs[4]: quartic double well, 5 levels, finest M_lat = 32768, a = 0.125.
         # The (level, chain) instances are cut into `world` contiguous shares of equal cost (mlmc.partition); a step =
@@ -672,6 +703,7 @@ def main():
                 e1.record()
                 events.append((e0, e1))
         acc_of = lambda: est.packed_finest()
+        outputs = lambda: {"moments": est.packed_finest()}
     elif a.workload == "quartic_mlmc_hier":
         # BASELINE configs[4] AS THE REFERENCE RUNS IT: sampler = 'hierarchical' -- HMC only on the
         # coarsest level (M_lat = 2048, nt = 100, dt = 0.095), two-level steps up (sampler/hierarchicalsampler.cc:55-81),
@@ -706,6 +738,7 @@ def main():
                 e1.record()
                 events.append((e0, e1))
         acc_of = lambda: est.packed_finest()
+        outputs = lambda: {"moments": est.packed_finest()}
     else:
         kind = {"rotor_hmc": abi.ROTOR, "quartic_hmc": abi.QUARTIC, "ho_hmc": abi.HARMONIC}[a.workload]
         # a = 0.125 at the BASELINE sizes; config 1 (HO, M_lat = 128) keeps T_final = 4
@@ -732,17 +765,22 @@ def main():
                 hmc.n_accepted += cnt
                 if record:
                     e1.record()
-                ops.stats_accumulate(acc, q[:, -1].contiguous() if q.dim() > 1 else q)
+                last["q"] = q[:, -1].contiguous() if q.dim() > 1 else q
             else:
                 hmc.draw(x)
                 if record:
                     e1.record()
-                ops.stats_accumulate(acc, ops.qoi_susceptibility(x, T_final) if kind == abi.ROTOR else ops.qoi_xsquared(x))
+                last["q"] = ops.qoi_susceptibility(x, T_final) if kind == abi.ROTOR else ops.qoi_xsquared(x)
+            ops.stats_accumulate(acc, last["q"])
             if record:
                 events.append((e0, e1))
         acc_of = lambda: acc
+        last = {}
+        outputs = lambda: {"qoi": last["q"], "moments": acc, "state": x}
 
     elapsed = time_steps(torch, dist, world, step, a.steps, a.warmup)
+    if a.dump_outputs and rank == 0:
+        dump_outputs(torch, a.dump_outputs, outputs())
     if a.workload == "quartic_mlmc_hier":
         # the work actually done in the timed steps (the sub-sampling follows the running tau_int)
         done = sum(lv.site_steps for lv in est.levels.values()) - hier_work["start"][0]
@@ -752,11 +790,11 @@ def main():
         sub = {l: (lv.n_sub_sum - hier_work["start"][1][l]) / a.steps for l, lv in est.levels.items()}
 
     # (side measurements on one rank only: at N > 1 they would only stagger the ranks in front of the statistics all-reduce)
-    if a.workload == "schwinger" and world == 1 and (a.probes or (not a.no_extra_points and a.chains == 0)):
+    if a.workload == "schwinger" and world == 1 and (a.probes or (a.full and not a.no_extra_points and a.chains == 0)):
         extra["hbm_bound_probes"] = hbm_bound_probes(torch, ops, W, a)
 
     # side measurements of the default workload (same kernels, other batch sizes), after the timed region
-    if a.workload == "schwinger" and world == 1 and not a.no_extra_points and a.chains == 0:
+    if a.workload == "schwinger" and world == 1 and a.full and not a.no_extra_points and a.chains == 0:
         # (a single-chain step is ~0.06 ms: 200 of them, so that the figure does not hang on a handful of launches)
         for name, b_extra, k_extra in (("single_chain", 1, max(10 * a.steps, 200)), ("chains_128", 128, max(2, a.steps // 4))):
             Wx = SweepWorkload(a, torch, abi, ops, "schwinger", size, b_extra, rank * b_extra)

@@ -20,6 +20,13 @@ def golden():
 
 
 @pytest.fixture(scope="session")
+def compiled_ref():
+    """outputs of the reference's own compiled classes at the tests' inputs (tests/golden/make_compiled_reference_fixture.py)"""
+    with open(os.path.join(ROOT, "tests", "golden", "compiled_reference.json")) as f:
+        return json.load(f)
+
+
+@pytest.fixture(scope="session")
 def orc():
     import oracle
     oracle.lib()

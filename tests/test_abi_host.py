@@ -1,6 +1,7 @@
 """CPU: the C-ABI library loads, exports every symbol include/mlmcpi_hip.h declares, its host-side
 integer index maps are bit-exact against the oracle and against the reference's own Lattice
-classes (oracle/_ref), and it fails loudly -- never falls back -- when no GPU is present."""
+classes (their recorded outputs, tests/golden/compiled_reference.json), and it fails loudly -- never
+falls back -- when no GPU is present."""
 import ctypes as C
 import os
 import re
@@ -129,100 +130,64 @@ def test_index_maps_match_oracle(orc, Mt, Mx):
 
 
 # ---- against the reference's own compiled Lattice / Statistics classes -----------------------------
-REF = os.path.join(ROOT, "oracle", "_ref", "libref.so")
-
-
-@pytest.fixture(scope="module")
-def ref():
-    if not os.path.exists(REF):
-        pytest.skip("oracle/_ref not built (reference sources absent)")
-    lib = C.CDLL(REF)
-    lib.ref_lattice2d_new.restype = C.c_void_p
-    lib.ref_lattice2d_new.argtypes = [C.c_uint, C.c_uint, C.c_int, C.c_int]
-    lib.ref_lattice2d_coarse.restype = C.c_void_p
-    lib.ref_lattice2d_coarse.argtypes = [C.c_void_p]
-    for f in ("ref_lattice2d_free",):
-        getattr(lib, f).argtypes = [C.c_void_p]
-    for f in ("ref_lattice2d_Mt", "ref_lattice2d_Mx", "ref_lattice2d_rotated", "ref_lattice2d_nvertices"):
-        getattr(lib, f).argtypes = [C.c_void_p]
-        getattr(lib, f).restype = C.c_uint
-    lib.ref_vertex_cart2lin.argtypes = [C.c_void_p, C.c_int, C.c_int]
-    lib.ref_vertex_cart2lin.restype = C.c_uint
-    lib.ref_link_cart2lin.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int]
-    lib.ref_link_cart2lin.restype = C.c_uint
-    lib.ref_lattice2d_neighbours.argtypes = [C.c_void_p, C.c_void_p]
-    lib.ref_lattice1d_neighbours.argtypes = [C.c_uint, C.c_double, C.c_void_p, C.POINTER(C.c_double)]
-    lib.ref_stats_new.restype = C.c_void_p
-    lib.ref_stats_new.argtypes = [C.c_uint]
-    lib.ref_stats_free.argtypes = [C.c_void_p]
-    lib.ref_stats_record.argtypes = [C.c_void_p, C.c_void_p, C.c_uint]
-    lib.ref_stats_reset.argtypes = [C.c_void_p, C.c_int]
-    lib.ref_stats_get.argtypes = [C.c_void_p, C.c_void_p]
-    return lib
+# (their outputs at these inputs, recorded by tests/golden/make_compiled_reference_fixture.py: fixture compiled_ref)
 
 
 @pytest.mark.parametrize("ctype", [0, 1, 2, 3, 4])
-def test_index_maps_match_compiled_reference(ref, ctype):
+def test_index_maps_match_compiled_reference(compiled_ref, ctype):
     """Whole coarsening hierarchy of a 16 x 8 lattice (incl. the rotated levels of CoarsenRotate):
     vertex/link maps and neighbour tables of the ABI == lattice/lattice2d.{hh,cc} compiled."""
     from mlmcpathintegral_amd import abi
     lib = abi.load()
-    h = ref.ref_lattice2d_new(16, 8, ctype, 0)
-    levels = 0
-    while h:
-        Mt, Mx, rot = ref.ref_lattice2d_Mt(h), ref.ref_lattice2d_Mx(h), ref.ref_lattice2d_rotated(h)
-        nv = ref.ref_lattice2d_nvertices(h)
-        theirs = np.zeros(nv * 8, dtype=np.uint32)
-        ref.ref_lattice2d_neighbours(h, theirs.ctypes.data_as(C.c_void_p))
-        mine = np.zeros(nv * 8, dtype=np.uint32)
+    levels = compiled_ref["index_maps_16x8"][str(ctype)]
+    assert (levels[0]["Mt"], levels[0]["Mx"]) == (16, 8)
+    for n, lv in enumerate(levels):
+        Mt, Mx, rot = lv["Mt"], lv["Mx"], lv["rotated"]
+        theirs = np.array(lv["neighbours"], dtype=np.uint32)
+        mine = np.zeros(theirs.size, dtype=np.uint32)
         assert lib.mlmcpi_neighbours_2d(Mt, Mx, rot, mine.ctypes.data_as(C.c_void_p)) == 0
-        assert (mine == theirs).all(), (ctype, levels)
-        for i in range(-2, Mt + 2):
-            for j in range(-2, Mx + 2):
-                if rot and (i + j) % 2:
-                    continue
-                assert lib.mlmcpi_vertex_cart2lin(Mt, Mx, rot, i, j) == ref.ref_vertex_cart2lin(h, i, j)
-                if not rot:
-                    for mu in (0, 1):
-                        assert lib.mlmcpi_link_cart2lin(Mt, Mx, i, j, mu) == ref.ref_link_cart2lin(h, i, j, mu)
-        nxt = ref.ref_lattice2d_coarse(h)
-        ref.ref_lattice2d_free(h)
-        h = nxt
-        levels += 1
-    assert levels >= 2
+        assert (mine == theirs).all(), (ctype, n)
+        assert len(lv["vertex_cart2lin"]) == sum(1 for i in range(-2, Mt + 2) for j in range(-2, Mx + 2)
+                                                 if not (rot and (i + j) % 2))
+        for i, j, want in lv["vertex_cart2lin"]:
+            assert lib.mlmcpi_vertex_cart2lin(Mt, Mx, rot, i, j) == want
+        assert len(lv["link_cart2lin"]) == (0 if rot else 2 * (Mt + 4) * (Mx + 4))
+        for i, j, mu, want in lv["link_cart2lin"]:
+            assert lib.mlmcpi_link_cart2lin(Mt, Mx, i, j, mu) == want
+    assert len(levels) >= 2
 
 
-def test_lattice1d_matches_compiled_reference(ref):
+def test_lattice1d_matches_compiled_reference(compiled_ref):
     from mlmcpathintegral_amd import abi
     for M in (2, 7, 128):
-        theirs = np.zeros(2 * M, dtype=np.uint32)
-        a = C.c_double()
-        ref.ref_lattice1d_neighbours(M, 4.0, theirs.ctypes.data_as(C.c_void_p), C.byref(a))
+        rec = compiled_ref["lattice1d_T4"][str(M)]
+        theirs = np.array(rec["neighbours"], dtype=np.uint32)
         mine = np.zeros(2 * M, dtype=np.uint32)
         abi.load().mlmcpi_neighbours_1d(M, mine.ctypes.data_as(C.c_void_p))
-        assert (mine == theirs).all() and a.value == 4.0 / M
+        assert theirs.size == 2 * M and (mine == theirs).all() and rec["a_lat"] == 4.0 / M
 
 
-def test_statistics_match_compiled_reference(ref, orc):
-    """common/statistics.cc compiled vs the oracle's restatement, bit for bit, on an AR(1) series."""
+def _ar1_series():
     rng = np.random.default_rng(11)
     q = np.zeros(5000)
     for k in range(1, q.size):
         q[k] = 0.7 * q[k - 1] + rng.normal()
-    q += 2.0
-    r = ref.ref_stats_new(20)
+    return q + 2.0
+
+
+def test_statistics_match_compiled_reference(compiled_ref, orc):
+    """common/statistics.cc compiled vs the oracle's restatement, bit for bit, on an AR(1) series."""
+    import hashlib
+    q = _ar1_series()
+    rec = compiled_ref["statistics_ar1"]   # Statistics(20): q[:1000], soft reset, q[1000:]
+    assert hashlib.sha256(q.tobytes()).hexdigest() == rec["input_sha256"], "the AR(1) series is not the recorded one"
     o = orc.Statistics(20)
-    for part in (q[:1000], q[1000:]):
-        ref.ref_stats_record(r, part.ctypes.data_as(C.c_void_p), part.size)
-        o.record(part)
-        if part is not q[1000:]:
-            ref.ref_stats_reset(r, 0)  # montecarlosinglelevel.cc:27-37: soft reset after burn-in
-            o.reset()
-    out = np.zeros(6)
-    ref.ref_stats_get(r, out.ctypes.data_as(C.c_void_p))
+    o.record(q[:1000])
+    o.reset()  # montecarlosinglelevel.cc:27-37: soft reset after burn-in
+    o.record(q[1000:])
     got = o.get()
-    assert list(out) == [got[k] for k in ("average", "variance", "variance_error", "tau_int", "error", "samples")]
-    ref.ref_stats_free(r)
+    assert got["samples"] == 4000
+    assert rec["get"] == [got[k] for k in ("average", "variance", "variance_error", "tau_int", "error", "samples")]
 
 
 @pytest.mark.parametrize("M,T,m0,mu2", [(16, 4.0, 1.0, 1.0), (128, 4.0, 1.0, 1.0), (100, 10.0, 0.7, 2.0)])

@@ -1,6 +1,6 @@
 """Gaussian free field multilevel glue: GFFAction on the levels of a coarsening hierarchy (rotated levels,
 Gibbs-smoothed coarse actions), GFFConditionedFineAction and the two-level step between GFF levels.
-CPU: vertex lists against the compiled reference (oracle/_ref), the library's dense matrices against the oracle's
+CPU: vertex lists against the compiled reference (its recorded output), the library's dense matrices against the oracle's
 independent construction and against the defining properties (n_gibbs = 0 gives the plain precision matrix, many sweeps
 give the exact marginal of the finer level).  GPU: evaluate / draw / fill-in / two-level step against the oracle, and the
 hierarchical chain against the closed form of <phi^2>."""
@@ -66,35 +66,14 @@ class OLevel:
         self.L.orc_gff_level_free(self.h)
 
 
-@pytest.fixture(scope="module")
-def ref():
-    path = os.path.join(ROOT, "oracle", "_ref", "libref.so")
-    if not os.path.exists(path):
-        pytest.skip("oracle/_ref not built (reference sources absent)")
-    lib = C.CDLL(path)
-    lib.ref_lattice2d_new.restype = C.c_void_p
-    lib.ref_lattice2d_new.argtypes = [C.c_uint, C.c_uint, C.c_int, C.c_int]
-    for f in ("ref_lattice2d_free", "ref_lattice2d_fineonly", "ref_lattice2d_fine2coarse"):
-        getattr(lib, f).restype = None
-    lib.ref_lattice2d_free.argtypes = [C.c_void_p]
-    lib.ref_lattice2d_fineonly.argtypes = [C.c_void_p, C.c_void_p]
-    lib.ref_lattice2d_fine2coarse.argtypes = [C.c_void_p, C.c_void_p]
-    lib.ref_lattice2d_n_fineonly.argtypes = [C.c_void_p]
-    lib.ref_lattice2d_n_coarse.argtypes = [C.c_void_p]
-    return lib
-
-
 @pytest.mark.parametrize("Mt,ctype,level", [(8, ROTATE, 0), (8, ROTATE, 1), (16, ROTATE, 0), (16, ROTATE, 1), (8, BOTH, 0), (4, ROTATE, 0),
                                             (32, ROTATE, 1)])
-def test_vertex_lists_match_compiled_reference(ref, orc, Mt, ctype, level):
+def test_vertex_lists_match_compiled_reference(compiled_ref, orc, Mt, ctype, level):
     """coarse / fine-only vertices and the fine -> coarse map of Lattice2D (lattice2d.cc:82-134), rotated levels included:
-    library == oracle == the reference's own class, bit for bit"""
-    h = ref.ref_lattice2d_new(Mt, Mt, ctype, level)
-    nf, nc = ref.ref_lattice2d_n_fineonly(h), ref.ref_lattice2d_n_coarse(h)
-    want_f, want_p = np.zeros(nf, dtype=np.uint32), np.zeros(2 * nc, dtype=np.uint32)
-    ref.ref_lattice2d_fineonly(h, want_f.ctypes.data_as(C.c_void_p))
-    ref.ref_lattice2d_fine2coarse(h, want_p.ctypes.data_as(C.c_void_p))
-    ref.ref_lattice2d_free(h)
+    library == oracle == the reference's own class (its recorded output), bit for bit"""
+    rec = compiled_ref["vertex_lists"][f"{Mt} {ctype} {level}"]
+    want_f, want_p = np.array(rec["fineonly"], dtype=np.uint32), np.array(rec["fine2coarse"], dtype=np.uint32)
+    nf, nc = want_f.size, want_p.size // 2
     for lv in (Level(Mt, ctype, level, 1.0), OLevel(orc, Mt, ctype, level, 1.0)):
         assert lv.n_coarse == nc and lv.N - lv.n_coarse == nf
         pairs, fineonly = lv.tables()

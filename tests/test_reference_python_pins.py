@@ -64,32 +64,16 @@ def test_link_maps_equal_the_reference_python(orc, pins):
             assert (ci.value, cj.value, cm.value) == (i, j, mu)
 
 
-def test_link_maps_of_the_compiled_reference_equal_the_reference_python(pins):
-    """oracle/_ref (the reference's own lattice2d.cc, compiled as shipped) against the author's Python: the two
+def test_link_maps_of_the_compiled_reference_equal_the_reference_python(pins, compiled_ref):
+    """the reference's own lattice2d.cc, compiled as shipped (its recorded output), against the author's Python: the two
     reference-held statements of the map agree, so either pins the oracle."""
-    ref = os.path.join(os.path.dirname(HERE), "oracle", "_ref", "libref.so")
-    if not os.path.exists(ref):
-        pytest.skip("oracle/_ref not built (no /root/reference on this machine)")
-    import ctypes as C
-    R = C.CDLL(ref)
-    R.ref_lattice2d_new.restype = C.c_void_p
-    R.ref_lattice2d_new.argtypes = [C.c_uint, C.c_uint, C.c_int, C.c_int]
-    R.ref_lattice2d_free.argtypes = [C.c_void_p]
-    R.ref_link_cart2lin.restype = C.c_uint
-    R.ref_link_cart2lin.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int]
-    R.ref_link_lin2cart.argtypes = [C.c_void_p, C.c_uint, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)]
-    for case in pins["schwinger"]:
-        if case["cart2lin"] is None:
-            continue
-        m = case["m"]
-        h = R.ref_lattice2d_new(m, m, 0, 0)
-        for i, j, mu, ell in case["cart2lin"] + case["cart2lin_wrapped"]:
-            assert R.ref_link_cart2lin(h, i, j, mu) == ell
-        for ell, i, j, mu in case["lin2cart"]:
-            ci, cj, cm = C.c_int(), C.c_int(), C.c_int()
-            R.ref_link_lin2cart(h, ell, C.byref(ci), C.byref(cj), C.byref(cm))
-            assert (ci.value, cj.value, cm.value) == (i, j, mu)
-        R.ref_lattice2d_free(h)
+    cases = [case for case in pins["schwinger"] if case["cart2lin"] is not None]
+    assert cases and set(compiled_ref["link_maps"]) == {str(case["m"]) for case in cases}
+    for case in cases:
+        rec = compiled_ref["link_maps"][str(case["m"])]
+        assert [r[:3] for r in rec["cart2lin"]] == [p[:3] for p in case["cart2lin"] + case["cart2lin_wrapped"]]
+        assert [r[3] for r in rec["cart2lin"]] == [p[3] for p in case["cart2lin"] + case["cart2lin_wrapped"]]
+        assert rec["lin2cart"] == [list(p) for p in case["lin2cart"]]
 
 
 # ---- action/qft/quenchedschwingeraction.cc:7-22, qoi/qft/qoiavgplaquette.cc:8-27, qoi2dsusceptibility.cc:8-27 ----------

@@ -1,8 +1,9 @@
 """Cross-rank Statistics as the reference defines them (common/statistics.cc:29-95): the product C++ class
 (include/mlmcpi/statistics.hh, through host/stats_check on thread ranks) and its Python twin (chains.Statistics, through
-gloo at world size 2) against the COMPILED reference (oracle/_ref): single rank bit for bit, several ranks against the
-reference's combination rules applied to one reference object per rank."""
+gloo at world size 2) against the COMPILED reference (its outputs at these inputs, tests/golden/compiled_reference.json):
+single rank bit for bit, several ranks against the reference's combination rules applied to one reference object per rank."""
 import ctypes as C
+import hashlib
 import math
 import multiprocessing as mp
 import os
@@ -17,26 +18,6 @@ import torch.distributed as dist
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 CHECK = os.path.join(ROOT, "host", "stats_check")
-
-
-@pytest.fixture(scope="module")
-def ref():
-    path = os.path.join(ROOT, "oracle", "_ref", "libref.so")
-    if not os.path.exists(path):
-        pytest.skip("oracle/_ref not built (reference sources absent)")
-    lib = C.CDLL(path)
-    lib.ref_stats_new.restype = C.c_void_p
-    lib.ref_stats_new.argtypes = [C.c_uint]
-    for f in ("ref_stats_free", "ref_stats_get", "ref_stats_autocorr", "ref_stats_record", "ref_stats_reset"):
-        getattr(lib, f).restype = None
-    lib.ref_stats_free.argtypes = [C.c_void_p]
-    lib.ref_stats_record.argtypes = [C.c_void_p, C.c_void_p, C.c_uint]
-    lib.ref_stats_reset.argtypes = [C.c_void_p, C.c_int]
-    lib.ref_stats_get.argtypes = [C.c_void_p, C.c_void_p]
-    lib.ref_stats_autocorr.argtypes = [C.c_void_p, C.c_void_p]
-    lib.ref_parallel_mt19937_64.argtypes = [C.c_ulonglong, C.c_uint, C.c_void_p]
-    lib.ref_parallel_mt19937_64.restype = None
-    return lib
 
 
 @pytest.fixture(scope="module")
@@ -55,25 +36,14 @@ def _samples(n, seed=3):
     return np.array(out)
 
 
-def _ref_rank(ref, q, k_max, nburn):
-    """one reference Statistics fed one rank's stream; returns (avg, variance, variance_error, tau, error, n, C_k, and the
-    raw long-term averages recovered from the getters)"""
-    h = ref.ref_stats_new(k_max)
-    q = np.ascontiguousarray(q, dtype=np.float64)
-    if nburn and nburn <= q.size:
-        ref.ref_stats_record(h, q[:nburn].ctypes.data_as(C.c_void_p), nburn)
-        ref.ref_stats_reset(h, 0)
-        rest = q[nburn:]
-    else:
-        rest = q
-    if rest.size:
-        ref.ref_stats_record(h, np.ascontiguousarray(rest).ctypes.data_as(C.c_void_p), rest.size)
-    out = np.zeros(6)
-    ck = np.zeros(k_max)
-    ref.ref_stats_get(h, out.ctypes.data_as(C.c_void_p))
-    ref.ref_stats_autocorr(h, ck.ctypes.data_as(C.c_void_p))
-    ref.ref_stats_free(h)
-    return out, ck
+def _ref_rank(compiled_ref, q, key, k_max, nburn):
+    """one reference Statistics fed one rank's stream q (burn-in of nburn samples, soft reset, the rest), as recorded under
+    key = (seed, n, world, rank) of the stream; returns (avg, variance, variance_error, tau, error, n) and C_k"""
+    seed, n, world, rank = key
+    rec = compiled_ref["statistics"][f"seed={seed} n={n} world={world} rank={rank} k_max={k_max} nburn={nburn}"]
+    assert hashlib.sha256(np.ascontiguousarray(q, dtype=np.float64).tobytes()).hexdigest() == rec["input_sha256"], \
+        f"{key}: the sample stream is not the recorded one"
+    return np.array(rec["get"]), np.array(rec["autocorr"])
 
 
 def _run_check(exe, args, q):
@@ -83,10 +53,10 @@ def _run_check(exe, args, q):
 
 
 @pytest.mark.parametrize("k_max,nburn,n", [(20, 0, 500), (20, 100, 700), (7, 3, 40), (100, 50, 3000)])
-def test_product_statistics_bit_exact_against_compiled_reference(ref, stats_check, k_max, nburn, n):
-    """include/mlmcpi/statistics.hh itself (not the oracle's copy) against oracle/_ref, one rank, bit for bit."""
+def test_product_statistics_bit_exact_against_compiled_reference(compiled_ref, stats_check, k_max, nburn, n):
+    """include/mlmcpi/statistics.hh itself (not the oracle's copy) against the compiled reference, one rank, bit for bit."""
     q = _samples(n)
-    want, ck = _ref_rank(ref, q, k_max, nburn)
+    want, ck = _ref_rank(compiled_ref, q, (3, n, 1, 0), k_max, nburn)
     got = _run_check(stats_check, ["single", k_max, nburn], q)
     assert got[:5] == list(want[:5]) and got[5] == want[5]
     assert got[6:6 + k_max] == list(ck)
@@ -108,10 +78,10 @@ def _combine(ranks_sums):
     return {"avg": g["avg"], "var": var, "tau": tau, "err": math.sqrt(tau * var / g["n"]), "n": g["n"], "C": C_k}
 
 
-def _raw_from_reference(ref, q, k_max, nburn):
+def _raw_from_reference(compiled_ref, q, key, k_max, nburn):
     """raw per-rank quantities of a reference object, recovered from its single-rank getters: avg_longterm via the
     autocorrelation at lag 0 and the variance (exact algebra: S_0 = C_0 + avg_lt^2, var = n/(n-1) C_0)."""
-    out, ck = _ref_rank(ref, q, k_max, nburn)
+    out, ck = _ref_rank(compiled_ref, q, key, k_max, nburn)
     n_lt = len(q)
     # avg_longterm is not exposed; recompute it with the reference's recurrence (statistics.cc:13-15), which is what
     # the object holds bit for bit (checked through variance() below)
@@ -123,13 +93,13 @@ def _raw_from_reference(ref, q, k_max, nburn):
 
 
 @pytest.mark.parametrize("world,k_max,nburn,n", [(2, 20, 0, 600), (2, 20, 40, 801), (3, 10, 5, 500), (4, 20, 10, 1000)])
-def test_product_statistics_over_thread_ranks_follow_the_reference_rules(ref, stats_check, world, k_max, nburn, n):
+def test_product_statistics_over_thread_ranks_follow_the_reference_rules(compiled_ref, stats_check, world, k_max, nburn, n):
     """W interleaved streams, one reference object per stream, combined by the reference's rules, against the product
     class over ThreadExchange (one packed all-reduce).  World 2 is bit exact up to the association of the two-term sums
     (commutative), larger worlds to rounding."""
     q = _samples(n, seed=11)
     parts = [q[r::world] for r in range(world)]
-    want = _combine([_raw_from_reference(ref, p, k_max, nburn) for p in parts])
+    want = _combine([_raw_from_reference(compiled_ref, p, (11, n, world, r), k_max, nburn) for r, p in enumerate(parts)])
     got = _run_check(stats_check, ["threads", world, k_max, nburn], q)
     tol = 1e-13
     assert got[0] == pytest.approx(want["avg"], rel=tol)
@@ -182,7 +152,7 @@ def _gloo_worker(rank, world, port, k_max, nburn, n, q_out):
     dist.destroy_process_group()
 
 
-def test_python_statistics_over_gloo_match_the_reference_rules(ref):
+def test_python_statistics_over_gloo_match_the_reference_rules(compiled_ref):
     """world 2 on gloo: two interleaved streams against two reference objects combined by the reference's rules."""
     world, port, k_max, nburn, n = 2, 29571, 20, 40, 801
     ctx = mp.get_context("spawn")
@@ -195,7 +165,7 @@ def test_python_statistics_over_gloo_match_the_reference_rules(ref):
         p.join(timeout=60)
         assert p.exitcode == 0
     q = _samples(n, seed=11)
-    want = _combine([_raw_from_reference(ref, q[r::world], k_max, nburn) for r in range(world)])
+    want = _combine([_raw_from_reference(compiled_ref, q[r::world], (11, n, world, r), k_max, nburn) for r in range(world)])
     stats = sorted(r for r in res if r[1] != "loop")
     assert stats[0][1:6] == stats[1][1:6]                     # every rank holds the same reduced view
     _, avg, var, tau, err, n_tot, counts = stats[0]
@@ -207,13 +177,13 @@ def test_python_statistics_over_gloo_match_the_reference_rules(ref):
     assert abs(loops[0][5] - 1.0) < 5 * loops[0][6]
 
 
-def test_rank_seeding_matches_compiled_reference(ref):
+def test_rank_seeding_matches_compiled_reference(compiled_ref):
     """mpi/mpi_random.cc as shipped (one rank in this build): the oracle's restatement of the per-rank seed list gives the
     same engine stream; for several ranks the list is sorted, distinct and contains the seed."""
     import oracle
     for seed in (21172817, 2481317, 8923759, 5):
-        want = np.zeros(8, dtype=np.uint64)
-        ref.ref_parallel_mt19937_64(seed, 8, want.ctypes.data_as(C.c_void_p))
+        want = np.array(compiled_ref["parallel_mt19937_64"][str(seed)], dtype=np.uint64)
+        assert want.size == 8
         got = np.zeros(8, dtype=np.uint64)
         oracle.lib().orc_rank_engine_outputs(seed, 0, 1, 8, got.ctypes.data_as(C.c_void_p))
         assert (got == want).all()
