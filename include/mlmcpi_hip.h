@@ -28,7 +28,9 @@
  *     (<= 4e-14 Schwinger at K = 10, <= 2e-15 rotor).  A heat-bath accept/reject decision that sits on
  *     such a difference flips, after which two chains diverge: compare, checkpoint and resume runs under
  *     one launch plan, and record it (K per launch: bench.py's config.overrelaxation_launches).  The
- *     sweep-by-sweep kernels (GFF always) agree bit for bit whatever the plan.  Spelled out in DESIGN.md 3 / 9.
+ *     sweep-by-sweep kernels (GFF always) agree bit for bit whatever the plan.  A QoI fused into the last launch of a
+ *     draw (mlmcpi_lattice_sweep_draw_qoi*) sums per-tile partials in the tile order of that launch: under another plan
+ *     (MLMCPI_OR_HEAT=split, MLMCPI_OR_KERNEL=block) it agrees to rounding (1e-13).  Spelled out in DESIGN.md 3 / 9.
  */
 #ifndef MLMCPI_HIP_H
 #define MLMCPI_HIP_H
@@ -89,10 +91,10 @@ int mlmcpi_copy_d2d(void *d_dst, const void *d_src, size_t bytes, void *stream);
 int mlmcpi_stream_synchronize(void *stream);
 /* Tuning knobs -- they change no result beyond the last bits.  Read from the environment once, at the first use in the
  * process; this call changes one afterwards (value "" or NULL resets it): MLMCPI_SWEEP_TILE=TWxTHxNT (tile and workgroup
- * size of the generic sweep kernels; also forces them), MLMCPI_OR_KERNEL=perm|block|lds|patch (Schwinger overrelaxation in
- * closed form -- the default where 64 x 64 or 64 x 32 tiles divide the lattice -- or sweep by sweep on 4 x 4 register
- * blocks, LDS resident, 2 x 2 register patches; the sweep-by-sweep kernels agree with each other bit for bit and with the
- * closed form to 4e-14), MLMCPI_OR_THREADS=256|512|1024 (workgroup size of the LDS-resident kernel), MLMCPI_OR_HEAT=
+ * size of the generic sweep kernels; also forces them), MLMCPI_OR_KERNEL=perm|block (Schwinger overrelaxation in closed
+ * form -- the default on even lattices of at least 64 x 32 -- or sweep by sweep on 4 x 4 register blocks where 64 x 64
+ * tiles divide the lattice, the generic kernels elsewhere, with the heat-bath sweep in a launch of its own; the
+ * sweep-by-sweep kernels agree with each other bit for bit and with the closed form to 4e-14), MLMCPI_OR_HEAT=
  * fused|split|wide|narrow (the heat-bath sweep behind the last overrelaxation launch: in it or in a launch of its own;
  * workgroup size of the fused launch). */
 int mlmcpi_set_option(const char *name, const char *value);

@@ -305,7 +305,7 @@ __device__ __forceinline__ double rng_normal0(const RngKey &k, uint32_t site, ui
 // stencil kernels are LDS-issue bound, so their loads are issued through inline asm, which the merger
 // does not see.  The caller issues a group of reads and then ONE lds_wait7() before the first use (the
 // compiler does not track inline-asm loads, cdna_hip_programming.md 5.7).  `addr` is the LDS byte address
-// (the callers add the LDS address of their dynamic array, see schwinger_or_kernel).
+// (the callers add the LDS address of their dynamic array: the low word of a flat LDS address is the LDS offset).
 template <int OFF>
 __device__ __forceinline__ double lds_read_f64(uint32_t addr) {
   double v;

@@ -22,8 +22,8 @@
 
 namespace mlmcpi {
 
-// Instrumentation build only (make EXTRA=-DMLMCPI_STAMPS; tools/exp_stamps.py): thread 0 of every workgroup of
-// schwinger_or_heat_kernel leaves the 100 MHz wall clock at ten points, plus the XCD / CU it ran on.
+// Instrumentation build only (make EXTRA=-DMLMCPI_STAMPS): thread 0 of every workgroup of
+// schwinger_perm_heat_kernel leaves the 100 MHz wall clock at ten points, plus the XCD / CU it ran on.
 #ifdef MLMCPI_STAMPS
 __device__ unsigned long long g_stamps[16 * 65536];
 #define MLMCPI_STAMP(k)                                                                                            \
@@ -356,247 +356,6 @@ __global__ void __launch_bounds__(NT, HEAT ? (NT == 256 ? 4 : NT == 512 ? 2 : 1)
   }
 }
 
-// ---- Schwinger overrelaxation, specialised ---------------------------------------------------------------
-// Same sweep (same colour order, same update regions, therefore bit-identical results) as
-// schwinger_sweep_kernel<false, 256>, for launches of K overrelaxation sweeps on lattices that the
-// TW x TH tiles divide.  Everything the generic kernel recomputes per update is hoisted:
-//   * tile geometry is compile time, so every neighbour is an immediate offset of one LDS address;
-//   * each thread's cells (linear index tid + 256 m) are the same in every sweep, so their LDS
-//     offsets are computed once and kept in registers (M0 + M1 VGPRs);
-//   * LDS rows are padded to an odd number of doubles and the mu = 1 phases run with lanes along
-//     rows, so column-parity phases are bank-conflict free instead of stride-2.
-// Per update that leaves the ~10 fp64 instructions of the update itself (6 adds, 1 mod_2pi: the staple angles are
-// not wrapped separately, the final mod_2pi takes care of it).
-template <int TW, int TH, int K, int NT>
-__global__ void __launch_bounds__(NT)
-    schwinger_or_kernel(uint32_t Mt, uint32_t Mx, const double2 *__restrict__ in, double2 *__restrict__ out,
-                        uint32_t tiles_x) {
-  constexpr int H = 2 * K, BW = TW + 2 * H, BH = TH + 2 * H, P = BW + 1;
-  constexpr int NR0 = (BH - 2) / 2, NC0 = BW - 1, T0 = NR0 * NC0, M0 = (T0 + NT - 1) / NT;
-  constexpr int NCI = (BW - 2) / 2, NR1 = BH - 1, T1 = NCI * NR1, M1 = (T1 + NT - 1) / NT;
-  extern __shared__ double lds[];
-  double *th0 = lds, *th1 = lds + BH * P;
-  // LDS byte address of lds[0] for the ds_read_b64 issued through inline asm (the low word of a flat LDS address is the
-  // LDS offset): 0 today, but static LDS added to this kernel would move it
-  const uint32_t lds0 = (uint32_t)(uintptr_t)lds;
-  const uint32_t tile = blockIdx.x, b = blockIdx.y, tid = threadIdx.x;
-  const uint32_t ty = tile / tiles_x, tx = tile - ty * tiles_x;
-  const uint32_t i0 = tx * TW, j0 = ty * TH;
-  const uint32_t sc = (uint32_t)(((uint64_t)i0 + Mt - (H % Mt)) % Mt);
-  const uint32_t sr = (uint32_t)(((uint64_t)j0 + Mx - (H % Mx)) % Mx);
-  const double2 *src = in + (size_t)b * Mt * Mx;
-
-  stage_region<NT, 5, double2>(
-      BH, BW, [&](uint32_t r, uint32_t c) { return src[(size_t)wrap_add(sr, r, Mx) * Mt + wrap_add(sc, c, Mt)]; },
-      [&](uint32_t r, uint32_t c, double2 v) {
-        th0[r * P + c] = v.x;
-        th1[r * P + c] = v.y;
-      });
-
-  // cell offsets: mu = 0, even rows (odd rows: - P); mu = 1, even columns (odd columns: - 1)
-  int o0[M0], o1[M1];
-#pragma unroll
-  for (int m = 0; m < M0; ++m) {
-    const int idx = tid + NT * m, ri = idx / NC0, c = idx - ri * NC0;
-    o0[m] = (2 + 2 * ri) * P + c;
-  }
-#pragma unroll
-  for (int m = 0; m < M1; ++m) {
-    const int idx = tid + NT * m, ci = idx / NR1, r = idx - ci * NR1;
-    o1[m] = r * P + 2 + 2 * ci;
-  }
-  __syncthreads();
-
-  for (int s = 0; s < K; ++s) {
-#pragma unroll
-    for (int par = 0; par < 2; ++par) {
-#pragma unroll
-      for (int m = 0; m < M0; ++m) {
-        if ((m + 1) * NT <= T0 || (int)tid + NT * m < T0) {
-          const int o = o0[m] - par * P;
-          const uint32_t a0 = lds0 + (uint32_t)(o - P) * 8u, a1 = a0 + (uint32_t)(BH * P) * 8u;  // th0 / th1 at (r-1, c)
-          double t0_up = lds_read_f64<2 * P * 8>(a0), t0_dn = lds_read_f64<0>(a0), t0_own = lds_read_f64<P * 8>(a0);
-          double t1_c = lds_read_f64<P * 8>(a1), t1_r = lds_read_f64<P * 8 + 8>(a1);
-          double t1_dc = lds_read_f64<0>(a1), t1_dr = lds_read_f64<8>(a1);
-          lds_wait7(t0_up, t0_dn, t0_own, t1_c, t1_r, t1_dc, t1_dr);
-          const double tp = t0_up + t1_c - t1_r;  // staple angles unwrapped: see the generic kernel
-          const double tm = t0_dn + t1_dr - t1_dc;
-          th0[o] = mod_2pi_fast((tp + tm) - t0_own);
-        }
-      }
-      __syncthreads();
-    }
-#pragma unroll
-    for (int par = 0; par < 2; ++par) {
-#pragma unroll
-      for (int m = 0; m < M1; ++m) {
-        if ((m + 1) * NT <= T1 || (int)tid + NT * m < T1) {
-          const int o = o1[m] - par;
-          const uint32_t a0 = lds0 + (uint32_t)(o - 1) * 8u, a1 = a0 + (uint32_t)(BH * P) * 8u;  // th0 / th1 at (r, c-1)
-          double t0_c = lds_read_f64<8>(a0), t0_u = lds_read_f64<P * 8 + 8>(a0);
-          double t0_lu = lds_read_f64<P * 8>(a0), t0_l = lds_read_f64<0>(a0);
-          double t1_r = lds_read_f64<16>(a1), t1_l = lds_read_f64<0>(a1), t1_own = lds_read_f64<8>(a1);
-          lds_wait7(t0_c, t0_u, t0_lu, t0_l, t1_r, t1_l, t1_own);
-          const double tp = t0_c + t1_r - t0_u;
-          const double tm = t0_lu + t1_l - t0_l;
-          th1[o] = mod_2pi_fast((tp + tm) - t1_own);
-        }
-      }
-      __syncthreads();
-    }
-  }
-
-  double2 *dst = out + (size_t)b * Mt * Mx;
-  for_region<NT>(TH, TW, [&](uint32_t r, uint32_t c) {
-    const uint32_t o = (r + H) * P + (c + H);
-    dst[(size_t)(j0 + r) * Mt + (i0 + c)] = make_double2(th0[o], th1[o]);
-  });
-}
-
-// ---- Schwinger overrelaxation, register-tiled ---------------------------------------------------------------
-// The LDS-resident kernel above reads 7 doubles from LDS and writes 1 per link update (64 B): at 128 B/clk per CU that
-// is the bound it runs into (16 waves x 64 LDS instructions x 4 clk per sweep and tile ~ the measured 0.43 ms per
-// 4-sweep launch), not HBM and not the VALU.  Here every thread keeps a 2 x 2 block of vertices -- 8 link angles -- in
-// registers for all K sweeps; LDS only carries what crosses block boundaries: per sweep a thread reads 16 neighbour
-// values (6, 3, 5, 2 in the four colour phases; values that cannot have changed in between are reused) and publishes
-// its 8 updated links, 24 B per update instead of 64.  The LDS image is eight structure-of-arrays planes
-// [mu][row parity][column parity] over blocks, so that consecutive lanes (consecutive blocks of a row) touch
-// consecutive doubles in every access.  Same updates, same order and the same arithmetic as the kernels above (every
-// link whose six staple links lie inside the buffer is updated), hence bit-identical results.
-// One block per thread: (64 + 4K)/2 x (32 + 4K)/2 <= 1024 blocks for K <= 4.
-template <int K>
-__global__ void __launch_bounds__(1024)
-    schwinger_or_patch_kernel(uint32_t Mt, uint32_t Mx, const double2 *__restrict__ in, double2 *__restrict__ out,
-                              uint32_t tiles_x) {
-  constexpr int TW = 64, TH = 32, H = 2 * K, BW = TW + 2 * H, BH = TH + 2 * H, NPX = BW / 2, NPY = BH / 2;
-  constexpr int NP = NPX * NPY;  // blocks per tile = active threads
-  static_assert(NP <= 1024, "one 2 x 2 block per thread");
-  extern __shared__ double lds[];
-  // plane(mu, c, a)[pj][pi]: link mu of vertex (2 pi + a, 2 pj + c)
-  auto plane = [&](int mu, int c, int a) { return lds + ((mu * 2 + c) * 2 + a) * NP; };
-  const uint32_t tile = blockIdx.x, b = blockIdx.y, tid = threadIdx.x;
-  const uint32_t ty = tile / tiles_x, tx = tile - ty * tiles_x;
-  const uint32_t i0 = tx * TW, j0 = ty * TH;
-  const bool active = tid < NP;
-  const int pj = active ? (int)tid / NPX : 0, pi = active ? (int)tid - pj * NPX : 0;
-  const double2 *src = in + (size_t)b * Mt * Mx;
-  // global coordinates of the block's lower-left vertex (even, so (gi, gi + 1) never straddles the wrap)
-  const uint32_t gi = (uint32_t)(((uint64_t)i0 + Mt - (H % Mt) + 2 * pi) % Mt);
-  const uint32_t gj0 = (uint32_t)(((uint64_t)j0 + Mx - (H % Mx) + 2 * pj) % Mx);
-  const uint32_t gj1 = gj0 + 1 == Mx ? 0 : gj0 + 1;
-  double t0[2][2] = {{0, 0}, {0, 0}}, t1[2][2] = {{0, 0}, {0, 0}};  // [c][a]
-  if (active) {
-    const double2 v00 = src[(size_t)gj0 * Mt + gi], v01 = src[(size_t)gj0 * Mt + gi + 1];
-    const double2 v10 = src[(size_t)gj1 * Mt + gi], v11 = src[(size_t)gj1 * Mt + gi + 1];
-    t0[0][0] = v00.x; t1[0][0] = v00.y; t0[0][1] = v01.x; t1[0][1] = v01.y;
-    t0[1][0] = v10.x; t1[1][0] = v10.y; t0[1][1] = v11.x; t1[1][1] = v11.y;
-#pragma unroll
-    for (int c = 0; c < 2; ++c)
-#pragma unroll
-      for (int a = 0; a < 2; ++a) {
-        plane(0, c, a)[tid] = t0[c][a];
-        plane(1, c, a)[tid] = t1[c][a];
-      }
-  }
-  // Neighbour blocks, clamped into the buffer.  Links on the buffer edge have no complete stencil; the kernels above
-  // leave them alone, here they are updated from the clamped (wrong) neighbours instead -- no predicates in the sweep
-  // loop.  Either way what an edge link holds only ever reaches links that are already outside the exact region
-  // (which shrinks by one block per sweep no matter what its surroundings hold), never the owned tile.
-  const int me = active ? (int)tid : 0;  // idle threads of the last wave: every index is entry 0, nothing is written
-  const int dn = pj > 0 ? me - NPX : me, up = pj + 1 < NPY ? me + NPX : me;
-  const int lf = pi > 0 ? me - 1 : me, rt = pi + 1 < NPX ? me + 1 : me;
-  const int rtdn = (pi + 1 < NPX ? 1 : 0) + (pj > 0 ? -NPX : 0) + me;
-  const int lfup = (pi > 0 ? -1 : 0) + (pj + 1 < NPY ? NPX : 0) + me;
-  __syncthreads();
-
-  for (int s = 0; s < K; ++s) {
-    // phase 0: mu = 0, even rows (c = 0)
-    // (the idle threads of the last wave read entry 0 and compute on zeros: no predicate, no zero fill in the loop)
-    const double D0 = plane(0, 1, 0)[dn], D1 = plane(0, 1, 1)[dn], E0 = plane(1, 1, 0)[dn], E1 = plane(1, 1, 1)[dn];
-    double R0 = plane(1, 0, 0)[rt];
-    const double RD = plane(1, 1, 0)[rtdn];
-    {
-      {  // a = 0
-        const double tp = t0[1][0] + t1[0][0] - t1[0][1];
-        const double tm = D0 + E1 - E0;
-        t0[0][0] = mod_2pi_fast((tp + tm) - t0[0][0]);
-        if (active) plane(0, 0, 0)[me] = t0[0][0];
-      }
-      {  // a = 1
-        const double tp = t0[1][1] + t1[0][1] - R0;
-        const double tm = D1 + RD - E1;
-        t0[0][1] = mod_2pi_fast((tp + tm) - t0[0][1]);
-        if (active) plane(0, 0, 1)[me] = t0[0][1];
-      }
-    }
-    __syncthreads();
-    // phase 1: mu = 0, odd rows (c = 1)
-    const double U0 = plane(0, 0, 0)[up], U1 = plane(0, 0, 1)[up];
-    double R1 = plane(1, 1, 0)[rt];
-    {
-      {
-        const double tp = U0 + t1[1][0] - t1[1][1];
-        const double tm = t0[0][0] + t1[0][1] - t1[0][0];
-        t0[1][0] = mod_2pi_fast((tp + tm) - t0[1][0]);
-        if (active) plane(0, 1, 0)[me] = t0[1][0];
-      }
-      {
-        const double tp = U1 + t1[1][1] - R1;
-        const double tm = t0[0][1] + R0 - t1[0][1];
-        t0[1][1] = mod_2pi_fast((tp + tm) - t0[1][1]);
-        if (active) plane(0, 1, 1)[me] = t0[1][1];
-      }
-    }
-    __syncthreads();
-    // phase 2: mu = 1, even columns (a = 0)
-    const double L01 = plane(0, 0, 1)[lf], L11 = plane(0, 1, 1)[lf], M01 = plane(1, 0, 1)[lf], M11 = plane(1, 1, 1)[lf];
-    const double LU = plane(0, 0, 1)[lfup];
-    {
-      {  // c = 0
-        const double tp = t0[0][0] + t1[0][1] - t0[1][0];
-        const double tm = L11 + M01 - L01;
-        t1[0][0] = mod_2pi_fast((tp + tm) - t1[0][0]);
-        if (active) plane(1, 0, 0)[me] = t1[0][0];
-      }
-      {  // c = 1
-        const double tp = t0[1][0] + t1[1][1] - U0;
-        const double tm = LU + M11 - L11;
-        t1[1][0] = mod_2pi_fast((tp + tm) - t1[1][0]);
-        if (active) plane(1, 1, 0)[me] = t1[1][0];
-      }
-    }
-    __syncthreads();
-    // phase 3: mu = 1, odd columns (a = 1); the right neighbour's mu = 1 links changed in phase 2
-    R0 = plane(1, 0, 0)[rt];
-    R1 = plane(1, 1, 0)[rt];
-    {
-      {  // c = 0
-        const double tp = t0[0][1] + R0 - t0[1][1];
-        const double tm = t0[1][0] + t1[0][0] - t0[0][0];
-        t1[0][1] = mod_2pi_fast((tp + tm) - t1[0][1]);
-        if (active) plane(1, 0, 1)[me] = t1[0][1];
-      }
-      {  // c = 1
-        const double tp = t0[1][1] + R1 - U1;
-        const double tm = U0 + t1[1][0] - t0[1][0];
-        t1[1][1] = mod_2pi_fast((tp + tm) - t1[1][1]);
-        if (active) plane(1, 1, 1)[me] = t1[1][1];
-      }
-    }
-    __syncthreads();
-  }
-
-  // owned vertices: buffer columns [H, H + TW), rows [H, H + TH); H is even, so a block is owned as a whole
-  if (active && pi >= H / 2 && pi < (H + TW) / 2 && pj >= H / 2 && pj < (H + TH) / 2) {
-    double2 *dst = out + (size_t)b * Mt * Mx;
-    const size_t o0 = (size_t)(j0 + 2 * pj - H) * Mt + (i0 + 2 * pi - H);
-    dst[o0] = make_double2(t0[0][0], t1[0][0]);
-    dst[o0 + 1] = make_double2(t0[0][1], t1[0][1]);
-    dst[o0 + Mt] = make_double2(t0[1][0], t1[1][0]);
-    dst[o0 + Mt + 1] = make_double2(t0[1][1], t1[1][1]);
-  }
-}
-
 // Experiment (-DMLMCPI_SKEW=n): the two workgroups a CU holds start together and stay in step -- both in their load / store
 // phases (HBM bound, issue slots idle), then both in their sweeps (issue bound, HBM idle).  Delaying the second workgroup
 // of every CU by n x 3.6 us at the start of the launch puts them half a period apart.
@@ -612,8 +371,8 @@ __global__ void __launch_bounds__(1024)
 #endif
 
 // ---- Schwinger overrelaxation, 4 x 4 register blocks on 64 x 64 tiles ------------------------------------------
-// The 2 x 2 kernel above recomputes (64 + 4K)(32 + 4K) / (64 * 32) = 1.875 x the owned updates at K = 4 and moves 24 B
-// through LDS per update.  Here a thread keeps a 4 x 4 block of vertices (32 link angles, 64 VGPRs) for all K sweeps and
+// A 2 x 2 block kernel on 64 x 32 tiles (retired; EXPERIMENTS 4.1) recomputes (64 + 4K)(32 + 4K) / (64 * 32) = 1.875 x
+// the owned updates at K = 4 and moves 24 B through LDS per update.  Here a thread keeps a 4 x 4 block of vertices (32 link angles, 64 VGPRs) for all K sweeps and
 // the tile is 64 x 64: redundancy (64 + 4K)^2 / 64^2 = 1.56 at K = 4 (1.72 at K = 5, which the 1024-thread limit of the
 // 2 x 2 kernel could not reach), and LDS holds only the 20 values per block that a neighbouring block reads:
 //   TOP0[a], TOP1[a]   both links of the top row        (read by the block above as its row -1)
@@ -623,10 +382,10 @@ __global__ void __launch_bounds__(1024)
 // with the four corner values that belong to two of these lists stored once.  Per sweep a thread reads 32 and writes
 // 20 doubles for its 32 updates (13 B per update).  Planes are [value][block], so consecutive lanes touch consecutive
 // doubles.  Same updates in the same colour order with the same arithmetic as every other overrelaxation kernel here:
-// bit-identical results.  Block edges of the buffer read clamped neighbours, as in the 2 x 2 kernel: what they compute
+// bit-identical results.  Block edges of the buffer read clamped neighbours: what they compute
 // is wrong, and never reaches the owned tile (the exact region shrinks by 2 sites per sweep from a halo of 2K).
 //
-// Measured on MI355X (1024 x 1024, 32 chains; tools/exp_or_block.py, timestamps taken inside the kernel): a sweep costs
+// Measured on MI355X (1024 x 1024, 32 chains; timestamps taken inside the kernel): a sweep costs
 // 0.028 ms of the launch, which is the fp64 issue time of its 9 instructions per update, and the rest of the launch
 // (0.21 ms at K = 1, against 0.17 ms for a plain copy of the state) is the load and store phase of the workgroups,
 // which the two workgroups a CU holds overlap only partly with each other's sweeps.  Persistent workgroups and an
@@ -838,7 +597,7 @@ __global__ void __launch_bounds__(OrBlockGeom<K>::NT)
   }
 }
 
-// The tail shared by schwinger_or_heat_kernel and schwinger_perm_heat_kernel: the heat-bath sweep on the LDS image of a
+// The tail of schwinger_perm_heat_kernel: the heat-bath sweep on the LDS image of a
 // 64 x 64 tile and its two rings (theta_0 plane th0, theta_1 plane th1, IW = IH = 68), the optional QoI, the write-out.
 template <int NT, bool STEP>
 __device__ __forceinline__ void schwinger_image_heat(double *th0, double *th1, VsPool<uint32_t> &vpool, HbPool &hpool, uint32_t Mt,
@@ -1021,85 +780,29 @@ __device__ __forceinline__ void schwinger_image_heat(double *th0, double *th1, V
   MLMCPI_STAMP(9);
 }
 
-// ---- Schwinger: K overrelaxation sweeps and the heat-bath sweep behind them in one launch ------------------------------
+// ---- Schwinger: the heat-bath sweep on an LDS image, behind the overrelaxation sweeps of the same launch ------------------
 // A draw ends "... K overrelaxation sweeps, heat bath, QoI".  As two launches the state makes two round trips through HBM,
 // and the two kernels leave opposite halves of the CU idle: the overrelaxation launch is bound by its load / store phases
-// and the latencies of its colour phases (vector issue 0.44), the heat bath by vector issue (0.88) with its memory
-// traffic hidden.  Here the workgroup that has just swept a tile K times in registers (or_block_sweeps on the geometry
-// with halo 2K + 2, i.e. OrBlockGeom<K + 1>) lays the tile and the two rings the heat bath reads down as an LDS image (the
-// plane area is dead by then, and large enough), runs the heat-bath sweep of schwinger_sweep_kernel<true, ., 64, 32, true>
-// on it -- same regions (the pruned last-sweep form), same cells, same Philox words, same arithmetic: bit-identical
-// results -- sums the QoI and writes the tile out.  One round trip instead of two, and the two workgroups of a CU are in
-// different phases most of the time: the loads of one run under the sampler arithmetic of the other.
-// Step-envelope sampler only (2 beta <= kVsKappaMax); lattices of at least 128 x 128 that 64 x 64 tiles divide.
-template <int K>
-struct OrHeatGeom {
-  using G = OrBlockGeom<K + 1>;
-  static constexpr int NT = G::NT, HB = 2, IW = G::TW + 2 * HB, IH = G::TH + 2 * HB;
+// and the latencies of its colour phases, the heat bath by vector issue with its memory traffic hidden.  In one launch
+// (schwinger_perm_heat_kernel) the workgroup that has just swept a tile K times lays the tile and the two rings the heat
+// bath reads down as an LDS image, runs the heat-bath sweep of schwinger_sweep_kernel<true, ., 64, 32, true> on it
+// (schwinger_image_heat) -- same regions (the pruned last-sweep form), same cells, same Philox words, same arithmetic:
+// bit-identical results -- sums the QoI and writes the tile out.  One round trip instead of two, and the two workgroups of
+// a CU are in different phases most of the time: the loads of one run under the sampler arithmetic of the other.
+// This struct holds the sizes of that image (a 64 x 64 tile and two rings) and of the sampler's list in front of it.
+struct HeatImageGeom {
+  static constexpr int HB = 2, IW = 64 + 2 * HB, IH = 64 + 2 * HB;
   static constexpr size_t image_bytes = (size_t)2 * IW * IH * sizeof(double);
   // in front of the image: the sampler's tables and the list of open cells -- a colour phase leaves about 5 % of its ~2200
   // cells on it at beta = 1 (110 entries on average; a list that overflows leaves cells to their own lanes, measured at
   // +20 % on the launch with 64 entries)
-  static constexpr uint32_t pool_cap = 544, hb_pool_cap = 128;   // step-envelope list (r05: 256 -> 544 for concentrations up to 16: a phase leaves up to a fifth of its ~2200 cells there; as many entries as the register-block geometry's LDS bound below admits); wrapped-Cauchy pool (24 B per entry)
-  static constexpr size_t pool_bytes_of(size_t a, size_t b) { return ((a > b ? a : b) + 15) / 16 * 16; }
-  static constexpr size_t pool_bytes = pool_bytes_of(VsPool<uint32_t>::bytes(pool_cap), HbPool::bytes(hb_pool_cap));
+  static constexpr uint32_t pool_cap = 544, hb_pool_cap = 128;   // step-envelope list (r05: 256 -> 544 for concentrations up to 16: a phase leaves up to a fifth of its ~2200 cells there); wrapped-Cauchy pool (24 B per entry)
+  static constexpr size_t vs_pool_bytes = VsPool<uint32_t>::bytes(pool_cap), hb_pool_bytes = HbPool::bytes(hb_pool_cap);
+  static constexpr size_t pool_bytes = ((vs_pool_bytes > hb_pool_bytes ? vs_pool_bytes : hb_pool_bytes) + 15) / 16 * 16;
   static constexpr size_t hb_bytes = image_bytes + pool_bytes;
+  static_assert(image_bytes == 73984 && pool_bytes == 3424 && hb_bytes == 77408, "LDS layout of the fused launch");
   static_assert(hb_bytes <= OrBlockGeom<6>::lds_bytes, "two workgroups per CU");
-  static constexpr size_t lds_bytes = G::lds_bytes > hb_bytes ? G::lds_bytes : hb_bytes;
 };
-
-// WIDE: 1024 threads per workgroup, for launches with at most one workgroup per CU (few chains): the register-block part
-// runs on the first OrHeatGeom<K>::NT threads as before, the heat-bath part on all sixteen waves.
-// STEP = false (r04): the heat-bath part draws from the wrapped-Cauchy envelope (heatbath_region, as
-// schwinger_sweep_kernel<true, ., 64, 32, false> does): actions beyond 2 beta = kVsKappaMax get the fused launch too.
-template <int K, bool WIDE = false, bool STEP = true>
-__global__ void __launch_bounds__(WIDE ? 1024 : OrHeatGeom<K>::NT, 4)
-    schwinger_or_heat_kernel(uint32_t Mt, uint32_t Mx, double beta, const double2 *__restrict__ in, double2 *__restrict__ out,
-                             uint32_t tiles_x, RngKey key0, int qoi_op, double *__restrict__ qoi_partial,
-                             const uint32_t *__restrict__ vs_table) {
-  using OH = OrHeatGeom<K>;
-  using G = typename OH::G;
-  constexpr int NT = WIDE ? 1024 : OH::NT, TW = G::TW, TH = G::TH, PW = G::PW, PH = G::PH, H = G::H, NPX = G::NPX, NP = G::NP;
-  constexpr int HB = OH::HB, IW = OH::IW, IH = OH::IH, O = H - HB;  // image (0, 0) = buffer (O, O)
-  extern __shared__ double lds[];
-  __shared__ double qoi_red[NT / kWave];
-  const uint32_t tile = blockIdx.x, b = blockIdx.y, tid = threadIdx.x;
-  const uint32_t ty = tile / tiles_x, tx = tile - ty * tiles_x;
-  const uint32_t i0 = tx * TW, j0 = ty * TH;
-  double t0[PH][PW], t1[PH][PW];
-  MLMCPI_STAMP(0);
-  MLMCPI_STAMP_WHERE();
-  MLMCPI_SKEW_START();
-  or_block_sweeps<G, K>(lds, in + (size_t)b * Mt * Mx, Mt, Mx, i0, j0, t0, t1);
-  MLMCPI_STAMP(3);  // K sweeps done
-
-  // The sampler's tables, round counters and retry pool at the START of the LDS (their addresses are then instruction
-  // offsets: a table look-up costs no address arithmetic beyond its index), the image behind them: theta_0 and theta_1
-  // planes of IH x IW vertices; every block that reaches into it puts its part down
-  VsPool<uint32_t> vpool = VsPool<uint32_t>::carve(lds, OH::pool_cap, STEP ? vs_table : nullptr);
-  HbPool hpool = HbPool::carve(lds, STEP ? 0u : OH::hb_pool_cap);
-  double *th0 = lds + OH::pool_bytes / sizeof(double), *th1 = th0 + IW * IH;
-  if (tid < NP) {
-    const int pj = (int)tid / NPX, pi = (int)tid - pj * NPX;
-#pragma unroll
-    for (int c = 0; c < PH; ++c) {
-      const int r = PH * pj + c - O;
-      if (r < 0 || r >= IH) continue;
-#pragma unroll
-      for (int a = 0; a < PW; ++a) {
-        const int q = PW * pi + a - O;
-        if (q >= 0 && q < IW) {
-          th0[r * IW + q] = t0[c][a];
-          th1[r * IW + q] = t1[c][a];
-        }
-      }
-    }
-  }
-  __syncthreads();
-  MLMCPI_STAMP(4);  // image down
-
-  schwinger_image_heat<NT, STEP>(th0, th1, vpool, hpool, Mt, Mx, beta, out, i0, j0, b, tile, key0, qoi_op, qoi_partial, qoi_red);
-}
 
 // ---- Schwinger overrelaxation in closed form: K sweeps are a fixed permutation of the plaquettes -----------------------
 // With P(i, j) = theta_0(i, j) + theta_1(i+1, j) - theta_0(i, j+1) - theta_1(i, j) the two staple sums of the mu = 0 link at
@@ -1451,7 +1154,7 @@ __device__ __forceinline__ void perm_sweeps(double *plane, const double2 *__rest
   // what K sweeps add to them
   auto gather = [&](int h, double2 (&d)[NV]) {
     const uint32_t row_off = 2 * K + (NB == 2 ? 0 : h * HR);  // plane row of output row 0 of this half (even)
-    const uint32_t lds0 = (uint32_t)(uintptr_t)plane;   // the LDS byte address of the plane (see schwinger_or_kernel)
+    const uint32_t lds0 = (uint32_t)(uintptr_t)plane;   // the LDS byte address of the plane (lds_read_f64)
 #pragma unroll
     for (int k = 0; k < NV; ++k) {
       if (!tasks.valid(k)) continue;
@@ -1623,13 +1326,13 @@ __global__ void __launch_bounds__(512, 4)
   }
 }
 
-// K overrelaxation sweeps in closed form, then the heat-bath sweep, the QoI and the write-out of schwinger_or_heat_kernel
-// (the same tail, schwinger_image_heat): the whole draw of the reference's sampler (10 + 1 sweeps) is ONE launch with one
+// K overrelaxation sweeps in closed form, then the heat-bath sweep, the QoI and the write-out on the LDS image
+// (schwinger_image_heat, HeatImageGeom): the whole draw of the reference's sampler (10 + 1 sweeps) is ONE launch with one
 // round trip of the state through HBM.  LDS: tables + list | the plane, then the image in the same place.
 template <int NT, bool STEP>
 struct PermHeatGeom {
   using PG = PermGeom<NT, 2>;
-  using OH = OrHeatGeom<1>;  // (pool and image sizes do not depend on K)
+  using OH = HeatImageGeom;
   static constexpr size_t lds_bytes(uint32_t K, uint32_t NB) {
     return OH::pool_bytes + (PG::plane_bytes(K, NB) > OH::image_bytes ? PG::plane_bytes(K, NB) : OH::image_bytes);
   }
@@ -1812,156 +1515,12 @@ __global__ void __launch_bounds__(NT)
   }
 }
 
-// ---- GFF overrelaxation, specialised --------------------------------------------------------------------
-// Compile-time tile geometry, per-thread cell offsets computed once, immediate neighbour offsets:
-// bit-identical to gff_sweep_kernel<false, 256> (same colour order and update regions).  The update is
-// 4 adds and one fused multiply-add, so anything per-update besides the LDS traffic matters.
-template <int TW, int TH, int K, int NT>
-__global__ void __launch_bounds__(NT)
-    gff_or_kernel(uint32_t Mt, uint32_t Mx, double mu2, const double *__restrict__ in, double *__restrict__ out,
-                  uint32_t tiles_x) {
-  constexpr int H = 2 * K, BW = TW + 2 * H, BH = TH + 2 * H, P = BW + 1;
-  constexpr int NRR = BH - 2, NCC = (BW - 2) / 2, T = NRR * NCC, M = (T + NT - 1) / NT;
-  extern __shared__ double lds[];
-  double *phi = lds;
-  const uint32_t lds0 = (uint32_t)(uintptr_t)lds;  // see schwinger_or_kernel
-  const uint32_t tile = blockIdx.x, b = blockIdx.y, tid = threadIdx.x;
-  const uint32_t ty = tile / tiles_x, tx = tile - ty * tiles_x;
-  const uint32_t i0 = tx * TW, j0 = ty * TH;
-  const uint32_t sc = (uint32_t)(((uint64_t)i0 + Mt - (H % Mt)) % Mt);
-  const uint32_t sr = (uint32_t)(((uint64_t)j0 + Mx - (H % Mx)) % Mx);
-  const double *src = in + (size_t)b * Mt * Mx;
-  const double two_over_kappa = 2. / (4. + mu2);
-
-  stage_region<NT, 5, double>(
-      BH, BW, [&](uint32_t r, uint32_t c) { return src[(size_t)wrap_add(sr, r, Mx) * Mt + wrap_add(sc, c, Mt)]; },
-      [&](uint32_t r, uint32_t c, double v) { phi[r * P + c] = v; });
-
-  // cell (r, c) of colour 0: r = 1 + ri, c = 1 + ((r + 1) & 1) + 2 ci; colour 1: the other cell of the pair
-  int o0[M], o1[M];
-#pragma unroll
-  for (int m = 0; m < M; ++m) {
-    const int idx = tid + NT * m, ri = idx / NCC, ci = idx - ri * NCC, r = 1 + ri;
-    o0[m] = r * P + 1 + ((r + 1) & 1) + 2 * ci;
-    o1[m] = r * P + 1 + (r & 1) + 2 * ci;
-  }
-  __syncthreads();
-
-  for (int s = 0; s < K; ++s) {
-#pragma unroll
-    for (int colour = 0; colour < 2; ++colour) {
-#pragma unroll
-      for (int m = 0; m < M; ++m) {
-        if ((m + 1) * NT <= T || (int)tid + NT * m < T) {
-          const int o = colour ? o1[m] : o0[m];
-          const uint32_t a = lds0 + (uint32_t)(o - P) * 8u;  // LDS byte address of the cell below
-          double dn = lds_read_f64<0>(a), lf = lds_read_f64<(P - 1) * 8>(a), own = lds_read_f64<P * 8>(a);
-          double rt = lds_read_f64<(P + 1) * 8>(a), up = lds_read_f64<2 * P * 8>(a), pad0 = 0.0, pad1 = 0.0;
-          lds_wait7(dn, lf, own, rt, up, pad0, pad1);
-          double Delta = 0.0;
-          Delta += rt;
-          Delta += lf;
-          Delta += up;
-          Delta += dn;
-          phi[o] = fma(two_over_kappa, Delta, -own);  // 2 Delta / kappa - phi, without the fp64 division
-        }
-      }
-      __syncthreads();
-    }
-  }
-
-  double *dst = out + (size_t)b * Mt * Mx;
-  for_region<NT>(TH, TW, [&](uint32_t r, uint32_t c) { dst[(size_t)(j0 + r) * Mt + (i0 + c)] = phi[(r + H) * P + (c + H)]; });
-}
-
-// ---- GFF overrelaxation, register-tiled ---------------------------------------------------------------------------
-// Same idea as schwinger_or_patch_kernel: a thread keeps a 2 x 2 block of sites in registers for all K sweeps and LDS
-// (four structure-of-arrays planes [row parity][column parity] over blocks) carries only the values that cross block
-// boundaries: 4 reads + 2 writes per colour phase for 2 updates (24 B per update; gff_or_kernel moves 48 B).  Same
-// updates, colour order and summation order (+i, -i, +j, -j): bit-identical to the kernels above.
-template <int K>
-__global__ void __launch_bounds__(1024)
-    gff_or_patch_kernel(uint32_t Mt, uint32_t Mx, double mu2, const double *__restrict__ in, double *__restrict__ out,
-                        uint32_t tiles_x) {
-  constexpr int TW = 64, TH = 32, H = 2 * K, BW = TW + 2 * H, BH = TH + 2 * H, NPX = BW / 2, NPY = BH / 2;
-  constexpr int NP = NPX * NPY;
-  static_assert(NP <= 1024, "one 2 x 2 block per thread");
-  extern __shared__ double lds[];
-  auto plane = [&](int c, int a) { return lds + (c * 2 + a) * NP; };  // site (2 pi + a, 2 pj + c)
-  const uint32_t tile = blockIdx.x, b = blockIdx.y, tid = threadIdx.x;
-  const uint32_t ty = tile / tiles_x, tx = tile - ty * tiles_x;
-  const uint32_t i0 = tx * TW, j0 = ty * TH;
-  const bool active = tid < NP;
-  const int pj = active ? (int)tid / NPX : 0, pi = active ? (int)tid - pj * NPX : 0;
-  const double *src = in + (size_t)b * Mt * Mx;
-  const double two_over_kappa = 2. / (4. + mu2);
-  const uint32_t gi = (uint32_t)(((uint64_t)i0 + Mt - (H % Mt) + 2 * pi) % Mt);
-  const uint32_t gj0 = (uint32_t)(((uint64_t)j0 + Mx - (H % Mx) + 2 * pj) % Mx);
-  const uint32_t gj1 = gj0 + 1 == Mx ? 0 : gj0 + 1;
-  double p[2][2] = {{0, 0}, {0, 0}};  // [c][a]
-  if (active) {
-    const double2 lo = *(const double2 *)(src + (size_t)gj0 * Mt + gi), hi = *(const double2 *)(src + (size_t)gj1 * Mt + gi);
-    p[0][0] = lo.x; p[0][1] = lo.y; p[1][0] = hi.x; p[1][1] = hi.y;
-#pragma unroll
-    for (int c = 0; c < 2; ++c)
-#pragma unroll
-      for (int a = 0; a < 2; ++a) plane(c, a)[tid] = p[c][a];
-  }
-  const int me = active ? (int)tid : 0;  // idle threads of the last wave: every index is entry 0, nothing is written
-  const int dn = pj > 0 ? me - NPX : me, up = pj + 1 < NPY ? me + NPX : me;
-  const int lf = pi > 0 ? me - 1 : me, rt = pi + 1 < NPX ? me + 1 : me;
-  // sites on the buffer edge are updated from clamped neighbours instead of being left alone: see
-  // schwinger_or_patch_kernel (their values never reach the owned tile)
-  __syncthreads();
-
-  for (int s = 0; s < K; ++s) {
-    // colour 0: sites (a, c) = (0, 0) and (1, 1)
-    // (no predicate and no zero fill in the loop: idle threads read entry 0 and compute on zeros)
-    double e_lf = plane(0, 1)[lf], e_dn = plane(1, 0)[dn], e_rt = plane(1, 0)[rt], e_up = plane(0, 1)[up];
-    {
-      double Delta = 0.0;
-      Delta += p[0][1]; Delta += e_lf; Delta += p[1][0]; Delta += e_dn;
-      p[0][0] = fma(two_over_kappa, Delta, -p[0][0]);
-      if (active) plane(0, 0)[me] = p[0][0];
-    }
-    {
-      double Delta = 0.0;
-      Delta += e_rt; Delta += p[1][0]; Delta += e_up; Delta += p[0][1];
-      p[1][1] = fma(two_over_kappa, Delta, -p[1][1]);
-      if (active) plane(1, 1)[me] = p[1][1];
-    }
-    __syncthreads();
-    // colour 1: sites (1, 0) and (0, 1)
-    e_rt = plane(0, 0)[rt]; e_dn = plane(1, 1)[dn]; e_lf = plane(1, 1)[lf]; e_up = plane(0, 0)[up];
-    {
-      double Delta = 0.0;
-      Delta += e_rt; Delta += p[0][0]; Delta += p[1][1]; Delta += e_dn;
-      p[0][1] = fma(two_over_kappa, Delta, -p[0][1]);
-      if (active) plane(0, 1)[me] = p[0][1];
-    }
-    {
-      double Delta = 0.0;
-      Delta += p[1][1]; Delta += e_lf; Delta += e_up; Delta += p[0][0];
-      p[1][0] = fma(two_over_kappa, Delta, -p[1][0]);
-      if (active) plane(1, 0)[me] = p[1][0];
-    }
-    __syncthreads();
-  }
-
-  if (active && pi >= H / 2 && pi < (H + TW) / 2 && pj >= H / 2 && pj < (H + TH) / 2) {
-    double *dst = out + (size_t)b * Mt * Mx;
-    const size_t o0 = (size_t)(j0 + 2 * pj - H) * Mt + (i0 + 2 * pi - H);
-    *(double2 *)(dst + o0) = make_double2(p[0][0], p[0][1]);
-    *(double2 *)(dst + o0 + Mt) = make_double2(p[1][0], p[1][1]);
-  }
-}
-
 // ---- GFF overrelaxation, 4 x 4 register blocks on 64 x 64 tiles ------------------------------------------------
 // The construction of schwinger_or_block_kernel for the scalar field: a thread keeps 16 sites for all K sweeps, LDS
 // carries the 12 sites on the rim of each block (TOP[a], BOT[a], LEFT[c], RIGHT[c], corners once), a colour phase reads
 // the 8 neighbour values across the block's edges that belong to the other colour.  Redundancy (64 + 4K)^2 / 64^2
 // (1.72 at K = 5) instead of 1.875 at K = 4 on 64 x 32 tiles, 1.75 LDS accesses per update instead of 3, three
-// workgroups per CU.  Same sums in the same order as gff_or_patch_kernel: bit-identical.
+// workgroups per CU.  Same sums in the same order as gff_sweep_kernel: bit-identical.
 // T: tile extent.  64 is the default; 32 x 32 tiles (r04) serve the lattices 64 x 64 tiles do not divide or that are too
 // small for the fused launch (96 x 96: 339 -> see DESIGN 7, fast_path_cliff) -- the halo recomputation is 2.6 x at K = 5
 // instead of 1.7 x, but the launches are bound by their passes over the state, not by the sweeps.
@@ -2106,7 +1665,7 @@ __global__ void __launch_bounds__((GffBlockGeom<K, T>::NT))
 }
 
 // ---- GFF: K overrelaxation sweeps and the heat-bath sweep behind them in one launch ----------------------------------
-// The construction of schwinger_or_heat_kernel for the scalar field: gff_block_sweeps on the geometry with halo 2K + 2,
+// The construction of schwinger_perm_heat_kernel (HeatImageGeom) for the scalar field: gff_block_sweeps on the geometry with halo 2K + 2,
 // then the field on the tile and two rings as an LDS image (with the plane of parked Box-Muller partners behind it), the
 // heat-bath sweep of gff_sweep_kernel<true, 256, 64, 32> in its pruned last-sweep form -- same cells, same Philox
 // words, same arithmetic: bit-identical -- the phi^2 sum and the write-out.  The second normal of a Box-Muller pair is
@@ -2792,6 +2351,20 @@ static int allow_full_lds() {
   return MLMCPI_OK;
 }
 
+// f(std::integral_constant<int, K>()) with the compile-time depth K = min(n, KMAX), n >= 1: one instantiation per depth
+template <int KMAX, int K = 1, class F>
+static int with_depth(uint32_t n, F &&f) {
+  if constexpr (K < KMAX) {
+    if (n > (uint32_t)K) return with_depth<KMAX, K + 1>(n, f);
+  }
+  return f(std::integral_constant<int, K>());
+}
+
+static int allow_lds(const void *kernel, size_t bytes) {
+  MLMCPI_HIP_TRY(hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes));
+  return MLMCPI_OK;
+}
+
 // hipFuncSetAttribute applies to the current device: once per device, under a lock (one process may drive several GPUs)
 static std::mutex g_lds_attr_mutex;
 static bool g_lds_attr_set[64] = {false};
@@ -2807,28 +2380,21 @@ static int init_sweep_kernels() {
   if (int rc = allow_full_lds<true, 512>()) return rc;
   if (int rc = allow_full_lds<false, 1024>()) return rc;
   if (int rc = allow_full_lds<true, 1024>()) return rc;
-  // specialised overrelaxation kernels whose LDS image exceeds the 64 KiB default (K = 5, 6)
-#define MLMCPI_OR_ATTR(KK, NN) MLMCPI_HIP_TRY(hipFuncSetAttribute((const void *)schwinger_or_kernel<64, 32, KK, NN>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024))
-  MLMCPI_OR_ATTR(5, 256); MLMCPI_OR_ATTR(5, 512); MLMCPI_OR_ATTR(5, 1024);
-  MLMCPI_OR_ATTR(6, 256); MLMCPI_OR_ATTR(6, 512); MLMCPI_OR_ATTR(6, 1024);
-#undef MLMCPI_OR_ATTR
-  MLMCPI_HIP_TRY(hipFuncSetAttribute((const void *)schwinger_or_block_kernel<5>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)OrBlockGeom<5>::lds_bytes));
-  MLMCPI_HIP_TRY(hipFuncSetAttribute((const void *)schwinger_or_block_kernel<6>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)OrBlockGeom<6>::lds_bytes));
-#define MLMCPI_OR_HEAT_ATTR(KK) \
-  MLMCPI_HIP_TRY(hipFuncSetAttribute((const void *)schwinger_or_heat_kernel<KK, false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)OrHeatGeom<KK>::lds_bytes)); \
-  MLMCPI_HIP_TRY(hipFuncSetAttribute((const void *)schwinger_or_heat_kernel<KK, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)OrHeatGeom<KK>::lds_bytes)); \
-  MLMCPI_HIP_TRY(hipFuncSetAttribute((const void *)schwinger_or_heat_kernel<KK, false, false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)OrHeatGeom<KK>::lds_bytes)); \
-  MLMCPI_HIP_TRY(hipFuncSetAttribute((const void *)gff_or_heat_kernel<KK>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)GffHeatGeom<KK>::lds_bytes))
-  MLMCPI_OR_HEAT_ATTR(1); MLMCPI_OR_HEAT_ATTR(2); MLMCPI_OR_HEAT_ATTR(3); MLMCPI_OR_HEAT_ATTR(4); MLMCPI_OR_HEAT_ATTR(5);
-#undef MLMCPI_OR_HEAT_ATTR
-#define MLMCPI_OR_HEAT_ATTR_W(KK) MLMCPI_HIP_TRY(hipFuncSetAttribute((const void *)schwinger_or_heat_kernel<KK, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)OrHeatGeom<KK>::lds_bytes))
-  MLMCPI_OR_HEAT_ATTR_W(6); MLMCPI_OR_HEAT_ATTR_W(7); MLMCPI_OR_HEAT_ATTR_W(8); MLMCPI_OR_HEAT_ATTR_W(9); MLMCPI_OR_HEAT_ATTR_W(10);
-#undef MLMCPI_OR_HEAT_ATTR_W
-  MLMCPI_HIP_TRY(hipFuncSetAttribute((const void *)schwinger_perm_kernel<64>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kPermPlaneMax));
-  MLMCPI_HIP_TRY(hipFuncSetAttribute((const void *)schwinger_perm_kernel<32>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kPermPlaneMax));
-#define MLMCPI_PERM_HEAT_ATTR(NN, SS) MLMCPI_HIP_TRY(hipFuncSetAttribute((const void *)schwinger_perm_heat_kernel<NN, SS>, hipFuncAttributeMaxDynamicSharedMemorySize, NN == 1024 ? 156 * 1024 : (int)OrHeatGeom<1>::hb_bytes))
-  MLMCPI_PERM_HEAT_ATTR(512, true); MLMCPI_PERM_HEAT_ATTR(512, false); MLMCPI_PERM_HEAT_ATTR(1024, true); MLMCPI_PERM_HEAT_ATTR(1024, false);
-#undef MLMCPI_PERM_HEAT_ATTR
+  // kernels whose LDS may exceed the 64 KiB default
+  if (int rc = allow_lds((const void *)schwinger_or_block_kernel<5>, OrBlockGeom<5>::lds_bytes)) return rc;
+  if (int rc = allow_lds((const void *)schwinger_or_block_kernel<6>, OrBlockGeom<6>::lds_bytes)) return rc;
+  for (uint32_t k = 1; k <= 5; ++k)
+    if (int rc = with_depth<5>(k, [](auto kc) {
+          constexpr int K = decltype(kc)::value;
+          return allow_lds((const void *)gff_or_heat_kernel<K>, GffHeatGeom<K>::lds_bytes);
+        }))
+      return rc;
+  if (int rc = allow_lds((const void *)schwinger_perm_kernel<64>, kPermPlaneMax)) return rc;
+  if (int rc = allow_lds((const void *)schwinger_perm_kernel<32>, kPermPlaneMax)) return rc;
+  if (int rc = allow_lds((const void *)schwinger_perm_heat_kernel<512, true>, HeatImageGeom::hb_bytes)) return rc;
+  if (int rc = allow_lds((const void *)schwinger_perm_heat_kernel<512, false>, HeatImageGeom::hb_bytes)) return rc;
+  if (int rc = allow_lds((const void *)schwinger_perm_heat_kernel<1024, true>, 156 * 1024)) return rc;
+  if (int rc = allow_lds((const void *)schwinger_perm_heat_kernel<1024, false>, 156 * 1024)) return rc;
   g_lds_attr_set[dev] = true;
   return MLMCPI_OK;
 }
@@ -2906,55 +2472,124 @@ static int sweep_draw_impl(const mlmcpi_lattice_action *act, double *d_phi, doub
   MLMCPI_REQUIRE(d_phi && d_w0 && d_w1 && d_phi != d_w0 && d_w0 != d_w1 && B > 0, "bad arguments");
   MLMCPI_REQUIRE(act->Mt % 2 == 0 && act->Mx % 2 == 0, "multicolour sweeps need even Mt, Mx (got %u x %u)", act->Mt,
                  act->Mx);
-  // library default: best measured whole-step time (DESIGN.md section 7) -- up to 6 sweeps per launch where the 4 x 4
-  // register-block kernel applies, 4 otherwise
+  const uint32_t Mt = act->Mt, Mx = act->Mx;
   const Tuning tune = tuning();  // ONE snapshot per draw: mlmcpi_set_option on another thread cannot split a launch plan
-  const bool or_blocks = !tune.or_lds && !tune.or_patch && !tune.tile_w && act->Mt % 64 == 0 && act->Mx % 64 == 0;
   const bool schw = act->kind == MLMCPI_SCHWINGER;
+  // 4 x 4 register-block overrelaxation on 64 x 64 tiles where they divide the lattice: the GFF default; for the Schwinger
+  // action the sweep-by-sweep plan (MLMCPI_OR_KERNEL=block, lattices the closed form does not take)
+  const bool or_blocks = !tune.tile_w && Mt % 64 == 0 && Mx % 64 == 0;
   // GFF lattices that 32 x 32 tiles divide and 64 x 64 ones do not (or that are below 128, where the 64-tile fused launch
   // does not apply): the register-block kernels on 32 x 32 tiles, same launch plan
   // (r05: also lattices no tile divides -- edge tiles computed whole and written in part -- unless the padding would more
   // than double the work)
-  const uint32_t g32_tx = (act->Mt + 31) / 32, g32_ty = (act->Mx + 31) / 32;
-  const bool gff_blocks32 = !schw && !tune.or_lds && !tune.or_patch && !tune.tile_w && act->Mt >= 64 && act->Mx >= 64 &&
-                            !(or_blocks && act->Mt >= 128 && act->Mx >= 128) &&
-                            (uint64_t)g32_tx * g32_ty * 1024 <= (uint64_t)2 * act->Mt * act->Mx + (uint64_t)act->Mt * act->Mx / 5;
-  // One chain (at most one workgroup of the fused launch per CU: nothing to overlap a second launch's load and store
-  // phases with): the whole draw in ONE launch of schwinger_or_heat_kernel<n_overrelax, wide> while its halo fits a
-  // workgroup (n_overrelax <= 10) -- the library default only; a caller's `fuse` is kept.
-  const bool whole_draw = fuse == 0 && schw && or_blocks && !tune.or_heat_split && tune.or_heat_wide >= 0 && n_heatbath >= 1 &&
-                          n_overrelax >= 6 && n_overrelax <= 10 && 2. * act->beta <= kVsKappaMax && act->Mt >= 128 && act->Mx >= 128 &&
-                          (uint64_t)(act->Mt / 64) * (act->Mx / 64) * B <= kComputeUnits;
-  // Schwinger overrelaxation in closed form (schwinger_perm_kernel, schwinger_perm_heat_kernel): the default where 64 x 64
-  // tiles divide the lattice; MLMCPI_OR_KERNEL=block|patch|lds select the sweep-by-sweep kernels
+  const uint32_t g32_tx = (Mt + 31) / 32, g32_ty = (Mx + 31) / 32;
+  const bool gff_blocks32 = !schw && !tune.tile_w && Mt >= 64 && Mx >= 64 && !(or_blocks && Mt >= 128 && Mx >= 128) &&
+                            (uint64_t)g32_tx * g32_ty * 1024 <= (uint64_t)2 * Mt * Mx + (uint64_t)Mt * Mx / 5;
+  // the GFF register-block tile (0: the generic kernels); 64 only on lattices of at least 128 x 128 (else gff_blocks32)
+  const int gff_T = schw ? 0 : gff_blocks32 ? 32 : or_blocks ? 64 : 0;
+  // Schwinger overrelaxation in closed form (schwinger_perm_kernel, schwinger_perm_heat_kernel): the default;
+  // MLMCPI_OR_KERNEL=block selects the sweep-by-sweep kernels
   // r05: any even lattice of at least one tile.  Tiles on the upper / right edge of a lattice the tiles do not divide reach
   // beyond it; what lies there are periodic images of vertices other tiles own (the plane wraps as often as needed):
   // computed like any halo, not written.  64 x 64 tiles where they divide Mx and wherever the fused launch applies (both
   // extents >= 128: its image must not wrap onto itself), else 64 x 32 (the heat bath is then a launch of its own);
   // lattices that would more than double the work through padding stay with the sweep-by-sweep kernels.
-  const bool perm_shape = schw && act->Mt >= 64 && act->Mx >= 32 && (uint64_t)act->Mt * act->Mx < (1ull << 28);   // (32-bit byte offsets)
-  const bool perm64 = perm_shape && (act->Mx % 64 == 0 || (act->Mt >= 128 && act->Mx >= 128));
-  const uint32_t perm_th = perm64 ? 64 : 32, perm_tx = (act->Mt + 63) / 64, perm_ty = (act->Mx + perm_th - 1) / perm_th;
-  const bool perm = perm_shape && !tune.or_block && !tune.or_lds && !tune.or_patch && !tune.tile_w &&
-                    (uint64_t)perm_tx * 64 * perm_ty * perm_th <= (uint64_t)2 * act->Mt * act->Mx + (uint64_t)act->Mt * act->Mx / 5;
+  const bool perm_shape = schw && Mt >= 64 && Mx >= 32 && (uint64_t)Mt * Mx < (1ull << 28);   // (32-bit byte offsets)
+  const bool perm64 = perm_shape && (Mx % 64 == 0 || (Mt >= 128 && Mx >= 128));
+  const uint32_t perm_th = perm64 ? 64 : 32, perm_tx = (Mt + 63) / 64, perm_ty = (Mx + perm_th - 1) / perm_th;
+  const bool perm = perm_shape && !tune.or_block && !tune.tile_w &&
+                    (uint64_t)perm_tx * 64 * perm_ty * perm_th <= (uint64_t)2 * Mt * Mx + (uint64_t)Mt * Mx / 5;
+  // library default: best measured whole-step time (DESIGN.md section 7) -- up to 6 sweeps per launch where the 4 x 4
+  // register-block kernels apply, 4 otherwise
   const uint32_t fuse_arg = fuse;
-  if (fuse == 0) fuse = whole_draw ? n_overrelax : (or_blocks || gff_blocks32) ? 6 : 4;
+  if (fuse == 0) fuse = (or_blocks || gff_blocks32) ? 6 : 4;
   if (fuse > kMaxFuse) fuse = kMaxFuse;
   hipStream_t st = as_stream(stream);
   const uint32_t total = n_overrelax + n_heatbath;
-  const size_t state_bytes = (size_t)B * act->Mt * act->Mx * (schw ? 16 : 8);
+  const size_t state_bytes = (size_t)B * Mt * Mx * (schw ? 16 : 8);
   if (int rc = init_sweep_kernels()) return rc;
   double *src = d_phi, *dst = d_w0;
   auto advance = [&]() {  // the buffer just written becomes the input; the next output is the other work buffer
     src = dst;
     dst = (dst == d_w0) ? d_w1 : d_w0;
   };
+  // A launch whose last sweep is the heat-bath sweep number h of the draw, `tiles` workgroups per chain:
+  // launch(key of sweep h, op, partial) sums the QoI into partial[b * tiles + tile] if that sweep ends the draw (op != 0),
+  // and this finishes the sum into d_qoi.
+  const int qoi_op = qoi_kind == 1 ? (int)L_PLAQ : qoi_kind == 2 ? (int)L_CHARGE : (int)L_PHI2;
+  auto heat_launch = [&](uint32_t h, uint32_t tiles, auto &&launch) -> int {
+    const bool with_qoi = qoi_kind && h + 1 == total;
+    void *partial = nullptr;
+    if (with_qoi)
+      if (int rc = scratch((size_t)B * tiles * sizeof(double), &partial, st)) return rc;
+    if (int rc = launch(make_key(seed, chain0, sweep0 + h), with_qoi ? qoi_op : 0, (double *)partial)) return rc;
+    if (with_qoi) {
+      hipLaunchKernelGGL(lattice_finish_kernel, dim3((B + 3) / 4), dim3(256), 0, st, (const double *)partial, tiles, B, qoi_op,
+                         1.0 / ((double)Mx * Mt), d_qoi, d_acc);
+      MLMCPI_LAUNCH_CHECK("lattice_finish_kernel");
+    }
+    return MLMCPI_OK;
+  };
   uint32_t s = 0;
   while (s < total) {
     // Overrelaxation sweeps are fused: they are bound by the passes over the state, and a fused launch trades halo
     // recomputation (cheap for them) for passes.  A heat-bath sweep is bound by its sampler arithmetic, which a wider halo
     // would only multiply: no sweep follows it inside a launch.  As the LAST sweep of an overrelaxation launch it needs no
-    // halo of its own beyond the two rings it reads (the *_or_heat_kernel branches below); otherwise it gets a launch to itself.
+    // halo of its own beyond the two rings it reads (schwinger_perm_heat_kernel, gff_or_heat_kernel); otherwise it gets a
+    // launch to itself.
+    const double2 *in2 = (const double2 *)src;
+    double2 *out2 = (double2 *)dst;
+    if (perm && s < n_overrelax) {
+      // as few launches as kPermMaxK (or the caller's `fuse`) allows, of equal depth
+      const uint32_t rem = n_overrelax - s, kmax = fuse_arg ? std::min(fuse_arg, kPermMaxK) : kPermMaxK;
+      const uint32_t launches = (rem + kmax - 1) / kmax, K = (rem + launches - 1) / launches;
+      const dim3 bgrid(perm_tx * perm_ty, B);
+      if (perm64 && !tune.or_heat_split && s + K == n_overrelax && n_heatbath >= 1 && Mt >= 128 && Mx >= 128) {
+        // the last overrelaxation launch takes the heat-bath sweep behind it along, and the QoI if that ends the draw
+        const bool step = 2. * act->beta <= kVsKappaMax;   // which sampler: a property of the action (device_common.hpp)
+        const uint32_t *vs_table = nullptr;
+        if (step)
+          if (int rc = vs_table_device(2. * act->beta, &vs_table)) return rc;
+        // at most one workgroup per CU: sixteen waves (MLMCPI_OR_HEAT=wide|narrow forces)
+        const bool wide = tune.or_heat_wide ? tune.or_heat_wide > 0 : (uint64_t)bgrid.x * B <= kComputeUnits;
+        using PHG = PermHeatGeom<512, true>;
+        // one plane for all 68 rows where it fits: beside a second workgroup (narrow) or in the whole LDS (wide)
+        const size_t lds_max = wide ? (size_t)156 * 1024 : HeatImageGeom::hb_bytes;
+        const uint32_t NB = PHG::lds_bytes(K, 1) <= lds_max ? 1 : 2;
+        const size_t lds = PHG::lds_bytes(K, NB);
+        if (lds > lds_max) return fail(MLMCPI_ERR_INVALID, "closed-form plane of %u sweeps does not fit", K);
+        if (int rc = heat_launch(s + K, bgrid.x, [&](RngKey hkey, int op, double *partial) -> int {
+              auto go = [&](auto nt, auto stp) -> int {
+                constexpr int NT = decltype(nt)::value;
+                hipLaunchKernelGGL((schwinger_perm_heat_kernel<NT, decltype(stp)::value>), bgrid, dim3(NT), lds, st, Mt, Mx,
+                                   act->beta, in2, out2, perm_tx, K, NB, hkey, op, partial, vs_table);
+                MLMCPI_LAUNCH_CHECK("schwinger_perm_heat_kernel");
+                return MLMCPI_OK;
+              };
+              using Wide = std::integral_constant<int, 1024>;
+              using Narrow = std::integral_constant<int, 512>;
+              return wide ? (step ? go(Wide(), std::true_type()) : go(Wide(), std::false_type()))
+                          : (step ? go(Narrow(), std::true_type()) : go(Narrow(), std::false_type()));
+            }))
+          return rc;
+        advance();
+        s += K + 1;
+        continue;
+      }
+      if (perm64) {
+        using PG0 = PermGeom<512, 0, 64>;
+        const uint32_t NB = PG0::plane_bytes(K, 1) <= kPermPlaneMax ? 1 : 2;
+        hipLaunchKernelGGL(schwinger_perm_kernel<64>, bgrid, dim3(512), perm_lds_bytes<64>(K, NB), st, Mt, Mx, in2, out2, perm_tx, K, NB);
+      } else {
+        using PG0 = PermGeom<512, 0, 32>;
+        const uint32_t NB = PG0::plane_bytes(K, 1) <= kPermPlaneMax ? 1 : 2;
+        hipLaunchKernelGGL(schwinger_perm_kernel<32>, bgrid, dim3(512), perm_lds_bytes<32>(K, NB), st, Mt, Mx, in2, out2, perm_tx, K, NB);
+      }
+      MLMCPI_LAUNCH_CHECK("schwinger_perm_kernel");
+      advance();
+      s += K;
+      continue;
+    }
     uint32_t n = 1;
     if (s < n_overrelax) {
       const uint32_t rem = n_overrelax - s;
@@ -2964,61 +2599,6 @@ static int sweep_draw_impl(const mlmcpi_lattice_action *act, double *d_phi, doub
         n = (rem + launches - 1) / launches;
       }
     }
-    if (perm && s < n_overrelax) {
-      // as few launches as kPermMaxK (or the caller's `fuse`) allows, of equal depth
-      const uint32_t rem = n_overrelax - s, kmax = fuse_arg ? std::min(fuse_arg, kPermMaxK) : kPermMaxK;
-      const uint32_t launches = (rem + kmax - 1) / kmax, K = (rem + launches - 1) / launches;
-      const dim3 bgrid(perm_tx * perm_ty, B);
-      const double2 *in2 = (const double2 *)src;
-      double2 *out2 = (double2 *)dst;
-      if (perm64 && !tune.or_heat_split && s + K == n_overrelax && n_heatbath >= 1 && act->Mt >= 128 && act->Mx >= 128) {
-        // the last overrelaxation launch takes the heat-bath sweep behind it along, and the QoI if that ends the draw
-        const bool step = 2. * act->beta <= kVsKappaMax;   // which sampler: a property of the action (device_common.hpp)
-        const uint32_t *vs_table = nullptr;
-        if (step)
-          if (int rcv = vs_table_device(2. * act->beta, &vs_table)) return rcv;
-        const bool with_qoi = qoi_kind && s + K + 1 == total;
-        void *partial = nullptr;
-        if (with_qoi)
-          if (int rcs = scratch((size_t)B * bgrid.x * sizeof(double), &partial, st)) return rcs;
-        const int op = !with_qoi ? 0 : qoi_kind == 1 ? (int)L_PLAQ : (int)L_CHARGE;
-        const RngKey hkey = make_key(seed, chain0, sweep0 + s + K);
-        // at most one workgroup per CU: sixteen waves (MLMCPI_OR_HEAT=wide|narrow forces)
-        const bool wide = tune.or_heat_wide ? tune.or_heat_wide > 0 : (uint64_t)bgrid.x * B <= kComputeUnits;
-        using PHG = PermHeatGeom<512, true>;
-        // one plane for all 68 rows where it fits: beside a second workgroup (narrow) or in the whole LDS (wide)
-        const size_t lds_max = wide ? (size_t)156 * 1024 : OrHeatGeom<1>::hb_bytes;
-        const uint32_t NB = PHG::lds_bytes(K, 1) <= lds_max ? 1 : 2;
-        const size_t lds = PHG::lds_bytes(K, NB);
-        if (lds > lds_max) return fail(MLMCPI_ERR_INVALID, "closed-form plane of %u sweeps does not fit", K);
-#define MLMCPI_PERM_HEAT(NN, SS) hipLaunchKernelGGL((schwinger_perm_heat_kernel<NN, SS>), bgrid, dim3(NN), lds, st, act->Mt, act->Mx, act->beta, in2, out2, perm_tx, K, NB, hkey, op, (double *)partial, vs_table)
-        if (wide) { if (step) MLMCPI_PERM_HEAT(1024, true); else MLMCPI_PERM_HEAT(1024, false); }
-        else { if (step) MLMCPI_PERM_HEAT(512, true); else MLMCPI_PERM_HEAT(512, false); }
-#undef MLMCPI_PERM_HEAT
-        MLMCPI_LAUNCH_CHECK("schwinger_perm_heat_kernel");
-        if (with_qoi) {
-          hipLaunchKernelGGL(lattice_finish_kernel, dim3((B + 3) / 4), dim3(256), 0, st, (const double *)partial, bgrid.x, B, op,
-                             1.0 / ((double)act->Mx * act->Mt), d_qoi, d_acc);
-          MLMCPI_LAUNCH_CHECK("lattice_finish_kernel");
-        }
-        advance();
-        s += K + 1;
-        continue;
-      }
-      if (perm64) {
-        using PG0 = PermGeom<512, 0, 64>;
-        const uint32_t NB = PG0::plane_bytes(K, 1) <= kPermPlaneMax ? 1 : 2;
-        hipLaunchKernelGGL(schwinger_perm_kernel<64>, bgrid, dim3(512), perm_lds_bytes<64>(K, NB), st, act->Mt, act->Mx, in2, out2, perm_tx, K, NB);
-      } else {
-        using PG0 = PermGeom<512, 0, 32>;
-        const uint32_t NB = PG0::plane_bytes(K, 1) <= kPermPlaneMax ? 1 : 2;
-        hipLaunchKernelGGL(schwinger_perm_kernel<32>, bgrid, dim3(512), perm_lds_bytes<32>(K, NB), st, act->Mt, act->Mx, in2, out2, perm_tx, K, NB);
-      }
-      MLMCPI_LAUNCH_CHECK("schwinger_perm_kernel");
-      advance();
-      s += K;
-      continue;
-    }
     SweepGeom g;
     uint32_t kinds = 0;
     for (;;) {  // shrink the fused count until the tile + halo fits in LDS
@@ -3026,249 +2606,66 @@ static int sweep_draw_impl(const mlmcpi_lattice_action *act, double *d_phi, doub
       for (uint32_t q = 0; q < n; ++q)
         if (s + q >= n_overrelax) kinds |= 1u << q;
       // Schwinger: two link angles per site; GFF heat bath: field + parked normal per site
-      g = choose_geometry(tune, act->Mt, act->Mx, n, (schw || kinds) ? 16 : 8);
+      g = choose_geometry(tune, Mt, Mx, n, (schw || kinds) ? 16 : 8);
       if (g.lds_bytes <= 160 * 1024 - 256 || n == 1) break;
       --n;
     }
-    const RngKey key = make_key(seed, chain0, sweep0 + s);
-    dim3 grid(g.tg.tiles_x * g.tiles_y, B);
+    const dim3 grid(g.tg.tiles_x * g.tiles_y, B);
+    uint32_t swept = n;
     int rc;
-    if (schw && !kinds && !g.overridden && act->Mt % 64 == 0 && act->Mx % 32 == 0 && (n <= 6 || whole_draw)) {
-      // specialised overrelaxation kernel (bit-identical to the generic one)
-      const size_t lds = (size_t)2 * (32 + 4 * n) * (64 + 4 * n + 1) * sizeof(double);
-      dim3 sgrid((act->Mt / 64) * (act->Mx / 32), B);
-      const double2 *in2 = (const double2 *)src;
-      double2 *out2 = (double2 *)dst;
-      // more fused sweeps -> larger LDS image -> fewer resident workgroups: keep the wave count per CU up
-      // with wider workgroups (MLMCPI_OR_THREADS overrides: tuning knob)
-      const bool use_patch = !tune.or_lds;
-      if (or_blocks) {  // 4 x 4 register blocks on 64 x 64 tiles (n <= 6)
-        dim3 bgrid((act->Mt / 64) * (act->Mx / 64), B);
-        // the last overrelaxation launch of the draw takes the heat-bath sweep behind it along (and the QoI, if that is
-        // the draw's last sweep): schwinger_or_heat_kernel, bit-identical to the two launches (MLMCPI_OR_HEAT=split)
-        if (!tune.or_heat_split && s + n == n_overrelax && n_heatbath >= 1 && (n <= 5 || whole_draw) && act->Mt >= 128 && act->Mx >= 128) {
-          const bool step = 2. * act->beta <= kVsKappaMax;   // which sampler: a property of the action (device_common.hpp)
-          const uint32_t *vs_table = nullptr;
-          if (step)
-            if (int rcv = vs_table_device(2. * act->beta, &vs_table)) return rcv;
-          const bool with_qoi = qoi_kind && s + n + 1 == total;
-          void *partial = nullptr;
-          if (with_qoi)
-            if (int rcs = scratch((size_t)B * bgrid.x * sizeof(double), &partial, st)) return rcs;
-          const int op = !with_qoi ? 0 : qoi_kind == 1 ? (int)L_PLAQ : (int)L_CHARGE;
-          const RngKey hkey = make_key(seed, chain0, sweep0 + s + n);
-          // at most one workgroup per CU: sixteen waves for the heat-bath part (bit-identical; MLMCPI_OR_HEAT=wide|narrow forces)
-          const bool wide = tune.or_heat_wide ? tune.or_heat_wide > 0 : (uint64_t)bgrid.x * B <= kComputeUnits;
-#define MLMCPI_OR_HEAT_W(KK, WW) hipLaunchKernelGGL((schwinger_or_heat_kernel<KK, WW>), bgrid, dim3(WW ? 1024 : OrHeatGeom<KK>::NT), OrHeatGeom<KK>::lds_bytes, st, act->Mt, act->Mx, act->beta, in2, out2, act->Mt / 64, hkey, op, (double *)partial, vs_table)
-#define MLMCPI_OR_HEAT_CAUCHY(KK) hipLaunchKernelGGL((schwinger_or_heat_kernel<KK, false, false>), bgrid, dim3(OrHeatGeom<KK>::NT), OrHeatGeom<KK>::lds_bytes, st, act->Mt, act->Mx, act->beta, in2, out2, act->Mt / 64, hkey, op, (double *)partial, vs_table)
-#define MLMCPI_OR_HEAT(KK) do { if (!step) MLMCPI_OR_HEAT_CAUCHY(KK); else if (wide) MLMCPI_OR_HEAT_W(KK, true); else MLMCPI_OR_HEAT_W(KK, false); } while (0)
-          switch (n) {
-            case 1: MLMCPI_OR_HEAT(1); break;
-            case 2: MLMCPI_OR_HEAT(2); break;
-            case 3: MLMCPI_OR_HEAT(3); break;
-            case 4: MLMCPI_OR_HEAT(4); break;
-            case 5: MLMCPI_OR_HEAT(5); break;
-            case 6: MLMCPI_OR_HEAT_W(6, true); break;  // whole_draw (wide workgroups only)
-            case 7: MLMCPI_OR_HEAT_W(7, true); break;
-            case 8: MLMCPI_OR_HEAT_W(8, true); break;
-            case 9: MLMCPI_OR_HEAT_W(9, true); break;
-            default: MLMCPI_OR_HEAT_W(10, true);
-          }
-#undef MLMCPI_OR_HEAT
-#undef MLMCPI_OR_HEAT_CAUCHY
-#undef MLMCPI_OR_HEAT_W
-          MLMCPI_LAUNCH_CHECK("schwinger_or_heat_kernel");
-          if (with_qoi) {
-            hipLaunchKernelGGL(lattice_finish_kernel, dim3((B + 3) / 4), dim3(256), 0, st, (const double *)partial, bgrid.x, B, op,
-                               1.0 / ((double)act->Mx * act->Mt), d_qoi, d_acc);
-            MLMCPI_LAUNCH_CHECK("lattice_finish_kernel");
-          }
-          advance();
-          s += n + 1;
-          continue;
-        }
-#define MLMCPI_OR_BLOCK(KK) hipLaunchKernelGGL((schwinger_or_block_kernel<KK>), bgrid, dim3(OrBlockGeom<KK>::NT), OrBlockGeom<KK>::lds_bytes, st, act->Mt, act->Mx, in2, out2, act->Mt / 64)
-        switch (n) {
-          case 1: MLMCPI_OR_BLOCK(1); break;
-          case 2: MLMCPI_OR_BLOCK(2); break;
-          case 3: MLMCPI_OR_BLOCK(3); break;
-          case 4: MLMCPI_OR_BLOCK(4); break;
-          case 5: MLMCPI_OR_BLOCK(5); break;
-          default: MLMCPI_OR_BLOCK(6);
-        }
-#undef MLMCPI_OR_BLOCK
+    if (schw && !kinds && !g.overridden && or_blocks && n <= 6) {
+      // 4 x 4 register blocks on 64 x 64 tiles, sweep by sweep (bit-identical to the generic kernel and the closed form)
+      const dim3 bgrid((Mt / 64) * (Mx / 64), B);
+      rc = with_depth<6>(n, [&](auto kc) -> int {
+        constexpr int K = decltype(kc)::value;
+        hipLaunchKernelGGL(schwinger_or_block_kernel<K>, bgrid, dim3(OrBlockGeom<K>::NT), OrBlockGeom<K>::lds_bytes, st, Mt, Mx,
+                           in2, out2, Mt / 64);
         MLMCPI_LAUNCH_CHECK("schwinger_or_block_kernel");
-        advance();
-        s += n;
-        continue;
-      }
-      if (use_patch && n <= 4) {  // register-tiled kernel (MLMCPI_OR_KERNEL=lds selects the LDS-resident one)
-        const uint32_t np = ((64 + 4 * n) / 2) * ((32 + 4 * n) / 2);
-        const dim3 pblock((np + 63) / 64 * 64);
-        const size_t plds = (size_t)8 * np * sizeof(double);
-        switch (n) {
-          case 1: hipLaunchKernelGGL((schwinger_or_patch_kernel<1>), sgrid, pblock, plds, st, act->Mt, act->Mx, in2, out2, act->Mt / 64); break;
-          case 2: hipLaunchKernelGGL((schwinger_or_patch_kernel<2>), sgrid, pblock, plds, st, act->Mt, act->Mx, in2, out2, act->Mt / 64); break;
-          case 3: hipLaunchKernelGGL((schwinger_or_patch_kernel<3>), sgrid, pblock, plds, st, act->Mt, act->Mx, in2, out2, act->Mt / 64); break;
-          default: hipLaunchKernelGGL((schwinger_or_patch_kernel<4>), sgrid, pblock, plds, st, act->Mt, act->Mx, in2, out2, act->Mt / 64);
-        }
-        MLMCPI_LAUNCH_CHECK("schwinger_or_patch_kernel");
-        advance();
-        s += n;
-        continue;
-      }
-      uint32_t nt_or = n >= 4 ? 1024 : 512;  // measured best (tools/scan_or.sh): K <= 3: 512, K >= 4: 1024
-      if (tune.or_threads) nt_or = tune.or_threads;
-#define MLMCPI_OR(KK, NN) hipLaunchKernelGGL((schwinger_or_kernel<64, 32, KK, NN>), sgrid, dim3(NN), lds, st, act->Mt, act->Mx, in2, out2, act->Mt / 64)
-#define MLMCPI_OR_K(KK) do { if (nt_or == 1024) MLMCPI_OR(KK, 1024); else if (nt_or == 512) MLMCPI_OR(KK, 512); else MLMCPI_OR(KK, 256); } while (0)
-      switch (n) {
-        case 1: MLMCPI_OR_K(1); break;
-        case 2: MLMCPI_OR_K(2); break;
-        case 3: MLMCPI_OR_K(3); break;
-        case 4: MLMCPI_OR_K(4); break;
-        case 5: MLMCPI_OR_K(5); break;
-        default: MLMCPI_OR_K(6);
-      }
-#undef MLMCPI_OR_K
-#undef MLMCPI_OR
-      MLMCPI_LAUNCH_CHECK("schwinger_or_kernel");
-      rc = MLMCPI_OK;
-    } else if (!schw && !kinds && !g.overridden && gff_blocks32 && n <= 6) {
+        return MLMCPI_OK;
+      });
+    } else if (gff_T && !kinds && !g.overridden && n <= 6) {
+      // GFF, 4 x 4 register blocks on gff_T x gff_T tiles.  The last overrelaxation launch of the draw takes the heat-bath
+      // sweep behind it along (and the QoI, if that ends the draw): gff_or_heat_kernel, bit-identical to the two launches
+      // (MLMCPI_OR_HEAT=split)
+      const bool fused = !tune.or_heat_split && s + n == n_overrelax && n_heatbath >= 1 && n <= 5;
       const double mu2 = gff_mu2(*act);
-      dim3 bgrid(g32_tx * g32_ty, B);
-      if (!tune.or_heat_split && s + n == n_overrelax && n_heatbath >= 1 && n <= 5) {
-        const bool with_qoi = qoi_kind && s + n + 1 == total;
-        void *partial = nullptr;
-        if (with_qoi)
-          if (int rcs = scratch((size_t)B * bgrid.x * sizeof(double), &partial, st)) return rcs;
-        const int op = with_qoi ? (int)L_PHI2 : 0;
-        const RngKey hkey = make_key(seed, chain0, sweep0 + s + n);
-#define MLMCPI_GFF_HEAT32(KK) hipLaunchKernelGGL((gff_or_heat_kernel<KK, 32>), bgrid, dim3((GffHeatGeom<KK, 32>::NT)), (GffHeatGeom<KK, 32>::lds_bytes), st, act->Mt, act->Mx, mu2, (const double *)src, dst, g32_tx, hkey, op, (double *)partial)
-        switch (n) {
-          case 1: MLMCPI_GFF_HEAT32(1); break;
-          case 2: MLMCPI_GFF_HEAT32(2); break;
-          case 3: MLMCPI_GFF_HEAT32(3); break;
-          case 4: MLMCPI_GFF_HEAT32(4); break;
-          default: MLMCPI_GFF_HEAT32(5);
-        }
-#undef MLMCPI_GFF_HEAT32
-        MLMCPI_LAUNCH_CHECK("gff_or_heat_kernel<., 32>");
-        if (with_qoi) {
-          hipLaunchKernelGGL(lattice_finish_kernel, dim3((B + 3) / 4), dim3(256), 0, st, (const double *)partial, bgrid.x, B, op,
-                             1.0 / ((double)act->Mx * act->Mt), d_qoi, d_acc);
-          MLMCPI_LAUNCH_CHECK("lattice_finish_kernel");
-        }
-        advance();
-        s += n + 1;
-        continue;
-      }
-#define MLMCPI_GFF_BLOCK32(KK) hipLaunchKernelGGL((gff_or_block_kernel<KK, 32>), bgrid, dim3((GffBlockGeom<KK, 32>::NT)), (GffBlockGeom<KK, 32>::lds_bytes), st, act->Mt, act->Mx, mu2, (const double *)src, dst, g32_tx)
-      switch (n) {
-        case 1: MLMCPI_GFF_BLOCK32(1); break;
-        case 2: MLMCPI_GFF_BLOCK32(2); break;
-        case 3: MLMCPI_GFF_BLOCK32(3); break;
-        case 4: MLMCPI_GFF_BLOCK32(4); break;
-        case 5: MLMCPI_GFF_BLOCK32(5); break;
-        default: MLMCPI_GFF_BLOCK32(6);
-      }
-#undef MLMCPI_GFF_BLOCK32
-      MLMCPI_LAUNCH_CHECK("gff_or_block_kernel<., 32>");
-      advance();
-      s += n;
-      continue;
-    } else if (!schw && !kinds && !g.overridden && act->Mt % 64 == 0 && act->Mx % 32 == 0 && n <= (or_blocks ? 6u : 4u)) {
-      const size_t lds = (size_t)(32 + 4 * n) * (64 + 4 * n + 1) * sizeof(double);
-      dim3 sgrid((act->Mt / 64) * (act->Mx / 32), B);
-      const double mu2 = gff_mu2(*act);
-      const bool use_gff_patch = !tune.or_lds;
-      if (or_blocks) {  // 4 x 4 register blocks on 64 x 64 tiles (n <= 6)
-        dim3 bgrid((act->Mt / 64) * (act->Mx / 64), B);
-        // as for the Schwinger action: the last overrelaxation launch takes the heat-bath sweep (and the QoI) along
-        if (!tune.or_heat_split && s + n == n_overrelax && n_heatbath >= 1 && n <= 5 && act->Mt >= 128 && act->Mx >= 128) {
-          const bool with_qoi = qoi_kind && s + n + 1 == total;
-          void *partial = nullptr;
-          if (with_qoi)
-            if (int rcs = scratch((size_t)B * bgrid.x * sizeof(double), &partial, st)) return rcs;
-          const int op = with_qoi ? (int)L_PHI2 : 0;
-          const RngKey hkey = make_key(seed, chain0, sweep0 + s + n);
-#define MLMCPI_GFF_HEAT(KK) hipLaunchKernelGGL((gff_or_heat_kernel<KK>), bgrid, dim3(GffHeatGeom<KK>::NT), GffHeatGeom<KK>::lds_bytes, st, act->Mt, act->Mx, mu2, (const double *)src, dst, act->Mt / 64, hkey, op, (double *)partial)
-          switch (n) {
-            case 1: MLMCPI_GFF_HEAT(1); break;
-            case 2: MLMCPI_GFF_HEAT(2); break;
-            case 3: MLMCPI_GFF_HEAT(3); break;
-            case 4: MLMCPI_GFF_HEAT(4); break;
-            default: MLMCPI_GFF_HEAT(5);
-          }
-#undef MLMCPI_GFF_HEAT
-          MLMCPI_LAUNCH_CHECK("gff_or_heat_kernel");
-          if (with_qoi) {
-            hipLaunchKernelGGL(lattice_finish_kernel, dim3((B + 3) / 4), dim3(256), 0, st, (const double *)partial, bgrid.x, B, op,
-                               1.0 / ((double)act->Mx * act->Mt), d_qoi, d_acc);
-            MLMCPI_LAUNCH_CHECK("lattice_finish_kernel");
-          }
-          advance();
-          s += n + 1;
-          continue;
-        }
-#define MLMCPI_GFF_BLOCK(KK) hipLaunchKernelGGL((gff_or_block_kernel<KK>), bgrid, dim3(GffBlockGeom<KK>::NT), GffBlockGeom<KK>::lds_bytes, st, act->Mt, act->Mx, mu2, (const double *)src, dst, act->Mt / 64)
-        switch (n) {
-          case 1: MLMCPI_GFF_BLOCK(1); break;
-          case 2: MLMCPI_GFF_BLOCK(2); break;
-          case 3: MLMCPI_GFF_BLOCK(3); break;
-          case 4: MLMCPI_GFF_BLOCK(4); break;
-          case 5: MLMCPI_GFF_BLOCK(5); break;
-          default: MLMCPI_GFF_BLOCK(6);
-        }
-#undef MLMCPI_GFF_BLOCK
-        MLMCPI_LAUNCH_CHECK("gff_or_block_kernel");
-        advance();
-        s += n;
-        continue;
-      }
-      if (use_gff_patch) {  // register-tiled kernel (MLMCPI_OR_KERNEL=lds selects the LDS-resident one)
-        const uint32_t np = ((64 + 4 * n) / 2) * ((32 + 4 * n) / 2);
-        const dim3 pblock((np + 63) / 64 * 64);
-        const size_t plds = (size_t)4 * np * sizeof(double);
-        switch (n) {
-          case 1: hipLaunchKernelGGL((gff_or_patch_kernel<1>), sgrid, pblock, plds, st, act->Mt, act->Mx, mu2, (const double *)src, dst, act->Mt / 64); break;
-          case 2: hipLaunchKernelGGL((gff_or_patch_kernel<2>), sgrid, pblock, plds, st, act->Mt, act->Mx, mu2, (const double *)src, dst, act->Mt / 64); break;
-          case 3: hipLaunchKernelGGL((gff_or_patch_kernel<3>), sgrid, pblock, plds, st, act->Mt, act->Mx, mu2, (const double *)src, dst, act->Mt / 64); break;
-          default: hipLaunchKernelGGL((gff_or_patch_kernel<4>), sgrid, pblock, plds, st, act->Mt, act->Mx, mu2, (const double *)src, dst, act->Mt / 64);
-        }
-        MLMCPI_LAUNCH_CHECK("gff_or_patch_kernel");
-        advance();
-        s += n;
-        continue;
-      }
-      switch (n) {
-        case 1: hipLaunchKernelGGL((gff_or_kernel<64, 32, 1, 256>), sgrid, dim3(256), lds, st, act->Mt, act->Mx, mu2, (const double *)src, dst, act->Mt / 64); break;
-        case 2: hipLaunchKernelGGL((gff_or_kernel<64, 32, 2, 256>), sgrid, dim3(256), lds, st, act->Mt, act->Mx, mu2, (const double *)src, dst, act->Mt / 64); break;
-        case 3: hipLaunchKernelGGL((gff_or_kernel<64, 32, 3, 256>), sgrid, dim3(256), lds, st, act->Mt, act->Mx, mu2, (const double *)src, dst, act->Mt / 64); break;
-        default: hipLaunchKernelGGL((gff_or_kernel<64, 32, 4, 256>), sgrid, dim3(256), lds, st, act->Mt, act->Mx, mu2, (const double *)src, dst, act->Mt / 64);
-      }
-      MLMCPI_LAUNCH_CHECK("gff_or_kernel");
-      rc = MLMCPI_OK;
-    } else
-    // launches without a heat-bath sweep use the lean instantiation (no sampler code, fewer VGPRs)
-    if (kinds && qoi_kind && s + n == total) {  // the last launch of the draw: sum the QoI while the tile is in LDS
-      void *partial = nullptr;
-      if (int rcs = scratch((size_t)B * grid.x * sizeof(double), &partial, st)) return rcs;
-      const int op = qoi_kind == 1 ? (int)L_PLAQ : qoi_kind == 2 ? (int)L_CHARGE : (int)L_PHI2;
-      rc = schw ? launch_sweep<true, true>(g, grid, st, act->Mt, act->Mx, act->beta, src, dst, n, kinds, key, op, (double *)partial)
-                : launch_sweep<false, true>(g, grid, st, act->Mt, act->Mx, gff_mu2(*act), src, dst, n, kinds, key, op, (double *)partial);
-      if (rc) return rc;
-      hipLaunchKernelGGL(lattice_finish_kernel, dim3((B + 3) / 4), dim3(256), 0, st, (const double *)partial, grid.x, B, op,
-                         1.0 / ((double)act->Mx * act->Mt), d_qoi, d_acc);
-      MLMCPI_LAUNCH_CHECK("lattice_finish_kernel");
-    } else if (schw)
-      rc = kinds ? launch_sweep<true, true>(g, grid, st, act->Mt, act->Mx, act->beta, src, dst, n, kinds, key)
-                 : launch_sweep<true, false>(g, grid, st, act->Mt, act->Mx, act->beta, src, dst, n, kinds, key);
-    else
-      rc = kinds ? launch_sweep<false, true>(g, grid, st, act->Mt, act->Mx, gff_mu2(*act), src, dst, n, kinds, key)
-                 : launch_sweep<false, false>(g, grid, st, act->Mt, act->Mx, gff_mu2(*act), src, dst, n, kinds, key);
+      auto gff_blocks = [&](auto tc) -> int {
+        constexpr int T = decltype(tc)::value;
+        const uint32_t tiles_x = (Mt + T - 1) / T;
+        const dim3 bgrid(tiles_x * ((Mx + T - 1) / T), B);
+        if (fused)
+          return heat_launch(s + n, bgrid.x, [&](RngKey hkey, int op, double *partial) -> int {
+            return with_depth<5>(n, [&](auto kc) -> int {
+              constexpr int K = decltype(kc)::value;
+              hipLaunchKernelGGL((gff_or_heat_kernel<K, T>), bgrid, dim3((GffHeatGeom<K, T>::NT)), (GffHeatGeom<K, T>::lds_bytes),
+                                 st, Mt, Mx, mu2, (const double *)src, dst, tiles_x, hkey, op, partial);
+              MLMCPI_LAUNCH_CHECK("gff_or_heat_kernel");
+              return MLMCPI_OK;
+            });
+          });
+        return with_depth<6>(n, [&](auto kc) -> int {
+          constexpr int K = decltype(kc)::value;
+          hipLaunchKernelGGL((gff_or_block_kernel<K, T>), bgrid, dim3((GffBlockGeom<K, T>::NT)), (GffBlockGeom<K, T>::lds_bytes),
+                             st, Mt, Mx, mu2, (const double *)src, dst, tiles_x);
+          MLMCPI_LAUNCH_CHECK("gff_or_block_kernel");
+          return MLMCPI_OK;
+        });
+      };
+      rc = gff_T == 32 ? gff_blocks(std::integral_constant<int, 32>()) : gff_blocks(std::integral_constant<int, 64>());
+      if (fused) swept = n + 1;
+    } else if (kinds) {  // a heat-bath sweep (a launch of its own: n == 1), with the QoI if it ends the draw
+      rc = heat_launch(s, grid.x, [&](RngKey key, int op, double *partial) -> int {
+        return schw ? launch_sweep<true, true>(g, grid, st, Mt, Mx, act->beta, src, dst, n, kinds, key, op, partial)
+                    : launch_sweep<false, true>(g, grid, st, Mt, Mx, gff_mu2(*act), src, dst, n, kinds, key, op, partial);
+      });
+    } else {  // launches without a heat-bath sweep use the lean instantiation (no sampler code, fewer VGPRs)
+      const RngKey key = make_key(seed, chain0, sweep0 + s);
+      rc = schw ? launch_sweep<true, false>(g, grid, st, Mt, Mx, act->beta, src, dst, n, kinds, key)
+                : launch_sweep<false, false>(g, grid, st, Mt, Mx, gff_mu2(*act), src, dst, n, kinds, key);
+    }
     if (rc) return rc;
     advance();
-    s += n;
+    s += swept;
   }
   if (result_in)
     *result_in = total == 0 ? -1 : (src == d_w0 ? 0 : 1);
@@ -4231,7 +3628,7 @@ static int gff_initialise_exact(const mlmcpi_lattice_action *act, double *d_phi,
 }
 
 #ifdef MLMCPI_STAMPS
-// instrumentation build only: the stamps of the last launch of schwinger_or_heat_kernel, 16 words per workgroup
+// instrumentation build only: the stamps of the last launch of schwinger_perm_heat_kernel, 16 words per workgroup
 int mlmcpi_debug_read_stamps(unsigned long long *h_out, uint32_t n_workgroups) {
   MLMCPI_HIP_TRY(hipDeviceSynchronize());
   MLMCPI_HIP_TRY(hipMemcpyFromSymbol(h_out, HIP_SYMBOL(mlmcpi::g_stamps), (size_t)n_workgroups * 16 * sizeof(unsigned long long)));

@@ -89,26 +89,19 @@ bool apply_option(Tuning &t, const char *name, const char *value) {
     return false;
   }
   if (n == "MLMCPI_OR_KERNEL") {
-    t.or_lds = v == "lds";
-    t.or_patch = v == "patch";
     t.or_block = v == "block";
-    return v.empty() || v == "lds" || v == "patch" || v == "block" || v == "perm";
+    return v.empty() || v == "block" || v == "perm";
   }
   if (n == "MLMCPI_OR_HEAT") {
     t.or_heat_split = v == "split";
     t.or_heat_wide = v == "wide" ? 1 : v == "narrow" ? -1 : 0;
     return v.empty() || v == "split" || v == "fused" || v == "wide" || v == "narrow";
   }
-  if (n == "MLMCPI_OR_THREADS") {
-    const unsigned x = (unsigned)atoi(v.c_str());
-    t.or_threads = (x == 256 || x == 512 || x == 1024) ? x : 0;
-    return v.empty() || t.or_threads != 0;
-  }
   return false;
 }
 void load_tuning_locked() {
   if (g_tuning_loaded) return;
-  for (const char *name : {"MLMCPI_SWEEP_TILE", "MLMCPI_OR_KERNEL", "MLMCPI_OR_THREADS", "MLMCPI_OR_HEAT"})
+  for (const char *name : {"MLMCPI_SWEEP_TILE", "MLMCPI_OR_KERNEL", "MLMCPI_OR_HEAT"})
     if (const char *e = getenv(name)) apply_option(g_tuning, name, e);
   g_tuning_loaded = true;
 }

@@ -274,18 +274,21 @@ def test_schwinger_beta_coarse_keeps_the_reference_domain():
         abi.call("mlmcpi_schwinger_beta_coarse_nonperturbative", 1000.5, 4096, 4, C.byref(bc))
 
 
-def test_tuning_options_are_checked_by_name_and_value():
+def test_tuning_options_are_checked_and_retired_ones_rejected():
     """mlmcpi_set_option (host code; the knobs never change results): every documented knob with every documented value is
     accepted, anything else is MLMCPI_ERR_INVALID with a message -- a typo in a benchmark's environment must not be a
-    silent no-op at run time."""
+    silent no-op at run time.  The knobs of retired kernels (MLMCPI_OR_KERNEL=lds|patch, MLMCPI_OR_THREADS) are rejected."""
     from mlmcpathintegral_amd import abi
-    good = {"MLMCPI_SWEEP_TILE": ["64x32x256", "128x64x512", ""], "MLMCPI_OR_KERNEL": ["block", "patch", "lds", "perm", ""],
-            "MLMCPI_OR_THREADS": ["256", "512", "1024", ""], "MLMCPI_OR_HEAT": ["fused", "split", "wide", "narrow", ""]}
+    good = {"MLMCPI_SWEEP_TILE": ["64x32x256", "128x64x512", ""], "MLMCPI_OR_KERNEL": ["block", "perm", ""],
+            "MLMCPI_OR_HEAT": ["fused", "split", "wide", "narrow", ""]}
     for name, values in good.items():
         for v in values:
             abi.set_option(name, v)
-    for name, v in (("MLMCPI_OR_HEAT", "sideways"), ("MLMCPI_OR_KERNEL", "blocks"), ("MLMCPI_SWEEP_TILE", "63x32x256"),
-                    ("MLMCPI_SWEEP_TILE", "64x32x100"), ("MLMCPI_OR_THREADS", "300"), ("MLMCPI_NO_SUCH_KNOB", "1")):
+    # (lds, patch and MLMCPI_OR_THREADS belonged to retired overrelaxation kernels)
+    for name, v in (("MLMCPI_OR_HEAT", "sideways"), ("MLMCPI_OR_KERNEL", "blocks"), ("MLMCPI_OR_KERNEL", "lds"),
+                    ("MLMCPI_OR_KERNEL", "patch"), ("MLMCPI_SWEEP_TILE", "63x32x256"), ("MLMCPI_SWEEP_TILE", "64x32x100"),
+                    ("MLMCPI_OR_THREADS", "300"), ("MLMCPI_OR_THREADS", "256"), ("MLMCPI_OR_THREADS", ""),
+                    ("MLMCPI_NO_SUCH_KNOB", "1")):
         with pytest.raises(abi.MlmcpiError) as e:
             abi.set_option(name, v)
         assert "unknown option or value" in str(e.value)

@@ -641,10 +641,10 @@ def test_closed_form_overrelaxation_matches_oracle(gpu_ops, orc, Mt, Mx, B, beta
                                           (256, 256, 2, 40.0),
                                           (200, 136, 2, 1.0), (130, 262, 1, 1.0)])   # r05: masked edge tiles of the fused launch
 def test_overrelaxation_and_heat_bath_in_one_launch_equal_two_launches(gpu_ops, Mt, Mx, B, beta):
-    """schwinger_or_heat_kernel<K> (the last K <= 5 overrelaxation sweeps of a draw, the heat-bath sweep behind them and
-    the QoI in one launch) against the same draw with the heat bath in a launch of its own (MLMCPI_OR_HEAT=split): states
-    bit for bit, for every depth K, with a second heat-bath sweep behind, and the fused QoI to rounding (its partial sums
-    run over 64 x 64 instead of 64 x 32 tiles)."""
+    """schwinger_perm_heat_kernel (the last K <= 10 overrelaxation sweeps of a draw in closed form, the heat-bath sweep
+    behind them and the QoI in one launch) against the same draw with the heat bath in a launch of its own
+    (MLMCPI_OR_HEAT=split): states bit for bit, for every depth K, with a second heat-bath sweep behind, and the fused QoI
+    to rounding (its partial sums run over 64 x 64 instead of 64 x 32 tiles)."""
     from mlmcpathintegral_amd import abi
     act = abi.lattice_action(abi.SCHWINGER, Mt, Mx, beta=beta)
     x0 = gpu_ops.lattice_initialise(act, B, SEED, 2)
@@ -671,12 +671,12 @@ def test_overrelaxation_and_heat_bath_in_one_launch_equal_two_launches(gpu_ops, 
 
 @pytest.mark.parametrize("Mt,Mx,B", [(128, 128, 2), (256, 192, 3), (1024, 1024, 1)])
 def test_wide_workgroups_of_the_fused_launch_change_nothing(gpu_ops, Mt, Mx, B):
-    """Launches with at most one workgroup per CU give the heat-bath part of schwinger_or_heat_kernel sixteen waves
-    (1024-thread workgroups; the register-block part stays on its 7 or 8): same draws, bit for bit, at every depth."""
+    """Launches with at most one workgroup per CU give schwinger_perm_heat_kernel sixteen waves (1024-thread workgroups
+    instead of 512): same draws, bit for bit, at every depth."""
     from mlmcpathintegral_amd import abi
     act = abi.lattice_action(abi.SCHWINGER, Mt, Mx, beta=1.0)
     x0 = gpu_ops.lattice_initialise(act, B, SEED, 4)
-    # "" at these sizes: the library's own plan -- wide workgroups, and the whole draw in one launch for 6 <= n_or <= 10
+    # "" at these sizes: the library's own plan -- wide workgroups, and the whole draw in one launch for n_or <= 10
     for n_or, n_hb in ([(1, 1), (2, 1), (3, 1), (4, 2), (5, 1), (6, 1), (7, 2), (8, 1), (9, 1), (10, 1), (11, 1)] if Mt < 1024 else [(10, 1), (7, 1)]):
         res = {}
         for mode in ("narrow", "wide", ""):
@@ -920,7 +920,7 @@ def test_lattice_hmc_matches_oracle(gpu_ops, orc, kind, Mt, Mx, kw):
 
 
 # ---- full-size properties (BASELINE sizes; the oracle would take too long) -----------------------------
-def test_schwinger_1024_properties(gpu_ops, orc, golden):
+def test_schwinger_1024_properties_of_the_kept_kernels(gpu_ops, orc, golden):
     """1024 x 1024, beta = 1: (i) overrelaxation sweeps conserve the action; (ii) the result is
     independent of how many sweeps are fused per launch (halo logic at scale, bit-exact); (iii) chain b
     of a batch equals the same chain run alone; (iv) QoIs of the uniform start agree with the oracle."""
@@ -965,21 +965,6 @@ def test_schwinger_1024_properties(gpu_ops, orc, golden):
     finally:
         abi.set_option("MLMCPI_SWEEP_TILE", "")
     assert torch.equal(a, gen), "specialised and generic sweep kernels must agree bit for bit"
-    # the LDS-resident kernel
-    abi.set_option("MLMCPI_OR_KERNEL", "lds")
-    try:
-        lds4 = x.clone()
-        gpu_ops.lattice_sweep_draw(act, lds4, scratch, 4, 2, SEED, 0, 0, fuse=4)
-    finally:
-        abi.set_option("MLMCPI_OR_KERNEL", "")
-    assert torch.equal(a, lds4), "register-tiled and LDS-resident overrelaxation kernels must agree bit for bit"
-    abi.set_option("MLMCPI_OR_KERNEL", "patch")  # 2 x 2 register blocks on 64 x 32 tiles (the default is 4 x 4 on 64 x 64)
-    try:
-        p4 = x.clone()
-        gpu_ops.lattice_sweep_draw(act, p4, scratch, 4, 2, SEED, 0, 0, fuse=4)
-    finally:
-        abi.set_option("MLMCPI_OR_KERNEL", "")
-    assert torch.equal(a, p4), "4 x 4 and 2 x 2 register-block overrelaxation kernels must agree bit for bit"
     # The default: K overrelaxation sweeps in closed form (schwinger_perm_kernel / schwinger_perm_heat_kernel).  The same map
     # up to the rounding of 4 K additions: to 1e-12 against the sweep-by-sweep kernels for every launch plan (the two
     # heat-bath sweeps behind take the same decisions); bit for bit among launches of the same depth.
@@ -1016,7 +1001,7 @@ def test_schwinger_1024_properties(gpu_ops, orc, golden):
     assert ((a >= -np.pi - 1e-12) & (a < np.pi + 1e-12)).all()
 
 
-def test_rotor_65536_and_gff_512_properties(gpu_ops):
+def test_rotor_65536_and_gff_512_properties_of_the_kept_kernels(gpu_ops):
     from mlmcpathintegral_amd import abi
     act = abi.path_action(2, 65536, 8192.0, 0.25)
     x = gpu_ops.path_initialise(act, 2, SEED)
@@ -1039,20 +1024,6 @@ def test_rotor_65536_and_gff_512_properties(gpu_ops):
     finally:
         abi.set_option("MLMCPI_SWEEP_TILE", "")
     assert torch.equal(a, gen), "specialised and generic GFF kernels must agree bit for bit"
-    abi.set_option("MLMCPI_OR_KERNEL", "lds")
-    try:
-        lds4 = phi.clone()
-        gpu_ops.lattice_sweep_draw(act, lds4, scratch, 6, 1, SEED, 0, 0, fuse=4)
-    finally:
-        abi.set_option("MLMCPI_OR_KERNEL", "")
-    assert torch.equal(a, lds4), "register-tiled and LDS-resident GFF overrelaxation kernels must agree bit for bit"
-    abi.set_option("MLMCPI_OR_KERNEL", "patch")  # 2 x 2 register blocks on 64 x 32 tiles (the default is 4 x 4 on 64 x 64)
-    try:
-        p4 = phi.clone()
-        gpu_ops.lattice_sweep_draw(act, p4, scratch, 6, 1, SEED, 0, 0, fuse=4)
-    finally:
-        abi.set_option("MLMCPI_OR_KERNEL", "")
-    assert torch.equal(a, p4), "4 x 4 and 2 x 2 register-block GFF overrelaxation kernels must agree bit for bit"
     for n in (5, 6, 10):  # every depth of the 4 x 4 kernel against single-sweep launches
         u, v = phi.clone(), phi.clone()
         gpu_ops.lattice_sweep_draw(act, u, scratch, n, 0, SEED, 0, 0, fuse=1)

@@ -22,7 +22,7 @@ def burn(label, fn, secs=4.0):
     print(f"{t0:.2f} .. {t0+el:.2f}  {label}: {1e3*el/n:.4f} ms/call", flush=True)
     time.sleep(1.0)
 time.sleep(2.0)
-for kernel, K in (("block", 6), ("block", 5), ("block", 1), ("patch", 4), ("block", 4)):
+for kernel, K in (("block", 6), ("block", 5), ("block", 1), ("block", 4)):
     abi.set_option("MLMCPI_OR_KERNEL", kernel)
     burn(f"OR {kernel} K={K}", lambda: ops.lattice_sweep_draw_pingpong(act, x, s, K, 0, seed, 0, 0, K))
 abi.set_option("MLMCPI_OR_KERNEL", "")

@@ -1,6 +1,6 @@
 #!/bin/bash
 # One chain per GPU (BASELINE configs[3] read literally): step time under the tuning knobs.
-for env in "" "MLMCPI_OR_KERNEL=patch" "MLMCPI_SWEEP_TILE=32x32x256" "MLMCPI_SWEEP_TILE=32x16x256" "MLMCPI_SWEEP_TILE=64x16x256"; do
+for env in "" "MLMCPI_SWEEP_TILE=32x32x256" "MLMCPI_SWEEP_TILE=32x16x256" "MLMCPI_SWEEP_TILE=64x16x256"; do
   for fuse in 0 2; do
     env $env python bench.py --chains 1 --steps 50 --warmup 10 --no-cpu-baseline --no-extra-points --fuse $fuse 2>/dev/null | python -c "
 import json,sys

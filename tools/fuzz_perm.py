@@ -1,7 +1,8 @@
 #!/usr/bin/env python3
 """Shape fuzz of the closed-form Schwinger overrelaxation kernels against the sweep-by-sweep ones (MLMCPI_OR_KERNEL=block; for
-lattices that 64 x 64 tiles do not divide the 2 x 2 patch / generic kernels run there): every lattice shape the closed form
-accepts up to 320 x 256, every depth 1 .. 13, with and without a heat-bath sweep behind; and the rotor's 1-D form."""
+lattices that 64 x 64 tiles do not divide the generic kernels run there): every lattice shape the closed form accepts up to
+320 x 256, every depth 1 .. 13, with and without a heat-bath sweep behind; and the rotor's 1-D form.  GFF: the register-block
+kernels against the generic sweep-by-sweep ones."""
 import itertools, sys
 import numpy as np
 import torch
@@ -60,23 +61,23 @@ for M in (2, 4, 6, 64, 1000, 2048, 4100, 65536):
             print(f"MISMATCH rotor M={M} ({n_or},{n_hb}): {d:.3e}", flush=True)
 print(f"rotor: {n} cases, largest overrelaxation-only difference {worst:.3e}", flush=True)
 
-# GFF register-block kernels on 32 x 32 tiles with masked edges (r05) against the LDS-resident sweep-by-sweep kernels: bit for bit
+# GFF register-block kernels on 32 x 32 tiles with masked edges (r05) against the generic sweep-by-sweep kernels: bit for bit
 worst, n = 0, 0
 for M in (64, 66, 70, 96, 100, 130, 190, 250):
     act = abi.lattice_action(abi.GFF, M, M, mass=3.0)
     x0 = ops.lattice_initialise(act, 2, SEED, 0)
     for n_or, n_hb in ((1, 0), (5, 0), (6, 1), (10, 1), (3, 2)):
         res = {}
-        for kern in ("lds", ""):
-            abi.set_option("MLMCPI_OR_KERNEL", kern)
+        for tile in ("64x32x256", ""):   # the generic kernels, then the library's plan
+            abi.set_option("MLMCPI_SWEEP_TILE", tile)
             try:
                 x = x0.clone()
                 ops.lattice_sweep_draw(act, x, torch.empty_like(x), n_or, n_hb, SEED, 0, 3)
-                res[kern] = x
+                res[tile] = x
             finally:
-                abi.set_option("MLMCPI_OR_KERNEL", "")
+                abi.set_option("MLMCPI_SWEEP_TILE", "")
         n += 1
-        if not torch.equal(res["lds"], res[""]):
+        if not torch.equal(res["64x32x256"], res[""]):
             worst += 1
-            print(f"MISMATCH gff {M}x{M} ({n_or},{n_hb}): {float((res['lds'] - res['']).abs().max()):.3e}", flush=True)
+            print(f"MISMATCH gff {M}x{M} ({n_or},{n_hb}): {float((res['64x32x256'] - res['']).abs().max()):.3e}", flush=True)
 print(f"gff: {n} cases, {worst} not bit-identical", flush=True)

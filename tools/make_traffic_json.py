@@ -77,15 +77,15 @@ for w, e in S.items():
         kind = None
         if "or_heat_kernel" in short or "perm_heat_kernel" in short:
             kind = "or_heat"   # K overrelaxation sweeps + the heat-bath sweep in one launch: fuse = K + 1 sweeps
-        elif "or_patch_kernel" in short or "or_block_kernel" in short or "or_kernel" in short or "sweep_kernel<false" in short or "schwinger_perm_kernel" in short:
+        elif "or_block_kernel" in short or "sweep_kernel<false" in short or "schwinger_perm_kernel" in short:
             kind = "overrelax"
         elif "sweep_kernel<true" in short:
             kind = "heatbath"
         fuse = 1
-        if "or_patch_kernel<" in short or "or_block_kernel<" in short:
+        if "or_block_kernel<" in short:
             fuse = int(short.split("<")[1].split(">")[0].split(",")[0])   # <K> or <K, tile>
         if "or_heat_kernel<" in short:
-            fuse = int(short.split("<")[1].split(">")[0].split(",")[0]) + 1   # <K> or <K, wide>
+            fuse = int(short.split("<")[1].split(">")[0].split(",")[0]) + 1   # <K> or <K, tile>
         if "perm_heat_kernel" in short:
             fuse = 11   # K is a launch argument: the profiled run is the reference's draw, 10 + 1 sweeps in one launch
         # bench.py's hbm_bound_probes (schwinger, --probes): single launches of the HBM-bound kernels of the path
