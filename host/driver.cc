@@ -9,6 +9,8 @@
 //   driver --method twolevel --action quarticoscillator --M_lat 256 --T_final 8 --coarsesampler hmc --n_samples 5000
 //   driver --method multilevel --action schwinger --Mt_lat 16 --beta 2 --coarsening both --coarsesampler heatbath
 //          --sampler hierarchical --n_level 2 --epsilon 0.005
+//   driver --action nonlinearsigma --Mt_lat 16 --beta 1 --sampler heatbath --n_samples 20000
+//          (O(3) sigma model: singlelevel and throughput with the heat-bath sampler only)
 //   driver --method throughput --action schwinger --Mt_lat 1024 --sampler heatbath --batch 32 --n_samples 20
 //          (the sampling loop of MonteCarloSingleLevel on a batch of chains, statistics accumulated on the device:
 //           prints link-updates/s of the C++ path)
@@ -87,6 +89,16 @@ int main(int argc, char **argv) {
       qoi_factory = std::make_shared<QoISusceptibilityFactory>();
       cfa_factory = std::make_shared<RotorConditionedFineActionFactory>();
     }
+  } else if (a == "nonlinearsigma") {  // driver_qft.cc:159-166, 241-246
+    auto lat = std::make_shared<Lattice2D>((unsigned)num("Mt_lat"), (unsigned)num("Mt_lat"), coarsenings.at(o["coarsening"]));
+    if (o["sampler"] != "heatbath")
+      fatal("nonlinearsigma: only --sampler heatbath is supported (HMC: the reference's force omits the sin theta of the measure "
+            "in (theta, phi) coordinates and would sample the wrong law; DESIGN.md 8)");
+    if (o["method"] != "singlelevel" && o["method"] != "throughput")
+      fatal("nonlinearsigma: --method " + o["method"] + " is not supported, only singlelevel and throughput (the reference's "
+            "driver refuses multilevel for this action; the two-level fill-in is an open question, DESIGN.md 8)");
+    action = std::make_shared<NonlinearSigmaAction>(lat, nullptr, renorm, num("beta"));
+    qoi = std::make_shared<QoI2DMagneticSusceptibility>(lat);
   } else if (a == "schwinger" || a == "gff") {
     auto lat = std::make_shared<Lattice2D>((unsigned)num("Mt_lat"), (unsigned)num("Mt_lat"), coarsenings.at(o["coarsening"]));
     if (a == "schwinger") {
@@ -199,7 +211,9 @@ int main(int argc, char **argv) {
     }
     const double sweeps = num("n_sweep_overrelax") + num("n_sweep_heatbath");
     const bool sweeping = o["sampler"] == "heatbath";
-    const double units = sweeping ? (double)action->sample_size() * sweeps : (double)action->sample_size() * (num("nt") + 1);
+    // updated units per sweep: state entries (links, vertices); vertices for the sigma model (one update moves both angles)
+    const double per_sweep = a == "nonlinearsigma" ? 0.5 * action->sample_size() : (double)action->sample_size();
+    const double units = sweeping ? per_sweep * sweeps : (double)action->sample_size() * (num("nt") + 1);
     std::cout << std::setprecision(6) << "{\"driver\": \"host/driver (C++ Sampler::draw + QoI::evaluate_device + stats_accumulate)\", "
               << "\"ranks\": " << (exchange ? exchange->size() : 1) << ", \"batch\": " << batch << ", \"samples\": " << n_samples
               << ", \"ms_per_sample\": " << 1e3 * tot[2] / n_samples << ", \"updates_per_s\": " << std::scientific

@@ -314,8 +314,9 @@ public:
   }
   int sweep_from_qoi(const double *d_src, double *d_w0, double *d_w1, unsigned batch, unsigned n_or, unsigned n_hb, uint32_t sweep0,
                      int qoi_kind, double *d_q, double *d_acc = nullptr) override {
-    // kinds 1, 2 (plaquette QoIs) belong to the Schwinger action, 3 (phi^2) to the GFF
-    if (n_hb == 0 || qoi_kind == 0 || (qoi_kind == 3) != (abi.kind == MLMCPI_GFF)) return -1;
+    // kinds 1, 2 (plaquette QoIs) belong to the Schwinger action, 3 (phi^2) to the GFF, 4 (chi_m) to the sigma model
+    const int own = abi.kind == MLMCPI_GFF ? 3 : abi.kind == MLMCPI_NONLINEAR_SIGMA ? 4 : 0;
+    if (n_hb == 0 || qoi_kind == 0 || (own ? qoi_kind != own : qoi_kind > 2)) return -1;
     int32_t where = 0;
     if (d_acc)  // record_sample in the same call (per-chain moments on the device)
       check(mlmcpi_lattice_sweep_draw_qoi_record(&abi, d_src, d_w0, d_w1, batch, n_or, n_hb, seed, chain0, sweep0, fuse, qoi_kind, d_q,
@@ -354,7 +355,7 @@ protected:
     if (!c || c->is_rotated()) return false;
     rt = fine->getMt_lat() / c->getMt_lat();
     rx = fine->getMx_lat() / c->getMx_lat();
-    const unsigned per = (abi.kind == MLMCPI_SCHWINGER) ? 2u : 1u;
+    const unsigned per = (abi.kind == MLMCPI_GFF) ? 1u : 2u;  // links (Schwinger) or (theta, phi) per vertex (sigma model)
     return coarse_state->size() == per * c->getMt_lat() * c->getMx_lat() && rt * rx >= 2;
   }
   const std::shared_ptr<Lattice2D> lattice, fine_lattice;
@@ -475,6 +476,37 @@ public:
     if (renormalisation == RenormalisationNonperturbative && beta > 4.0)
       check(mlmcpi_schwinger_beta_coarse_nonperturbative(beta, lattice->getNcells(), both ? 4 : 2, &beta_c), "schwinger_beta_coarse_nonperturbative");
     return std::make_shared<QuenchedSchwingerAction>(coarse_lattice, lattice, renormalisation, beta_c);
+  }
+  std::string info_string() const override { return QFTAction::info_string() + ", beta = " + std::to_string(beta); }
+
+private:
+  const double beta;
+};
+
+/** action/qft/nonlinearsigmaaction.hh: the O(3) nonlinear sigma model, (theta, phi) per vertex.  Heat-bath and
+ *  overrelaxation updates (the index set is the vertices: site_updates takes a vertex index), sweeps, evaluate, force and
+ *  initialise_state run on the device.  Not built: coarse_action / copy_from_* (the reference's driver refuses
+ *  multilevel for this action) and HMC (the reference's force misses the sin theta of the measure). */
+class NonlinearSigmaAction : public QFTAction {
+public:
+  NonlinearSigmaAction(const std::shared_ptr<Lattice2D> lattice_, const std::shared_ptr<Lattice2D> fine_lattice_,
+                       const RenormalisationType r, const double beta_)
+      : QFTAction(lattice_, fine_lattice_, r, MLMCPI_NONLINEAR_SIGMA, beta_, 0.0), beta(beta_) {
+    if (lattice->is_rotated()) fatal("nonlinear sigma action is only built for unrotated lattices");
+    // nonlinearsigmaaction.hh: the heat-bath index set is the vertices (an update changes both angles of one vertex)
+    heatbath_indexset.resize(lattice->getNvertices());
+    for (unsigned int l = 0; l < heatbath_indexset.size(); ++l) heatbath_indexset[l] = l;
+  }
+  unsigned int sample_size() const override { return 2 * lattice->getNvertices(); }
+  double getbeta() const { return beta; }
+  std::shared_ptr<Action> coarse_action() override {
+    fatal("nonlinear sigma action: multilevel / two-level methods are not supported (DESIGN.md 8)");
+  }
+  void copy_from_coarse(const std::shared_ptr<SampleState>, std::shared_ptr<SampleState>) override {
+    fatal("nonlinear sigma action: copy_from_coarse is not supported (DESIGN.md 8)");
+  }
+  void copy_from_fine(const std::shared_ptr<SampleState>, std::shared_ptr<SampleState>) override {
+    fatal("nonlinear sigma action: copy_from_fine is not supported (DESIGN.md 8)");
   }
   std::string info_string() const override { return QFTAction::info_string() + ", beta = " + std::to_string(beta); }
 

@@ -101,5 +101,18 @@ private:
   const unsigned int M_lat;
 };
 
+/** qoi/qft/qoi2dmagneticsusceptibility.cc:7-21: |sum_n sigma_n|^2 / N of the O(3) sigma model */
+class QoI2DMagneticSusceptibility : public QoI {
+public:
+  explicit QoI2DMagneticSusceptibility(const std::shared_ptr<Lattice2D> lattice) : Mt_lat(lattice->getMt_lat()), Mx_lat(lattice->getMx_lat()) {}
+  int fused_kind() const override { return 4; }
+  void evaluate_device(const std::shared_ptr<SampleState> phi, double *d_out) override {
+    if (phi->size() != 2 * Mt_lat * Mx_lat) fatal("Evaluating QoI2DMagneticSusceptibility on state of wrong size.");
+    check(mlmcpi_qoi_magnetic_susceptibility(phi->device(), Mt_lat, Mx_lat, phi->batch(), d_out, nullptr), "qoi_magnetic_susceptibility");
+  }
+private:
+  const unsigned int Mt_lat, Mx_lat;
+};
+
 }  // namespace mlmcpi
 #endif

@@ -16,6 +16,7 @@
  *       1-D paths      x[b*M + j]                         (common/samplestate.hh:19-53)
  *       GFF            phi[b*Mt*Mx + Mt*j + i]            (lattice/lattice2d.hh:230-245)
  *       Schwinger      theta[b*2*Mt*Mx + 2*Mt*j + 2*i + mu]  (lattice/lattice2d.hh:348-354)
+ *       sigma model    phi[b*2*Mt*Mx + 2*(Mt*j + i) + {0: theta, 1: phi}]  (action/qft/nonlinearsigmaaction.hh:381-392)
  *   - randomness is counter based: Philox4x32-10 keyed by `seed`, counter =
  *     (site, chain0 + b, step, purpose<<24 | sub).  Results do not depend on grid shape, tile
  *     size, batch composition or number of GPUs -- to the last bit.
@@ -28,7 +29,7 @@
  *     (<= 4e-14 Schwinger at K = 10, <= 2e-15 rotor).  A heat-bath accept/reject decision that sits on
  *     such a difference flips, after which two chains diverge: compare, checkpoint and resume runs under
  *     one launch plan, and record it (K per launch: bench.py's config.overrelaxation_launches).  The
- *     sweep-by-sweep kernels (GFF always) agree bit for bit whatever the plan.  A QoI fused into the last launch of a
+ *     sweep-by-sweep kernels (GFF and the sigma model always) agree bit for bit whatever the plan.  A QoI fused into the last launch of a
  *     draw (mlmcpi_lattice_sweep_draw_qoi*) sums per-tile partials in the tile order of that launch: under another plan
  *     (MLMCPI_OR_HEAT=split, MLMCPI_OR_KERNEL=block) it agrees to rounding (1e-13).  Spelled out in DESIGN.md 3 / 9.
  */
@@ -57,7 +58,12 @@ enum mlmcpi_action_kind {
   MLMCPI_QUARTIC = 1,   /* action/qm/quarticoscillatoraction.{hh,cc} */
   MLMCPI_ROTOR = 2,     /* action/qm/rotoraction.{hh,cc} */
   MLMCPI_GFF = 3,       /* action/qft/gffaction.{hh,cc} (n_gibbs_smooth = 0) */
-  MLMCPI_SCHWINGER = 4  /* action/qft/quenchedschwingeraction.{hh,cc} */
+  MLMCPI_SCHWINGER = 4, /* action/qft/quenchedschwingeraction.{hh,cc} */
+  MLMCPI_NONLINEAR_SIGMA = 5 /* action/qft/nonlinearsigmaaction.{hh,cc}: O(3) spins as (theta, phi) per vertex; uses `beta`.
+                              * Sweeps, evaluate, force, initialise, site updates and QoI 4; NOT HMC (the reference's force
+                              * samples exp(-S) dtheta dphi, without the sin theta of the measure), copy_from_* or the two-level
+                              * step: MLMCPI_ERR_UNSUPPORTED.  Sweeps are bit-identical whatever the launch plan:
+                              * every update reads spins recomputed from the stored angles. */
 };
 
 /* 1-D path action: lattice/lattice1d.hh:60-101 (M_lat, T_final, a = T_final/M_lat) + the action's
@@ -69,7 +75,7 @@ typedef struct mlmcpi_path_action {
 } mlmcpi_path_action;
 
 /* 2-D lattice action on an unrotated Mt x Mx periodic lattice (lattice/lattice2d.hh:98-437).
- * GFF uses `mass` (mu2 = (mass/Mt)^2, action/qft/gffaction.hh:174-181); Schwinger uses `beta`. */
+ * GFF uses `mass` (mu2 = (mass/Mt)^2, action/qft/gffaction.hh:174-181); Schwinger and the sigma model use `beta`. */
 typedef struct mlmcpi_lattice_action {
   int32_t kind;
   uint32_t Mt, Mx;
@@ -234,7 +240,8 @@ int mlmcpi_lattice_evaluate(const mlmcpi_lattice_action *act, const double *d_ph
                             void *stream);
 int mlmcpi_lattice_force(const mlmcpi_lattice_action *act, const double *d_phi, double *d_f, uint32_t B,
                          void *stream);
-/* Schwinger: U(-pi,pi) per link (quenchedschwingeraction.cc:198-204).  GFF: an exact draw from the action's
+/* Schwinger: U(-pi,pi) per link (quenchedschwingeraction.cc:198-204).  Sigma model: uniform on the sphere
+ * (nonlinearsigmaaction.cc:141-162), cos theta = 1 - 2u, phi = 2 pi u' - pi from the uniforms of entries 2l, 2l + 1.  GFF: an exact draw from the action's
  * distribution, as in the reference (gffaction.cc:121-123: initialise_state = draw) -- by spectral synthesis
  * (see mlmcpi_lattice_exact_draw; its own Philox sub-stream) instead of the reference's sparse Cholesky solve. */
 int mlmcpi_lattice_initialise(const mlmcpi_lattice_action *act, double *d_phi, uint32_t B, uint64_t seed,
@@ -242,7 +249,8 @@ int mlmcpi_lattice_initialise(const mlmcpi_lattice_action *act, double *d_phi, u
 /* OverrelaxedHeatBathSampler::draw on a 2-D action: n_overrelax overrelaxation sweeps then
  * n_heatbath heat-bath sweeps (gffaction.cc:33-42,68-77; quenchedschwingeraction.cc:25-65 with
  * distribution/expcosdistribution.hh:51-65), multicolour order (GFF: (i+j) even, odd; Schwinger:
- * mu=0 & j even, mu=0 & j odd, mu=1 & i even, mu=1 & i odd).  Mt and Mx must be even.  Sweep s
+ * mu=0 & j even, mu=0 & j odd, mu=1 & i even, mu=1 & i odd; sigma model: nonlinearsigmaaction.cc:24-91, (i+j) even,
+ * odd, heat bath by one Philox call of purpose 14 per vertex).  Mt and Mx must be even.  Sweep s
  * uses Philox step sweep0 + s.  d_phi is updated in place; d_scratch has the same size.
  * `fuse` = max number of consecutive overrelaxation sweeps fused into one launch (0 = library default: Schwinger closed
  * form 10; register-block kernels 6, in launches of equal depth, on lattices that 64 x 64 tiles divide; 4 otherwise.  The
@@ -252,7 +260,8 @@ int mlmcpi_lattice_sweep_draw(const mlmcpi_lattice_action *act, double *d_phi, d
                               uint32_t n_overrelax, uint32_t n_heatbath, uint64_t seed, uint32_t chain0,
                               uint32_t sweep0, uint32_t fuse, void *stream);
 /* Action::heatbath_update / overrelaxation_update(state, l) on a 2-D action (gffaction.cc:33-42,68-77;
- * quenchedschwingeraction.cc:46-65): as mlmcpi_path_site_updates; l is a vertex (GFF) or link (Schwinger) index. */
+ * quenchedschwingeraction.cc:46-65; nonlinearsigmaaction.cc:24-91): as mlmcpi_path_site_updates; l is a vertex (GFF, sigma
+ * model: both angles of the vertex) or link (Schwinger) index. */
 int mlmcpi_lattice_site_updates(const mlmcpi_lattice_action *act, double *d_state, uint32_t B, const uint32_t *d_sites,
                                 uint32_t n, uint32_t site, int32_t heat, uint64_t seed, uint32_t chain0, uint32_t step,
                                 void *stream);
@@ -272,7 +281,8 @@ int mlmcpi_lattice_sweep_draw_from(const mlmcpi_lattice_action *act, const doubl
  * still in LDS: Sampler::draw + QoI::evaluate of the loop at montecarlo/montecarlosinglelevel.cc:59-77 in one pass over
  * the state instead of two.  qoi_kind 1 = QoIAvgPlaquette (qoi/qft/qoiavgplaquette.cc:8-27), 2 = QoI2DSusceptibility
  * (qoi/qft/qoi2dsusceptibility.cc:8-27), both for the quenched Schwinger action; 3 = QoI2DPhiSquared
- * (qoi/qft/qoi2dphisquared.cc:8-15) for the GFF action; d_qoi[b].  n_heatbath >= 1 (the draw has to end with a heat-bath
+ * (qoi/qft/qoi2dphisquared.cc:8-15) for the GFF action; 4 = QoI2DMagneticSusceptibility
+ * (qoi/qft/qoi2dmagneticsusceptibility.cc:7-21) for the sigma model; d_qoi[b].  n_heatbath >= 1 (the draw has to end with a heat-bath
  * sweep) and a QoI of the action at hand: MLMCPI_ERR_UNSUPPORTED otherwise, and the caller evaluates the QoI
  * separately.  Same values as mlmcpi_qoi_* on the result up to the order of the summation. */
 int mlmcpi_lattice_sweep_draw_qoi(const mlmcpi_lattice_action *act, const double *d_src, double *d_w0, double *d_w1, uint32_t B,
@@ -378,6 +388,9 @@ int mlmcpi_qoi_avg_plaquette(const double *d_theta, uint32_t Mt, uint32_t Mx, ui
                              void *stream);
 int mlmcpi_qoi_2d_susceptibility(const double *d_theta, uint32_t Mt, uint32_t Mx, uint32_t B, double *d_out,
                                  void *stream);
+/* QoI2DMagneticSusceptibility (qoi/qft/qoi2dmagneticsusceptibility.cc:7-21): d_out[b] = |sum_n sigma_n|^2 / (Mt Mx) of a
+ * sigma-model state */
+int mlmcpi_qoi_magnetic_susceptibility(const double *d_phi, uint32_t Mt, uint32_t Mx, uint32_t B, double *d_out, void *stream);
 
 /* Generic HMCSampler::draw for a 2-D action (streaming leapfrog: one fused force + momentum +
  * position kernel per step).  Same contract as mlmcpi_path_hmc_draw. */

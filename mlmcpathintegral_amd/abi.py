@@ -15,6 +15,7 @@ _VARIANT = os.environ.get("MLMCPI_LIB_VARIANT", "")
 LIB_PATH = os.path.join(_HERE, f"libmlmcpi_hip_{_VARIANT}.so" if _VARIANT else "libmlmcpi_hip.so")
 
 HARMONIC, QUARTIC, ROTOR, GFF, SCHWINGER = range(5)
+NONLINEAR_SIGMA = 5  # O(3) nonlinear sigma model (2-D lattice action, uses beta)
 
 
 class MlmcpiError(RuntimeError):
@@ -109,6 +110,7 @@ SIGNATURES = {
     "mlmcpi_qoi_phi_squared": (_i, [_vp, _u32, _u32, _vp, _vp]),
     "mlmcpi_qoi_avg_plaquette": (_i, [_vp, _u32, _u32, _u32, _vp, _vp]),
     "mlmcpi_qoi_2d_susceptibility": (_i, [_vp, _u32, _u32, _u32, _vp, _vp]),
+    "mlmcpi_qoi_magnetic_susceptibility": (_i, [_vp, _u32, _u32, _u32, _vp, _vp]),
     "mlmcpi_lattice_hmc_workspace_bytes": (_i, [_LA, _u32, C.POINTER(_sz)]),
     "mlmcpi_lattice_hmc_draw": (_i, [_LA, _vp, _u32, _u32, _d, _u32, _u64, _u32, _u32, _vp, _vp, _vp, _vp]),
     "mlmcpi_stats_accumulate": (_i, [_vp, _vp, _u32, _vp]),

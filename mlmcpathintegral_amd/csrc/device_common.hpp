@@ -195,6 +195,7 @@ enum Purpose : uint32_t {
   P_BESSEL = 9,   // two-level step, Schwinger coarsened in both directions: Bessel-product fill-in, sub = call counter
   P_EXACT = 10,   // exact Gaussian sampler of the harmonic oscillator: normals of entries (2 m, 2 m + 1) from site m
   P_GAUSSFILL = 13,  // two-level step, Schwinger coarsened in both directions, Gaussian fill-in: sub 0 (xi, omega), 1, 2 normals
+  P_SIGMA_HB = 14,   // O(3) sigma model heat bath: (u, v) of vertex l = (projection on the neighbour sum, azimuth), sub 0
 };
 
 struct RngKey {

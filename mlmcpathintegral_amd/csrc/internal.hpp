@@ -55,6 +55,16 @@ Tuning tuning();  // a copy taken under the lock: callers snapshot it once per c
 // current device: built and uploaded on first use (device_common.hpp, runtime.hip).
 int vs_table_device(double scale, const uint32_t **d_table);
 
+// the O(3) nonlinear sigma model (sigma2d.hip); arguments checked by the lattice2d.hip entry points that dispatch here
+int sigma_evaluate(const mlmcpi_lattice_action *act, const double *d_phi, uint32_t B, double *d_S, hipStream_t st);
+int sigma_force(const mlmcpi_lattice_action *act, const double *d_phi, double *d_f, uint32_t B, hipStream_t st);
+int sigma_initialise(const mlmcpi_lattice_action *act, double *d_phi, uint32_t B, uint64_t seed, uint32_t chain0, hipStream_t st);
+int sigma_site_updates(const mlmcpi_lattice_action *act, double *d_state, uint32_t B, const uint32_t *d_sites, uint32_t n,
+                       uint32_t site, int32_t heat, uint64_t seed, uint32_t chain0, uint32_t step, hipStream_t st);
+int sigma_sweep_draw(const mlmcpi_lattice_action *act, double *d_phi, double *d_w0, double *d_w1, uint32_t B, uint32_t n_overrelax,
+                     uint32_t n_heatbath, uint64_t seed, uint32_t chain0, uint32_t sweep0, uint32_t fuse, int32_t *result_in,
+                     hipStream_t st, int qoi_kind, double *d_qoi, double *d_acc);
+
 constexpr uint32_t kComputeUnits = 256;  // MI355X
 constexpr uint32_t kMaxFuse = 16;  // max sweeps fused in one launch (kinds travel in a bitmask)
 

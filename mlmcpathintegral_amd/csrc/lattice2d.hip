@@ -2179,7 +2179,7 @@ __global__ void __launch_bounds__(64)
 // ---- host dispatch ----------------------------------------------------------------------------------------
 static int check_lattice_dims(const mlmcpi_lattice_action *act) {
   if (!act) return fail(MLMCPI_ERR_INVALID, "action is NULL");
-  if (act->kind != MLMCPI_GFF && act->kind != MLMCPI_SCHWINGER)
+  if (act->kind != MLMCPI_GFF && act->kind != MLMCPI_SCHWINGER && act->kind != MLMCPI_NONLINEAR_SIGMA)
     return fail(MLMCPI_ERR_INVALID, "kind %d is not a 2-D lattice action", act->kind);
   if (act->Mt < 2 || act->Mx < 2) return fail(MLMCPI_ERR_INVALID, "lattice %u x %u too small", act->Mt, act->Mx);
   if ((uint64_t)act->Mt * act->Mx > (1ull << 30)) return fail(MLMCPI_ERR_INVALID, "lattice too large for 32-bit site indices");
@@ -2188,13 +2188,20 @@ static int check_lattice_dims(const mlmcpi_lattice_action *act) {
 
 static int check_lattice(const mlmcpi_lattice_action *act) {
   if (!act) return fail(MLMCPI_ERR_INVALID, "action is NULL");
-  if (act->kind != MLMCPI_GFF && act->kind != MLMCPI_SCHWINGER)
+  if (act->kind != MLMCPI_GFF && act->kind != MLMCPI_SCHWINGER && act->kind != MLMCPI_NONLINEAR_SIGMA)
     return fail(MLMCPI_ERR_INVALID, "kind %d is not a 2-D lattice action", act->kind);
   if (act->Mt < 2 || act->Mx < 2) return fail(MLMCPI_ERR_INVALID, "lattice %u x %u too small", act->Mt, act->Mx);
   if ((uint64_t)act->Mt * act->Mx > (1ull << 30)) return fail(MLMCPI_ERR_INVALID, "lattice too large for 32-bit site indices");
   // gffaction.hh:169-173: the GFF action requires a square lattice
   if (act->kind == MLMCPI_GFF && act->Mt != act->Mx)
     return fail(MLMCPI_ERR_INVALID, "Lattice has to be squared for GFF action");
+  return MLMCPI_OK;
+}
+
+// the entry points the O(3) sigma model does not take
+static int refuse_sigma(const mlmcpi_lattice_action *act, const char *what) {
+  if (act && act->kind == MLMCPI_NONLINEAR_SIGMA)
+    return fail(MLMCPI_ERR_UNSUPPORTED, "%s is not available for the O(3) nonlinear sigma model (DESIGN 8)", what);
   return MLMCPI_OK;
 }
 
@@ -2408,7 +2415,7 @@ extern "C" {
 int mlmcpi_lattice_state_size(const mlmcpi_lattice_action *act, uint32_t *n) {
   if (int rc = check_lattice(act)) return rc;
   MLMCPI_REQUIRE(n, "n is NULL");
-  *n = (act->kind == MLMCPI_SCHWINGER ? 2u : 1u) * act->Mt * act->Mx;
+  *n = (act->kind == MLMCPI_GFF ? 1u : 2u) * act->Mt * act->Mx;
   return MLMCPI_OK;
 }
 
@@ -2416,6 +2423,7 @@ int mlmcpi_lattice_evaluate(const mlmcpi_lattice_action *act, const double *d_ph
                             void *stream) {
   if (int rc = check_lattice(act)) return rc;
   MLMCPI_REQUIRE(d_phi && d_S && B > 0, "bad arguments");
+  if (act->kind == MLMCPI_NONLINEAR_SIGMA) return sigma_evaluate(act, d_phi, B, d_S, as_stream(stream));
   if (act->kind == MLMCPI_GFF)
     return launch_lattice_reduce<L_GFF_ENERGY>(act->Mt, act->Mx, gff_mu2(*act), d_phi, B, 0.5, d_S, as_stream(stream));
   return launch_lattice_reduce<L_SCHW_ENERGY>(act->Mt, act->Mx, 0.0, d_phi, B, act->beta, d_S, as_stream(stream));
@@ -2425,6 +2433,7 @@ int mlmcpi_lattice_force(const mlmcpi_lattice_action *act, const double *d_phi, 
                          void *stream) {
   if (int rc = check_lattice(act)) return rc;
   MLMCPI_REQUIRE(d_phi && d_f && d_phi != d_f && B > 0, "bad arguments");
+  if (act->kind == MLMCPI_NONLINEAR_SIGMA) return sigma_force(act, d_phi, d_f, B, as_stream(stream));
   dim3 grid(row_blocks(act->Mx, B), B), block(256);
   if (act->kind == MLMCPI_GFF)
     hipLaunchKernelGGL(gff_force_kernel, grid, block, 0, as_stream(stream), act->Mt, act->Mx, gff_mu2(*act), d_phi, d_f);
@@ -2443,6 +2452,7 @@ int mlmcpi_lattice_initialise(const mlmcpi_lattice_action *act, double *d_phi, u
   if (int rc = check_lattice(act)) return rc;
   MLMCPI_REQUIRE(d_phi && B > 0, "bad arguments");
   if (act->kind == MLMCPI_GFF) return gff_initialise_exact(act, d_phi, B, seed, chain0, as_stream(stream));
+  if (act->kind == MLMCPI_NONLINEAR_SIGMA) return sigma_initialise(act, d_phi, B, seed, chain0, as_stream(stream));
   uint32_t n = 0;
   mlmcpi_lattice_state_size(act, &n);
   uint32_t nb = (n + 255) / 256;
@@ -2464,14 +2474,18 @@ static int sweep_draw_impl(const mlmcpi_lattice_action *act, double *d_phi, doub
                            double *d_acc = nullptr) {
   if (int rc = check_lattice(act)) return rc;
   if (qoi_kind) {
-    MLMCPI_REQUIRE(d_qoi && qoi_kind >= 1 && qoi_kind <= 3, "bad QoI arguments");
-    if ((qoi_kind == 3) != (act->kind == MLMCPI_GFF))
+    MLMCPI_REQUIRE(d_qoi && qoi_kind >= 1 && qoi_kind <= 4, "bad QoI arguments");
+    const int own = act->kind == MLMCPI_GFF ? 3 : act->kind == MLMCPI_NONLINEAR_SIGMA ? 4 : 0;
+    if (own ? qoi_kind != own : qoi_kind > 2)
       return fail(MLMCPI_ERR_UNSUPPORTED, "fused QoI %d does not belong to this action", qoi_kind);
     if (n_heatbath == 0) return fail(MLMCPI_ERR_UNSUPPORTED, "the fused QoI needs a draw that ends with a heat-bath sweep");
   }
   MLMCPI_REQUIRE(d_phi && d_w0 && d_w1 && d_phi != d_w0 && d_w0 != d_w1 && B > 0, "bad arguments");
   MLMCPI_REQUIRE(act->Mt % 2 == 0 && act->Mx % 2 == 0, "multicolour sweeps need even Mt, Mx (got %u x %u)", act->Mt,
                  act->Mx);
+  if (act->kind == MLMCPI_NONLINEAR_SIGMA)
+    return sigma_sweep_draw(act, d_phi, d_w0, d_w1, B, n_overrelax, n_heatbath, seed, chain0, sweep0, fuse, result_in,
+                            as_stream(stream), qoi_kind, d_qoi, d_acc);
   const uint32_t Mt = act->Mt, Mx = act->Mx;
   const Tuning tune = tuning();  // ONE snapshot per draw: mlmcpi_set_option on another thread cannot split a launch plan
   const bool schw = act->kind == MLMCPI_SCHWINGER;
@@ -2704,7 +2718,7 @@ int mlmcpi_lattice_sweep_draw_qoi(const mlmcpi_lattice_action *act, const double
                                   uint32_t n_overrelax, uint32_t n_heatbath, uint64_t seed, uint32_t chain0, uint32_t sweep0,
                                   uint32_t fuse, int32_t qoi_kind, double *d_qoi, int32_t *result_in, void *stream) {
   MLMCPI_REQUIRE(result_in, "result_in is NULL");
-  MLMCPI_REQUIRE(qoi_kind >= 1 && qoi_kind <= 3, "qoi_kind %d: 1 = average plaquette, 2 = Q^2 / (4 pi^2), 3 = phi^2 (GFF)", qoi_kind);
+  MLMCPI_REQUIRE(qoi_kind >= 1 && qoi_kind <= 4, "qoi_kind %d: 1 = average plaquette, 2 = Q^2 / (4 pi^2), 3 = phi^2 (GFF), 4 = chi_m (sigma model)", qoi_kind);
   return sweep_draw_impl(act, const_cast<double *>(d_src), d_w0, d_w1, B, n_overrelax, n_heatbath, seed, chain0, sweep0, fuse,
                          result_in, stream, qoi_kind, d_qoi);
 }
@@ -2714,7 +2728,7 @@ int mlmcpi_lattice_sweep_draw_qoi_record(const mlmcpi_lattice_action *act, const
                                          uint32_t sweep0, uint32_t fuse, int32_t qoi_kind, double *d_qoi, double *d_acc,
                                          int32_t *result_in, void *stream) {
   MLMCPI_REQUIRE(result_in && d_acc, "result_in or d_acc is NULL");
-  MLMCPI_REQUIRE(qoi_kind >= 1 && qoi_kind <= 3, "qoi_kind %d: 1 = average plaquette, 2 = Q^2 / (4 pi^2), 3 = phi^2 (GFF)", qoi_kind);
+  MLMCPI_REQUIRE(qoi_kind >= 1 && qoi_kind <= 4, "qoi_kind %d: 1 = average plaquette, 2 = Q^2 / (4 pi^2), 3 = phi^2 (GFF), 4 = chi_m (sigma model)", qoi_kind);
   return sweep_draw_impl(act, const_cast<double *>(d_src), d_w0, d_w1, B, n_overrelax, n_heatbath, seed, chain0, sweep0, fuse,
                          result_in, stream, qoi_kind, d_qoi, d_acc);
 }
@@ -2753,6 +2767,10 @@ int mlmcpi_lattice_site_updates(const mlmcpi_lattice_action *act, double *d_stat
     n = 1;
   }
   if (n == 0) return MLMCPI_OK;
+  if (act->kind == MLMCPI_NONLINEAR_SIGMA) {  // l is a vertex
+    MLMCPI_REQUIRE(d_sites || site < act->Mt * act->Mx, "vertex %u out of range (%u vertices)", site, act->Mt * act->Mx);
+    return sigma_site_updates(act, d_state, B, d_sites, n, site, heat, seed, chain0, step, as_stream(stream));
+  }
   const bool schw = act->kind == MLMCPI_SCHWINGER;
   const uint32_t *vs_table = nullptr;
   if (schw && heat && 2. * act->beta <= kVsKappaMax)
@@ -2909,6 +2927,7 @@ extern "C" {
 // workspace: p | trial A | trial B | energies [4][B] | flags [2][B]
 int mlmcpi_lattice_hmc_workspace_bytes(const mlmcpi_lattice_action *act, uint32_t B, size_t *bytes) {
   if (int rc = check_lattice(act)) return rc;
+  if (int rc = refuse_sigma(act, "HMC (in (theta, phi) the target density carries sin theta, which the reference's force leaves out)")) return rc;
   MLMCPI_REQUIRE(bytes && B > 0, "bad arguments");
   uint32_t n = 0;
   mlmcpi_lattice_state_size(act, &n);
@@ -2920,6 +2939,7 @@ int mlmcpi_lattice_hmc_draw(const mlmcpi_lattice_action *act, double *d_phi, uin
                             uint32_t n_rep, uint64_t seed, uint32_t chain0, uint32_t traj0, void *d_work,
                             int32_t *d_accept, double *d_energies, void *stream) {
   if (int rc = check_lattice(act)) return rc;
+  if (int rc = refuse_sigma(act, "HMC (in (theta, phi) the target density carries sin theta, which the reference's force leaves out)")) return rc;
   MLMCPI_REQUIRE(d_phi && d_work && B > 0 && n_rep > 0, "bad arguments");
   uint32_t n = 0;
   mlmcpi_lattice_state_size(act, &n);
@@ -3037,6 +3057,7 @@ extern "C" {
 
 static int check_levels(const mlmcpi_lattice_action *fine, uint32_t rt, uint32_t rx) {
   if (int rc = check_lattice_dims(fine)) return rc;
+  if (int rc = refuse_sigma(fine, "copying between levels")) return rc;
   if (!((rt == 1 || rt == 2) && (rx == 1 || rx == 2) && rt * rx > 1))
     return fail(MLMCPI_ERR_INVALID, "cannot copy between these lattices (coarsening factors %u x %u)", rt, rx);
   if (fine->Mt % rt || fine->Mx % rx) return fail(MLMCPI_ERR_INVALID, "fine lattice %u x %u cannot be coarsened by %u x %u", fine->Mt, fine->Mx, rt, rx);
@@ -3428,6 +3449,8 @@ static BesselFill make_bessel_fill(double beta) {
 static int check_twolevel(const mlmcpi_lattice_action *fine, const mlmcpi_lattice_action *coarse, uint32_t *rt, uint32_t *rx) {
   if (int rc = check_lattice(fine)) return rc;
   if (int rc = check_lattice(coarse)) return rc;
+  if (int rc = refuse_sigma(fine, "the two-level step")) return rc;
+  if (int rc = refuse_sigma(coarse, "the two-level step")) return rc;
   if (fine->kind != MLMCPI_SCHWINGER || coarse->kind != MLMCPI_SCHWINGER)
     return fail(MLMCPI_ERR_UNSUPPORTED, "two-level step: only the quenched Schwinger action has a device conditioned fine action");
   *rt = (coarse->Mt && fine->Mt == 2 * coarse->Mt) ? 2 : (fine->Mt == coarse->Mt ? 1 : 0);

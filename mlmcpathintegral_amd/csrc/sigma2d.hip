@@ -1,0 +1,455 @@
+// sigma2d.hip -- the O(3) nonlinear sigma model on the 2-D lattice (action/qft/nonlinearsigmaaction.{hh,cc}).
+//
+// State: two doubles per vertex, (theta, phi) = phi[b * 2 Mt Mx + 2 (Mt j + i) + {0, 1}], one double2 per vertex; the spin
+// is sigma(theta, phi) = (sin theta cos phi, sin theta sin phi, cos theta).  S = -1/2 beta sum_n sigma_n . Delta_n, Delta_n
+// the sum of the four neighbours (+i, -i, +j, -j: lattice2d.cc:137-155).
+//
+// CANONICAL FORM.  Every update reads its neighbours as sigma(theta, phi) recomputed from the stored angles (sigma_of), and
+// stores the angles of its result (angles_of).  The sweep kernel keeps the canonical vectors sigma(angles_of(sigma')) in
+// LDS between the fused sweeps of a launch, which is exactly what a later launch would recompute from the stored angles;
+// so a draw gives the same bits whatever the fuse depth, tile or workgroup size (the GFF contract of mlmcpi_hip.h).  The
+// file is compiled without fp contraction (below) so that the same expression cannot round differently in two kernels.
+//
+// Randomness: heat bath of vertex l in sweep s = ONE Philox call (site l, chain, step sweep0 + s, P_SIGMA_HB, sub 0) ->
+// (u, v); initialise: P_INIT, one uniform per state entry (entry 2l -> cos theta = 1 - 2u, 2l + 1 -> phi = 2 pi u - pi).
+#include <mutex>
+
+#include "internal.hpp"
+
+#pragma clang fp contract(off)
+
+namespace mlmcpi {
+
+struct V3 {
+  double x, y, z;
+};
+
+__device__ __forceinline__ V3 sigma_of(double2 a) {
+  double st, ct, sp, cp;
+  sincos(a.x, &st, &ct);
+  sincos(a.y, &sp, &cp);
+  return V3{st * cp, st * sp, ct};
+}
+
+__device__ __forceinline__ double2 angles_of(const V3 &s) {
+  return make_double2(atan2(sqrt(s.x * s.x + s.y * s.y), s.z), atan2(s.y, s.x));
+}
+
+// x ~ p(x) ∝ exp(s x) on [-1, 1] (distribution/compactexpdistribution.{hh,cc}) by inversion:
+//   x = log1p(u expm1(2 s)) / s - 1 = 1 + log1p((1 - u) expm1(-2 s)) / s,
+// the second form because it cannot overflow at large s; x = 2 u - 1 at s = 0 (the reference's form is NaN there).
+__device__ __forceinline__ double compact_exp_inverse(double s, double u) {
+  if (!(s > 0.0)) return 2.0 * u - 1.0;
+  double x = 1.0 + log1p((1.0 - u) * expm1(-2.0 * s)) / s;
+  return x < -1.0 ? -1.0 : (x > 1.0 ? 1.0 : x);
+}
+
+// NonlinearSigmaAction::heatbath_update (nonlinearsigmaaction.cc:24-72) in one frame: sigma' = x D + sqrt(1 - x^2)
+// (cos a E + sin a D x E), D = Delta / |Delta|, E the reference's perpendicular (the component of D of smallest modulus
+// zeroed; std::min_element picks the first), a = 2 pi v.  Delta = 0 leaves the spin as it is.
+__device__ __forceinline__ V3 sigma_heatbath(const V3 &sig, const V3 &Dl, double beta, double u, double v) {
+  const double n2 = Dl.x * Dl.x + Dl.y * Dl.y + Dl.z * Dl.z;
+  if (!(n2 > 0.0)) return sig;
+  const double nrm = sqrt(n2);
+  const V3 d{Dl.x / nrm, Dl.y / nrm, Dl.z / nrm};
+  const double ax = fabs(d.x), ay = fabs(d.y), az = fabs(d.z);
+  int idx = 0;
+  double m = ax;
+  if (ay < m) { idx = 1; m = ay; }
+  if (az < m) { idx = 2; m = az; }
+  const double r = 1.0 / sqrt(1.0 - m * m);
+  V3 e;
+  if (idx == 0) e = V3{0.0, -d.z * r, d.y * r};
+  else if (idx == 1) e = V3{-d.z * r, 0.0, d.x * r};
+  else e = V3{d.y * r, -d.x * r, 0.0};
+  const V3 f{d.y * e.z - d.z * e.y, d.z * e.x - d.x * e.z, d.x * e.y - d.y * e.x};
+  const double x = compact_exp_inverse(beta * nrm, u);
+  const double t = 1.0 - x * x;
+  const double rp = t > 0.0 ? sqrt(t) : 0.0;
+  double sa, ca;
+  sincos(kTwoPi * v, &sa, &ca);
+  const double p = rp * ca, q = rp * sa;
+  return V3{x * d.x + (p * e.x + q * f.x), x * d.y + (p * e.y + q * f.y), x * d.z + (p * e.z + q * f.z)};
+}
+
+// NonlinearSigmaAction::overrelaxation_update (nonlinearsigmaaction.cc:75-91): sigma' = 2 (sigma . D) D - sigma
+__device__ __forceinline__ V3 sigma_overrelax(const V3 &sig, const V3 &Dl) {
+  const double n2 = Dl.x * Dl.x + Dl.y * Dl.y + Dl.z * Dl.z;
+  if (!(n2 > 0.0)) return sig;
+  const double nrm = sqrt(n2);
+  const V3 d{Dl.x / nrm, Dl.y / nrm, Dl.z / nrm};
+  const double c = 2.0 * (sig.x * d.x + sig.y * d.y + sig.z * d.z);
+  return V3{c * d.x - sig.x, c * d.y - sig.y, c * d.z - sig.z};
+}
+
+__device__ __forceinline__ V3 sigma_update(const V3 &sig, const V3 &Dl, bool heat, double beta, const RngKey &key,
+                                           uint32_t site) {
+  if (!heat) return sigma_overrelax(sig, Dl);
+  double u, v;
+  rng_uniforms(key, site, P_SIGMA_HB, 0, u, v);
+  return sigma_heatbath(sig, Dl, beta, u, v);
+}
+
+__device__ __forceinline__ V3 add4(const V3 &a, const V3 &b, const V3 &c, const V3 &d) {
+  return V3{((a.x + b.x) + c.x) + d.x, ((a.y + b.y) + c.y) + d.y, ((a.z + b.z) + c.z) + d.z};
+}
+
+// ---- the multicolour sweep kernel ------------------------------------------------------------------------------------
+// One workgroup = one TW x TH tile of one chain, loaded with a halo of H = 2 K vertices into LDS as three SoA planes of
+// canonical unit vectors; K sweeps (k < k_heat overrelaxation, the rest heat bath), two colour phases each ((i + j) even,
+// then odd), one barrier per phase.  Phase p of the launch updates the sites at least p + 1 from the edge of the loaded
+// region (the region whose values are still exact); the last phase reaches exactly the tile.  The last sweep writes the
+// tile's angles (non-temporal) and, with `partial`, the tile's magnetisation sums partial[(b * tiles + tile) * 3 + c].
+// Tiles on the upper / right edge of a lattice the tiles do not divide reach beyond it: what lies there are periodic images
+// (the plane wraps as often as needed, so any even lattice >= 2 x 2 works), updated like the halo and not written.
+template <int NT>
+__global__ void __launch_bounds__(NT)
+    sigma_sweep_kernel(uint32_t Mt, uint32_t Mx, double beta, const double2 *__restrict__ src, double2 *__restrict__ dst,
+                       uint32_t TW, uint32_t TH, uint32_t tiles_t, uint32_t K, uint32_t k_heat, RngKey key,
+                       double *__restrict__ partial) {
+  extern __shared__ double lds[];
+  __shared__ double red[3][NT / kWave];
+  const uint32_t H = 2 * K, W = TW + 2 * H, HH = TH + 2 * H, P = W * HH;
+  double *sx = lds, *sy = lds + P, *sz = lds + 2 * P;
+  const uint32_t b = blockIdx.y, tile = blockIdx.x, tid = threadIdx.x;
+  const uint32_t i0 = (tile % tiles_t) * TW, j0 = (tile / tiles_t) * TH;
+  // global coordinate of local (li, lj) = ((ai + li) mod Mt, (aj + lj) mod Mx); ai = i0 - H mod Mt, kept non-negative
+  const uint32_t ai = i0 + (H / Mt + 1) * Mt - H, aj = j0 + (H / Mx + 1) * Mx - H;
+  const size_t N = (size_t)Mt * Mx;
+  const double2 *s = src + b * N;
+  double2 *d = dst + b * N;
+  key.chain += b;
+
+  for (uint32_t q = tid; q < P; q += NT) {
+    const uint32_t li = q % W, lj = q / W;
+    const uint32_t gi = (ai + li) % Mt, gj = (aj + lj) % Mx;
+    const V3 v = sigma_of(s[(size_t)gj * Mt + gi]);
+    sx[q] = v.x;
+    sy[q] = v.y;
+    sz[q] = v.z;
+  }
+  __syncthreads();
+
+  double mx = 0.0, my = 0.0, mz = 0.0;
+  for (uint32_t k = 0; k < K; ++k) {
+    const bool heat = k >= k_heat, last = k + 1 == K;
+    RngKey kk = key;
+    kk.step += k;
+    for (uint32_t c = 0; c < 2; ++c) {
+      const uint32_t m = 2 * k + c + 1, rw2 = (W - 2 * m) / 2, rh = HH - 2 * m;
+      for (uint32_t t = tid; t < rw2 * rh; t += NT) {
+        const uint32_t lj = m + t / rw2;
+        const uint32_t li = m + 2 * (t % rw2) + ((c + ai + aj + lj + m) & 1u);
+        const uint32_t q = lj * W + li;
+        const V3 sig{sx[q], sy[q], sz[q]};
+        const V3 Dl = add4(V3{sx[q + 1], sy[q + 1], sz[q + 1]}, V3{sx[q - 1], sy[q - 1], sz[q - 1]},
+                           V3{sx[q + W], sy[q + W], sz[q + W]}, V3{sx[q - W], sy[q - W], sz[q - W]});
+        const uint32_t gi = (ai + li) % Mt, gj = (aj + lj) % Mx;
+        const double2 a = angles_of(sigma_update(sig, Dl, heat, beta, kk, gj * Mt + gi));
+        const V3 cv = sigma_of(a);
+        sx[q] = cv.x;
+        sy[q] = cv.y;
+        sz[q] = cv.z;
+        if (last && li >= H && li < H + TW && lj >= H && lj < H + TH && i0 + (li - H) < Mt && j0 + (lj - H) < Mx) {
+          __builtin_nontemporal_store(a.x, &d[(size_t)gj * Mt + gi].x);
+          __builtin_nontemporal_store(a.y, &d[(size_t)gj * Mt + gi].y);
+          mx += cv.x;
+          my += cv.y;
+          mz += cv.z;
+        }
+      }
+      __syncthreads();
+    }
+  }
+  if (partial) {
+    mx = wave_sum(mx);
+    my = wave_sum(my);
+    mz = wave_sum(mz);
+    if (tid % kWave == 0) {
+      red[0][tid / kWave] = mx;
+      red[1][tid / kWave] = my;
+      red[2][tid / kWave] = mz;
+    }
+    __syncthreads();
+    if (tid < 3) {
+      double acc = 0.0;
+      for (int w = 0; w < NT / kWave; ++w) acc += red[tid][w];
+      partial[((size_t)b * gridDim.x + tile) * 3 + tid] = acc;
+    }
+  }
+}
+
+// ---- streaming kernels: evaluate, magnetisation, force, initialise ----------------------------------------------------
+// per-workgroup partial sums over the vertices of chain b: OP 0 = sigma_n . (sigma_{n+i} + sigma_{n+j}) (the action's bond
+// sum), OP 1 = sigma_n (three components); partial[(b * gridDim.x + blockIdx.x) * NV + c]
+template <int OP>
+__global__ void __launch_bounds__(256) sigma_reduce_kernel(uint32_t Mt, uint32_t Mx, const double2 *__restrict__ phi,
+                                                           double *__restrict__ partial) {
+  constexpr int NV = OP == 0 ? 1 : 3;
+  __shared__ double red[NV][256 / kWave];
+  const uint32_t b = blockIdx.y, N = Mt * Mx;
+  const double2 *p = phi + (size_t)b * N;
+  double acc[NV] = {};
+  for (uint32_t l = blockIdx.x * 256 + threadIdx.x; l < N; l += gridDim.x * 256) {
+    const V3 s = sigma_of(p[l]);
+    if constexpr (OP == 0) {
+      const uint32_t i = l % Mt, j = l / Mt;
+      const V3 a = sigma_of(p[j * Mt + (i + 1 == Mt ? 0 : i + 1)]);
+      const V3 c = sigma_of(p[(j + 1 == Mx ? 0 : j + 1) * Mt + i]);
+      acc[0] += s.x * (a.x + c.x) + s.y * (a.y + c.y) + s.z * (a.z + c.z);
+    } else {
+      acc[0] += s.x;
+      acc[1] += s.y;
+      acc[2] += s.z;
+    }
+  }
+  for (int c = 0; c < NV; ++c) {
+    const double w = wave_sum(acc[c]);
+    if (threadIdx.x % kWave == 0) red[c][threadIdx.x / kWave] = w;
+  }
+  __syncthreads();
+  if (threadIdx.x < NV) {
+    double t = 0.0;
+    for (int w = 0; w < 256 / kWave; ++w) t += red[threadIdx.x][w];
+    partial[((size_t)b * gridDim.x + blockIdx.x) * NV + threadIdx.x] = t;
+  }
+}
+
+// one workgroup per chain: sums the nparts partials of chain b in a fixed order.  OP 0: out[b] = -beta * sum (evaluate);
+// OP 1: out[b] = |M|^2 / N (QoI2DMagneticSusceptibility, qoi2dmagneticsusceptibility.cc:7-21) and, with acc, the
+// record_sample moments acc[b][5] (mlmcpi_stats_accumulate's recurrence)
+template <int OP>
+__global__ void __launch_bounds__(256) sigma_finish_kernel(const double *__restrict__ partial, uint32_t nparts, double scale,
+                                                           double *__restrict__ out, double *__restrict__ acc) {
+  constexpr int NV = OP == 0 ? 1 : 3;
+  __shared__ double red[NV][256 / kWave];
+  const uint32_t b = blockIdx.x;
+  double t[NV] = {};
+  for (uint32_t k = threadIdx.x; k < nparts; k += 256)
+    for (int c = 0; c < NV; ++c) t[c] += partial[((size_t)b * nparts + k) * NV + c];
+  for (int c = 0; c < NV; ++c) {
+    const double w = wave_sum(t[c]);
+    if (threadIdx.x % kWave == 0) red[c][threadIdx.x / kWave] = w;
+  }
+  __syncthreads();
+  if (threadIdx.x != 0) return;
+  double v[NV];
+  for (int c = 0; c < NV; ++c) {
+    v[c] = 0.0;
+    for (int w = 0; w < 256 / kWave; ++w) v[c] += red[c][w];
+  }
+  double q;
+  if constexpr (OP == 0) q = scale * v[0];
+  else q = (v[0] * v[0] + v[1] * v[1] + v[2] * v[2]) * scale;
+  out[b] = q;
+  if (acc) {
+    double *a = acc + 5 * (size_t)b;
+    a[0] += 1.0;
+    a[1] += q;
+    a[2] += q * q;
+    a[3] += q * q * q;
+    a[4] += q * q * q * q;
+  }
+}
+
+// NonlinearSigmaAction::force (nonlinearsigmaaction.cc:94-112): dS/dtheta, dS/dphi per vertex
+__global__ void __launch_bounds__(256) sigma_force_kernel(uint32_t Mt, uint32_t Mx, double beta, const double2 *__restrict__ phi,
+                                                          double2 *__restrict__ f) {
+  const uint32_t b = blockIdx.y, N = Mt * Mx;
+  const double2 *p = phi + (size_t)b * N;
+  double2 *o = f + (size_t)b * N;
+  for (uint32_t l = blockIdx.x * 256 + threadIdx.x; l < N; l += gridDim.x * 256) {
+    const uint32_t i = l % Mt, j = l / Mt;
+    const V3 Dl = add4(sigma_of(p[j * Mt + (i + 1 == Mt ? 0 : i + 1)]), sigma_of(p[j * Mt + (i == 0 ? Mt - 1 : i - 1)]),
+                       sigma_of(p[(j + 1 == Mx ? 0 : j + 1) * Mt + i]), sigma_of(p[(j == 0 ? Mx - 1 : j - 1) * Mt + i]));
+    const double2 a = p[l];
+    double st, ct, sp, cp;
+    sincos(a.x, &st, &ct);
+    sincos(a.y, &sp, &cp);
+    const double dth = -beta * ((Dl.x * cp + Dl.y * sp) * ct - Dl.z * st);
+    const double dph = -beta * (-Dl.x * sp + Dl.y * cp) * st;
+    __builtin_nontemporal_store(dth, &o[l].x);
+    __builtin_nontemporal_store(dph, &o[l].y);
+  }
+}
+
+// initialise_state (nonlinearsigmaaction.cc:141-162): uniform on the sphere, cos theta = 1 - 2u, phi = 2 pi u' - pi, with
+// u, u' the P_INIT uniforms of entries 2l, 2l + 1 (the same stream as the Schwinger links' initialisation)
+__global__ void __launch_bounds__(256) sigma_init_kernel(uint32_t N, RngKey key0, double2 *__restrict__ x) {
+  const uint32_t b = blockIdx.y;
+  RngKey key = key0;
+  key.chain += b;
+  double2 *xb = x + (size_t)b * N;
+  for (uint32_t l = blockIdx.x * 256 + threadIdx.x; l < N; l += gridDim.x * 256) {
+    double u, u2, dummy;
+    rng_uniforms(key, 2 * l, P_INIT, 0, u, dummy);
+    rng_uniforms(key, 2 * l + 1, P_INIT, 0, u2, dummy);
+    xb[l] = make_double2(acos(1.0 - 2.0 * u), -kPi + 2.0 * kPi * u2);
+  }
+}
+
+// Action::heatbath_update / overrelaxation_update(state, l) for a list of vertices: one thread per chain walks the list in
+// order on the state in global memory (mlmcpi_lattice_site_updates), the sweep kernel's arithmetic and random numbers
+__global__ void __launch_bounds__(64) sigma_site_update_kernel(uint32_t Mt, uint32_t Mx, double beta, double2 *__restrict__ phi,
+                                                               uint32_t B, const uint32_t *__restrict__ sites, uint32_t n,
+                                                               uint32_t site, int heat, RngKey key) {
+  const uint32_t b = blockIdx.x * 64 + threadIdx.x;
+  if (b >= B) return;
+  key.chain += b;
+  double2 *p = phi + (size_t)b * Mt * Mx;
+  for (uint32_t k = 0; k < n; ++k) {
+    const uint32_t l = sites ? sites[k] : site;
+    if (l >= Mt * Mx) continue;  // not a vertex: ignored (the list is device memory the host cannot check)
+    const uint32_t i = l % Mt, j = l / Mt;
+    const V3 Dl = add4(sigma_of(p[j * Mt + (i + 1 == Mt ? 0 : i + 1)]), sigma_of(p[j * Mt + (i == 0 ? Mt - 1 : i - 1)]),
+                       sigma_of(p[(j + 1 == Mx ? 0 : j + 1) * Mt + i]), sigma_of(p[(j == 0 ? Mx - 1 : j - 1) * Mt + i]));
+    p[l] = angles_of(sigma_update(sigma_of(p[l]), Dl, heat != 0, beta, key, l));
+  }
+}
+
+// ---- host side ----------------------------------------------------------------------------------------------------
+namespace {
+
+constexpr uint32_t kSigmaLdsMax = 160 * 1024 - 512;  // dynamic LDS a workgroup may take (static: the 3 x NT/64 reduction)
+// default plan (profiles/sigma_fuse_tile.json, 1024^2 x 32, 10 + 1 sweeps): 64 x 32 tiles of 256 threads,
+// 2 sweeps per launch -- 8.78 ms per draw against 9.94 ms at fuse = 1 and 10.25 ms on 32 x 32 tiles; the kernel is
+// issue-bound, so deeper fusion buys little (fuse 3: 8.75 ms) and at fuse 4 the 92 KB tile leaves one workgroup per CU
+constexpr uint32_t kSigmaTileW = 64, kSigmaTileH = 32;
+constexpr uint32_t kSigmaFuse = 2;
+
+uint32_t stream_blocks(uint32_t N, uint32_t B) {
+  uint32_t want = (2048 + B - 1) / B, need = (N + 255) / 256;
+  return want < need ? (want ? want : 1) : need;
+}
+
+std::mutex g_sigma_attr_mutex;
+bool g_sigma_attr_set[64] = {false};
+
+int sigma_init_attrs() {
+  int dev = 0;
+  MLMCPI_HIP_TRY(hipGetDevice(&dev));
+  if (dev < 0 || dev >= 64) return fail(MLMCPI_ERR_INVALID, "device index %d out of range", dev);
+  std::lock_guard<std::mutex> lock(g_sigma_attr_mutex);
+  if (g_sigma_attr_set[dev]) return MLMCPI_OK;
+  MLMCPI_HIP_TRY(hipFuncSetAttribute((const void *)sigma_sweep_kernel<256>, hipFuncAttributeMaxDynamicSharedMemorySize, kSigmaLdsMax));
+  MLMCPI_HIP_TRY(hipFuncSetAttribute((const void *)sigma_sweep_kernel<512>, hipFuncAttributeMaxDynamicSharedMemorySize, kSigmaLdsMax));
+  MLMCPI_HIP_TRY(hipFuncSetAttribute((const void *)sigma_sweep_kernel<1024>, hipFuncAttributeMaxDynamicSharedMemorySize, kSigmaLdsMax));
+  g_sigma_attr_set[dev] = true;
+  return MLMCPI_OK;
+}
+
+template <int OP>
+int sigma_reduce(uint32_t Mt, uint32_t Mx, const double *d_phi, uint32_t B, double scale, double *d_out, hipStream_t st) {
+  constexpr int NV = OP == 0 ? 1 : 3;
+  const uint32_t nb = stream_blocks(Mt * Mx, B);
+  void *part = nullptr;
+  if (int rc = scratch((size_t)B * nb * NV * sizeof(double), &part, st)) return rc;
+  hipLaunchKernelGGL(sigma_reduce_kernel<OP>, dim3(nb, B), dim3(256), 0, st, Mt, Mx, (const double2 *)d_phi, (double *)part);
+  MLMCPI_LAUNCH_CHECK("sigma_reduce_kernel");
+  hipLaunchKernelGGL(sigma_finish_kernel<OP>, dim3(B), dim3(256), 0, st, (const double *)part, nb, scale, d_out, (double *)nullptr);
+  MLMCPI_LAUNCH_CHECK("sigma_finish_kernel");
+  return MLMCPI_OK;
+}
+
+}  // namespace
+
+int sigma_evaluate(const mlmcpi_lattice_action *act, const double *d_phi, uint32_t B, double *d_S, hipStream_t st) {
+  return sigma_reduce<0>(act->Mt, act->Mx, d_phi, B, -act->beta, d_S, st);
+}
+
+int sigma_force(const mlmcpi_lattice_action *act, const double *d_phi, double *d_f, uint32_t B, hipStream_t st) {
+  hipLaunchKernelGGL(sigma_force_kernel, dim3(stream_blocks(act->Mt * act->Mx, B), B), dim3(256), 0, st, act->Mt, act->Mx, act->beta,
+                     (const double2 *)d_phi, (double2 *)d_f);
+  MLMCPI_LAUNCH_CHECK("sigma_force_kernel");
+  return MLMCPI_OK;
+}
+
+int sigma_initialise(const mlmcpi_lattice_action *act, double *d_phi, uint32_t B, uint64_t seed, uint32_t chain0, hipStream_t st) {
+  hipLaunchKernelGGL(sigma_init_kernel, dim3(stream_blocks(act->Mt * act->Mx, B), B), dim3(256), 0, st, act->Mt * act->Mx,
+                     make_key(seed, chain0, 0), (double2 *)d_phi);
+  MLMCPI_LAUNCH_CHECK("sigma_init_kernel");
+  return MLMCPI_OK;
+}
+
+int sigma_site_updates(const mlmcpi_lattice_action *act, double *d_state, uint32_t B, const uint32_t *d_sites, uint32_t n,
+                       uint32_t site, int32_t heat, uint64_t seed, uint32_t chain0, uint32_t step, hipStream_t st) {
+  hipLaunchKernelGGL(sigma_site_update_kernel, dim3((B + 63) / 64), dim3(64), 0, st, act->Mt, act->Mx, act->beta, (double2 *)d_state,
+                     B, d_sites, n, site, (int)heat, make_key(seed, chain0, step));
+  MLMCPI_LAUNCH_CHECK("sigma_site_update_kernel");
+  return MLMCPI_OK;
+}
+
+// the sweeps of mlmcpi_lattice_sweep_draw* (argument checks done by the caller): launches of up to `fuse` sweeps, read
+// `src`, write `dst`, then src <- dst and dst <- the other work buffer (lattice2d.hip's convention); qoi_kind 4 sums the
+// magnetisation in the last launch and finishes chi_m (and the record_sample moments with d_acc) in one more.
+int sigma_sweep_draw(const mlmcpi_lattice_action *act, double *d_phi, double *d_w0, double *d_w1, uint32_t B, uint32_t n_overrelax,
+                     uint32_t n_heatbath, uint64_t seed, uint32_t chain0, uint32_t sweep0, uint32_t fuse, int32_t *result_in,
+                     hipStream_t st, int qoi_kind, double *d_qoi, double *d_acc) {
+  if (int rc = sigma_init_attrs()) return rc;
+  const uint32_t Mt = act->Mt, Mx = act->Mx;
+  const Tuning tune = tuning();
+  const uint32_t TW = tune.tile_w ? tune.tile_w : kSigmaTileW, TH = tune.tile_h ? tune.tile_h : kSigmaTileH;
+  const uint32_t NT = tune.tile_w ? tune.tile_nt : 256;
+  uint32_t kmax = fuse ? fuse : kSigmaFuse;
+  if (kmax > kMaxFuse) kmax = kMaxFuse;
+  auto lds_bytes = [&](uint32_t K) { return (size_t)(TW + 4 * K) * (TH + 4 * K) * 3 * sizeof(double); };
+  while (kmax > 1 && lds_bytes(kmax) > kSigmaLdsMax) --kmax;
+  if (lds_bytes(kmax) > kSigmaLdsMax) return fail(MLMCPI_ERR_INVALID, "sigma sweep tile %u x %u does not fit in LDS", TW, TH);
+  const uint32_t tiles_t = (Mt + TW - 1) / TW, tiles = tiles_t * ((Mx + TH - 1) / TH);
+  const uint32_t total = n_overrelax + n_heatbath;
+  const size_t state_bytes = (size_t)B * 2 * Mt * Mx * sizeof(double);
+  double *part = nullptr;
+  if (qoi_kind) {
+    void *p = nullptr;
+    if (int rc = scratch((size_t)B * tiles * 3 * sizeof(double), &p, st)) return rc;
+    part = (double *)p;
+  }
+  double *src = d_phi, *dst = d_w0;
+  for (uint32_t s = 0; s < total;) {
+    const uint32_t K = total - s < kmax ? total - s : kmax;
+    const uint32_t k_heat = s >= n_overrelax ? 0 : (n_overrelax - s < K ? n_overrelax - s : K);
+    const bool last = s + K == total;
+    const RngKey key = make_key(seed, chain0, sweep0 + s);
+    const dim3 grid(tiles, B);
+    const size_t lds = lds_bytes(K);
+    double *pp = last ? part : nullptr;
+    if (NT == 1024)
+      hipLaunchKernelGGL(sigma_sweep_kernel<1024>, grid, dim3(1024), lds, st, Mt, Mx, act->beta, (const double2 *)src, (double2 *)dst,
+                         TW, TH, tiles_t, K, k_heat, key, pp);
+    else if (NT == 512)
+      hipLaunchKernelGGL(sigma_sweep_kernel<512>, grid, dim3(512), lds, st, Mt, Mx, act->beta, (const double2 *)src, (double2 *)dst,
+                         TW, TH, tiles_t, K, k_heat, key, pp);
+    else
+      hipLaunchKernelGGL(sigma_sweep_kernel<256>, grid, dim3(256), lds, st, Mt, Mx, act->beta, (const double2 *)src, (double2 *)dst,
+                         TW, TH, tiles_t, K, k_heat, key, pp);
+    MLMCPI_LAUNCH_CHECK("sigma_sweep_kernel");
+    src = dst;
+    dst = dst == d_w0 ? d_w1 : d_w0;
+    s += K;
+  }
+  if (qoi_kind) {
+    hipLaunchKernelGGL(sigma_finish_kernel<1>, dim3(B), dim3(256), 0, st, (const double *)part, tiles, 1.0 / ((double)Mt * Mx), d_qoi,
+                       d_acc);
+    MLMCPI_LAUNCH_CHECK("sigma_finish_kernel");
+  }
+  if (result_in)
+    *result_in = total == 0 ? -1 : (src == d_w0 ? 0 : 1);
+  else if (src != d_phi)
+    MLMCPI_HIP_TRY(hipMemcpyAsync(d_phi, src, state_bytes, hipMemcpyDeviceToDevice, st));
+  return MLMCPI_OK;
+}
+
+}  // namespace mlmcpi
+
+using namespace mlmcpi;
+
+extern "C" {
+
+// QoI2DMagneticSusceptibility::evaluate (qoi/qft/qoi2dmagneticsusceptibility.cc:7-21): chi_m = |sum_n sigma_n|^2 / N
+int mlmcpi_qoi_magnetic_susceptibility(const double *d_phi, uint32_t Mt, uint32_t Mx, uint32_t B, double *d_out, void *stream) {
+  MLMCPI_REQUIRE(d_phi && d_out && B > 0 && Mt > 1 && Mx > 1, "bad arguments");
+  MLMCPI_REQUIRE((uint64_t)Mt * Mx <= (1ull << 30), "lattice too large for 32-bit site indices");
+  return sigma_reduce<1>(Mt, Mx, d_phi, B, 1.0 / ((double)Mt * Mx), d_out, as_stream(stream));
+}
+
+}  // extern "C"

@@ -9,7 +9,7 @@ import ctypes as C
 import torch
 
 from . import abi
-from .abi import GFF, HARMONIC, QUARTIC, ROTOR, SCHWINGER  # noqa: F401
+from .abi import GFF, HARMONIC, NONLINEAR_SIGMA, QUARTIC, ROTOR, SCHWINGER  # noqa: F401
 
 
 def _p(t):
@@ -296,7 +296,7 @@ def lattice_sweep_draw_pingpong(act, a, b, n_overrelax, n_heatbath, seed, chain0
 
 def lattice_sweep_draw_qoi(act, src, w0, w1, n_overrelax, n_heatbath, seed, chain0, sweep0, qoi_kind, fuse=0, acc=None):
     """draw + QoI in one pass (mlmcpi_lattice_sweep_draw_qoi): reads `src` (w1 may be src), returns (result tensor, the
-    other work tensor, qoi [B]); qoi_kind 1 = average plaquette, 2 = Q^2 / (4 pi^2).  acc [B, 5]: record_sample of the QoI
+    other work tensor, qoi [B]); qoi_kind 1 = average plaquette, 2 = Q^2 / (4 pi^2), 3 = phi^2 (GFF), 4 = chi_m (sigma model).  acc [B, 5]: record_sample of the QoI
     as well, in the same call (mlmcpi_lattice_sweep_draw_qoi_record)."""
     where = C.c_int32(0)
     q = torch.empty(src.shape[0], dtype=torch.float64, device=src.device)
@@ -348,6 +348,14 @@ def qoi_avg_plaquette(theta, Mt, Mx):
 def qoi_2d_susceptibility(theta, Mt, Mx):
     out = torch.empty(theta.shape[0], dtype=torch.float64, device=theta.device)
     abi.call("mlmcpi_qoi_2d_susceptibility", _p(theta), Mt, Mx, theta.shape[0], _p(out), _stream())
+    return out
+
+
+def qoi_magnetic_susceptibility(phi, Mt, Mx):
+    """QoI2DMagneticSusceptibility of sigma-model states [B, 2 Mt Mx]: |sum_n sigma_n|^2 / (Mt Mx) per chain"""
+    _check_state(phi, 2 * Mt * Mx)
+    out = torch.empty(phi.shape[0], dtype=torch.float64, device=phi.device)
+    abi.call("mlmcpi_qoi_magnetic_susceptibility", _p(phi), Mt, Mx, phi.shape[0], _p(out), _stream())
     return out
 
 
