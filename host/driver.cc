@@ -11,6 +11,8 @@
 //          --sampler hierarchical --n_level 2 --epsilon 0.005
 //   driver --action nonlinearsigma --Mt_lat 16 --beta 1 --sampler heatbath --n_samples 20000
 //          (O(3) sigma model: singlelevel and throughput with the heat-bath sampler only)
+//   driver --action rotor --M_lat 256 --T_final 25.6 --m0 0.25 --sampler cluster --n_updates 10 --n_samples 20000
+//          (cluster samplers: rotor and schwinger; also --coarsesampler cluster for twolevel / hierarchical rotor runs)
 //   driver --method throughput --action schwinger --Mt_lat 1024 --sampler heatbath --batch 32 --n_samples 20
 //          (the sampling loop of MonteCarloSingleLevel on a batch of chains, statistics accumulated on the device:
 //           prints link-updates/s of the C++ path)
@@ -34,7 +36,7 @@ int main(int argc, char **argv) {
       {"sampler", "hmc"}, {"nt", "100"}, {"dt", "0.1"}, {"n_burnin", "100"}, {"n_samples", "20000"}, {"n_sweep_overrelax", "10"},
       {"n_sweep_heatbath", "1"}, {"autotune", "1"}, {"window", "20"}, {"method", "singlelevel"}, {"n_level", "3"},
       {"epsilon", "0.01"}, {"coarsening", "both"}, {"coarsesampler", "hmc"}, {"renormalisation", "none"}, {"n_meas", "200"},
-      {"batch", "1"}, {"seed", "2481317"}, {"warmup", "5"}, {"random_order", "0"}};
+      {"batch", "1"}, {"seed", "2481317"}, {"warmup", "5"}, {"random_order", "0"}, {"n_updates", "10"}};
   for (int i = 1; i + 1 < argc; i += 2) {
     if (std::strncmp(argv[i], "--", 2) || !o.count(argv[i] + 2)) fatal(std::string("unknown option ") + argv[i]);
     o[argv[i] + 2] = argv[i + 1];
@@ -69,6 +71,13 @@ int main(int argc, char **argv) {
   const std::map<std::string, CoarseningType> coarsenings = {{"both", CoarsenBoth}, {"temporal", CoarsenTemporal},
       {"spatial", CoarsenSpatial}, {"alternate", CoarsenAlternate}, {"rotate", CoarsenRotate}};
   if (!coarsenings.count(o["coarsening"])) fatal("unknown coarsening " + o["coarsening"]);
+  // driver_qm.cc:62-70, driver_qft.cc:69-80: the cluster sampler exists for the rotor and the quenched Schwinger action
+  const bool wants_cluster = o["sampler"] == "cluster" ||
+                             (o["coarsesampler"] == "cluster" && (o["sampler"] == "hierarchical" || o["method"] == "twolevel"));
+  if (wants_cluster && a == "nonlinearsigma")
+    fatal(" cluster not supported for chosen action: nonlinearsigma needs the generic 2-D cluster update (connected components "
+          "on the lattice), which is not built (DESIGN.md 8)");
+  if (wants_cluster && a != "rotor" && a != "schwinger") fatal(" cluster not supported for chosen action.");
   if (a == "harmonicoscillator" || a == "quarticoscillator" || a == "rotor") {
     auto lat = std::make_shared<Lattice1D>((unsigned)num("M_lat"), num("T_final"));
     if (a == "harmonicoscillator") {
@@ -85,6 +94,9 @@ int main(int argc, char **argv) {
       cfa_factory = std::make_shared<GaussianConditionedFineActionFactory>();
     } else {
       action = std::make_shared<RotorAction>(lat, renorm, num("m0"));
+      // RotorAction::chit_exact (rotoraction.cc:92-95) = Phi_chit(m0 / a, M) / m0 = [(M / kappa) Phi_chit(kappa, M)] / T_final
+      check(mlmcpi_schwinger_chit_analytical(num("m0") / lat->geta_lat(), lat->getM_lat(), &analytic), "chit_analytical");
+      analytic /= lat->getT_final();
       qoi = std::make_shared<QoISusceptibility>(lat);
       qoi_factory = std::make_shared<QoISusceptibilityFactory>();
       cfa_factory = std::make_shared<RotorConditionedFineActionFactory>();
@@ -125,6 +137,11 @@ int main(int argc, char **argv) {
       return std::make_shared<HMCSamplerFactory>(hp);
     }
     if (name == "exact") return std::make_shared<ExactSamplerFactory>();  // driver_qm.cc: sampler = 'exact' (harmonic oscillator, GFF)
+    if (name == "cluster") {  // driver_qm.cc:62-70, driver_qft.cc:69-80
+      ClusterParameters cp;
+      cp.n_burnin = (unsigned)num("n_burnin"); cp.n_updates = (unsigned)num("n_updates"); cp.batch = batch;
+      return std::make_shared<ClusterSamplerFactory>(cp);
+    }
     if (name != "heatbath") fatal("unknown sampler " + name);
     OverrelaxedHeatBathParameters hb;
     hb.n_sweep_overrelax = (unsigned)num("n_sweep_overrelax"); hb.n_sweep_heatbath = (unsigned)num("n_sweep_heatbath");
@@ -213,8 +230,17 @@ int main(int argc, char **argv) {
     const bool sweeping = o["sampler"] == "heatbath";
     // updated units per sweep: state entries (links, vertices); vertices for the sigma model (one update moves both angles)
     const double per_sweep = a == "nonlinearsigma" ? 0.5 * action->sample_size() : (double)action->sample_size();
-    const double units = sweeping ? per_sweep * sweeps : (double)action->sample_size() * (num("nt") + 1);
+    double units = sweeping ? per_sweep * sweeps : (double)action->sample_size() * (num("nt") + 1);
+    std::string unit_name = sweeping ? "site updates per draw" : "force evaluations per draw";
+    if (auto rotor_cluster = std::dynamic_pointer_cast<ClusterSampler>(sampler)) {  // what a draw moved: flipped sites
+      units = rotor_cluster->mean_cluster_size() * num("n_updates");
+      unit_name = "flipped sites per draw (measured mean)";
+    } else if (o["sampler"] == "cluster") {  // Schwinger: every draw rewrites the whole link field
+      units = (double)action->sample_size();
+      unit_name = "state entries written per draw";
+    }
     std::cout << std::setprecision(6) << "{\"driver\": \"host/driver (C++ Sampler::draw + QoI::evaluate_device + stats_accumulate)\", "
+              << "\"units\": \"" << unit_name << "\", \"units_per_draw\": " << units << ", "
               << "\"ranks\": " << (exchange ? exchange->size() : 1) << ", \"batch\": " << batch << ", \"samples\": " << n_samples
               << ", \"ms_per_sample\": " << 1e3 * tot[2] / n_samples << ", \"updates_per_s\": " << std::scientific
               << units * batch * world * n_samples / tot[2] << std::fixed << ", \"qoi_mean\": " << tot[1] / tot[0] << "}" << std::endl;

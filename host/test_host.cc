@@ -309,6 +309,18 @@ int main(int argc, char **argv) {
     // (the O(a) formula of rotoraction.cc:92-95 is only a rough guide at a/m0 = 0.5: printed, not gated; the gate above is the
     // combined-error comparison of the two samplers)
     std::printf(" rotor chi_t O(a) formula: %.6f\n", act->chit_perturbative());
+    // the cluster sampler (reflection clusters, 10 updates per draw) against the same direct heat-bath chain
+    ClusterParameters cp;
+    cp.n_burnin = 100; cp.n_updates = 10;
+    MonteCarloSingleLevel cl(act, std::make_shared<QoISusceptibility>(lat), std::make_shared<ClusterSamplerFactory>(cp), mp);
+    cl.evaluate();
+    auto c = cl.get_statistics();
+    double exact = 0;
+    check(mlmcpi_schwinger_chit_analytical(act->getm0() / lat->geta_lat(), lat->getM_lat(), &exact), "chit_analytical");
+    exact /= lat->getT_final();
+    std::printf(" rotor chi_t: cluster %.6f +- %.6f, exact %.6f\n", c->average(), c->error(), exact);
+    ZEXPECT(c->average(), std::hypot(c->error(), b->error()), b->average(), 5, "rotor cluster chi_t vs heat bath");
+    ZEXPECT(c->average(), c->error(), exact, 5, "rotor cluster chi_t vs exact");
   }
   // ---- Schwinger 16 x 16, beta = 2, CoarsenAlternate: hierarchical sampler (16x16 -> 8x16 -> 8x8) and a
   //      3-level multilevel estimate of the average plaquette (I1(2)/I0(2) = 0.697775) -----------------------------

@@ -3,6 +3,7 @@
 // OverrelaxedHeatBathSampler (sampler/overrelaxedheatbathsampler.{hh,cc}) driving device chains.
 #ifndef MLMCPI_SAMPLER_HH
 #define MLMCPI_SAMPLER_HH
+#include <chrono>
 #include <cmath>
 #include <iomanip>
 #include <iostream>
@@ -379,6 +380,137 @@ public:
   }
 private:
   const unsigned int batch;
+};
+
+/** sampler/clustersampler.hh:29 (section clusteralgorithm: of the parameter file) */
+struct ClusterParameters {
+  unsigned int n_burnin = 100;
+  unsigned int n_updates = 10;
+  unsigned int batch = 1;
+  unsigned int n_meas = 20;  // draws timed for cost_per_sample (10 000 in the reference's constructor)
+};
+
+/** ClusterSampler on a 1-D lattice (sampler/clustersampler.{hh,cc}; single_cluster_update1d): the rotor.  One draw =
+ *  n_updates reflection-cluster updates of every chain in one launch (mlmcpi_path_cluster_draw), then the copy out.
+ *  Counters advance by n_updates per draw (clustersampler.cc:44-48); set_state is a no-op (clustersampler.hh:116). */
+class ClusterSampler : public Sampler {
+public:
+  ClusterSampler(const std::shared_ptr<Action> action_, const ClusterParameters p)
+      : Sampler(), action(std::dynamic_pointer_cast<RotorAction>(action_)), n_burnin(p.n_burnin), n_updates(p.n_updates),
+        B(p.batch), sites(p.batch, sizeof(uint32_t)) {
+    if (!action) fatal(" cluster not supported for chosen action.");
+    fold_period = std::max<uint64_t>(1, std::min<uint64_t>(1024, (1ull << 31) / ((uint64_t)std::max(1u, n_updates) * action->sample_size())));
+    x_path_cur = std::make_shared<SampleState>(action->sample_size(), B);
+    action->initialise_state(x_path_cur);
+    std::shared_ptr<SampleState> tmp = std::make_shared<SampleState>(action->sample_size(), B);
+    for (unsigned int i = 0; i < n_burnin; ++i) draw(tmp);
+    check(mlmcpi_stream_synchronize(nullptr), "sync");
+    const auto t0 = std::chrono::steady_clock::now();
+    for (unsigned int k = 0; k < p.n_meas; ++k) draw(tmp);
+    check(mlmcpi_stream_synchronize(nullptr), "sync");
+    cost_per_sample_ = 1.E6 * std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count() / (p.n_meas ? p.n_meas : 1);
+    reset_stats();
+    fold_sites();
+    flipped_total = 0.0;
+  }
+  void draw(std::shared_ptr<SampleState> x_path) override {
+    if (update_counter > 0xFFFFFFFFu - n_updates) fatal("ClusterSampler: the 32-bit update counter of the Philox contract is used up.");
+    check(mlmcpi_path_cluster_draw(&action->abi_action(), x_path_cur->device_mutable(), B, n_updates, action->get_seed(),
+                                   action->get_chain0(), update_counter, (uint32_t *)sites.ptr(), nullptr), "path_cluster_draw");
+    update_counter += n_updates;
+    if (++draws_unfolded >= fold_period) fold_sites();
+    n_total_samples += n_updates;
+    n_accepted_samples += n_updates;
+    x_path->data = x_path_cur->data;
+    accept = true;
+  }
+  void set_state(std::shared_ptr<SampleState>) override {}
+  double cost_per_sample() override { return cost_per_sample_; }
+  /** flipped sites per update, averaged over chains and over the updates since construction */
+  double mean_cluster_size() {
+    if (!n_total_samples) return 0.0;
+    fold_sites();
+    return flipped_total / B / n_total_samples;
+  }
+  void show_stats() override {
+    std::cout << std::setprecision(3) << std::fixed << "  cluster updates per draw = " << n_updates << std::endl
+              << "  mean cluster size        = " << mean_cluster_size() << " sites" << std::endl;
+  }
+
+private:
+  /** the device counters are 32 bits per chain: add them to the host total and zero them before they can wrap */
+  void fold_sites() {
+    for (uint32_t v : sites.download<uint32_t>()) flipped_total += v;
+    check(mlmcpi_memset(sites.ptr(), 0, B * sizeof(uint32_t), nullptr), "mlmcpi_memset");
+    draws_unfolded = 0;
+  }
+  const std::shared_ptr<RotorAction> action;
+  const unsigned int n_burnin, n_updates, B;
+  std::shared_ptr<SampleState> x_path_cur;
+  DeviceVector sites;  // uint32 per chain: flipped sites since the last fold, added up on the device
+  double flipped_total = 0.0;
+  // an update flips at most M sites: fold before 2^31 could have been added to a chain's counter, at least every 1024 draws
+  uint64_t fold_period = 1;
+  uint64_t draws_unfolded = 0;
+  uint32_t update_counter = 0;
+  double cost_per_sample_ = 0.0;
+};
+
+/** sampler/quenchedschwingerclustersampler.{hh,cc}: the sampler's state is the plaquette path psi (a rotor with
+ *  m0 / a = beta on Mt Mx sites); a draw advances it by n_updates cluster updates and overwrites the link field. */
+class QuenchedSchwingerClusterSampler : public Sampler {
+public:
+  QuenchedSchwingerClusterSampler(const std::shared_ptr<Action> action_, const ClusterParameters p)
+      : Sampler(), action(std::dynamic_pointer_cast<QuenchedSchwingerAction>(action_)), n_updates(p.n_updates), B(p.batch) {
+    if (!action) fatal(" cluster not supported for chosen action.");
+    const mlmcpi_lattice_action &abi = action->abi_action();
+    size_t bytes = 0;
+    check(mlmcpi_schwinger_cluster_workspace_bytes(&abi, B, &bytes), "schwinger_cluster_workspace_bytes");
+    work = std::make_shared<DeviceBuffer>(bytes);
+    check(mlmcpi_memset(work->p, 0, bytes, nullptr), "mlmcpi_memset");
+    psi = std::make_shared<DeviceBuffer>((size_t)B * abi.Mt * abi.Mx * sizeof(double));
+    check(mlmcpi_schwinger_cluster_init(&abi, psi->p, B, action->get_seed(), action->get_chain0(), nullptr), "schwinger_cluster_init");
+    std::shared_ptr<SampleState> tmp = std::make_shared<SampleState>(action->sample_size(), B);
+    for (unsigned int i = 0; i < p.n_burnin; ++i) draw(tmp);
+    check(mlmcpi_stream_synchronize(nullptr), "sync");
+    const auto t0 = std::chrono::steady_clock::now();
+    for (unsigned int k = 0; k < p.n_meas; ++k) draw(tmp);
+    check(mlmcpi_stream_synchronize(nullptr), "sync");
+    cost_per_sample_ = 1.E6 * std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count() / (p.n_meas ? p.n_meas : 1);
+    reset_stats();
+  }
+  void draw(std::shared_ptr<SampleState> phi_state) override {
+    if (phi_state->batch() != B || phi_state->size() != action->sample_size()) fatal("cluster draw into a state of wrong shape.");
+    check(mlmcpi_schwinger_cluster_draw(&action->abi_action(), psi->p, phi_state->device_overwrite(), B, n_updates,
+                                        action->get_seed(), action->get_chain0(), draw_counter++, work->p, nullptr),
+          "schwinger_cluster_draw");
+    accept = true;
+    n_total_samples++;
+    n_accepted_samples++;
+  }
+  void set_state(std::shared_ptr<SampleState>) override {}
+  double cost_per_sample() override { return cost_per_sample_; }
+
+private:
+  const std::shared_ptr<QuenchedSchwingerAction> action;
+  const unsigned int n_updates, B;
+  std::shared_ptr<DeviceBuffer> psi, work;  // work: the library's 32-bit flipped-site counters; this class never reads them (they may wrap)
+  uint32_t draw_counter = 0;
+  double cost_per_sample_ = 0.0;
+};
+
+/** driver_qm.cc:62-70, driver_qft.cc:69-80: the cluster sampler of the action at hand */
+class ClusterSamplerFactory : public SamplerFactory {
+public:
+  explicit ClusterSamplerFactory(const ClusterParameters p) : param(p) {}
+  std::shared_ptr<Sampler> get(std::shared_ptr<Action> action) override {
+    if (std::dynamic_pointer_cast<QuenchedSchwingerAction>(action)) return std::make_shared<QuenchedSchwingerClusterSampler>(action, param);
+    if (std::dynamic_pointer_cast<NonlinearSigmaAction>(action))
+      fatal(" cluster not supported for chosen action: the generic 2-D cluster update of the sigma model is not built (DESIGN.md 8).");
+    return std::make_shared<ClusterSampler>(action, param);  // fatal unless the action is the rotor
+  }
+private:
+  const ClusterParameters param;
 };
 
 }  // namespace mlmcpi

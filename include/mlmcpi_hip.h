@@ -234,7 +234,42 @@ int mlmcpi_ho_cholesky_factor(const mlmcpi_path_action *act, double *h_LT);
 int mlmcpi_path_exact_draw(const mlmcpi_path_action *act, const double *d_LT, double *d_x, uint32_t B, uint64_t seed,
                            uint32_t chain0, uint32_t step, void *stream);
 
+/* ClusterSampler::draw on a 1-D lattice (sampler/clustersampler.cc:36-49, single_cluster_update1d :92-132, with
+ * RotorAction::new_reflection / S_ell / flip, action/qm/rotoraction.hh:226-253): n_updates reflection-cluster updates of
+ * every chain, in place, one launch.  MLMCPI_ROTOR only; MLMCPI_ERR_UNSUPPORTED for the oscillators (no reflection symmetry
+ * of the bond form).  Update k of this call has the counter update0 + k: xbar = 2 pi u - pi and the seed site
+ * i0 = min(floor(v M), M - 1) from Philox (site 0, purpose 15); link l = (l, l + 1 mod M) is bonded iff its uniform (site
+ * l >> 1, purpose 16: u for l even, v for l odd) < 1 - exp(min(0, -(2 m0 / a) cos(x_l - xbar) cos(x_{l+1} - xbar))) on the
+ * path BEFORE the update; the run of bonded links around i0 is reflected, x <- mod_2pi(pi + 2 xbar - x).  A run that
+ * reaches all M sites flips all M once (the reference's walk re-tests the link into its own seed there: DESIGN.md 5).
+ * Ten updates in one call equal 5 + 5; results do not depend on the batch split.
+ *   d_cluster_sites  optional [B] uint32: the flipped sites of this call's updates are ADDED to it, per chain (the caller
+ *                    zeroes it when it wants the count of one call; 32 bits: a caller that lets it run must read and zero
+ *                    it before 2^32 flipped sites per chain).  update0 + n_updates must fit 32 bits: MLMCPI_ERR_INVALID. */
+int mlmcpi_path_cluster_draw(const mlmcpi_path_action *act, double *d_x, uint32_t B, uint32_t n_updates, uint64_t seed,
+                             uint32_t chain0, uint32_t update0, uint32_t *d_cluster_sites, void *stream);
+
 /* ---- 2-D lattices --------------------------------------------------------------------------- */
+/* QuenchedSchwingerClusterSampler (sampler/quenchedschwingerclustersampler.{hh,cc}).  The sampler's state is a closed path
+ * d_psi [B][Mt Mx] of plaquette angles, a rotor with m0 / a = beta (:19-26); the link field is rebuilt from it on every draw.
+ *   _init   RotorAction::initialise_state of the path (U(-pi, pi) per site)
+ *   _draw   :40-86: n_updates cluster updates of d_psi (update counters draw0 n_updates + k), then the rebuild with the
+ *           gauge transformation of draw `draw0`; d_theta [B][2 Mt Mx] is overwritten, its previous content ignored;
+ *           d_work: _workspace_bytes, zeroed by the caller once (uint32 [B]: flipped sites per chain, added up over the draws)
+ *   _links  the rebuild alone: theta_1(i, j) = sum_{i' < i} (psi[i' Mx + j + 1] - psi[i' Mx + j]), theta_0 = 0 except row
+ *           Mt - 1, theta_0(Mt - 1, j) = -sum_{i'} (psi[i' Mx + j] - psi[i' Mx]) (the closed form of :52-68), then
+ *           theta_0(i, j) += g(i, j) - g(i + 1, j), theta_1(i, j) += g(i, j) - g(i, j + 1) with one uniform angle per vertex
+ *           (Philox site (Mt j + i) >> 1, purpose 17, step draw0; gauge = 0: g = 0) and mod_2pi.  The plaquette of cell
+ *           c = i Mx + j is mod_2pi(psi[c + 1] - psi[c]), psi[Mt Mx] = psi[0].
+ * MLMCPI_SCHWINGER only: MLMCPI_ERR_UNSUPPORTED otherwise (the sigma model's generic 2-D cluster update is not implemented). */
+int mlmcpi_schwinger_cluster_workspace_bytes(const mlmcpi_lattice_action *act, uint32_t B, size_t *bytes);
+int mlmcpi_schwinger_cluster_init(const mlmcpi_lattice_action *act, double *d_psi, uint32_t B, uint64_t seed, uint32_t chain0,
+                                  void *stream);
+int mlmcpi_schwinger_cluster_draw(const mlmcpi_lattice_action *act, double *d_psi, double *d_theta, uint32_t B,
+                                  uint32_t n_updates, uint64_t seed, uint32_t chain0, uint32_t draw0, double *d_work,
+                                  void *stream);
+int mlmcpi_schwinger_cluster_links(const mlmcpi_lattice_action *act, const double *d_psi, double *d_theta, uint32_t B, int gauge,
+                                   uint64_t seed, uint32_t chain0, uint32_t draw0, void *stream);
 int mlmcpi_lattice_state_size(const mlmcpi_lattice_action *act, uint32_t *n); /* Action::sample_size */
 int mlmcpi_lattice_evaluate(const mlmcpi_lattice_action *act, const double *d_phi, uint32_t B, double *d_S,
                             void *stream);

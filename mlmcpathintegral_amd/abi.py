@@ -125,6 +125,11 @@ SIGNATURES = {
     "mlmcpi_schwinger_beta_coarse_nonperturbative": (_i, [_d, _u32, C.c_int32, _vp]),
     "mlmcpi_test_vs_draw": (_i, [_u64, _u32, _u32, _d, _vp, _vp, _u32, _vp, _vp]),
     "mlmcpi_vs_table": (_i, [_d, _vp, _vp]),
+    "mlmcpi_path_cluster_draw": (_i, [_PA, _vp, _u32, _u32, _u64, _u32, _u32, _vp, _vp]),
+    "mlmcpi_schwinger_cluster_workspace_bytes": (_i, [_LA, _u32, C.POINTER(_sz)]),
+    "mlmcpi_schwinger_cluster_init": (_i, [_LA, _vp, _u32, _u64, _u32, _vp]),
+    "mlmcpi_schwinger_cluster_draw": (_i, [_LA, _vp, _vp, _u32, _u32, _u64, _u32, _u32, _vp, _vp]),
+    "mlmcpi_schwinger_cluster_links": (_i, [_LA, _vp, _vp, _u32, _i, _u64, _u32, _u32, _vp]),
 }
 
 # functions whose int return value is a status code

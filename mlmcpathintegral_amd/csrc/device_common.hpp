@@ -196,6 +196,9 @@ enum Purpose : uint32_t {
   P_EXACT = 10,   // exact Gaussian sampler of the harmonic oscillator: normals of entries (2 m, 2 m + 1) from site m
   P_GAUSSFILL = 13,  // two-level step, Schwinger coarsened in both directions, Gaussian fill-in: sub 0 (xi, omega), 1, 2 normals
   P_SIGMA_HB = 14,   // O(3) sigma model heat bath: (u, v) of vertex l = (projection on the neighbour sum, azimuth), sub 0
+  P_CLUSTER_REFLECT = 15,  // cluster update, site 0, step = update counter: xbar = 2 pi u - pi, seed site = min(floor(v M), M - 1)
+  P_CLUSTER_BOND = 16,     // cluster update, site l >> 1, step = update counter: u decides link l even, v link l odd
+  P_GAUGE = 17,            // Schwinger cluster draw, site vertex >> 1, step = draw counter: g = 2 pi (u | v by parity) - pi
 };
 
 struct RngKey {

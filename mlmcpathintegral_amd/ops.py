@@ -254,6 +254,46 @@ def lattice_site_updates(act, x, sites, heat, seed, chain0, step):
     abi.call("mlmcpi_lattice_site_updates", C.byref(act), _p(x), x.shape[0], d, n, single, int(bool(heat)), seed, chain0, step, _stream())
 
 
+def path_cluster_draw(act, x, n_updates, seed, chain0, update0, count=True):
+    """ClusterSampler::draw on a 1-D lattice (rotor): n_updates reflection-cluster updates of every chain of x, in place;
+    returns the flipped sites per chain of this call (int32 [B]; None with count=False)"""
+    _check_state(x, act.M)
+    sites = torch.zeros(x.shape[0], dtype=torch.int32, device=x.device) if count else None
+    abi.call("mlmcpi_path_cluster_draw", C.byref(act), _p(x), x.shape[0], n_updates, seed, chain0, update0, _p(sites), _stream())
+    return sites
+
+
+class SchwingerClusterSampler:
+    """QuenchedSchwingerClusterSampler on B device chains: the state is the plaquette path psi [B, Mt Mx]."""
+
+    def __init__(self, act, B, n_updates=10, seed=1, chain0=0, device="cuda"):
+        self.act, self.B, self.n_updates, self.seed, self.chain0 = act, B, n_updates, seed, chain0
+        nbytes = C.c_size_t(0)
+        abi.call("mlmcpi_schwinger_cluster_workspace_bytes", C.byref(act), B, C.byref(nbytes))
+        self.work = torch.zeros(nbytes.value // 4, dtype=torch.int32, device=device)
+        self.psi = torch.empty((B, act.Mt * act.Mx), dtype=torch.float64, device=device)
+        abi.call("mlmcpi_schwinger_cluster_init", C.byref(act), _p(self.psi), B, seed, chain0, _stream())
+        self.draws = 0
+
+    def draw(self, theta):
+        _check_state(theta, 2 * self.act.Mt * self.act.Mx)
+        abi.call("mlmcpi_schwinger_cluster_draw", C.byref(self.act), _p(self.psi), _p(theta), self.B, self.n_updates, self.seed,
+                 self.chain0, self.draws, _p(self.work), _stream())
+        self.draws += 1
+
+    def cluster_sites(self):
+        return self.work[:self.B]
+
+
+def schwinger_cluster_links(act, psi, gauge, seed, chain0, draw0):
+    """the link field of a plaquette path (mlmcpi_schwinger_cluster_links): theta [B, 2 Mt Mx]"""
+    _check_state(psi, act.Mt * act.Mx)
+    theta = torch.empty((psi.shape[0], 2 * act.Mt * act.Mx), dtype=torch.float64, device=psi.device)
+    abi.call("mlmcpi_schwinger_cluster_links", C.byref(act), _p(psi), _p(theta), psi.shape[0], int(gauge), seed, chain0, draw0,
+             _stream())
+    return theta
+
+
 # ---- 2-D lattices ---------------------------------------------------------------------------------
 def lattice_size(act):
     n = C.c_uint32(0)
