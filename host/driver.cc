@@ -148,7 +148,14 @@ int main(int argc, char **argv) {
     hb.n_burnin = (unsigned)num("n_burnin");
     hb.batch = batch;
     // heatbath.random_order of the reference's parameter file (template: true).  Default here: 0, the multicolour kernels.
+    // 2: random order as well, drawn on the device and run in parallel rounds (2-D actions).
     hb.random_order = num("random_order") != 0;
+    hb.random_order_mode = num("random_order") == 2 ? 1 : 0;
+    if (hb.random_order_mode == 1) {
+      if (a != "schwinger" && a != "gff" && a != "nonlinearsigma")
+        fatal("--random_order 2: the parallel random order is built for the 2-D actions (schwinger, gff, nonlinearsigma), not " + a);
+      std::cerr << "heatbath: random_order = true (device order per chain and sweep, parallel rounds, one launch per draw)" << std::endl;
+    } else
     std::cerr << "heatbath: random_order = " << (hb.random_order ? "true (shuffled index set, site-at-a-time updates)"
                                                                  : "false (multicolour sweep kernels)") << std::endl;
     return std::make_shared<OverrelaxedHeatBathSamplerFactory>(hb);

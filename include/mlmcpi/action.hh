@@ -52,6 +52,12 @@ public:
     fatal(std::string(heat ? "heat bath" : "overrelaxation") + " update not implemented for this action ");
   }
   /** the Philox step the next site-at-a-time call draws from */
+  /** One draw of OverrelaxedHeatBathSampler with random_order = true in the device's own order (overrelaxedheatbathsampler.cc:8-31;
+   *  mlmcpi_lattice_random_sweep_draw): n_or + n_hb sweeps, parallel within a chain, one launch. */
+  virtual void random_sweep_draw(std::shared_ptr<SampleState>, unsigned int, unsigned int, uint32_t) {
+    fatal("random_order_mode = 1: the parallel random order is built for the 2-D actions (GFF, Schwinger, sigma model); "
+          "1-D actions keep the host shuffle (random_order_mode = 0)");
+  }
   void set_site_step(uint32_t s) { site_step = s; }
   uint32_t get_site_step() const { return site_step; }
   /** Does OverrelaxedHeatBathSampler work with this action? */
@@ -293,6 +299,17 @@ public:
     check(mlmcpi_lattice_initialise(&abi, phi->device_mutable(), phi->batch(), seed, chain0, nullptr), "lattice_initialise");
   }
   /** gffaction.cc:33-42,68-77; quenchedschwingeraction.cc:46-65 */
+  void random_sweep_draw(std::shared_ptr<SampleState> phi, unsigned int n_or, unsigned int n_hb, uint32_t sweep0) override {
+    if (phi->size() != sample_size()) fatal("random-order sweep on a state of wrong size.");
+    size_t bytes = 0;
+    check(mlmcpi_lattice_random_sweep_workspace_bytes(&abi, phi->batch(), &bytes), "lattice_random_sweep_workspace_bytes");
+    if (!random_sweep_work || random_sweep_work_bytes < bytes) {
+      random_sweep_work = std::make_shared<DeviceBuffer>(bytes);
+      random_sweep_work_bytes = bytes;
+    }
+    check(mlmcpi_lattice_random_sweep_draw(&abi, phi->device_mutable(), phi->batch(), n_or, n_hb, seed, chain0, sweep0,
+                                           random_sweep_work->p, nullptr), "lattice_random_sweep_draw");
+  }
   void site_updates(std::shared_ptr<SampleState> phi, const uint32_t *d_sites, unsigned int n, unsigned int ell, bool heat) override {
     if (phi->size() != sample_size()) fatal("site update on a state of wrong size.");
     check(mlmcpi_lattice_site_updates(&abi, phi->device_mutable(), phi->batch(), d_sites, n, ell, heat ? 1 : 0, seed, chain0,
@@ -349,6 +366,8 @@ public:
   unsigned fuse = 0;  // sweeps fused per launch (0 = library default); results do not depend on it
 
 protected:
+  std::shared_ptr<DeviceBuffer> random_sweep_work;  // workspace of random_sweep_draw, allocated on first use
+  size_t random_sweep_work_bytes = 0;
   /** coarsening factors between `fine` (this level's lattice) and the state of the next-coarser level */
   bool factors(const std::shared_ptr<Lattice2D> fine, const std::shared_ptr<SampleState> coarse_state, unsigned &rt, unsigned &rx) const {
     auto c = fine->get_coarse_lattice();

@@ -177,6 +177,10 @@ struct OverrelaxedHeatBathParameters {
   // valid fixed order; said once on stderr).  true: the reference's own loop, every sweep over a freshly shuffled index
   // set, through the site-at-a-time updates (sequential within a chain, chains in parallel): exact semantics, slow.
   bool random_order = false;
+  // with random_order = true: 0 = the host shuffle (std::mt19937_64) and the site-at-a-time loop, as above; 1 = the device
+  // order (Philox purpose 18: every chain and sweep its own order) run in parallel rounds, one launch per draw, exactly the
+  // sequential sweep in that order (mlmcpi_lattice_random_sweep_draw; 2-D actions)
+  unsigned int random_order_mode = 0;
   unsigned int batch = 1;
 };
 
@@ -192,9 +196,12 @@ class OverrelaxedHeatBathSampler : public Sampler {
 public:
   OverrelaxedHeatBathSampler(const std::shared_ptr<Action> action_, const OverrelaxedHeatBathParameters p)
       : Sampler(), action(action_), n_sweep_heatbath(p.n_sweep_heatbath), n_sweep_overrelax(p.n_sweep_overrelax),
-        n_burnin(p.n_burnin), random_order(p.random_order) {
+        n_burnin(p.n_burnin), random_order(p.random_order), random_order_mode(p.random_order_mode) {
     if (!action->has_local_updates()) fatal("heat bath update not implemented for this action ");
-    if (random_order) {  // overrelaxedheatbathsampler.hh:110-116: the action's index set, or every entry
+    if (random_order_mode > 1) fatal("random_order_mode must be 0 (host shuffle) or 1 (device order)");
+    if (random_order && random_order_mode == 1) {
+      // no index set on the host: the order is a function of (seed, chain, sweep)
+    } else if (random_order) {  // overrelaxedheatbathsampler.hh:110-116: the action's index set, or every entry
       index_map = action->get_heatbath_indexset();
       if (index_map.empty()) {
         index_map.resize(action->sample_size());
@@ -227,6 +234,9 @@ public:
   /** the draw without handing the sample out (callers that read current_state()) */
   bool advance(int qoi_kind = 0, double *d_q = nullptr, double *d_acc = nullptr) {
     if (qoi_kind && (n_sweep_heatbath == 0 || random_order)) return false;
+    if (random_order && random_order_mode == 1) {  // one launch per draw: no host shuffle, no copy to the device
+      action->random_sweep_draw(phi_state_cur, n_sweep_overrelax, n_sweep_heatbath, sweep_counter);
+    } else
     if (random_order) {  // overrelaxedheatbathsampler.cc:8-31 as written: shuffle, then one local update per index
       // (site_updates works in place; a sample handed out earlier keeps its values: SampleState::device_mutable detaches)
       for (unsigned int s = 0; s < n_sweep_overrelax + n_sweep_heatbath; ++s) {
@@ -273,6 +283,7 @@ protected:
   const std::shared_ptr<Action> action;
   const unsigned int n_sweep_heatbath, n_sweep_overrelax, n_burnin;
   bool random_order;
+  unsigned int random_order_mode;
   std::vector<unsigned int> index_map;      // random_order: the index set, reshuffled per sweep
   std::shared_ptr<DeviceVector> d_index;    // ... and its device copy
   std::mt19937_64 engine{871417};           // overrelaxedheatbathsampler.hh:111

@@ -300,6 +300,29 @@ int mlmcpi_lattice_sweep_draw(const mlmcpi_lattice_action *act, double *d_phi, d
 int mlmcpi_lattice_site_updates(const mlmcpi_lattice_action *act, double *d_state, uint32_t B, const uint32_t *d_sites,
                                 uint32_t n, uint32_t site, int32_t heat, uint64_t seed, uint32_t chain0, uint32_t step,
                                 void *stream);
+/* OverrelaxedHeatBathSampler::draw with random_order = true (sampler/overrelaxedheatbathsampler.cc:8-31: the index set is
+ * shuffled before every sweep, then one local update per index), parallel within a chain: GFF, Schwinger and the sigma model.
+ * ORDER: index l of a chain (Schwinger: the 2 Mt Mx links; GFF, sigma model: the Mt Mx vertices -- the index set
+ * mlmcpi_lattice_site_updates walks) takes word l & 3 of Philox (site l >> 2, chain0 + b, step sweep0 + s, purpose 18, sub 0) as
+ * its 32-bit key; sweep s visits the indices in ascending (key, l).  Every chain and every sweep has its own order; results do
+ * not depend on the batch split.  The updates run in rounds (round of an index = 1 + the largest round of the indices it
+ * shares a stencil with that precede it), one workgroup per chain, all n_overrelax + n_heatbath sweeps in ONE launch, and give
+ * exactly what mlmcpi_lattice_site_updates gives when it walks that order: same arithmetic, same random numbers (step
+ * sweep0 + s).  Mt, Mx >= 2, odd extents included.  The state lives in LDS where it fits (Schwinger 64 x 64, GFF 96 x 96,
+ * sigma model 64 x 64), in global memory beyond (any lattice; MLMCPI_RANDOM_SWEEP_HOME=global through mlmcpi_set_option forces
+ * it; MLMCPI_RANDOM_SWEEP_CHUNK=k, 1 <= k <= 254, sets how many rounds are scheduled at a time: neither changes a bit).
+ *   d_work   workspace of mlmcpi_lattice_random_sweep_workspace_bytes() bytes (keys, rounds: no need to zero it)
+ * Other kinds: MLMCPI_ERR_UNSUPPORTED (the 1-D paths keep mlmcpi_path_site_updates). */
+int mlmcpi_lattice_random_sweep_workspace_bytes(const mlmcpi_lattice_action *act, uint32_t B, size_t *bytes);
+int mlmcpi_lattice_random_sweep_draw(const mlmcpi_lattice_action *act, double *d_state, uint32_t B, uint32_t n_overrelax,
+                                     uint32_t n_heatbath, uint64_t seed, uint32_t chain0, uint32_t sweep0, void *d_work, void *stream);
+/* The order and the schedule of sweep `sweep` of mlmcpi_lattice_random_sweep_draw (the shuffle of
+ * sampler/overrelaxedheatbathsampler.cc:8-31), so that a caller can walk the very same order through
+ * mlmcpi_lattice_site_updates: d_order [B][n] the indices in visiting order, d_round [B][n] (may be NULL) the round of each
+ * index, counted from 1.  Synchronises nothing; uses the library's scratch buffer of the stream. */
+int mlmcpi_lattice_random_sweep_order(const mlmcpi_lattice_action *act, uint32_t B, uint64_t seed, uint32_t chain0, uint32_t sweep,
+                                      uint32_t *d_order /* [B][n] indices in visiting order */,
+                                      uint32_t *d_round /* [B][n] round of each index, may be NULL */, void *stream);
 /* Same, without the final device-to-device copy: the sweeps ping-pong between d_a (input) and d_b;
  * *result_in_b tells the caller which buffer holds the result (swap your pointers when it is 1). */
 int mlmcpi_lattice_sweep_draw_pingpong(const mlmcpi_lattice_action *act, double *d_a, double *d_b, uint32_t B,

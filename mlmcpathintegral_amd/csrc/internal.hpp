@@ -48,6 +48,8 @@ struct Tuning {
   bool or_block = false;                         // MLMCPI_OR_KERNEL=block: 4 x 4 register blocks sweep by sweep instead of the closed form (Schwinger)
   bool or_heat_split = false;                    // MLMCPI_OR_HEAT=split: the heat-bath sweep behind the last overrelaxation launch gets a launch of its own
   int or_heat_wide = 0;                          // MLMCPI_OR_HEAT=wide|narrow: 1024-thread workgroups for the fused launch (+1 / -1; 0: by the number of tiles)
+  bool random_sweep_global = false;               // MLMCPI_RANDOM_SWEEP_HOME=global: the random-order sweep keeps the state in global memory whatever the lattice
+  uint32_t random_sweep_chunk = 0;                // MLMCPI_RANDOM_SWEEP_CHUNK=k: rounds scheduled per pass of the random-order sweep (0: 254)
 };
 Tuning tuning();  // a copy taken under the lock: callers snapshot it once per call
 
@@ -64,6 +66,11 @@ int sigma_site_updates(const mlmcpi_lattice_action *act, double *d_state, uint32
 int sigma_sweep_draw(const mlmcpi_lattice_action *act, double *d_phi, double *d_w0, double *d_w1, uint32_t B, uint32_t n_overrelax,
                      uint32_t n_heatbath, uint64_t seed, uint32_t chain0, uint32_t sweep0, uint32_t fuse, int32_t *result_in,
                      hipStream_t st, int qoi_kind, double *d_qoi, double *d_acc);
+
+inline double gff_mu2(const mlmcpi_lattice_action &A) {  // gffaction.hh:174-181 (unrotated lattice)
+  const double a_lat = 1. / A.Mt;
+  return a_lat * a_lat * A.mass * A.mass;
+}
 
 constexpr uint32_t kComputeUnits = 256;  // MI355X
 constexpr uint32_t kMaxFuse = 16;  // max sweeps fused in one launch (kinds travel in a bitmask)

@@ -2127,52 +2127,14 @@ __global__ void __launch_bounds__(64)
   key.chain += b;
   if (SCHW) {
     double *th = state + (size_t)b * 2 * Mt * Mx;
-    auto link = [&](uint32_t i, uint32_t j, uint32_t mu) -> double & { return th[2 * (Mt * j + i) + mu]; };
     const bool step = 2. * coupling <= kVsKappaMax;
     const VsTable tab = VsTable::in_global(vs_table);
-    for (uint32_t q = 0; q < n; ++q) {
-      const uint32_t l = sites ? sites[q] : single;
-      const uint32_t mu = l & 1u, v = l >> 1, j = v / Mt, i = v - j * Mt;
-      const uint32_t ip = i + 1 == Mt ? 0 : i + 1, im = i == 0 ? Mt - 1 : i - 1, jp = j + 1 == Mx ? 0 : j + 1, jm = j == 0 ? Mx - 1 : j - 1;
-      double tp, tm;  // staple sums, unwrapped (quenchedschwingeraction.cc:25-43; same sums as schwinger_sweep_kernel)
-      if (mu == 0) {
-        tp = link(i, jp, 0) + link(i, j, 1) - link(ip, j, 1);
-        tm = link(i, jm, 0) + link(ip, jm, 1) - link(i, jm, 1);
-      } else {
-        tp = link(i, j, 0) + link(ip, j, 1) - link(i, jp, 0);
-        tm = link(im, jp, 0) + link(im, j, 1) - link(im, j, 0);
-      }
-      double &x = th[l];
-      if (!heat) {
-        x = mod_2pi_fast((tp + tm) - x);
-      } else if (step) {
-        x = vs_draw(key, l, 2. * coupling, tp, tm, tab);
-      } else {
-        double tau, centre;
-        expcos_params(coupling, tp, tm, tau, centre);
-        x = mod_2pi_fast(vonmises_draw(key, l, tau) + centre);
-      }
-    }
+    for (uint32_t q = 0; q < n; ++q) schwinger_site_update(th, Mt, Mx, sites ? sites[q] : single, heat != 0, step, coupling, key, tab);
   } else {
     double *phi = state + (size_t)b * Mt * Mx;
     const double inv_kappa = 1. / (4. + coupling), two_over_kappa = 2. / (4. + coupling), sigma = 1. / sqrt(4. + coupling);
-    for (uint32_t q = 0; q < n; ++q) {
-      const uint32_t l = sites ? sites[q] : single;
-      const uint32_t j = l / Mt, i = l - j * Mt;
-      const uint32_t ip = i + 1 == Mt ? 0 : i + 1, im = i == 0 ? Mt - 1 : i - 1, jp = j + 1 == Mx ? 0 : j + 1, jm = j == 0 ? Mx - 1 : j - 1;
-      double Delta = 0.0;  // the order of the reference's neighbour table: +i, -i, +j, -j
-      Delta += phi[Mt * j + ip];
-      Delta += phi[Mt * j + im];
-      Delta += phi[Mt * jp + i];
-      Delta += phi[Mt * jm + i];
-      if (!heat) {
-        phi[l] = fma(two_over_kappa, Delta, -phi[l]);
-      } else {
-        double n0, n1;
-        rng_normals(key, l >> 1, P_GFF_NORMAL, 0, n0, n1);
-        phi[l] = fma(Delta, inv_kappa, sigma * ((l & 1u) ? n1 : n0));
-      }
-    }
+    for (uint32_t q = 0; q < n; ++q)
+      gff_site_update(phi, Mt, Mx, sites ? sites[q] : single, heat != 0, inv_kappa, two_over_kappa, sigma, key);
   }
 }
 
@@ -2205,10 +2167,6 @@ static int refuse_sigma(const mlmcpi_lattice_action *act, const char *what) {
   return MLMCPI_OK;
 }
 
-static double gff_mu2(const mlmcpi_lattice_action &A) {  // gffaction.hh:174-181 (unrotated lattice)
-  const double a_lat = 1. / A.Mt;
-  return a_lat * a_lat * A.mass * A.mass;
-}
 
 static uint32_t row_blocks(uint32_t Mx, uint32_t B) {
   uint32_t want = (2048 + B - 1) / B;

@@ -97,11 +97,25 @@ bool apply_option(Tuning &t, const char *name, const char *value) {
     t.or_heat_wide = v == "wide" ? 1 : v == "narrow" ? -1 : 0;
     return v.empty() || v == "split" || v == "fused" || v == "wide" || v == "narrow";
   }
+  if (n == "MLMCPI_RANDOM_SWEEP_HOME") {
+    t.random_sweep_global = v == "global";
+    return v.empty() || v == "global" || v == "lds";
+  }
+  if (n == "MLMCPI_RANDOM_SWEEP_CHUNK") {
+    unsigned k = 0;
+    t.random_sweep_chunk = 0;
+    if (v.empty()) return true;
+    if (sscanf(v.c_str(), "%u", &k) == 1 && k >= 1 && k <= 254) {
+      t.random_sweep_chunk = k;
+      return true;
+    }
+    return false;
+  }
   return false;
 }
 void load_tuning_locked() {
   if (g_tuning_loaded) return;
-  for (const char *name : {"MLMCPI_SWEEP_TILE", "MLMCPI_OR_KERNEL", "MLMCPI_OR_HEAT"})
+  for (const char *name : {"MLMCPI_SWEEP_TILE", "MLMCPI_OR_KERNEL", "MLMCPI_OR_HEAT", "MLMCPI_RANDOM_SWEEP_HOME", "MLMCPI_RANDOM_SWEEP_CHUNK"})
     if (const char *e = getenv(name)) apply_option(g_tuning, name, e);
   g_tuning_loaded = true;
 }

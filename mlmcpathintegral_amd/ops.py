@@ -325,6 +325,32 @@ def lattice_sweep_draw(act, phi, scratch, n_overrelax, n_heatbath, seed, chain0,
              seed, chain0, sweep0, fuse, _stream())
 
 
+def lattice_random_sweep_workspace(act, B, device="cuda"):
+    """workspace of lattice_random_sweep_draw for B chains (uint8 tensor)"""
+    nbytes = C.c_size_t(0)
+    abi.call("mlmcpi_lattice_random_sweep_workspace_bytes", C.byref(act), B, C.byref(nbytes))
+    return torch.empty(nbytes.value, dtype=torch.uint8, device=device)
+
+
+def lattice_random_sweep_draw(act, phi, n_overrelax, n_heatbath, seed, chain0, sweep0, work=None):
+    """OverrelaxedHeatBathSampler::draw with random_order = true, parallel within a chain (mlmcpi_lattice_random_sweep_draw):
+    n_overrelax + n_heatbath sweeps of phi, in place, every sweep in its own random order (Philox purpose 18)"""
+    _check_state(phi, lattice_size(act))
+    if work is None:
+        work = lattice_random_sweep_workspace(act, phi.shape[0], phi.device)
+    abi.call("mlmcpi_lattice_random_sweep_draw", C.byref(act), _p(phi), phi.shape[0], n_overrelax, n_heatbath, seed, chain0, sweep0,
+             _p(work), _stream())
+
+
+def lattice_random_sweep_order(act, B, seed, chain0, sweep, rounds=True, device="cuda"):
+    """the visiting order (int32 [B, n]) and the round of every index (int32 [B, n], or None) of that sweep"""
+    n = (2 if act.kind == abi.SCHWINGER else 1) * act.Mt * act.Mx
+    order = torch.empty((B, n), dtype=torch.int32, device=device)
+    rnd = torch.empty((B, n), dtype=torch.int32, device=device) if rounds else None
+    abi.call("mlmcpi_lattice_random_sweep_order", C.byref(act), B, seed, chain0, sweep, _p(order), _p(rnd), _stream())
+    return order, rnd
+
+
 def lattice_sweep_draw_pingpong(act, a, b, n_overrelax, n_heatbath, seed, chain0, sweep0, fuse=0):
     """Sweeps without the final copy; returns (state, scratch) -- the tensors swapped when needed."""
     _check_state(a, lattice_size(act))
