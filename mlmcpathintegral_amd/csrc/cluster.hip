@@ -241,8 +241,6 @@ static int launch_links(const mlmcpi_lattice_action *act, const double *d_psi, d
   return MLMCPI_OK;
 }
 
-static size_t align256(size_t n) { return (n + 255) & ~(size_t)255; }
-
 }  // namespace mlmcpi
 
 using namespace mlmcpi;

@@ -397,8 +397,6 @@ static int level_energy(mlmcpi_gff_level *L, const double *d_phi, uint32_t B, do
   return MLMCPI_OK;
 }
 
-static size_t align256(size_t n) { return (n + 255) & ~(size_t)255; }
-
 }  // namespace mlmcpi
 
 extern "C" {

@@ -57,7 +57,7 @@ Tuning tuning();  // a copy taken under the lock: callers snapshot it once per c
 // current device: built and uploaded on first use (device_common.hpp, runtime.hip).
 int vs_table_device(double scale, const uint32_t **d_table);
 
-// the O(3) nonlinear sigma model (sigma2d.hip); arguments checked by the lattice2d.hip entry points that dispatch here
+// the O(3) nonlinear sigma model (sigma2d.hip); arguments checked by the lattice entry points that dispatch here
 int sigma_evaluate(const mlmcpi_lattice_action *act, const double *d_phi, uint32_t B, double *d_S, hipStream_t st);
 int sigma_force(const mlmcpi_lattice_action *act, const double *d_phi, double *d_f, uint32_t B, hipStream_t st);
 int sigma_initialise(const mlmcpi_lattice_action *act, double *d_phi, uint32_t B, uint64_t seed, uint32_t chain0, hipStream_t st);
@@ -71,6 +71,25 @@ inline double gff_mu2(const mlmcpi_lattice_action &A) {  // gffaction.hh:174-181
   const double a_lat = 1. / A.Mt;
   return a_lat * a_lat * A.mass * A.mass;
 }
+
+inline size_t align256(size_t n) { return (n + 255) & ~(size_t)255; }  // workspace sections
+// workgroups of 256 threads in x for a grid-stride loop over n entries (y: the chains)
+inline uint32_t stream_blocks(size_t n) { return n > 1024 * 256 ? 1024u : (uint32_t)((n + 255) / 256); }
+
+// ---- GFF and Schwinger on the 2-D lattice: what the translation units of lattice2d.hip's family call in each other.
+// Kernels are launched only by the unit that defines them.
+// lattice_reduce.hip
+int check_lattice(const mlmcpi_lattice_action *act, bool square_gff = true);  // square_gff: the GFF action's own demand, Mt == Mx
+int refuse_sigma(const mlmcpi_lattice_action *act, const char *what);          // the entry points the O(3) sigma model does not take
+uint32_t row_blocks(uint32_t Mx, uint32_t B);                                  // workgroups per chain of the kernels that stride over rows
+int lattice_energy(const mlmcpi_lattice_action *act, const double *d_phi, uint32_t B, double *d_S, hipStream_t st);
+// d_out[b] = scale * sum of the squares of the n entries of chain b
+int lattice_sum_squares(const double *d_x, uint32_t n, uint32_t B, double scale, double *d_out, hipStream_t st);
+// partial[b * tiles + t] summed over t in a fixed order -> d_out[b] (op L_CHARGE: its square / 4 pi^2; else scale * sum);
+// d_acc != NULL: the value recorded there as well (mlmcpi_stats_accumulate's sums)
+int lattice_finish(const double *partial, uint32_t tiles, uint32_t B, int op, double scale, double *d_out, double *d_acc, hipStream_t st);
+// gff_exact.hip: GFFAction::initialise_state, the exact sampler on the library's scratch
+int gff_initialise_exact(const mlmcpi_lattice_action *act, double *d_phi, uint32_t B, uint64_t seed, uint32_t chain0, hipStream_t st);
 
 constexpr uint32_t kComputeUnits = 256;  // MI355X
 constexpr uint32_t kMaxFuse = 16;  // max sweeps fused in one launch (kinds travel in a bitmask)

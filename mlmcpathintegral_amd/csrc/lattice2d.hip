@@ -9,11 +9,13 @@
 // RNG makes those recomputations bit-identical.  Per sweep HBM sees ~(1 + halo overhead) reads and
 // one write of every entry -- instead of the 4-5 passes of one-kernel-per-colour -- and k fused
 // sweeps divide that by k.
+// This file is the sweep path only: the kernels, the launch plan (sweep_draw_impl) and the site-at-a-time updates.
+// Reductions, force and HMC, level transfers and the two-level step, and the exact GFF sampler are in lattice_reduce.hip,
+// lattice_hmc.hip, lattice_twolevel.hip and gff_exact.hip.
 #include <algorithm>
 #include <type_traits>
 #include <mutex>
 
-#include <hipfft/hipfft.h>
 #include <stdio.h>
 #include <string.h>
 #include <stdlib.h>
@@ -38,6 +40,12 @@ __device__ unsigned long long g_stamps[16 * 65536];
           ((unsigned long long)__builtin_amdgcn_s_getreg((20 /*XCC_ID*/) | (0 << 6) | (31 << 11)) << 32) |         \
           __builtin_amdgcn_s_getreg((4 /*HW_ID*/) | (0 << 6) | (31 << 11));                                        \
   } while (0)
+// the stamps of the last launch of schwinger_perm_heat_kernel, 16 words per workgroup
+extern "C" int mlmcpi_debug_read_stamps(unsigned long long *h_out, uint32_t n_workgroups) {
+  MLMCPI_HIP_TRY(hipDeviceSynchronize());
+  MLMCPI_HIP_TRY(hipMemcpyFromSymbol(h_out, HIP_SYMBOL(g_stamps), (size_t)n_workgroups * 16 * sizeof(unsigned long long)));
+  return MLMCPI_OK;
+}
 #else
 #define MLMCPI_STAMP(k) do { } while (0)
 #define MLMCPI_STAMP_WHERE() do { } while (0)
@@ -160,15 +168,6 @@ struct TileGeom {
   uint32_t TW, TH;      // owned tile extent (even)
   uint32_t tiles_x;     // tiles per row of tiles
 };
-
-// The state a launch writes is read next by another launch, from HBM either way (one chain's state is 16 MiB against 4 MiB of
-// L2 per XCD): a non-temporal store keeps it from pushing the halos the resident workgroups share out of the L2
-// (measured on the one-launch Schwinger draw: -3.5 %).
-__device__ __forceinline__ void store_streaming(double2 *p, double x, double y) {
-  typedef double d2_t __attribute__((ext_vector_type(2)));
-  const d2_t v = {x, y};
-  __builtin_nontemporal_store(v, reinterpret_cast<d2_t *>(p));
-}
 
 __device__ __forceinline__ uint32_t wrap_add(uint32_t base, uint32_t off, uint32_t n) {
   uint32_t v = base + off;
@@ -355,20 +354,6 @@ __global__ void __launch_bounds__(NT, HEAT ? (NT == 256 ? 4 : NT == 512 ? 2 : 1)
     if (threadIdx.x == 0) qoi_partial[(size_t)b * gridDim.x + blockIdx.x] = acc[0];
   }
 }
-
-// Experiment (-DMLMCPI_SKEW=n): the two workgroups a CU holds start together and stay in step -- both in their load / store
-// phases (HBM bound, issue slots idle), then both in their sweeps (issue bound, HBM idle).  Delaying the second workgroup
-// of every CU by n x 3.6 us at the start of the launch puts them half a period apart.
-#ifdef MLMCPI_SKEW
-#define MLMCPI_SKEW_START()                                                                      \
-  do {                                                                                           \
-    const uint32_t lin_ = blockIdx.y * gridDim.x + blockIdx.x;                                   \
-    if (lin_ >= kComputeUnits && lin_ < 2 * kComputeUnits)                                       \
-      for (int i_ = 0; i_ < MLMCPI_SKEW; ++i_) __builtin_amdgcn_s_sleep(127);                    \
-  } while (0)
-#else
-#define MLMCPI_SKEW_START() do { } while (0)
-#endif
 
 // ---- Schwinger overrelaxation, 4 x 4 register blocks on 64 x 64 tiles ------------------------------------------
 // A 2 x 2 block kernel on 64 x 32 tiles (retired; EXPERIMENTS 4.1) recomputes (64 + 4K)(32 + 4K) / (64 * 32) = 1.875 x
@@ -560,7 +545,6 @@ __global__ void __launch_bounds__(OrBlockGeom<K>::NT)
   const uint32_t ty = tile / tiles_x, tx = tile - ty * tiles_x;
   const uint32_t i0 = tx * TW, j0 = ty * TH;
   double t0[PH][PW], t1[PH][PW];
-  MLMCPI_SKEW_START();
   or_block_sweeps<G, K>(lds, in + (size_t)b * Mt * Mx, Mt, Mx, i0, j0, t0, t1);
 
   // Owned vertices: buffer columns [H, H + TW), rows [H, H + TH).  A thread holds PW consecutive vertices of a row
@@ -617,13 +601,8 @@ __device__ __forceinline__ void schwinger_image_heat(double *th0, double *th1, V
   skey.chain += b;
   const double beta2 = 2. * beta;
   // Step-envelope phases with whole waves per round (NT = 512, 1024): the cells of pass 0 by a closed-form map
-  // (heatbath_cells_step_mapped); other workgroup sizes, the wrapped-Cauchy sampler and -DMLMCPI_HB_LINEAR (the form this
-  // replaces, for same-box A/B) hand them out by linear index.
-#ifdef MLMCPI_HB_LINEAR
-  constexpr bool kMapped = false;
-#else
+  // (heatbath_cells_step_mapped); other workgroup sizes and the wrapped-Cauchy sampler hand them out by linear index.
   constexpr bool kMapped = STEP && 32 % (NT / kWave) == 0;
-#endif
   constexpr uint32_t NW = NT / kWave, NIT = kMapped ? 32 / NW : 1;
   // the stencil reads of the mapped phases go out as single ds_read_b64 at immediate offsets from one address (the compiler
   // pairs neighbouring doubles into ds_read2_b64: 8 LDS cycles against 2 + 2, MI355X_MICROARCH.md); th1 lies IW IH doubles
@@ -839,22 +818,6 @@ constexpr uint32_t kPermMaxK = 10;  // sweeps per launch
 #define MLMCPI_PERM_U 0    // rows in flight per thread in the first plane build; 0 = all of a thread's rows at the deepest launch (19 at 512 threads; r05: one round trip to HBM instead of two, 10 + 9 rows: -4.2 % on the launch, same-box A/B)
 #endif
 
-// Workgroups are handed to the 8 XCDs round robin by their linear index; each XCD has its own L2.  Experiment
-// (-DMLMCPI_XCD_MAP): XCD x takes the x-th eighth of the (chain, tile) list instead, so that the workgroups resident on an
-// XCD at any time are neighbouring tiles of one or two chains, whose halos -- 65 % of what a workgroup of the 10-sweep
-// launch loads -- could be L2 hits.
-__device__ __forceinline__ void perm_tile_of_workgroup(uint32_t &tile, uint32_t &b) {
-  tile = blockIdx.x;
-  b = blockIdx.y;
-#ifdef MLMCPI_XCD_MAP   // measured (r04, same-box A/B at 1024 x 1024 x 32 and x 128): no difference
-  const uint32_t total = gridDim.x * gridDim.y;
-  if (total % 8 == 0) {
-    const uint32_t lin = blockIdx.y * gridDim.x + blockIdx.x, id = (lin % 8) * (total / 8) + lin / 8;
-    b = id / gridDim.x;
-    tile = id - b * gridDim.x;
-  }
-#endif
-}
 // The plane in LDS.  Every stream of the closed form walks a diagonal of the plaquettes of ONE parity class: column and
 // row parity do not change along it, the column moves by 2 e_c and the row by +-2 per step s.  So the plane is kept as four
 // quadrants by (column parity, row parity), each Rh = rows / 2 rows of Wh = WP / 2 values, with the ODD index mirrored:
@@ -877,7 +840,7 @@ struct PermPlane {
 
 // where a thread stands in a build: its theta column, its rows [r, rend) of the `rows`, whether it owns a plaquette column
 struct PermBuildPos {
-  uint32_t c, r, rend, row_off, gj;   // row_off = gj Mt: the lattice row of build row r, in vertices (< 2^32: check_lattice_dims)
+  uint32_t c, r, rend, row_off, gj;   // row_off = gj Mt: the lattice row of build row r, in vertices (< 2^32: check_lattice)
   uint32_t cb;                        // PermPlane::col of the plaquette column
   const double2 *p;                   // src + the lattice column
   bool active, owns;
@@ -970,8 +933,6 @@ struct PermGeom {
 // coordinates (own angles, gather, image) is scalar work plus a few additions.  The columns beyond 64 of the 68-wide
 // output of the fused launch (4 x HR / 2 mu = 0 tasks, 2 x HR mu = 1 tasks) are left-over wave-tasks of one kind each, in
 // the last slot of waves that have no main task there.  Which lane computes a task does not enter its result.
-// (-DMLMCPI_PERM_TASKS_LINEAR: thread t takes tasks t, t + NT, ... of the list "mu = 0 row pairs, then mu = 1 rows", r04.)
-#ifndef MLMCPI_PERM_TASKS_LINEAR
 template <int NT, int RING, int TH = 64>
 struct PermTasks {
   using PG = PermGeom<NT, RING, TH>;
@@ -1037,41 +998,6 @@ struct PermTasks {
     task(k, mu1, r, c);
   }
 };
-#else
-// Task k of a thread, t = threadIdx.x + k NT: a column pair (mu = 0: rows r, r + 1 of column c; t < NT0) or a row pair
-// (mu = 1: columns c, c + 1 of row r), coordinates inside the half.  Two divisions per thread (PermTasks), then constants.
-template <int NT, int RING, int TH = 64>
-struct PermTasks {
-  using PG = PermGeom<NT, RING, TH>;
-  static constexpr int OW = PG::OW, HR = PG::HR, NT0 = (HR / 2) * OW, OW2 = OW / 2;
-  uint32_t q0, c0, q1, c1;   // threadIdx.x = q0 OW + c0 = q1 OW2 + c1
-  __device__ PermTasks() {
-    q0 = threadIdx.x / OW;
-    c0 = threadIdx.x - q0 * OW;
-    q1 = threadIdx.x / OW2;
-    c1 = threadIdx.x - q1 * OW2;
-  }
-  __device__ __forceinline__ bool valid(int k) const { return threadIdx.x + k * NT < (uint32_t)PG::NTASK; }
-  __device__ __forceinline__ bool is_mu1(int k) const { return threadIdx.x + k * NT >= (uint32_t)NT0; }
-  __device__ __forceinline__ void coords(int k, uint32_t &r, uint32_t &c) const {
-    if (!is_mu1(k)) {   // t = (q0 + dq) OW + c0 + dc
-      const uint32_t dq = (k * NT) / OW, dc = (k * NT) % OW;
-      uint32_t q = q0 + dq, cc = c0 + dc;
-      if (cc >= (uint32_t)OW) { cc -= OW; ++q; }
-      r = 2 * q;
-      // the first OW / 2 tasks of a row pair take the even columns, the rest the odd ones: a 32-lane group of a gather read
-      // stays inside one quadrant of the plane, contiguous banks (r05, same-box A/B: 0.7703 against 0.7747 ms with c = cc)
-      c = cc < (uint32_t)(OW / 2) ? 2 * cc : 2 * (cc - OW / 2) + 1;
-    } else {            // t - NT0 = (q1 + dq) OW2 + c1 + dc, dq possibly negative
-      const int off = k * NT - NT0, dq = off >= 0 ? off / OW2 : -((-off + OW2 - 1) / OW2), dc = off - dq * OW2;   // 0 <= dc < OW2
-      uint32_t q = q1 + (uint32_t)dq, cc = c1 + (uint32_t)dc;
-      if (cc >= (uint32_t)OW2) { cc -= OW2; ++q; }
-      r = q;
-      c = 2 * cc;
-    }
-  }
-};
-#endif
 
 // Five steps of the three streams of a task: fifteen 8-byte LDS reads at immediate offsets from three addresses, through
 // inline asm (lds_read_f64: the compiler would pair the reads of a stream into ds_read2_b64, half the rate --
@@ -1226,11 +1152,6 @@ __device__ __forceinline__ void perm_sweeps(double *plane, const double2 *__rest
   perm_rows_load<UB>(qb, Mt, Mx, true, curb, vb);
   gather(0, res[0]);
   MLMCPI_STAMP(2);  // first half gathered
-#ifdef MLMCPI_THETA_EARLY
-  // experiment (r05, same-box A/B: 0.781 against 0.778 ms without): the angles of the first half in flight while the plane's
-  // rows move -- the longer live range costs a spill inside the second gather, which then waits for every load in flight
-  load_theta(0, th);
-#endif
   // rows [HR, rows) of the plane become rows [0, rows - HR), the HR new rows go on top.  HR is even: a row keeps its parity
   // and moves by HR / 2 quadrant rows -- down in the quadrants of the even rows, up (mirrored) in those of the odd rows
   constexpr int NC = (4 * 2 * (int)kPermMaxK * PP::Wh + NT - 1) / NT;   // 4 quadrants x (rows - HR) / 2 = 2 K quadrant rows
@@ -1253,13 +1174,8 @@ __device__ __forceinline__ void perm_sweeps(double *plane, const double2 *__rest
       if (e < nkeep) *reinterpret_cast<double *>(pbw + qd * P.QB + e * 8u + ((qd & 2u) ? shift : 0u)) = keep[q];
     }
   }
-#ifdef MLMCPI_THETA_MID
-  load_theta(0, th);
-#endif
   perm_rows_store<UB>(qb, P, plane, rows - HR, curb, vb);
-#if !defined(MLMCPI_THETA_EARLY) && !defined(MLMCPI_THETA_MID)
-  load_theta(0, th);
-#endif
+  load_theta(0, th);   // (earlier -- before the rows move, or before they are stored -- costs a spill or gains nothing: EXPERIMENTS 0.1, 0.6)
   double2 th1[NV];
   load_theta(1, th1);
   __syncthreads();
@@ -1307,8 +1223,7 @@ __global__ void __launch_bounds__(512, 4)
   constexpr int NT = 512;
   using PG = PermGeom<NT, 0, TH>;
   extern __shared__ double lds[];
-  uint32_t tile, b;
-  perm_tile_of_workgroup(tile, b);
+  const uint32_t tile = blockIdx.x, b = blockIdx.y;
   const uint32_t ty = tile / tiles_x, tx = tile - ty * tiles_x;
   const uint32_t i0 = tx * 64, j0 = ty * TH;
   double2 res[2][PG::NV];
@@ -1350,15 +1265,11 @@ __global__ void __launch_bounds__(NT, 4)
   static_assert(PG::OW == IW && 2 * PG::HR == IH, "the closed-form stage fills the heat bath's image");
   extern __shared__ double lds[];
   __shared__ double qoi_red[NT / kWave];
-  uint32_t tile, b;
-  perm_tile_of_workgroup(tile, b);
+  const uint32_t tile = blockIdx.x, b = blockIdx.y;
   const uint32_t ty = tile / tiles_x, tx = tile - ty * tiles_x;
   const uint32_t i0 = tx * 64, j0 = ty * 64;
   MLMCPI_STAMP(0);
   MLMCPI_STAMP_WHERE();
-#ifdef MLMCPI_PRIO_A
-  __builtin_amdgcn_s_setprio(MLMCPI_PRIO_A);
-#endif
   // the sampler's table: one word per thread, fetched now, put down when the sweeps are done (nothing waits for it here;
   // staged at the start it cost a round trip in front of the plane's loads: 1 % of the launch)
   uint32_t tabw = 0;
@@ -1378,9 +1289,6 @@ __global__ void __launch_bounds__(NT, 4)
   perm_store_image<NT, 2>(th0, th1, res);
   __syncthreads();
   MLMCPI_STAMP(4);  // image down
-#ifdef MLMCPI_PRIO_B
-  __builtin_amdgcn_s_setprio(MLMCPI_PRIO_B);
-#endif
   schwinger_image_heat<NT, STEP>(th0, th1, vpool, hpool, Mt, Mx, beta, out, i0, j0, b, tile, key0, qoi_op, qoi_partial, qoi_red);
 }
 
@@ -1837,280 +1745,6 @@ __global__ void __launch_bounds__((GffHeatGeom<K, T>::NT), 4)
   }
 }
 
-// ---- streaming kernels: evaluate, force, QoI ----------------------------------------------------------
-enum LatOp { L_GFF_ENERGY = 0, L_PHI2 = 1, L_SCHW_ENERGY = 2, L_PLAQ = 3, L_CHARGE = 4 };
-
-__device__ __forceinline__ double plaquette_angle(const double2 *t, uint32_t Mt, uint32_t Mx, uint32_t i, uint32_t j) {
-  const uint32_t ip = (i + 1 == Mt) ? 0 : i + 1, jp = (j + 1 == Mx) ? 0 : j + 1;
-  // theta(i,j,0) + theta(i+1,j,1) - theta(i,j+1,0) - theta(i,j,1)   (quenchedschwingeraction.cc:14-17)
-  const double2 here = t[(size_t)j * Mt + i];
-  return here.x + t[(size_t)j * Mt + ip].y - t[(size_t)jp * Mt + i].x - here.y;
-}
-
-// grid (nrows_blocks, B): each workgroup strides over lattice rows j
-template <int OP>
-__global__ void __launch_bounds__(256) lattice_reduce_kernel(uint32_t Mt, uint32_t Mx, double mu2,
-                                                             const double *__restrict__ state,
-                                                             double *__restrict__ partial) {
-  __shared__ double red[4];
-  const uint32_t b = blockIdx.y;
-  double acc[1] = {0.0};
-  if (OP == L_GFF_ENERGY || OP == L_PHI2) {
-    const double *phi = state + (size_t)b * Mt * Mx;
-    const double kappa = 4. + mu2;
-    for (uint32_t j = blockIdx.x; j < Mx; j += gridDim.x) {
-      const uint32_t jm = j == 0 ? Mx - 1 : j - 1, jp = j + 1 == Mx ? 0 : j + 1;
-      for (uint32_t i = threadIdx.x; i < Mt; i += blockDim.x) {
-        const double v = phi[(size_t)j * Mt + i];
-        if (OP == L_PHI2) {
-          acc[0] += v * v;
-        } else {  // gffaction.cc:15-23
-          const uint32_t im = i == 0 ? Mt - 1 : i - 1, ip = i + 1 == Mt ? 0 : i + 1;
-          double loc = kappa * v;
-          loc -= phi[(size_t)j * Mt + ip];
-          loc -= phi[(size_t)j * Mt + im];
-          loc -= phi[(size_t)jp * Mt + i];
-          loc -= phi[(size_t)jm * Mt + i];
-          acc[0] += v * loc;
-        }
-      }
-    }
-  } else {
-    const double2 *t = (const double2 *)state + (size_t)b * Mt * Mx;
-    for (uint32_t j = blockIdx.x; j < Mx; j += gridDim.x)
-      for (uint32_t i = threadIdx.x; i < Mt; i += blockDim.x) {
-        const double th = plaquette_angle(t, Mt, Mx, i, j);
-        if (OP == L_SCHW_ENERGY) acc[0] += 1. - cos_reduced(th);
-        if (OP == L_PLAQ) acc[0] += cos_reduced(th);
-        if (OP == L_CHARGE) acc[0] += mod_2pi(th);
-      }
-  }
-  block_sum<1>(acc, red);
-  if (threadIdx.x == 0) partial[(size_t)b * gridDim.x + blockIdx.x] = acc[0];
-}
-
-// Plaquette reductions (Schwinger energy, average plaquette, topological charge), one pass with ONE load per site.
-// Grid (bands, B): a workgroup walks a band of consecutive rows bottom-up; a thread owns the columns tid + 256 c and
-// keeps the current row of its columns in registers, so theta(i, j+1, 0) of this row is the `here` of the next one;
-// theta(i+1, j, 1) comes from the neighbouring lane (the last lane of a wave loads it).  The generic kernel above issues
-// three 16-byte loads per plaquette and runs at ~2.9 TB/s; this one is bound by the 16 B per site it has to read.
-template <int OP, int NC>
-__global__ void __launch_bounds__(256) schwinger_reduce_band_kernel(uint32_t Mt, uint32_t Mx, uint32_t rows_per_band,
-                                                                    const double2 *__restrict__ state,
-                                                                    double *__restrict__ partial) {
-  __shared__ double red[4];
-  const uint32_t b = blockIdx.y, j0 = blockIdx.x * rows_per_band;
-  const uint32_t j1 = min(j0 + rows_per_band, Mx);
-  const double2 *t = state + (size_t)b * Mt * Mx;
-  const uint32_t lane = threadIdx.x & (kWave - 1);
-  double2 cur[NC], nxt[NC];
-  uint32_t col[NC];
-#pragma unroll
-  for (int c = 0; c < NC; ++c) {
-    col[c] = threadIdx.x + 256u * c;
-    cur[c] = col[c] < Mt ? t[(size_t)j0 * Mt + col[c]] : make_double2(0., 0.);
-  }
-  double acc[1] = {0.0};
-  for (uint32_t j = j0; j < j1; ++j) {
-    const uint32_t jp = j + 1 == Mx ? 0 : j + 1;
-    double edge[NC];
-#pragma unroll
-    for (int c = 0; c < NC; ++c) {
-      nxt[c] = col[c] < Mt ? t[(size_t)jp * Mt + col[c]] : make_double2(0., 0.);
-      // the right neighbour of a wave's last lane (or of the last column) lives in another wave / at column 0
-      const uint32_t ip = col[c] + 1 == Mt ? 0 : col[c] + 1;
-      edge[c] = (col[c] < Mt && (lane == kWave - 1 || col[c] + 1 == Mt)) ? t[(size_t)j * Mt + ip].y : 0.0;
-    }
-#pragma unroll
-    for (int c = 0; c < NC; ++c) {
-      const double from_lane = __shfl_down(cur[c].y, 1, kWave);
-      const double right = (lane == kWave - 1 || col[c] + 1 == Mt) ? edge[c] : from_lane;
-      if (col[c] < Mt) {
-        // theta(i,j,0) + theta(i+1,j,1) - theta(i,j+1,0) - theta(i,j,1)   (quenchedschwingeraction.cc:14-17)
-        const double th = cur[c].x + right - nxt[c].x - cur[c].y;
-        if (OP == L_SCHW_ENERGY) acc[0] += 1. - cos_reduced(th);
-        if (OP == L_PLAQ) acc[0] += cos_reduced(th);
-        if (OP == L_CHARGE) acc[0] += mod_2pi(th);
-      }
-      cur[c] = nxt[c];
-    }
-  }
-  block_sum<1>(acc, red);
-  if (threadIdx.x == 0) partial[(size_t)b * gridDim.x + blockIdx.x] = acc[0];
-}
-
-__global__ void __launch_bounds__(256) lattice_finish_kernel(const double *__restrict__ partial, uint32_t nsplit, uint32_t B,
-                                                              int op, double scale, double *__restrict__ out,
-                                                              double *__restrict__ acc = nullptr) {
-  // one wave per chain: lane l sums partials l, l + 64, ... in order, then a fixed shuffle tree -- the result depends on
-  // nsplit only, never on the launch.  acc != NULL: stats->record_sample of the value as well (stats_accumulate_kernel's
-  // recurrence), for callers that would launch that next.
-  const uint32_t b = blockIdx.x * (blockDim.x / 64) + threadIdx.x / 64, lane = threadIdx.x % 64;
-  if (b >= B) return;
-  double s = 0.0;
-  for (uint32_t k = lane; k < nsplit; k += 64) s += partial[(size_t)b * nsplit + k];
-  for (int off = 32; off > 0; off >>= 1) s += __shfl_down(s, off, 64);
-  if (lane == 0) {
-    const double v = (op == L_CHARGE) ? (1. / (4. * kPi * kPi)) * s * s : scale * s;  // qoi2dsusceptibility.cc:26
-    out[b] = v;
-    if (acc) {
-      double *a = acc + 5 * (size_t)b;
-      a[0] += 1.0;
-      a[1] += v;
-      a[2] += v * v;
-      a[3] += v * v * v;
-      a[4] += v * v * v * v;
-    }
-  }
-}
-
-// gffaction.cc:80-94
-__global__ void __launch_bounds__(256) gff_force_kernel(uint32_t Mt, uint32_t Mx, double mu2,
-                                                        const double *__restrict__ phi_all, double *__restrict__ f_all) {
-  const uint32_t b = blockIdx.y;
-  const double *phi = phi_all + (size_t)b * Mt * Mx;
-  double *f = f_all + (size_t)b * Mt * Mx;
-  const double kappa = 4. + mu2;
-  for (uint32_t j = blockIdx.x; j < Mx; j += gridDim.x) {
-    const uint32_t jm = j == 0 ? Mx - 1 : j - 1, jp = j + 1 == Mx ? 0 : j + 1;
-    for (uint32_t i = threadIdx.x; i < Mt; i += blockDim.x) {
-      const uint32_t im = i == 0 ? Mt - 1 : i - 1, ip = i + 1 == Mt ? 0 : i + 1;
-      double m = kappa * phi[(size_t)j * Mt + i];
-      m -= phi[(size_t)j * Mt + ip];
-      m -= phi[(size_t)j * Mt + im];
-      m -= phi[(size_t)jp * Mt + i];
-      m -= phi[(size_t)jm * Mt + i];
-      f[(size_t)j * Mt + i] = m;
-    }
-  }
-}
-
-// Gather form of quenchedschwingeraction.cc:68-89: the reference scatters +-beta sin(theta_P) of
-// plaquette (i,j) onto its four links; link (i,j,0) therefore receives F(i,j) - F(i,j-1) and link
-// (i,j,1) receives F(i-1,j) - F(i,j) (each a two-term sum, so the value is order independent).
-//
-// One sine per plaquette.  (Until r03 every thread computed the three plaquettes its two links touch -- three sines per
-// site, 0.37 ms for 1024^2 x 32 = 0.36 of the HBM roofline for a kernel that reads and writes the state once.)  A WAVE
-// walks up a band of rows with 64 consecutive columns: lane l holds column (62 tile + l - 1) mod Mt, takes theta_1 of the
-// column to its right from lane l + 1 and F of the column to its left from lane l - 1 (DPP rotations: no LDS, no barrier),
-// and keeps F of the row below in a register.  Lanes 1 .. 62 emit; lane 0 only supplies F, lane 63 only theta_1: tiles step
-// by 62 columns, 3 % redundant loads and sines, and nothing at the edge of a wave is special.  Rows are loaded two ahead
-// of their use.  Same arithmetic per plaquette as before (same sum order): bit-identical forces.
-#ifndef MLMCPI_FORCE_ROWS
-#define MLMCPI_FORCE_ROWS 128
-#endif
-constexpr uint32_t kForceCols = 62, kForceRows = MLMCPI_FORCE_ROWS;
-__host__ __device__ inline uint32_t force_waves(uint32_t Mt, uint32_t Mx) {
-  return ((Mt + kForceCols - 1) / kForceCols) * ((Mx + kForceRows - 1) / kForceRows);
-}
-// emit(j, i, F_0, F_1): force on the two links of vertex (i, j)
-template <class Emit>
-__device__ __forceinline__ void schwinger_force_band(const double2 *__restrict__ t, uint32_t Mt, uint32_t Mx, double coupling,
-                                                     uint32_t wave_id, Emit emit) {
-  const uint32_t tiles = (Mt + kForceCols - 1) / kForceCols;
-  const uint32_t band = wave_id / tiles, tile = wave_id - band * tiles, lane = threadIdx.x & (kWave - 1);
-  const uint32_t col = tile * kForceCols + lane;                       // column + 1, not wrapped
-  const uint32_t i = (uint32_t)(((uint64_t)col + Mt - 1) % Mt);
-  const bool owner = lane >= 1 && lane <= kForceCols && col <= Mt;     // col - 1 < Mt: not a column of the next lap
-  const uint32_t jb = band * kForceRows, je = min(jb + kForceRows, Mx);
-  auto up_of = [&](uint32_t j) { return j + 1 == Mx ? 0u : j + 1; };
-  auto F_of = [&](const double2 &a, const double2 &above) {
-    // theta(i,j,0) + theta(i+1,j,1) - theta(i,j+1,0) - theta(i,j,1)   (quenchedschwingeraction.cc:14-17)
-    return coupling * sin_reduced(a.x + wave_rotate_down(a.y) - above.x - a.y);
-  };
-  // Rows are loaded four ahead of their use, at the TOP of an iteration (vmcnt counts stores too and retires in order, so
-  // waiting for a row implies waiting for every store issued before its load).  Measured: 0.234 ms with two rows of
-  // lookahead as with four, bands of 32 rows; 0.228 ms with bands of 128 (fewer band edges); EXPERIMENTS 1.6.
-  const uint32_t jm = jb == 0 ? Mx - 1 : jb - 1;
-  uint32_t jn = jb;
-  auto next_row = [&]() {   // (up to four rows past the band at its end: valid rows, not used -- guarding the load cost 5 %)
-    jn = up_of(jn);
-    return t[(size_t)jn * Mt + i];
-  };
-  const double2 below = t[(size_t)jm * Mt + i];
-  double2 here = t[(size_t)jb * Mt + i], above = next_row(), ahead1 = next_row(), ahead2 = next_row();
-  double F_below = F_of(below, here);
-  for (uint32_t j = jb; j < je; ++j) {
-    const double2 ahead3 = next_row();
-    const double F = F_of(here, above);
-    const double F_left = wave_rotate_up(F);
-    if (owner) emit(j, i, F - F_below, F_left - F);
-    F_below = F;
-    here = above;
-    above = ahead1;
-    ahead1 = ahead2;
-    ahead2 = ahead3;
-  }
-}
-
-// grid (ceil(force_waves / 4), B)
-__global__ void __launch_bounds__(256) schwinger_force_kernel(uint32_t Mt, uint32_t Mx, double beta,
-                                                              const double2 *__restrict__ t_all,
-                                                              double2 *__restrict__ f_all) {
-  const uint32_t b = blockIdx.y, wave_id = blockIdx.x * 4 + threadIdx.x / kWave;
-  if (wave_id >= force_waves(Mt, Mx)) return;   // (a whole wave)
-  double2 *f = f_all + (size_t)b * Mt * Mx;
-  schwinger_force_band(t_all + (size_t)b * Mt * Mx, Mt, Mx, beta, wave_id,
-                       // (non-temporal stores, r05: 0.227 -> 0.221 ms over three same-box pairs, 0.59 -> 0.61 of 8 TB/s by the floor bytes)
-                       [&](uint32_t j, uint32_t i, double f0, double f1) { store_streaming(&f[(size_t)j * Mt + i], f0, f1); });
-}
-
-__global__ void __launch_bounds__(256) lattice_init_kernel(int kind, uint32_t n, RngKey key0, double *__restrict__ x) {
-  const uint32_t b = blockIdx.y;
-  RngKey key = key0;
-  key.chain += b;
-  double *xb = x + (size_t)b * n;
-  for (uint32_t l = blockIdx.x * blockDim.x + threadIdx.x; l < n; l += gridDim.x * blockDim.x) {
-    if (kind == MLMCPI_SCHWINGER) {
-      double u, v;
-      rng_uniforms(key, l, P_INIT, 0, u, v);
-      xb[l] = -kPi + 2.0 * kPi * u;
-    } else {
-      xb[l] = rng_normal0(key, l, P_INIT, 0);
-    }
-  }
-}
-
-// Statistics::record_sample with its autocorrelation window (common/statistics.cc:4-27), one chain per thread: per chain
-// [n, a1 = running average, S_0 .. S_{W-1} = running averages of Q_j Q_{j-k}, head, ring of the last W values].  The same
-// recurrences as the reference: a1 <- ((n - 1) a1 + Q) / n; S_k <- ((N_k - 1) S_k + Q Q_{-k}) / N_k, N_k = n - k, over the k
-// the window holds.  tau_int = max(1, 1 + 2 sum_{k >= 1} (1 - k / n) (S_k - a1^2) / (S_0 - a1^2)) is left to the caller
-// (:38-61): the multilevel driver reads it between draws (montecarlomultilevel.cc:170-190).
-__global__ void stats_window_record_kernel(double *__restrict__ state, const double *__restrict__ q, uint32_t B, uint32_t W) {
-  const uint32_t b = blockIdx.x * blockDim.x + threadIdx.x;
-  if (b >= B) return;
-  double *st = state + (size_t)b * (2 * W + 3);
-  double *S = st + 2, *ring = st + 3 + W;
-  const double Q = q[b];
-  const double n = st[0] + 1.0;
-  uint32_t head = (uint32_t)st[2 + W];   // slot of the most recent value
-  head = head + 1 == W ? 0 : head + 1;
-  ring[head] = Q;
-  st[2 + W] = (double)head;
-  st[0] = n;
-  st[1] = ((n - 1.0) * st[1] + Q) / n;
-  const uint32_t filled = n < (double)W ? (uint32_t)n : W;
-  uint32_t slot = head;
-  for (uint32_t k = 0; k < filled; ++k) {
-    const double Nk = n - (double)k;
-    S[k] = ((Nk - 1.0) * S[k] + Q * ring[slot]) / Nk;
-    slot = slot == 0 ? W - 1 : slot - 1;
-  }
-}
-
-// packed per-chain sums for the cross-rank reduction: [n, sum q, sum q^2, sum q^3, sum q^4]
-__global__ void stats_accumulate_kernel(double *__restrict__ acc, const double *__restrict__ q, uint32_t B) {
-  const uint32_t b = blockIdx.x * blockDim.x + threadIdx.x;
-  if (b >= B) return;
-  const double v = q[b];
-  double *a = acc + 5 * (size_t)b;
-  a[0] += 1.0;
-  a[1] += v;
-  a[2] += v * v;
-  a[3] += v * v * v;
-  a[4] += v * v * v * v;
-}
-
 // ---- site-at-a-time updates: Action::heatbath_update / overrelaxation_update(state, l), action/action.hh:73-96 -----------
 // gffaction.cc:33-42,68-77; quenchedschwingeraction.cc:25-65.  One thread per chain walks the site list in order (the
 // reference's own sequential semantics: every update sees the ones before it), straight on the state in global memory.
@@ -2139,81 +1773,6 @@ __global__ void __launch_bounds__(64)
 }
 
 // ---- host dispatch ----------------------------------------------------------------------------------------
-static int check_lattice_dims(const mlmcpi_lattice_action *act) {
-  if (!act) return fail(MLMCPI_ERR_INVALID, "action is NULL");
-  if (act->kind != MLMCPI_GFF && act->kind != MLMCPI_SCHWINGER && act->kind != MLMCPI_NONLINEAR_SIGMA)
-    return fail(MLMCPI_ERR_INVALID, "kind %d is not a 2-D lattice action", act->kind);
-  if (act->Mt < 2 || act->Mx < 2) return fail(MLMCPI_ERR_INVALID, "lattice %u x %u too small", act->Mt, act->Mx);
-  if ((uint64_t)act->Mt * act->Mx > (1ull << 30)) return fail(MLMCPI_ERR_INVALID, "lattice too large for 32-bit site indices");
-  return MLMCPI_OK;
-}
-
-static int check_lattice(const mlmcpi_lattice_action *act) {
-  if (!act) return fail(MLMCPI_ERR_INVALID, "action is NULL");
-  if (act->kind != MLMCPI_GFF && act->kind != MLMCPI_SCHWINGER && act->kind != MLMCPI_NONLINEAR_SIGMA)
-    return fail(MLMCPI_ERR_INVALID, "kind %d is not a 2-D lattice action", act->kind);
-  if (act->Mt < 2 || act->Mx < 2) return fail(MLMCPI_ERR_INVALID, "lattice %u x %u too small", act->Mt, act->Mx);
-  if ((uint64_t)act->Mt * act->Mx > (1ull << 30)) return fail(MLMCPI_ERR_INVALID, "lattice too large for 32-bit site indices");
-  // gffaction.hh:169-173: the GFF action requires a square lattice
-  if (act->kind == MLMCPI_GFF && act->Mt != act->Mx)
-    return fail(MLMCPI_ERR_INVALID, "Lattice has to be squared for GFF action");
-  return MLMCPI_OK;
-}
-
-// the entry points the O(3) sigma model does not take
-static int refuse_sigma(const mlmcpi_lattice_action *act, const char *what) {
-  if (act && act->kind == MLMCPI_NONLINEAR_SIGMA)
-    return fail(MLMCPI_ERR_UNSUPPORTED, "%s is not available for the O(3) nonlinear sigma model (DESIGN 8)", what);
-  return MLMCPI_OK;
-}
-
-
-static uint32_t row_blocks(uint32_t Mx, uint32_t B) {
-  uint32_t want = (2048 + B - 1) / B;
-  return want < Mx ? (want ? want : 1) : Mx;
-}
-
-template <int OP>
-static int launch_lattice_reduce(uint32_t Mt, uint32_t Mx, double mu2, const double *d_state, uint32_t B, double scale,
-                                 double *d_out, hipStream_t st) {
-  uint32_t nsplit = row_blocks(Mx, B);
-  constexpr bool plaquettes = OP == L_SCHW_ENERGY || OP == L_PLAQ || OP == L_CHARGE;
-  // plaquette reductions on lattices up to 2048 columns: bands of consecutive rows, one load per site
-  uint32_t rows_per_band = 0;
-  if (plaquettes && Mt <= 2048 && Mt >= 64) {
-    rows_per_band = (Mx + nsplit - 1) / nsplit;
-    if (rows_per_band < 8) rows_per_band = Mx < 8 ? Mx : 8;  // the first row of a band is loaded twice: keep bands tall
-    nsplit = (Mx + rows_per_band - 1) / rows_per_band;
-  }
-  void *ws = nullptr;
-  if (int rc = scratch((size_t)B * nsplit * sizeof(double), &ws, st)) return rc;
-  if constexpr (plaquettes) if (rows_per_band) {
-    const double2 *t = (const double2 *)d_state;
-    const int nc = (int)((Mt + 255) / 256);
-#define MLMCPI_BAND(NC) hipLaunchKernelGGL((schwinger_reduce_band_kernel<OP, NC>), dim3(nsplit, B), dim3(256), 0, st, Mt, Mx, rows_per_band, t, (double *)ws)
-    switch (nc) {
-      case 1: MLMCPI_BAND(1); break;
-      case 2: MLMCPI_BAND(2); break;
-      case 3: MLMCPI_BAND(3); break;
-      case 4: MLMCPI_BAND(4); break;
-      case 5: MLMCPI_BAND(5); break;
-      case 6: MLMCPI_BAND(6); break;
-      case 7: MLMCPI_BAND(7); break;
-      default: MLMCPI_BAND(8);
-    }
-#undef MLMCPI_BAND
-    MLMCPI_LAUNCH_CHECK("schwinger_reduce_band_kernel");
-  }
-  if (!rows_per_band) {
-    hipLaunchKernelGGL((lattice_reduce_kernel<OP>), dim3(nsplit, B), dim3(256), 0, st, Mt, Mx, mu2, d_state, (double *)ws);
-    MLMCPI_LAUNCH_CHECK("lattice_reduce_kernel");
-  }
-  hipLaunchKernelGGL(lattice_finish_kernel, dim3((B + 3) / 4), dim3(256), 0, st, (const double *)ws, nsplit, B, OP,
-                     scale, d_out);
-  MLMCPI_LAUNCH_CHECK("lattice_finish_kernel");
-  return MLMCPI_OK;
-}
-
 struct SweepGeom {
   TileGeom tg;
   uint32_t tiles_y, NT;
@@ -2370,57 +1929,6 @@ using namespace mlmcpi;
 
 extern "C" {
 
-int mlmcpi_lattice_state_size(const mlmcpi_lattice_action *act, uint32_t *n) {
-  if (int rc = check_lattice(act)) return rc;
-  MLMCPI_REQUIRE(n, "n is NULL");
-  *n = (act->kind == MLMCPI_GFF ? 1u : 2u) * act->Mt * act->Mx;
-  return MLMCPI_OK;
-}
-
-int mlmcpi_lattice_evaluate(const mlmcpi_lattice_action *act, const double *d_phi, uint32_t B, double *d_S,
-                            void *stream) {
-  if (int rc = check_lattice(act)) return rc;
-  MLMCPI_REQUIRE(d_phi && d_S && B > 0, "bad arguments");
-  if (act->kind == MLMCPI_NONLINEAR_SIGMA) return sigma_evaluate(act, d_phi, B, d_S, as_stream(stream));
-  if (act->kind == MLMCPI_GFF)
-    return launch_lattice_reduce<L_GFF_ENERGY>(act->Mt, act->Mx, gff_mu2(*act), d_phi, B, 0.5, d_S, as_stream(stream));
-  return launch_lattice_reduce<L_SCHW_ENERGY>(act->Mt, act->Mx, 0.0, d_phi, B, act->beta, d_S, as_stream(stream));
-}
-
-int mlmcpi_lattice_force(const mlmcpi_lattice_action *act, const double *d_phi, double *d_f, uint32_t B,
-                         void *stream) {
-  if (int rc = check_lattice(act)) return rc;
-  MLMCPI_REQUIRE(d_phi && d_f && d_phi != d_f && B > 0, "bad arguments");
-  if (act->kind == MLMCPI_NONLINEAR_SIGMA) return sigma_force(act, d_phi, d_f, B, as_stream(stream));
-  dim3 grid(row_blocks(act->Mx, B), B), block(256);
-  if (act->kind == MLMCPI_GFF)
-    hipLaunchKernelGGL(gff_force_kernel, grid, block, 0, as_stream(stream), act->Mt, act->Mx, gff_mu2(*act), d_phi, d_f);
-  else
-    hipLaunchKernelGGL(schwinger_force_kernel, dim3((force_waves(act->Mt, act->Mx) + 3) / 4, B), block, 0, as_stream(stream),
-                       act->Mt, act->Mx, act->beta, (const double2 *)d_phi, (double2 *)d_f);
-  MLMCPI_LAUNCH_CHECK("lattice force kernel");
-  return MLMCPI_OK;
-}
-
-static int gff_initialise_exact(const mlmcpi_lattice_action *act, double *d_phi, uint32_t B, uint64_t seed, uint32_t chain0,
-                                hipStream_t st);
-
-int mlmcpi_lattice_initialise(const mlmcpi_lattice_action *act, double *d_phi, uint32_t B, uint64_t seed,
-                              uint32_t chain0, void *stream) {
-  if (int rc = check_lattice(act)) return rc;
-  MLMCPI_REQUIRE(d_phi && B > 0, "bad arguments");
-  if (act->kind == MLMCPI_GFF) return gff_initialise_exact(act, d_phi, B, seed, chain0, as_stream(stream));
-  if (act->kind == MLMCPI_NONLINEAR_SIGMA) return sigma_initialise(act, d_phi, B, seed, chain0, as_stream(stream));
-  uint32_t n = 0;
-  mlmcpi_lattice_state_size(act, &n);
-  uint32_t nb = (n + 255) / 256;
-  if (nb > 1024) nb = 1024;
-  hipLaunchKernelGGL(lattice_init_kernel, dim3(nb, B), dim3(256), 0, as_stream(stream), act->kind, n,
-                     make_key(seed, chain0, 0), d_phi);
-  MLMCPI_LAUNCH_CHECK("lattice_init_kernel");
-  return MLMCPI_OK;
-}
-
 // The launches read `src` and write `dst`; after each one src <- dst and dst <- the other work buffer.  d_phi is only
 // read unless it is also d_w1.  result_in (may be NULL: then the result is copied into d_phi, which must be writable):
 // 0 -> the result is in d_w0, 1 -> in d_w1, -1 -> no sweep was run (result is the input).
@@ -2495,11 +2003,8 @@ static int sweep_draw_impl(const mlmcpi_lattice_action *act, double *d_phi, doub
     if (with_qoi)
       if (int rc = scratch((size_t)B * tiles * sizeof(double), &partial, st)) return rc;
     if (int rc = launch(make_key(seed, chain0, sweep0 + h), with_qoi ? qoi_op : 0, (double *)partial)) return rc;
-    if (with_qoi) {
-      hipLaunchKernelGGL(lattice_finish_kernel, dim3((B + 3) / 4), dim3(256), 0, st, (const double *)partial, tiles, B, qoi_op,
-                         1.0 / ((double)Mx * Mt), d_qoi, d_acc);
-      MLMCPI_LAUNCH_CHECK("lattice_finish_kernel");
-    }
+    if (with_qoi)
+      return lattice_finish((const double *)partial, tiles, B, qoi_op, 1.0 / ((double)Mx * Mt), d_qoi, d_acc, st);
     return MLMCPI_OK;
   };
   uint32_t s = 0;
@@ -2691,28 +2196,6 @@ int mlmcpi_lattice_sweep_draw_qoi_record(const mlmcpi_lattice_action *act, const
                          result_in, stream, qoi_kind, d_qoi, d_acc);
 }
 
-int mlmcpi_qoi_phi_squared(const double *d_phi, uint32_t n_vertices, uint32_t B, double *d_out, void *stream) {
-  MLMCPI_REQUIRE(d_phi && d_out && B > 0 && n_vertices > 0, "bad arguments");
-  // treat the field as a 1 x n strip: the reduction does not need the geometry
-  uint32_t Mt = n_vertices, Mx = 1;
-  if (n_vertices > 4096)
-    for (uint32_t w = 4096; w >= 64; w >>= 1)
-      if (n_vertices % w == 0) { Mt = w; Mx = n_vertices / w; break; }
-  return launch_lattice_reduce<L_PHI2>(Mt, Mx, 0.0, d_phi, B, 1.0 / n_vertices, d_out, as_stream(stream));
-}
-
-int mlmcpi_qoi_avg_plaquette(const double *d_theta, uint32_t Mt, uint32_t Mx, uint32_t B, double *d_out,
-                             void *stream) {
-  MLMCPI_REQUIRE(d_theta && d_out && B > 0 && Mt > 1 && Mx > 1, "bad arguments");
-  return launch_lattice_reduce<L_PLAQ>(Mt, Mx, 0.0, d_theta, B, 1.0 / ((double)Mx * Mt), d_out, as_stream(stream));
-}
-
-int mlmcpi_qoi_2d_susceptibility(const double *d_theta, uint32_t Mt, uint32_t Mx, uint32_t B, double *d_out,
-                                 void *stream) {
-  MLMCPI_REQUIRE(d_theta && d_out && B > 0 && Mt > 1 && Mx > 1, "bad arguments");
-  return launch_lattice_reduce<L_CHARGE>(Mt, Mx, 0.0, d_theta, B, 1.0, d_out, as_stream(stream));
-}
-
 int mlmcpi_lattice_site_updates(const mlmcpi_lattice_action *act, double *d_state, uint32_t B, const uint32_t *d_sites,
                                 uint32_t n, uint32_t site, int32_t heat, uint64_t seed, uint32_t chain0, uint32_t step,
                                 void *stream) {
@@ -2744,877 +2227,5 @@ int mlmcpi_lattice_site_updates(const mlmcpi_lattice_action *act, double *d_stat
   MLMCPI_LAUNCH_CHECK("lattice_site_update_kernel");
   return MLMCPI_OK;
 }
-
-int mlmcpi_stats_window_record(double *d_state, const double *d_q, uint32_t B, uint32_t window, void *stream) {
-  MLMCPI_REQUIRE(d_state && d_q && B > 0 && window > 0 && window <= 1024, "bad arguments");
-  hipLaunchKernelGGL(stats_window_record_kernel, dim3((B + 255) / 256), dim3(256), 0, as_stream(stream), d_state, d_q, B, window);
-  MLMCPI_LAUNCH_CHECK("stats_window_record_kernel");
-  return MLMCPI_OK;
-}
-
-int mlmcpi_stats_accumulate(double *d_acc, const double *d_q, uint32_t B, void *stream) {
-  MLMCPI_REQUIRE(d_acc && d_q && B > 0, "bad arguments");
-  hipLaunchKernelGGL(stats_accumulate_kernel, dim3((B + 255) / 256), dim3(256), 0, as_stream(stream), d_acc, d_q, B);
-  MLMCPI_LAUNCH_CHECK("stats_accumulate_kernel");
-  return MLMCPI_OK;
-}
-
-}  // extern "C"
-
-// =================================================================================================
-// Generic HMC for 2-D actions (sampler/hmcsampler.cc:8-69), streaming form: momenta and the trial
-// state live in HBM, one fused force + momentum + position kernel per leapfrog step (ping-pong on
-// the trial state because neighbours need the old positions).
-// =================================================================================================
-namespace mlmcpi {
-
-// p ~ N(0,1) per entry (Philox site = entry index), trial <- current
-__global__ void __launch_bounds__(256)
-    lat_hmc_init_kernel(uint32_t n, const double *__restrict__ x_cur, double *__restrict__ x_trial,
-                        double *__restrict__ p, const int32_t *__restrict__ done, RngKey key0) {
-  const uint32_t b = blockIdx.y;
-  if (done[b]) return;
-  RngKey key = key0;
-  key.chain += b;
-  const size_t off = (size_t)b * n;
-  for (uint32_t l = blockIdx.x * blockDim.x + threadIdx.x; l < n; l += gridDim.x * blockDim.x) {
-    p[off + l] = rng_normal0(key, l, P_MOMENTUM, 0);
-    x_trial[off + l] = x_cur[off + l];
-  }
-}
-
-// one leapfrog step: F(x_in); p -= dtp F; x_out = x_in + dtx p
-template <int KIND>
-__global__ void __launch_bounds__(256)
-    lat_hmc_step_kernel(uint32_t Mt, uint32_t Mx, double coupling, const double *__restrict__ x_in,
-                        double *__restrict__ x_out, double *__restrict__ p_all, const int32_t *__restrict__ done,
-                        double dtp, double dtx) {
-  const uint32_t b = blockIdx.y;
-  if (done[b]) return;
-  if (KIND == MLMCPI_GFF) {
-    const double *phi = x_in + (size_t)b * Mt * Mx;
-    double *out = x_out + (size_t)b * Mt * Mx, *p = p_all + (size_t)b * Mt * Mx;
-    const double kappa = 4. + coupling;
-    for (uint32_t j = blockIdx.x; j < Mx; j += gridDim.x) {
-      const uint32_t jm = j == 0 ? Mx - 1 : j - 1, jp = j + 1 == Mx ? 0 : j + 1;
-      for (uint32_t i = threadIdx.x; i < Mt; i += blockDim.x) {
-        const uint32_t im = i == 0 ? Mt - 1 : i - 1, ip = i + 1 == Mt ? 0 : i + 1;
-        const size_t o = (size_t)j * Mt + i;
-        double F = kappa * phi[o];
-        F -= phi[(size_t)j * Mt + ip];
-        F -= phi[(size_t)j * Mt + im];
-        F -= phi[(size_t)jp * Mt + i];
-        F -= phi[(size_t)jm * Mt + i];
-        const double pn = p[o] - dtp * F;
-        p[o] = pn;
-        out[o] = phi[o] + dtx * pn;
-      }
-    }
-  } else {
-    // grid (ceil(force_waves / 4), B): one sine per plaquette (schwinger_force_band)
-    const uint32_t wave_id = blockIdx.x * 4 + threadIdx.x / kWave;
-    if (wave_id >= force_waves(Mt, Mx)) return;
-    const double2 *t = (const double2 *)x_in + (size_t)b * Mt * Mx;
-    double2 *out = (double2 *)x_out + (size_t)b * Mt * Mx, *p = (double2 *)p_all + (size_t)b * Mt * Mx;
-    schwinger_force_band(t, Mt, Mx, coupling, wave_id, [&](uint32_t j, uint32_t i, double f0, double f1) {
-      const size_t o = (size_t)j * Mt + i;
-      double2 pn = p[o];
-      pn.x -= dtp * f0;
-      pn.y -= dtp * f1;
-      p[o] = pn;
-      const double2 xo = t[o];
-      out[o] = make_double2(xo.x + dtx * pn.x, xo.y + dtx * pn.y);
-    });
-  }
-}
-
-// en4 = [4][B]: S0, T0, S1, T1 (already scaled).  hmcsampler.cc:50-67.
-__global__ void __launch_bounds__(256)
-    lat_hmc_accept_kernel(uint32_t n, double *__restrict__ x_cur, const double *__restrict__ x_trial,
-                          const double *__restrict__ en4, uint32_t B, const int32_t *__restrict__ done_in,
-                          int32_t *__restrict__ done_out, double *__restrict__ energies, RngKey key0) {
-  const uint32_t b = blockIdx.y;
-  if (done_in[b]) {
-    if (blockIdx.x == 0 && threadIdx.x == 0) done_out[b] = 1;
-    return;
-  }
-  const double S0 = en4[b], T0 = en4[B + b], S1 = en4[2 * B + b], T1 = en4[3 * B + b];
-  const double dH = (S1 - S0) + (T1 - T0);
-  bool acc;
-  if (dH < 0.0) {
-    acc = true;
-  } else {
-    RngKey key = key0;
-    key.chain += b;
-    double u, v;
-    rng_uniforms(key, 0, P_ACCEPT, 0, u, v);
-    acc = u < exp(-dH);
-  }
-  if (blockIdx.x == 0 && threadIdx.x == 0) {
-    done_out[b] = acc ? 1 : 0;
-    if (energies) {
-      energies[4 * b + 0] = S0; energies[4 * b + 1] = T0; energies[4 * b + 2] = S1; energies[4 * b + 3] = T1;
-    }
-  }
-  if (!acc) return;
-  const size_t off = (size_t)b * n;
-  for (uint32_t l = blockIdx.x * blockDim.x + threadIdx.x; l < n; l += gridDim.x * blockDim.x)
-    x_cur[off + l] = x_trial[off + l];
-}
-
-static size_t align256_(size_t n) { return (n + 255) & ~(size_t)255; }
-
-static int lattice_energy(const mlmcpi_lattice_action *act, const double *d_phi, uint32_t B, double *d_S, hipStream_t st) {
-  if (act->kind == MLMCPI_GFF)
-    return launch_lattice_reduce<L_GFF_ENERGY>(act->Mt, act->Mx, gff_mu2(*act), d_phi, B, 0.5, d_S, st);
-  return launch_lattice_reduce<L_SCHW_ENERGY>(act->Mt, act->Mx, 0.0, d_phi, B, act->beta, d_S, st);
-}
-
-static int kinetic_energy(const double *d_p, uint32_t n, uint32_t B, double *d_T, hipStream_t st) {
-  uint32_t w = n, h = 1;
-  if (n > 4096)
-    for (uint32_t c = 4096; c >= 64; c >>= 1)
-      if (n % c == 0) { w = c; h = n / c; break; }
-  return launch_lattice_reduce<L_PHI2>(w, h, 0.0, d_p, B, 0.5, d_T, st);
-}
-
-}  // namespace mlmcpi
-
-extern "C" {
-
-// workspace: p | trial A | trial B | energies [4][B] | flags [2][B]
-int mlmcpi_lattice_hmc_workspace_bytes(const mlmcpi_lattice_action *act, uint32_t B, size_t *bytes) {
-  if (int rc = check_lattice(act)) return rc;
-  if (int rc = refuse_sigma(act, "HMC (in (theta, phi) the target density carries sin theta, which the reference's force leaves out)")) return rc;
-  MLMCPI_REQUIRE(bytes && B > 0, "bad arguments");
-  uint32_t n = 0;
-  mlmcpi_lattice_state_size(act, &n);
-  *bytes = 3 * align256_((size_t)B * n * 8) + align256_((size_t)4 * B * 8) + align256_((size_t)2 * B * 4);
-  return MLMCPI_OK;
-}
-
-int mlmcpi_lattice_hmc_draw(const mlmcpi_lattice_action *act, double *d_phi, uint32_t B, uint32_t nt, double dt,
-                            uint32_t n_rep, uint64_t seed, uint32_t chain0, uint32_t traj0, void *d_work,
-                            int32_t *d_accept, double *d_energies, void *stream) {
-  if (int rc = check_lattice(act)) return rc;
-  if (int rc = refuse_sigma(act, "HMC (in (theta, phi) the target density carries sin theta, which the reference's force leaves out)")) return rc;
-  MLMCPI_REQUIRE(d_phi && d_work && B > 0 && n_rep > 0, "bad arguments");
-  uint32_t n = 0;
-  mlmcpi_lattice_state_size(act, &n);
-  hipStream_t st = as_stream(stream);
-  char *w = (char *)d_work;
-  const size_t sb = align256_((size_t)B * n * 8);
-  double *p = (double *)w, *xa = (double *)(w + sb), *xb = (double *)(w + 2 * sb);
-  double *en4 = (double *)(w + 3 * sb);
-  int32_t *flags = (int32_t *)(w + 3 * sb + align256_((size_t)4 * B * 8));
-  MLMCPI_HIP_TRY(hipMemsetAsync(flags, 0, (size_t)2 * B * 4, st));
-  uint32_t nb = (n + 255) / 256;
-  if (nb > 1024) nb = 1024;
-  const dim3 lin_grid(nb, B), row_grid(row_blocks(act->Mx, B), B), block(256);
-  const double coupling = act->kind == MLMCPI_GFF ? gff_mu2(*act) : act->beta;
-  for (uint32_t r = 0; r < n_rep; ++r) {
-    const int32_t *done_in = flags + (size_t)(r & 1) * B;
-    int32_t *done_out = flags + (size_t)((r + 1) & 1) * B;
-    const RngKey key = make_key(seed, chain0, traj0 + r);
-    hipLaunchKernelGGL(lat_hmc_init_kernel, lin_grid, block, 0, st, n, (const double *)d_phi, xa, p, done_in, key);
-    MLMCPI_LAUNCH_CHECK("lat_hmc_init_kernel");
-    if (int rc = lattice_energy(act, d_phi, B, en4, st)) return rc;
-    if (int rc = kinetic_energy(p, n, B, en4 + B, st)) return rc;
-    double *src = xa, *dst = xb;
-    for (uint32_t k = 0; k <= nt; ++k) {
-      const double dtp = (k == 0 || k == nt) ? 0.5 * dt : dt;
-      const double dtx = (k == nt) ? 0.0 : dt;
-      if (act->kind == MLMCPI_GFF)
-        hipLaunchKernelGGL(lat_hmc_step_kernel<MLMCPI_GFF>, row_grid, block, 0, st, act->Mt, act->Mx, coupling,
-                           (const double *)src, dst, p, done_in, dtp, dtx);
-      else
-        hipLaunchKernelGGL(lat_hmc_step_kernel<MLMCPI_SCHWINGER>, dim3((force_waves(act->Mt, act->Mx) + 3) / 4, B), block, 0, st, act->Mt, act->Mx, coupling,
-                           (const double *)src, dst, p, done_in, dtp, dtx);
-      MLMCPI_LAUNCH_CHECK("lat_hmc_step_kernel");
-      double *tmp = src; src = dst; dst = tmp;
-    }
-    if (int rc = lattice_energy(act, src, B, en4 + 2 * (size_t)B, st)) return rc;
-    if (int rc = kinetic_energy(p, n, B, en4 + 3 * (size_t)B, st)) return rc;
-    hipLaunchKernelGGL(lat_hmc_accept_kernel, lin_grid, block, 0, st, n, d_phi, (const double *)src,
-                       (const double *)en4, B, done_in, done_out, d_energies, key);
-    MLMCPI_LAUNCH_CHECK("lat_hmc_accept_kernel");
-  }
-  if (d_accept)
-    MLMCPI_HIP_TRY(hipMemcpyAsync(d_accept, flags + (size_t)(n_rep & 1) * B, (size_t)B * 4, hipMemcpyDeviceToDevice, st));
-  return MLMCPI_OK;
-}
-
-}  // extern "C"
-
-// =================================================================================================
-// Transfers between lattice levels: Action::copy_from_fine / copy_from_coarse for the 2-D actions.
-//   Schwinger  quenchedschwingeraction.cc:92-195 (three coarsening cases: both, temporal, spatial)
-//   GFF        gffaction.cc:97-118 (fine2coarse_map of lattice2d.cc:126-134; unrotated coarsenings)
-// Grid (rows, B); rt, rx in {1, 2} are the coarsening factors in the temporal / spatial direction.
-// =================================================================================================
-namespace mlmcpi {
-
-__global__ void __launch_bounds__(256)
-    schwinger_copy_from_fine_kernel(uint32_t Mt, uint32_t Mx, uint32_t rt, uint32_t rx, const double2 *__restrict__ fine_all,
-                                    double2 *__restrict__ coarse_all) {
-  const uint32_t b = blockIdx.y, Mtf = Mt * rt, Mxf = Mx * rx;  // Mt, Mx: coarse extents
-  const double2 *fine = fine_all + (size_t)b * Mtf * Mxf;
-  double2 *coarse = coarse_all + (size_t)b * Mt * Mx;
-  for (uint32_t j = blockIdx.x; j < Mx; j += gridDim.x)
-    for (uint32_t i = threadIdx.x; i < Mt; i += blockDim.x) {
-      const size_t f = (size_t)(rx * j) * Mtf + rt * i;
-      // mu = 0 links add up along the temporal direction, mu = 1 links along the spatial one
-      const double t0 = (rt == 2) ? fine[f].x + fine[f + 1].x : fine[f].x;
-      const double t1 = (rx == 2) ? fine[f].y + fine[f + Mtf].y : fine[f].y;
-      coarse[(size_t)j * Mt + i] = make_double2(mod_2pi(t0), mod_2pi(t1));
-    }
-}
-
-// writes only the links the reference writes (the others are filled by the conditioned fine action)
-__global__ void __launch_bounds__(256)
-    schwinger_copy_from_coarse_kernel(uint32_t Mt, uint32_t Mx, uint32_t rt, uint32_t rx,
-                                      const double2 *__restrict__ coarse_all, double *__restrict__ fine_all) {
-  const uint32_t b = blockIdx.y, Mtf = Mt * rt, Mxf = Mx * rx;
-  const double2 *coarse = coarse_all + (size_t)b * Mt * Mx;
-  double *fine = fine_all + (size_t)b * 2 * Mtf * Mxf;
-  for (uint32_t j = blockIdx.x; j < Mx; j += gridDim.x)
-    for (uint32_t i = threadIdx.x; i < Mt; i += blockDim.x) {
-      const double2 c = coarse[(size_t)j * Mt + i];
-      const size_t f = 2 * ((size_t)(rx * j) * Mtf + rt * i);  // link index of (rt i, rx j, 0)
-      if (rt == 2) {
-        fine[f] = 0.5 * c.x;
-        fine[f + 2] = 0.5 * c.x;
-      } else {
-        fine[f] = c.x;
-      }
-      if (rx == 2) {
-        fine[f + 1] = 0.5 * c.y;
-        fine[f + 2 * Mtf + 1] = 0.5 * c.y;
-      } else {
-        fine[f + 1] = c.y;
-      }
-    }
-}
-
-// to_coarse != 0: coarse(i,j) = fine(rt i, rx j); else fine(rt i, rx j) = coarse(i,j)
-__global__ void __launch_bounds__(256)
-    vertex_transfer_kernel(uint32_t Mt, uint32_t Mx, uint32_t rt, uint32_t rx, double *__restrict__ fine_all,
-                           double *__restrict__ coarse_all, int to_coarse) {
-  const uint32_t b = blockIdx.y, Mtf = Mt * rt, Mxf = Mx * rx;
-  double *fine = fine_all + (size_t)b * Mtf * Mxf, *coarse = coarse_all + (size_t)b * Mt * Mx;
-  for (uint32_t j = blockIdx.x; j < Mx; j += gridDim.x)
-    for (uint32_t i = threadIdx.x; i < Mt; i += blockDim.x) {
-      const size_t f = (size_t)(rx * j) * Mtf + rt * i, c = (size_t)j * Mt + i;
-      if (to_coarse) coarse[c] = fine[f]; else fine[f] = coarse[c];
-    }
-}
-
-}  // namespace mlmcpi
-
-extern "C" {
-
-static int check_levels(const mlmcpi_lattice_action *fine, uint32_t rt, uint32_t rx) {
-  if (int rc = check_lattice_dims(fine)) return rc;
-  if (int rc = refuse_sigma(fine, "copying between levels")) return rc;
-  if (!((rt == 1 || rt == 2) && (rx == 1 || rx == 2) && rt * rx > 1))
-    return fail(MLMCPI_ERR_INVALID, "cannot copy between these lattices (coarsening factors %u x %u)", rt, rx);
-  if (fine->Mt % rt || fine->Mx % rx) return fail(MLMCPI_ERR_INVALID, "fine lattice %u x %u cannot be coarsened by %u x %u", fine->Mt, fine->Mx, rt, rx);
-  return MLMCPI_OK;
-}
-
-int mlmcpi_lattice_copy_from_fine(const mlmcpi_lattice_action *fine, uint32_t rt, uint32_t rx, const double *d_fine,
-                                  double *d_coarse, uint32_t B, void *stream) {
-  if (int rc = check_levels(fine, rt, rx)) return rc;
-  MLMCPI_REQUIRE(d_fine && d_coarse && B > 0, "bad arguments");
-  const uint32_t Mt = fine->Mt / rt, Mx = fine->Mx / rx;
-  dim3 grid(row_blocks(Mx, B), B), block(256);
-  if (fine->kind == MLMCPI_SCHWINGER)
-    hipLaunchKernelGGL(schwinger_copy_from_fine_kernel, grid, block, 0, as_stream(stream), Mt, Mx, rt, rx,
-                       (const double2 *)d_fine, (double2 *)d_coarse);
-  else
-    hipLaunchKernelGGL(vertex_transfer_kernel, grid, block, 0, as_stream(stream), Mt, Mx, rt, rx, (double *)d_fine, d_coarse, 1);
-  MLMCPI_LAUNCH_CHECK("copy_from_fine kernel");
-  return MLMCPI_OK;
-}
-
-int mlmcpi_lattice_copy_from_coarse(const mlmcpi_lattice_action *fine, uint32_t rt, uint32_t rx, const double *d_coarse,
-                                    double *d_fine, uint32_t B, void *stream) {
-  if (int rc = check_levels(fine, rt, rx)) return rc;
-  MLMCPI_REQUIRE(d_fine && d_coarse && B > 0, "bad arguments");
-  const uint32_t Mt = fine->Mt / rt, Mx = fine->Mx / rx;
-  dim3 grid(row_blocks(Mx, B), B), block(256);
-  if (fine->kind == MLMCPI_SCHWINGER)
-    hipLaunchKernelGGL(schwinger_copy_from_coarse_kernel, grid, block, 0, as_stream(stream), Mt, Mx, rt, rx,
-                       (const double2 *)d_coarse, d_fine);
-  else
-    hipLaunchKernelGGL(vertex_transfer_kernel, grid, block, 0, as_stream(stream), Mt, Mx, rt, rx, d_fine, (double *)d_coarse, 0);
-  MLMCPI_LAUNCH_CHECK("copy_from_coarse kernel");
-  return MLMCPI_OK;
-}
-
-}  // extern "C"
-
-// =================================================================================================
-// Two-level Metropolis step on the Schwinger lattice with semi-coarsening (one direction halved):
-//   TwoLevelMetropolisStep::draw                               montecarlo/twolevelmetropolisstep.cc:35-89
-//   QuenchedSchwingerAction::copy_from_{coarse,fine}           action/qft/quenchedschwingeraction.cc:92-195
-//   QuenchedSchwingerSemiConditionedFineAction::{fill_fine_points,evaluate}
-//                                                              action/qft/quenchedschwingerconditionedfineaction.cc:130-204,332-379
-// One coarse cell (i, j) owns two fine vertices.  In the coarsened direction d the coarse link splits into a
-// pair  a0 = theta_c/2 + dtheta, a1 = theta_c/2 - dtheta  (dtheta ~ U(-pi, pi)); the coarse link in the other
-// direction is copied; the remaining fine link (direction 1-d, between the two halves) is drawn from its
-// heat-bath conditional (ExpCos) given the staples  theta_p = s0 + b0 - a0,  theta_m = a1 + s2 - b1, where
-// (b0, b1) is the pair of the neighbouring cell and s2 the copied link of the next cell.  The neighbour's pair
-// is recomputed from its own Philox stream (no exchange).  RNG: dtheta of coarse cell c = Philox(site c,
-// P_FILLIN, 0); the ExpCos draw of fine link l = von Mises stream (site l, kVmFillin).
-// =================================================================================================
-namespace mlmcpi {
-
-// theta (fine, double2 per vertex) in reference order; rt = 2: temporal coarsening, else spatial (rx = 2).
-// partial[(b * gridDim.x + blockIdx.x) * 2 + {0, 1}] = CFA sums of (theta', theta).
-__global__ void __launch_bounds__(256)
-    schwinger_twolevel_propose_kernel(uint32_t Mtc, uint32_t Mxc, uint32_t rt, double beta,
-                                      const double2 *__restrict__ coarse_all, const double2 *__restrict__ theta_all,
-                                      double2 *__restrict__ prime_all, double *__restrict__ partial, RngKey key0) {
-  __shared__ double red[2 * 4];
-  const uint32_t b = blockIdx.y;
-  const uint32_t Mtf = (rt == 2) ? 2 * Mtc : Mtc, Mxf = (rt == 2) ? Mxc : 2 * Mxc;
-  const double2 *coarse = coarse_all + (size_t)b * Mtc * Mxc;
-  const double2 *theta = theta_all + (size_t)b * Mtf * Mxf;
-  double2 *prime = prime_all + (size_t)b * Mtf * Mxf;
-  RngKey key = key0;
-  key.chain += b;
-  double acc[2] = {0.0, 0.0};
-  for (uint32_t j = blockIdx.x; j < Mxc; j += gridDim.x) {
-    const uint32_t jp = j + 1 == Mxc ? 0 : j + 1;
-    for (uint32_t i = threadIdx.x; i < Mtc; i += blockDim.x) {
-      const uint32_t ip = i + 1 == Mtc ? 0 : i + 1;
-      const uint32_t c = j * Mtc + i;
-      // neighbour cell in the direction the pair does NOT point in, and the next cell along the pair
-      const uint32_t cn = (rt == 2) ? jp * Mtc + i : j * Mtc + ip;
-      const uint32_t cs = (rt == 2) ? j * Mtc + ip : jp * Mtc + i;
-      const double2 lc = coarse[c], ln = coarse[cn], ls = coarse[cs];
-      const double pair_c = (rt == 2) ? lc.x : lc.y, pair_n = (rt == 2) ? ln.x : ln.y;
-      const double s0 = (rt == 2) ? lc.y : lc.x, s2 = (rt == 2) ? ls.y : ls.x;
-      double u, v;
-      rng_uniforms(key, c, P_FILLIN, 0, u, v);
-      const double d_c = (2. * u - 1.) * kPi;
-      rng_uniforms(key, cn, P_FILLIN, 0, u, v);
-      const double d_n = (2. * u - 1.) * kPi;
-      const double a0 = mod_2pi(0.5 * pair_c + d_c), a1 = mod_2pi(0.5 * pair_c - d_c);
-      const double b0 = mod_2pi(0.5 * pair_n + d_n), b1 = mod_2pi(0.5 * pair_n - d_n);
-      const double th_p = mod_2pi(s0 + b0 - a0), th_m = mod_2pi(a1 + s2 - b1);
-      // fine vertices of this cell and the linear index of the filled link
-      size_t v0, v1;
-      uint32_t l_fill;
-      if (rt == 2) {
-        v0 = (size_t)j * Mtf + 2 * i;
-        v1 = v0 + 1;
-        l_fill = 2 * (uint32_t)v1 + 1;
-      } else {
-        v0 = (size_t)(2 * j) * Mtf + i;
-        v1 = v0 + Mtf;
-        l_fill = 2 * (uint32_t)v1;
-      }
-      const double fill = expcos_draw(key, l_fill, beta, th_p, th_m, kVmFillin);
-      if (rt == 2) {
-        prime[v0] = make_double2(a0, s0);
-        prime[v1] = make_double2(a1, fill);
-      } else {
-        prime[v0] = make_double2(s0, a0);
-        prime[v1] = make_double2(fill, a1);
-      }
-      acc[0] += expcos_neg_log_pdf(beta, fill, th_p, th_m);
-      // the same term for the current fine state
-      double t_a0, t_a1, t_b0, t_b1, t_s0, t_s2, t_x;
-      if (rt == 2) {
-        const uint32_t i2 = 2 * i, i2p = (i2 + 2 == Mtf) ? 0 : i2 + 2;
-        const double2 q0 = theta[(size_t)j * Mtf + i2], q1 = theta[(size_t)j * Mtf + i2 + 1];
-        const double2 n0 = theta[(size_t)jp * Mtf + i2], n1 = theta[(size_t)jp * Mtf + i2 + 1];
-        t_a0 = q0.x; t_a1 = q1.x; t_s0 = q0.y; t_x = q1.y; t_b0 = n0.x; t_b1 = n1.x;
-        t_s2 = theta[(size_t)j * Mtf + i2p].y;
-      } else {
-        const uint32_t j2 = 2 * j, j2p = (j2 + 2 == Mxf) ? 0 : j2 + 2;
-        const double2 q0 = theta[(size_t)j2 * Mtf + i], q1 = theta[(size_t)(j2 + 1) * Mtf + i];
-        const double2 n0 = theta[(size_t)j2 * Mtf + ip], n1 = theta[(size_t)(j2 + 1) * Mtf + ip];
-        t_a0 = q0.y; t_a1 = q1.y; t_s0 = q0.x; t_x = q1.x; t_b0 = n0.y; t_b1 = n1.y;
-        t_s2 = theta[(size_t)j2p * Mtf + i].x;
-      }
-      acc[1] += expcos_neg_log_pdf(beta, mod_2pi(t_x), mod_2pi(-t_a0 + t_s0 + t_b0), mod_2pi(t_a1 + t_s2 - t_b1));
-    }
-  }
-  block_sum<2>(acc, red);
-  if (threadIdx.x == 0) {
-    partial[((size_t)b * gridDim.x + blockIdx.x) * 2 + 0] = acc[0];
-    partial[((size_t)b * gridDim.x + blockIdx.x) * 2 + 1] = acc[1];
-  }
-}
-
-// ---- coarsening in both directions: QuenchedSchwingerConditionedFineAction (quenchedschwingerconditionedfineaction.cc:7-78,
-// 207-289).  Three kernels: (A) per coarse cell, steps 1 and 2 -- uniform shifts of the two split coarse links, then the
-// two interior spatial links from the Bessel-product law of their sum (the staples of the 2 x 2 block need the split
-// links of the cells (i+1, j) and (i, j+1), recomputed from those cells' Philox streams); (B) per fine link
-// (i, 2 jc + 1, 0), step 3 -- the ExpCos heat-bath conditional, reading what (A) wrote; (C) the conditioned fine action
-// of a state.
-__device__ __forceinline__ void split_pair(const RngKey &key, uint32_t cell, double2 coarse_link, double (&t)[2], double (&x)[2]) {
-  double u, v;
-  rng_uniforms(key, cell, P_FILLIN, 0, u, v);
-  const double dt = (2. * u - 1.) * kPi, dx = (2. * v - 1.) * kPi;
-  t[0] = mod_2pi(0.5 * coarse_link.x + dt);
-  t[1] = mod_2pi(0.5 * coarse_link.x - dt);
-  x[0] = mod_2pi(0.5 * coarse_link.y + dx);
-  x[1] = mod_2pi(0.5 * coarse_link.y - dx);
-}
-
-__global__ void __launch_bounds__(256)
-    schwinger_both_fill_kernel(uint32_t Mtc, uint32_t Mxc, BesselFill P, const double2 *__restrict__ coarse_all,
-                               double2 *__restrict__ prime_all, RngKey key0) {
-  const uint32_t b = blockIdx.y, Mtf = 2 * Mtc;
-  const double2 *coarse = coarse_all + (size_t)b * Mtc * Mxc;
-  double *prime = (double *)(prime_all + (size_t)b * 4 * Mtc * Mxc);
-  RngKey key = key0;
-  key.chain += b;
-  for (uint32_t j = blockIdx.x; j < Mxc; j += gridDim.x) {
-    const uint32_t jp = j + 1 == Mxc ? 0 : j + 1;
-    for (uint32_t i = threadIdx.x; i < Mtc; i += blockDim.x) {
-      const uint32_t ip = i + 1 == Mtc ? 0 : i + 1;
-      const uint32_t c = j * Mtc + i, c_t = j * Mtc + ip, c_x = jp * Mtc + i;
-      double t[2], x[2], tt[2], tx[2], xt[2], xx[2];
-      split_pair(key, c, coarse[c], t, x);         // this cell
-      split_pair(key, c_t, coarse[c_t], tt, tx);   // cell (i+1, j): its spatial pair closes the block on the right
-      split_pair(key, c_x, coarse[c_x], xt, xx);   // cell (i, j+1): its temporal pair closes the block on top
-      // theta_p = th(2i+1,2j,0) + th(2i+2,2j,1) + th(2i+2,2j+1,1) - th(2i+1,2j+2,0)
-      const double theta_p = mod_2pi(t[1] + tx[0] + tx[1] - xt[1]);
-      // theta_m = th(2i,2j,1) + th(2i,2j+1,1) + th(2i,2j+2,0) - th(2i,2j,0)
-      const double theta_m = mod_2pi(x[0] + x[1] + xt[0] - t[0]);
-      const double tilde = P.approximate ? approx_bessel_draw(key, c, P.beta, theta_p, theta_m)
-                                         : bessel_product_draw(key, c, P, theta_p, theta_m);
-      double u, v;
-      rng_uniforms(key, c, P_FILLIN, 1, u, v);
-      const double d = (2. * u - 1.) * kPi;
-      // fine vertices (2i, 2j), (2i+1, 2j), (2i, 2j+1), (2i+1, 2j+1); link index = 2 * vertex + mu
-      const size_t v00 = (size_t)(2 * j) * Mtf + 2 * i, v01 = v00 + Mtf;
-      prime[2 * v00] = t[0];
-      prime[2 * v00 + 1] = x[0];
-      prime[2 * (v00 + 1)] = t[1];
-      prime[2 * (v00 + 1) + 1] = mod_2pi(0.5 * tilde + d);
-      prime[2 * v01 + 1] = x[1];
-      prime[2 * (v01 + 1) + 1] = mod_2pi(0.5 * tilde - d);
-    }
-  }
-}
-
-// step 3: links (i, 2 jc + 1, 0), i = 0..Mt-1, jc = 0..Mx/2-1
-__global__ void __launch_bounds__(256)
-    schwinger_both_rows_kernel(uint32_t Mt, uint32_t Mx, double beta, double2 *__restrict__ prime_all, RngKey key0) {
-  const uint32_t b = blockIdx.y;
-  double *prime = (double *)(prime_all + (size_t)b * Mt * Mx);
-  RngKey key = key0;
-  key.chain += b;
-  for (uint32_t jc = blockIdx.x; jc < Mx / 2; jc += gridDim.x) {
-    const uint32_t j0 = 2 * jc, j1 = j0 + 1, j2 = (j0 + 2 == Mx) ? 0 : j0 + 2;
-    for (uint32_t i = threadIdx.x; i < Mt; i += blockDim.x) {
-      const uint32_t ip = i + 1 == Mt ? 0 : i + 1;
-      auto link = [&](uint32_t ii, uint32_t jj, uint32_t mu) { return prime[2 * ((size_t)jj * Mt + ii) + mu]; };
-      const double theta_p = mod_2pi(link(i, j0, 0) + link(ip, j0, 1) - link(i, j0, 1));
-      const double theta_m = mod_2pi(link(i, j1, 1) + link(i, j2, 0) - link(ip, j1, 1));
-      const uint32_t l = 2 * (j1 * Mt + i);
-      prime[l] = expcos_draw(key, l, beta, theta_p, theta_m, kVmFillin);
-    }
-  }
-}
-
-// partial[(b * gridDim.x + blockIdx.x) * 2 + slot] = conditioned fine action of `state`, one 2 x 2 block per thread
-__global__ void __launch_bounds__(256)
-    schwinger_both_cfa_kernel(uint32_t Mt, uint32_t Mx, BesselFill P, const double2 *__restrict__ state_all,
-                              double *__restrict__ partial, uint32_t slot) {
-  __shared__ double red[4];
-  const uint32_t b = blockIdx.y;
-  const double *th = (const double *)(state_all + (size_t)b * Mt * Mx);
-  auto link = [&](uint32_t ii, uint32_t jj, uint32_t mu) { return th[2 * ((size_t)jj * Mt + ii) + mu]; };
-  double acc[1] = {0.0};
-  for (uint32_t jc = blockIdx.x; jc < Mx / 2; jc += gridDim.x) {
-    const uint32_t j0 = 2 * jc, j1 = j0 + 1, j2 = (j0 + 2 == Mx) ? 0 : j0 + 2;
-    for (uint32_t ic = threadIdx.x; ic < Mt / 2; ic += blockDim.x) {
-      const uint32_t i0 = 2 * ic, i1 = i0 + 1, i2 = (i0 + 2 == Mt) ? 0 : i0 + 2;
-      if (!P.approximate) {
-        const double phi_12 = +link(i0, j1, 1) + link(i0, j2, 0);
-        const double phi_23 = +link(i1, j2, 0) - link(i2, j1, 1);
-        const double phi_34 = -link(i1, j0, 0) - link(i2, j0, 1);
-        const double phi_41 = -link(i0, j0, 0) + link(i0, j0, 1);
-        const double theta_1 = +link(i0, j1, 0), theta_2 = -link(i1, j1, 1), theta_3 = -link(i1, j1, 0),
-                     theta_4 = +link(i1, j0, 1);
-        const double Phi = phi_12 + phi_23 + phi_34 + phi_41;
-        acc[0] -= P.beta * (cos(theta_1 - theta_2 - phi_12) + cos(theta_2 - theta_3 - phi_23) +
-                            cos(theta_3 - theta_4 - phi_34) + cos(theta_4 - theta_1 - phi_41));
-        acc[0] -= log(bessel_znorm_inv_rescaled(P, Phi));
-      } else {
-        const double phi_p = mod_2pi(+link(i1, j0, 0) + link(i2, j0, 1) + link(i2, j1, 1) - link(i1, j2, 0));
-        const double phi_m = mod_2pi(-link(i0, j0, 0) + link(i0, j0, 1) + link(i0, j1, 1) + link(i0, j2, 0));
-        const double theta = mod_2pi(+link(i1, j0, 1) + link(i1, j1, 1));
-        acc[0] -= log(approx_bessel_pdf(P.beta, theta, phi_p, phi_m));
-        // the two horizontal links (i0, j1, 0), (i1, j1, 0) of this block
-        for (uint32_t r = 0; r < 2; ++r) {
-          const uint32_t i = i0 + r, ip = (r == 0) ? i1 : i2;
-          const double hp = mod_2pi(-link(i, j0, 1) + link(i, j0, 0) + link(ip, j0, 1));
-          const double hm = mod_2pi(+link(i, j1, 1) + link(i, j2, 0) - link(ip, j1, 1));
-          acc[0] += expcos_neg_log_pdf(P.beta, mod_2pi(link(i, j1, 0)), hp, hm);
-        }
-      }
-    }
-  }
-  block_sum<1>(acc, red);
-  if (threadIdx.x == 0) partial[((size_t)b * gridDim.x + blockIdx.x) * 2 + slot] = acc[0];
-}
-
-// QuenchedSchwingerGaussianConditionedFineAction (quenchedschwingerconditionedfineaction.cc:81-134, 293-327): the Gaussian
-// variant of the fill-in for lattices coarsened in both directions.  One thread per coarse cell = one 2 x 2 block of fine
-// vertices: the perimeter links come from the uniform splits of the coarse links (this cell's and, for the far sides, the
-// cells (i+1, j) and (i, j+1), recomputed from their Philox streams as in schwinger_both_fill_kernel); the four interior
-// links from GaussianFillinDistribution::draw.
-__global__ void __launch_bounds__(256)
-    schwinger_gauss_fill_kernel(uint32_t Mtc, uint32_t Mxc, double beta, const double2 *__restrict__ coarse_all,
-                                double2 *__restrict__ prime_all, RngKey key0) {
-  const uint32_t b = blockIdx.y, Mtf = 2 * Mtc;
-  const double2 *coarse = coarse_all + (size_t)b * Mtc * Mxc;
-  double2 *prime = prime_all + (size_t)b * 4 * Mtc * Mxc;
-  RngKey key = key0;
-  key.chain += b;
-  for (uint32_t j = blockIdx.x; j < Mxc; j += gridDim.x) {
-    const uint32_t jp = j + 1 == Mxc ? 0 : j + 1;
-    for (uint32_t i = threadIdx.x; i < Mtc; i += blockDim.x) {
-      const uint32_t ip = i + 1 == Mtc ? 0 : i + 1;
-      const uint32_t c = j * Mtc + i, c_t = j * Mtc + ip, c_x = jp * Mtc + i;
-      double t[2], x[2], tt[2], tx[2], xt[2], xx[2];
-      split_pair(key, c, coarse[c], t, x);
-      split_pair(key, c_t, coarse[c_t], tt, tx);
-      split_pair(key, c_x, coarse[c_x], xt, xx);
-      const double phi_12 = mod_2pi(+x[1] + xt[0]);    // th(2i, 2j+1, 1) + th(2i, 2j+2, 0)
-      const double phi_23 = mod_2pi(+xt[1] - tx[1]);   // th(2i+1, 2j+2, 0) - th(2i+2, 2j+1, 1)
-      const double phi_34 = mod_2pi(-tx[0] - t[1]);    // -th(2i+2, 2j, 1) - th(2i+1, 2j, 0)
-      const double phi_41 = mod_2pi(-t[0] + x[0]);     // -th(2i, 2j, 0) + th(2i, 2j, 1)
-      double th[4];
-      gaussfill_draw(key, c, beta, phi_12, phi_23, phi_34, phi_41, th);
-      const size_t v00 = (size_t)(2 * j) * Mtf + 2 * i, v01 = v00 + Mtf;
-      prime[v00] = make_double2(t[0], x[0]);
-      prime[v00 + 1] = make_double2(t[1], +th[3]);     // (2i+1, 2j): temporal half, interior spatial link theta_4
-      prime[v01] = make_double2(+th[0], x[1]);         // (2i, 2j+1): interior temporal link theta_1, spatial half
-      prime[v01 + 1] = make_double2(-th[2], -th[1]);   // (2i+1, 2j+1): -theta_3, -theta_2
-    }
-  }
-}
-
-// partial[(b * gridDim.x + blockIdx.x) * 2 + slot] = -sum log pdf over the 2 x 2 blocks of `state`
-__global__ void __launch_bounds__(256)
-    schwinger_gauss_cfa_kernel(uint32_t Mt, uint32_t Mx, double beta, const double2 *__restrict__ state_all, double *__restrict__ partial,
-                               uint32_t slot) {
-  __shared__ double red[4];
-  const uint32_t b = blockIdx.y;
-  const double *th = (const double *)(state_all + (size_t)b * Mt * Mx);
-  auto link = [&](uint32_t ii, uint32_t jj, uint32_t mu) { return th[2 * ((size_t)jj * Mt + ii) + mu]; };
-  double acc[1] = {0.0};
-  for (uint32_t jc = blockIdx.x; jc < Mx / 2; jc += gridDim.x) {
-    const uint32_t j0 = 2 * jc, j1 = j0 + 1, j2 = (j0 + 2 == Mx) ? 0 : j0 + 2;
-    for (uint32_t ic = threadIdx.x; ic < Mt / 2; ic += blockDim.x) {
-      const uint32_t i0 = 2 * ic, i1 = i0 + 1, i2 = (i0 + 2 == Mt) ? 0 : i0 + 2;
-      const double phi_12 = mod_2pi(+link(i0, j1, 1) + link(i0, j2, 0));
-      const double phi_23 = mod_2pi(+link(i1, j2, 0) - link(i2, j1, 1));
-      const double phi_34 = mod_2pi(-link(i2, j0, 1) - link(i1, j0, 0));
-      const double phi_41 = mod_2pi(-link(i0, j0, 0) + link(i0, j0, 1));
-      const double theta_1 = mod_2pi(+link(i0, j1, 0)), theta_2 = mod_2pi(-link(i1, j1, 1)), theta_3 = mod_2pi(-link(i1, j1, 0)),
-                   theta_4 = mod_2pi(+link(i1, j0, 1));
-      acc[0] -= log(gaussfill_pdf(beta, theta_1, theta_2, theta_3, theta_4, phi_12, phi_23, phi_34, phi_41));
-    }
-  }
-  block_sum<1>(acc, red);
-  if (threadIdx.x == 0) partial[((size_t)b * gridDim.x + blockIdx.x) * 2 + slot] = acc[0];
-}
-
-// en4 = [4][B]: S_f(theta'), S_f(theta), S_c(theta_C), S_c(phi_c); twolevelmetropolisstep.cc:46-84
-__global__ void __launch_bounds__(256)
-    lattice_twolevel_accept_kernel(uint32_t n, double *__restrict__ theta, const double *__restrict__ theta_prime,
-                                   const double *__restrict__ en4, const double *__restrict__ cfa_partial, uint32_t nblk,
-                                   uint32_t B, int32_t *__restrict__ accept, double *__restrict__ terms, RngKey key0) {
-  const uint32_t b = blockIdx.y;
-  double cfa_p = 0.0, cfa_c = 0.0;
-  for (uint32_t k = 0; k < nblk; ++k) {
-    cfa_p += cfa_partial[((size_t)b * nblk + k) * 2 + 0];
-    cfa_c += cfa_partial[((size_t)b * nblk + k) * 2 + 1];
-  }
-  const double dS_fine = en4[b] - en4[B + b];
-  const double dS_coarse = en4[2 * B + b] - en4[3 * B + b];
-  const double dS_trial = cfa_c - cfa_p;
-  const double dS = dS_fine + dS_coarse + dS_trial;
-  bool acc;
-  if (dS < 0.0) {
-    acc = true;
-  } else {
-    RngKey key = key0;
-    key.chain += b;
-    double u, v;
-    rng_uniforms(key, 0, P_ACCEPT2, 0, u, v);
-    acc = u < exp(-dS);
-  }
-  if (blockIdx.x == 0 && threadIdx.x == 0) {
-    accept[b] = acc ? 1 : 0;
-    if (terms) {
-      terms[3 * b + 0] = dS_fine; terms[3 * b + 1] = dS_coarse; terms[3 * b + 2] = dS_trial;
-    }
-  }
-  if (!acc) return;
-  const size_t off = (size_t)b * n;
-  for (uint32_t l = blockIdx.x * blockDim.x + threadIdx.x; l < n; l += gridDim.x * blockDim.x)
-    theta[off + l] = theta_prime[off + l];
-}
-
-}  // namespace mlmcpi
-
-extern "C" {
-
-// besselproductdistribution.hh:44-72: I0(2 beta), the envelope width and the Fourier coefficients alpha_k of the
-// normalisation constant (k <= 16, sums truncated at n, m <= 32)
-static BesselFill make_bessel_fill(double beta) {
-  static BesselFill cached;
-  static bool have = false;
-  static std::mutex guard;
-  std::lock_guard<std::mutex> lock(guard);
-  if (have && cached.beta == beta) return cached;
-  BesselFill P;
-  P.beta = beta;
-  P.approximate = beta > 8.0 ? 1 : 0;
-  P.I0_twobeta = std::cyl_bessel_i(0.0, 2. * beta);
-  P.sigma_beta = kPi / std::sqrt(2. * std::log(P.I0_twobeta));
-  double logfact[65];
-  logfact[0] = logfact[1] = 0.0;
-  for (int n = 2; n <= 64; ++n) logfact[n] = logfact[n - 1] + std::log((double)n);
-  auto log_binom = [&](int n, int k) { return logfact[n] - logfact[k] - logfact[n - k]; };
-  double alpha0 = 1.0;
-  for (int k = 0; k <= 16; ++k) {
-    double sum = 0.0;
-    for (int n = k; n <= 32; ++n)
-      for (int m = k; m <= 32; ++m)
-        sum += std::pow(0.5 * beta, 2.0 * (n + m)) *
-               std::exp(log_binom(2 * n, n - k) + log_binom(2 * m, m - k) - 2 * (logfact[n] + logfact[m]));
-    const double alpha = ((k == 0) ? 2 : 4) * kPi * sum;
-    if (k == 0) alpha0 = alpha;
-    P.alphaZ[k] = (k == 0) ? alpha : alpha / alpha0;
-  }
-  cached = P;
-  have = true;
-  return P;
-}
-
-static int check_twolevel(const mlmcpi_lattice_action *fine, const mlmcpi_lattice_action *coarse, uint32_t *rt, uint32_t *rx) {
-  if (int rc = check_lattice(fine)) return rc;
-  if (int rc = check_lattice(coarse)) return rc;
-  if (int rc = refuse_sigma(fine, "the two-level step")) return rc;
-  if (int rc = refuse_sigma(coarse, "the two-level step")) return rc;
-  if (fine->kind != MLMCPI_SCHWINGER || coarse->kind != MLMCPI_SCHWINGER)
-    return fail(MLMCPI_ERR_UNSUPPORTED, "two-level step: only the quenched Schwinger action has a device conditioned fine action");
-  *rt = (coarse->Mt && fine->Mt == 2 * coarse->Mt) ? 2 : (fine->Mt == coarse->Mt ? 1 : 0);
-  *rx = (coarse->Mx && fine->Mx == 2 * coarse->Mx) ? 2 : (fine->Mx == coarse->Mx ? 1 : 0);
-  if (*rt == 0 || *rx == 0 || *rt * *rx == 1)
-    return fail(MLMCPI_ERR_INVALID, "invalid coarsening for fill-in (%u x %u from %u x %u)", coarse->Mt, coarse->Mx, fine->Mt, fine->Mx);
-  return MLMCPI_OK;
-}
-
-// workspace: theta' | theta_C | energies [4][B] | CFA partials [B * nblk * 2]
-int mlmcpi_lattice_twolevel_workspace_bytes(const mlmcpi_lattice_action *fine, const mlmcpi_lattice_action *coarse,
-                                            uint32_t B, size_t *bytes) {
-  uint32_t rt, rx;
-  if (int rc = check_twolevel(fine, coarse, &rt, &rx)) return rc;
-  MLMCPI_REQUIRE(bytes && B > 0, "bad arguments");
-  const size_t nf = (size_t)2 * fine->Mt * fine->Mx, nc = (size_t)2 * coarse->Mt * coarse->Mx;
-  *bytes = align256_((size_t)B * nf * 8) + align256_((size_t)B * nc * 8) + align256_((size_t)4 * B * 8) +
-           align256_((size_t)B * row_blocks(coarse->Mx, B) * 2 * 8);
-  return MLMCPI_OK;
-}
-
-int mlmcpi_lattice_twolevel_draw(const mlmcpi_lattice_action *fine, const mlmcpi_lattice_action *coarse,
-                                 const double *d_phi_coarse, double *d_theta, uint32_t B, uint64_t seed, uint32_t chain0,
-                                 uint32_t step, void *d_work, int32_t *d_accept, double *d_terms, void *stream) {
-  return mlmcpi_lattice_twolevel_draw_cfa(fine, coarse, 0, d_phi_coarse, d_theta, B, seed, chain0, step, d_work, d_accept, d_terms,
-                                          stream);
-}
-
-int mlmcpi_lattice_twolevel_draw_cfa(const mlmcpi_lattice_action *fine, const mlmcpi_lattice_action *coarse, int32_t cfa_kind,
-                                     const double *d_phi_coarse, double *d_theta, uint32_t B, uint64_t seed, uint32_t chain0,
-                                     uint32_t step, void *d_work, int32_t *d_accept, double *d_terms, void *stream) {
-  uint32_t rt, rx;
-  if (int rc = check_twolevel(fine, coarse, &rt, &rx)) return rc;
-  MLMCPI_REQUIRE(d_phi_coarse && d_theta && d_work && d_accept && B > 0, "bad arguments");
-  MLMCPI_REQUIRE(cfa_kind == 0 || cfa_kind == 1, "unknown conditioned fine action %d", cfa_kind);
-  MLMCPI_REQUIRE(cfa_kind == 0 || rt * rx == 4, "the Gaussian conditioned fine action needs a lattice coarsened in both directions");
-  hipStream_t st = as_stream(stream);
-  const size_t nf = (size_t)2 * fine->Mt * fine->Mx, nc = (size_t)2 * coarse->Mt * coarse->Mx;
-  char *w = (char *)d_work;
-  double *theta_prime = (double *)w;
-  w += align256_((size_t)B * nf * 8);
-  double *theta_c = (double *)w;
-  w += align256_((size_t)B * nc * 8);
-  double *en4 = (double *)w;
-  w += align256_((size_t)4 * B * 8);
-  double *cfa = (double *)w;
-  const RngKey key = make_key(seed, chain0, step);
-  const uint32_t nblk = row_blocks(coarse->Mx, B);
-  if (rt * rx == 4 && cfa_kind == 1) {  // QuenchedSchwingerGaussianConditionedFineAction
-    const dim3 grid(nblk, B), block(256);
-    hipLaunchKernelGGL(schwinger_gauss_fill_kernel, grid, block, 0, st, coarse->Mt, coarse->Mx, fine->beta, (const double2 *)d_phi_coarse,
-                       (double2 *)theta_prime, key);
-    MLMCPI_LAUNCH_CHECK("schwinger_gauss_fill_kernel");
-    hipLaunchKernelGGL(schwinger_gauss_cfa_kernel, grid, block, 0, st, fine->Mt, fine->Mx, fine->beta, (const double2 *)theta_prime, cfa, 0u);
-    hipLaunchKernelGGL(schwinger_gauss_cfa_kernel, grid, block, 0, st, fine->Mt, fine->Mx, fine->beta, (const double2 *)d_theta, cfa, 1u);
-    MLMCPI_LAUNCH_CHECK("schwinger_gauss_cfa_kernel");
-  } else if (rt * rx == 4) {
-    const BesselFill P = make_bessel_fill(fine->beta);
-    const dim3 grid(nblk, B), block(256);
-    hipLaunchKernelGGL(schwinger_both_fill_kernel, grid, block, 0, st, coarse->Mt, coarse->Mx, P, (const double2 *)d_phi_coarse,
-                       (double2 *)theta_prime, key);
-    MLMCPI_LAUNCH_CHECK("schwinger_both_fill_kernel");
-    hipLaunchKernelGGL(schwinger_both_rows_kernel, grid, block, 0, st, fine->Mt, fine->Mx, fine->beta, (double2 *)theta_prime, key);
-    MLMCPI_LAUNCH_CHECK("schwinger_both_rows_kernel");
-    hipLaunchKernelGGL(schwinger_both_cfa_kernel, grid, block, 0, st, fine->Mt, fine->Mx, P, (const double2 *)theta_prime, cfa, 0u);
-    hipLaunchKernelGGL(schwinger_both_cfa_kernel, grid, block, 0, st, fine->Mt, fine->Mx, P, (const double2 *)d_theta, cfa, 1u);
-    MLMCPI_LAUNCH_CHECK("schwinger_both_cfa_kernel");
-  } else {
-    hipLaunchKernelGGL(schwinger_twolevel_propose_kernel, dim3(nblk, B), dim3(256), 0, st, coarse->Mt, coarse->Mx, rt,
-                       fine->beta, (const double2 *)d_phi_coarse, (const double2 *)d_theta, (double2 *)theta_prime, cfa, key);
-    MLMCPI_LAUNCH_CHECK("schwinger_twolevel_propose_kernel");
-  }
-  if (int rc = lattice_energy(fine, theta_prime, B, en4, st)) return rc;
-  if (int rc = lattice_energy(fine, d_theta, B, en4 + B, st)) return rc;
-  if (int rc = mlmcpi_lattice_copy_from_fine(fine, rt, rx, d_theta, theta_c, B, stream)) return rc;
-  if (int rc = lattice_energy(coarse, theta_c, B, en4 + 2 * (size_t)B, st)) return rc;
-  if (int rc = lattice_energy(coarse, d_phi_coarse, B, en4 + 3 * (size_t)B, st)) return rc;
-  uint32_t nb = (uint32_t)((nf + 255) / 256);
-  if (nb > 1024) nb = 1024;
-  hipLaunchKernelGGL(lattice_twolevel_accept_kernel, dim3(nb, B), dim3(256), 0, st, (uint32_t)nf, d_theta,
-                     (const double *)theta_prime, (const double *)en4, (const double *)cfa, nblk, B, d_accept, d_terms, key);
-  MLMCPI_LAUNCH_CHECK("lattice_twolevel_accept_kernel");
-  return MLMCPI_OK;
-}
-
-}  // extern "C"
-
-// =================================================================================================
-// Exact sampler of the Gaussian free field: GFFAction::draw / initialise_state (action/qft/gffaction.cc:121-123,
-// 200-213).  The reference solves with a sparse Cholesky factor of the precision matrix Q = (4 + mu2) 1 - A built by
-// Eigen (infeasible beyond ~64^2).  On the periodic lattice Q is diagonal in Fourier space,
-//   lambda(k) = 4 + mu2 - 2 cos(2 pi k_t / Mt) - 2 cos(2 pi k_x / Mx),
-// so a draw from N(0, Q^-1) is  phi(x) = Re sum_k w_k e^{+i k x} / sqrt(N lambda(k))  with w_k = n0 + i n1 complex
-// white noise (E |w|^2 = 2; then E phi(x) phi(y) = (1/N) sum_k cos(k (x - y)) / lambda(k) = (Q^-1)_xy): one kernel
-// fills the spectrum from Philox (site = mode index, purpose P_EXACT), hipFFT does the batched 2-D inverse
-// transform in place, one kernel keeps the real part.  O(N log N) per chain at any lattice size.
-// =================================================================================================
-namespace mlmcpi {
-
-__global__ void __launch_bounds__(256)
-    gff_spectrum_kernel(uint32_t Mt, uint32_t Mx, double mu2, double2 *__restrict__ w_all, RngKey key0, uint32_t sub) {
-  const uint32_t b = blockIdx.y, n = Mt * Mx;
-  RngKey key = key0;
-  key.chain += b;
-  double2 *w = w_all + (size_t)b * n;
-  const double inv_n = 1.0 / (double)n;
-  for (uint32_t l = blockIdx.x * blockDim.x + threadIdx.x; l < n; l += gridDim.x * blockDim.x) {
-    const uint32_t kx = l / Mt, kt = l - kx * Mt;  // same layout as the field: mode (kt, kx) at kx * Mt + kt
-    const double lambda = 4.0 + mu2 - 2.0 * cos(kTwoPi * kt / Mt) - 2.0 * cos(kTwoPi * kx / Mx);
-    double n0, n1;
-    rng_normals(key, l, P_EXACT, sub, n0, n1);
-    const double s = sqrt(inv_n / lambda);
-    w[l] = make_double2(s * n0, s * n1);
-  }
-}
-
-__global__ void __launch_bounds__(256)
-    gff_real_part_kernel(uint32_t n, const double2 *__restrict__ w_all, double *__restrict__ phi_all) {
-  const uint32_t b = blockIdx.y;
-  const double2 *w = w_all + (size_t)b * n;
-  double *phi = phi_all + (size_t)b * n;
-  for (uint32_t l = blockIdx.x * blockDim.x + threadIdx.x; l < n; l += gridDim.x * blockDim.x) phi[l] = w[l].x;
-}
-
-}  // namespace mlmcpi
-
-extern "C" {
-
-int mlmcpi_lattice_exact_workspace_bytes(const mlmcpi_lattice_action *act, uint32_t B, size_t *bytes) {
-  if (int rc = check_lattice(act)) return rc;
-  MLMCPI_REQUIRE(bytes && B > 0, "bad arguments");
-  if (act->kind != MLMCPI_GFF) return fail(MLMCPI_ERR_UNSUPPORTED, "exact sampler only for the GFF action");
-  *bytes = (size_t)B * act->Mt * act->Mx * sizeof(double2);
-  return MLMCPI_OK;
-}
-
-// one batch of chains: spectrum -> inverse FFT (in place, d_work) -> real part
-static int gff_exact_batch(const mlmcpi_lattice_action *act, double *d_phi, uint32_t B, uint64_t seed, uint32_t chain0,
-                           uint32_t step, uint32_t sub, void *d_work, hipStream_t st) {
-  const uint32_t n = act->Mt * act->Mx;
-  // one cached plan per device and (Mt, Mx, B): plan creation costs milliseconds; a plan is bound to the device that was
-  // current when it was made.  The lock is held across the enqueue: hipfftSetStream + Exec on a shared plan is not
-  // re-entrant.
-  struct PlanSlot { hipfftHandle plan = 0; uint32_t mt = 0, mx = 0, b = 0; };
-  static std::mutex guard;
-  static PlanSlot slots[64];
-  int dev = 0;
-  MLMCPI_HIP_TRY(hipGetDevice(&dev));
-  if (dev < 0 || dev >= 64) return fail(MLMCPI_ERR_INVALID, "device index %d out of range", dev);
-  std::lock_guard<std::mutex> lock(guard);
-  hipfftHandle &plan = slots[dev].plan;
-  uint32_t &p_mt = slots[dev].mt, &p_mx = slots[dev].mx, &p_b = slots[dev].b;
-  if (!plan || p_mt != act->Mt || p_mx != act->Mx || p_b != B) {
-    if (plan) hipfftDestroy(plan);
-    plan = 0;
-    int dims[2] = {(int)act->Mx, (int)act->Mt};  // slowest index first
-    if (hipfftPlanMany(&plan, 2, dims, nullptr, 1, (int)n, nullptr, 1, (int)n, HIPFFT_Z2Z, (int)B) != HIPFFT_SUCCESS) {
-      plan = 0;
-      return fail(MLMCPI_ERR_HIP, "hipfftPlanMany failed for %u x %u x %u", act->Mt, act->Mx, B);
-    }
-    p_mt = act->Mt; p_mx = act->Mx; p_b = B;
-  }
-  if (hipfftSetStream(plan, st) != HIPFFT_SUCCESS) return fail(MLMCPI_ERR_HIP, "hipfftSetStream failed");
-  uint32_t nb = (n + 255) / 256;
-  if (nb > 1024) nb = 1024;
-  hipLaunchKernelGGL(gff_spectrum_kernel, dim3(nb, B), dim3(256), 0, st, act->Mt, act->Mx, gff_mu2(*act), (double2 *)d_work,
-                     make_key(seed, chain0, step), sub);
-  MLMCPI_LAUNCH_CHECK("gff_spectrum_kernel");
-  if (hipfftExecZ2Z(plan, (hipfftDoubleComplex *)d_work, (hipfftDoubleComplex *)d_work, HIPFFT_BACKWARD) != HIPFFT_SUCCESS)
-    return fail(MLMCPI_ERR_HIP, "hipfftExecZ2Z failed");
-  hipLaunchKernelGGL(gff_real_part_kernel, dim3(nb, B), dim3(256), 0, st, n, (const double2 *)d_work, d_phi);
-  MLMCPI_LAUNCH_CHECK("gff_real_part_kernel");
-  return MLMCPI_OK;
-}
-
-int mlmcpi_lattice_exact_draw(const mlmcpi_lattice_action *act, double *d_phi, uint32_t B, uint64_t seed, uint32_t chain0,
-                              uint32_t step, void *d_work, void *stream) {
-  if (int rc = check_lattice(act)) return rc;
-  MLMCPI_REQUIRE(d_phi && d_work && B > 0, "bad arguments");
-  if (act->kind != MLMCPI_GFF) return fail(MLMCPI_ERR_UNSUPPORTED, "exact sampler only for the GFF action");
-  return gff_exact_batch(act, d_phi, B, seed, chain0, step, 0, d_work, as_stream(stream));
-}
-
-// GFFAction::initialise_state = draw (gffaction.cc:121-123): the exact sampler with its own Philox sub-stream, in
-// batches of chains that keep the library scratch below 256 MiB
-static int gff_initialise_exact(const mlmcpi_lattice_action *act, double *d_phi, uint32_t B, uint64_t seed, uint32_t chain0,
-                                hipStream_t st) {
-  const size_t per_chain = (size_t)act->Mt * act->Mx * sizeof(double2);
-  uint32_t chunk = (uint32_t)std::max<size_t>(1, ((size_t)256 << 20) / per_chain);
-  if (chunk > B) chunk = B;
-  void *work = nullptr;
-  if (int rc = scratch((size_t)chunk * per_chain, &work, st)) return rc;
-  for (uint32_t b0 = 0; b0 < B; b0 += chunk) {
-    const uint32_t nb = std::min(chunk, B - b0);
-    if (int rc = gff_exact_batch(act, d_phi + (size_t)b0 * act->Mt * act->Mx, nb, seed, chain0 + b0, 0, 1, work, st)) return rc;
-  }
-  return MLMCPI_OK;
-}
-
-#ifdef MLMCPI_STAMPS
-// instrumentation build only: the stamps of the last launch of schwinger_perm_heat_kernel, 16 words per workgroup
-int mlmcpi_debug_read_stamps(unsigned long long *h_out, uint32_t n_workgroups) {
-  MLMCPI_HIP_TRY(hipDeviceSynchronize());
-  MLMCPI_HIP_TRY(hipMemcpyFromSymbol(h_out, HIP_SYMBOL(mlmcpi::g_stamps), (size_t)n_workgroups * 16 * sizeof(unsigned long long)));
-  return MLMCPI_OK;
-}
-#endif
 
 }  // extern "C"

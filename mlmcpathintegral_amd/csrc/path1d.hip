@@ -900,8 +900,6 @@ static int launch_traj(const HmcPlan &pl, const PathP &P, const double *x_cur, d
   return MLMCPI_OK;
 }
 
-static size_t align256(size_t n) { return (n + 255) & ~(size_t)255; }
-
 }  // namespace mlmcpi
 
 using namespace mlmcpi;

@@ -228,10 +228,7 @@ int rs_check(const mlmcpi_lattice_action *act, int *act_out, uint32_t *n) {
   if (act->kind != MLMCPI_GFF && act->kind != MLMCPI_SCHWINGER && act->kind != MLMCPI_NONLINEAR_SIGMA)
     return fail(MLMCPI_ERR_UNSUPPORTED, "the parallel random-order sweep is built for the 2-D actions (GFF, Schwinger, sigma model), not kind %d",
                 act->kind);
-  if (act->Mt < 2 || act->Mx < 2) return fail(MLMCPI_ERR_INVALID, "lattice %u x %u too small", act->Mt, act->Mx);
-  if ((uint64_t)act->Mt * act->Mx > (1ull << 30)) return fail(MLMCPI_ERR_INVALID, "lattice too large for 32-bit site indices");
-  if (act->kind == MLMCPI_GFF && act->Mt != act->Mx)  // gffaction.hh:169-173, as every other entry point
-    return fail(MLMCPI_ERR_INVALID, "Lattice has to be squared for GFF action");
+  if (int rc = check_lattice(act)) return rc;  // extents, as every other entry point
   *act_out = act->kind == MLMCPI_GFF ? RS_GFF : act->kind == MLMCPI_SCHWINGER ? RS_SCHW : RS_SIGMA;
   *n = (act->kind == MLMCPI_SCHWINGER ? 2u : 1u) * act->Mt * act->Mx;
   return MLMCPI_OK;

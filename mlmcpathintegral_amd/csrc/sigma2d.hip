@@ -240,10 +240,7 @@ constexpr uint32_t kSigmaLdsMax = 160 * 1024 - 512;  // dynamic LDS a workgroup 
 constexpr uint32_t kSigmaTileW = 64, kSigmaTileH = 32;
 constexpr uint32_t kSigmaFuse = 2;
 
-uint32_t stream_blocks(uint32_t N, uint32_t B) {
-  uint32_t want = (2048 + B - 1) / B, need = (N + 255) / 256;
-  return want < need ? (want ? want : 1) : need;
-}
+uint32_t sigma_blocks(uint32_t N, uint32_t B) { return row_blocks((N + 255) / 256, B); }  // workgroups of 256 per chain
 
 std::mutex g_sigma_attr_mutex;
 bool g_sigma_attr_set[64] = {false};
@@ -264,7 +261,7 @@ int sigma_init_attrs() {
 template <int OP>
 int sigma_reduce(uint32_t Mt, uint32_t Mx, const double *d_phi, uint32_t B, double scale, double *d_out, hipStream_t st) {
   constexpr int NV = OP == 0 ? 1 : 3;
-  const uint32_t nb = stream_blocks(Mt * Mx, B);
+  const uint32_t nb = sigma_blocks(Mt * Mx, B);
   void *part = nullptr;
   if (int rc = scratch((size_t)B * nb * NV * sizeof(double), &part, st)) return rc;
   hipLaunchKernelGGL(sigma_reduce_kernel<OP>, dim3(nb, B), dim3(256), 0, st, Mt, Mx, (const double2 *)d_phi, (double *)part);
@@ -281,14 +278,14 @@ int sigma_evaluate(const mlmcpi_lattice_action *act, const double *d_phi, uint32
 }
 
 int sigma_force(const mlmcpi_lattice_action *act, const double *d_phi, double *d_f, uint32_t B, hipStream_t st) {
-  hipLaunchKernelGGL(sigma_force_kernel, dim3(stream_blocks(act->Mt * act->Mx, B), B), dim3(256), 0, st, act->Mt, act->Mx, act->beta,
+  hipLaunchKernelGGL(sigma_force_kernel, dim3(sigma_blocks(act->Mt * act->Mx, B), B), dim3(256), 0, st, act->Mt, act->Mx, act->beta,
                      (const double2 *)d_phi, (double2 *)d_f);
   MLMCPI_LAUNCH_CHECK("sigma_force_kernel");
   return MLMCPI_OK;
 }
 
 int sigma_initialise(const mlmcpi_lattice_action *act, double *d_phi, uint32_t B, uint64_t seed, uint32_t chain0, hipStream_t st) {
-  hipLaunchKernelGGL(sigma_init_kernel, dim3(stream_blocks(act->Mt * act->Mx, B), B), dim3(256), 0, st, act->Mt * act->Mx,
+  hipLaunchKernelGGL(sigma_init_kernel, dim3(sigma_blocks(act->Mt * act->Mx, B), B), dim3(256), 0, st, act->Mt * act->Mx,
                      make_key(seed, chain0, 0), (double2 *)d_phi);
   MLMCPI_LAUNCH_CHECK("sigma_init_kernel");
   return MLMCPI_OK;

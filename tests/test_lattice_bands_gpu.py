@@ -1,14 +1,14 @@
 """GPU: the 2-D force, the streaming 2-D HMC and the plaquette / energy reductions at the shapes where their index logic
 runs: more than one row band and column tile of schwinger_force_band, both stride loops of gff_force_kernel, every
 column count NC of schwinger_reduce_band_kernel, the band heights row_blocks() produces over the number of chains B,
-both branches of kinetic_energy's factoring, and the done flags of repeated HMC trajectories.
+both branches of lattice_sum_squares' factoring (the HMC's kinetic energy), and the done flags of repeated HMC trajectories.
 
 Two references.  (i) tests/lattice_reference.py: the formulas in long double (pinned on the CPU by
 tests/test_lattice_reference.py), at tolerances DERIVED from fp64 rounding, stated where they are used; the worst
 observed error of every case is printed (`pytest -s`, or the captured output of a failing case), so the margin is
 visible.  (ii) the oracle (fp64, the reference's order of operations) at the tolerances tests/test_gpu_parity.py uses.
 
-Geometry of the Schwinger force (mlmcpathintegral_amd/csrc/lattice2d.hip): a wave walks a band of FORCE_ROWS = 128 rows
+Geometry of the Schwinger force (mlmcpathintegral_amd/csrc/lattice_hmc.hip): a wave walks a band of FORCE_ROWS = 128 rows
 and 64 columns of which it owns FORCE_COLS = 62; a failure names (band, row in band, column tile, lane) of the worst
 entry.
 """
@@ -409,7 +409,7 @@ def kinetic_bound(p):
 
 
 HMC_CASES = [
-    # kind, Mt, Mx, kw, B: kinetic_energy sums n = w * h momenta as h rows of w, w the largest power of two in
+    # kind, Mt, Mx, kw, B: the kinetic energy (lattice_sum_squares) sums n = w * h momenta as h rows of w, w the largest power of two in
     # [64, 4096] that divides n, or as one row of n where there is none
     ("schwinger", 192, 260, dict(beta=1.0), 3),   # 3 bands x 4 tiles; n = 99840 = 2^9 * 195: w = 512
     ("schwinger", 130, 70, dict(beta=2.0), 3),    # n = 18200 = 2^3 * 5^2 * 7 * 13: the one-row fall-back
@@ -421,8 +421,8 @@ HMC_CASES = [
 
 @pytest.mark.parametrize("kind,Mt,Mx,kw,B", HMC_CASES)
 def test_lattice_hmc_on_many_bands_matches_oracle(gpu_ops, orc, kind, Mt, Mx, kw, B):
-    """tolerances of test_lattice_hmc_matches_oracle: energies 1e-11, state 1e-10, accept flags equal.  kinetic_energy
-    cannot be called on its own: it is pinned through T0 = energies[:, 1] of the first trajectory against 1/2 sum p^2 in
+    """tolerances of test_lattice_hmc_matches_oracle: energies 1e-11, state 1e-10, accept flags equal.  The HMC's kinetic
+    energy cannot be called on its own: it is pinned through T0 = energies[:, 1] of the first trajectory against 1/2 sum p^2 in
     long double, with p rebuilt by the oracle's momentum draw (orc_dev_random, purpose P_MOMENTUM), for three chains."""
     act, A = make_lattice(orc, kind, Mt, Mx, **kw)
     n, nt, dt, chain0 = A.size, 8, 0.05, 2
