@@ -524,5 +524,94 @@ private:
   const ClusterParameters param;
 };
 
+/** The Wolff single-cluster sampler of the O(3) nonlinear sigma model (mlmcpi_sigma_cluster_draw).  It is NOT
+ *  the reference's ClusterSampler for this action: single_cluster_update (clustersampler.cc:52-89) bonds all eight entries of
+ *  Lattice2D::neighbour_vertices while the action couples four, which samples another model; this is the same
+ *  walk over the four links per vertex the action has.  One draw = n_updates updates of every chain in one launch, then the
+ *  copy out; counters advance by n_updates per draw; set_state is a no-op, as for ClusterSampler. */
+class WolffClusterSampler : public Sampler {
+public:
+  WolffClusterSampler(const std::shared_ptr<Action> action_, const ClusterParameters p)
+      : Sampler(), action(std::dynamic_pointer_cast<NonlinearSigmaAction>(action_)), n_updates(p.n_updates), B(p.batch),
+        sites(p.batch, sizeof(uint32_t)) {
+    if (!action) fatal(" wolff sampler not supported for chosen action: it is built for the nonlinear sigma model only.");
+    // the device adds the flipped vertices of one call to a uint32 per chain: n_updates updates of at most N vertices each
+    if ((uint64_t)n_updates * (action->sample_size() / 2) > 0xFFFFFFFFull)
+      fatal("WolffClusterSampler: n_updates x vertices must stay below 2^32 (the per-chain counter of one draw).");
+    size_t bytes = 0;
+    check(mlmcpi_sigma_cluster_workspace_bytes(&action->abi_action(), B, &bytes), "sigma_cluster_workspace_bytes");
+    work = std::make_shared<DeviceBuffer>(bytes);
+    // an update flips at most N = sample_size / 2 vertices: fold before 2^31 could have been added to a chain's counter
+    fold_period = std::max<uint64_t>(1, std::min<uint64_t>(1024, (1ull << 32) / ((uint64_t)std::max(1u, n_updates) * action->sample_size())));
+    phi_state_cur = std::make_shared<SampleState>(action->sample_size(), B);
+    action->initialise_state(phi_state_cur);
+    std::shared_ptr<SampleState> tmp = std::make_shared<SampleState>(action->sample_size(), B);
+    for (unsigned int i = 0; i < p.n_burnin; ++i) draw(tmp);
+    check(mlmcpi_stream_synchronize(nullptr), "sync");
+    const auto t0 = std::chrono::steady_clock::now();
+    for (unsigned int k = 0; k < p.n_meas; ++k) draw(tmp);
+    check(mlmcpi_stream_synchronize(nullptr), "sync");
+    cost_per_sample_ = 1.E6 * std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count() / (p.n_meas ? p.n_meas : 1);
+    reset_stats();
+    fold_sites();
+    flipped_total = 0.0;
+    updates_counted = 0;
+  }
+  void draw(std::shared_ptr<SampleState> phi_state) override {
+    if (update_counter > 0xFFFFFFFFu - n_updates) fatal("WolffClusterSampler: the 32-bit update counter of the Philox contract is used up.");
+    check(mlmcpi_sigma_cluster_draw(&action->abi_action(), phi_state_cur->device_mutable(), B, n_updates, action->get_seed(),
+                                    action->get_chain0(), update_counter, (uint32_t *)sites.ptr(), work->p, nullptr),
+          "sigma_cluster_draw");
+    update_counter += n_updates;
+    updates_counted += n_updates;
+    if (++draws_unfolded >= fold_period) fold_sites();
+    n_total_samples += n_updates;
+    n_accepted_samples += n_updates;
+    phi_state->data = phi_state_cur->data;
+    accept = true;
+  }
+  void set_state(std::shared_ptr<SampleState>) override {}
+  double cost_per_sample() override { return cost_per_sample_; }
+  /** flipped vertices per update, averaged over chains and over the updates since construction (burn-in and timing draws
+   *  excluded); it keeps its own count of updates, so reset_stats() does not touch it */
+  double mean_cluster_size() {
+    if (!updates_counted) return 0.0;
+    fold_sites();
+    return flipped_total / B / (double)updates_counted;
+  }
+  void show_stats() override {
+    std::cout << std::setprecision(3) << std::fixed << "  cluster updates per draw = " << n_updates << std::endl
+              << "  mean cluster size        = " << mean_cluster_size() << " sites" << std::endl;
+  }
+
+private:
+  void fold_sites() {
+    for (uint32_t v : sites.download<uint32_t>()) flipped_total += v;
+    check(mlmcpi_memset(sites.ptr(), 0, B * sizeof(uint32_t), nullptr), "mlmcpi_memset");
+    draws_unfolded = 0;
+  }
+  const std::shared_ptr<NonlinearSigmaAction> action;
+  const unsigned int n_updates, B;
+  std::shared_ptr<SampleState> phi_state_cur;
+  std::shared_ptr<DeviceBuffer> work;
+  DeviceVector sites;  // uint32 per chain: flipped vertices since the last fold, added up on the device
+  double flipped_total = 0.0;
+  uint64_t fold_period = 1;
+  uint64_t draws_unfolded = 0;
+  uint64_t updates_counted = 0;  // the updates flipped_total belongs to
+  uint32_t update_counter = 0;
+  double cost_per_sample_ = 0.0;
+};
+
+class WolffClusterSamplerFactory : public SamplerFactory {
+public:
+  explicit WolffClusterSamplerFactory(const ClusterParameters p) : param(p) {}
+  std::shared_ptr<Sampler> get(std::shared_ptr<Action> action) override {
+    return std::make_shared<WolffClusterSampler>(action, param);  // fatal unless the action is the nonlinear sigma model
+  }
+private:
+  const ClusterParameters param;
+};
+
 }  // namespace mlmcpi
 #endif

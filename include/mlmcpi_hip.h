@@ -270,6 +270,27 @@ int mlmcpi_schwinger_cluster_draw(const mlmcpi_lattice_action *act, double *d_ps
                                   void *stream);
 int mlmcpi_schwinger_cluster_links(const mlmcpi_lattice_action *act, const double *d_psi, double *d_theta, uint32_t B, int gauge,
                                    uint64_t seed, uint32_t chain0, uint32_t draw0, void *stream);
+/* Wolff single-cluster update of the O(3) nonlinear sigma model (sigma_cluster.hip): n_updates updates of
+ * every chain of d_phi [B][2 Mt Mx], in place, one launch.  NOT the reference's ClusterSampler for this action, whose walk
+ * bonds the four diagonal neighbours as well and samples another model: this is that walk over the four links
+ * per vertex the action couples.  Vertex l = Mt j + i; link (l, 0) joins l to its +i neighbour, link (l, 1) to its +j
+ * neighbour (periodic; on an extent of 2 the two links between a pair of vertices are two links).  Update k of this call
+ * has the counter update0 + k: Philox (site 0, purpose 19) sub 0 (u, v) -> the reflection normal r, r_z = 1 - 2 u, azimuth
+ * 2 pi v - pi; sub 1 u -> the seed vertex min(floor(u N), N - 1).  With a_l = r . sigma_l of the field BEFORE the update, link
+ * (x, y) is bonded iff its uniform (site l, purpose 20: u for link (l, 0), v for link (l, 1)) < 1 - exp(min(0, -2 beta
+ * (a_x a_y))).  Every vertex of the connected component of the seed is reflected once, sigma' = sigma - 2 a r, and stored in
+ * the canonical form theta = atan2(sqrt(sx^2 + sy^2), sz), phi = atan2(sy, sx).  Ten updates in one call equal 5 + 5;
+ * results do not depend on the batch split, chain0, the launch plan or the order of the traversal.
+ *   d_cluster_sites  optional [B] uint32: the flipped sites of this call's updates are ADDED to it, per chain (32 bits, as
+ *                    for mlmcpi_path_cluster_draw: it wraps, also inside one call when n_updates Mt Mx >= 2^32; a caller
+ *                    that wants exact counts keeps n_updates Mt Mx below that and reads and zeroes it in time)
+ *   d_work           _workspace_bytes (12 B per vertex and chain for the queue, 1 bit for the membership map); its content
+ *                    at entry is ignored
+ * MLMCPI_NONLINEAR_SIGMA only: MLMCPI_ERR_UNSUPPORTED otherwise.  Any lattice of the sigma sweep (and odd extents): Mt, Mx >= 2,
+ * Mt Mx <= 2^30.  update0 + n_updates must fit 32 bits: MLMCPI_ERR_INVALID. */
+int mlmcpi_sigma_cluster_workspace_bytes(const mlmcpi_lattice_action *act, uint32_t B, size_t *bytes);
+int mlmcpi_sigma_cluster_draw(const mlmcpi_lattice_action *act, double *d_phi, uint32_t B, uint32_t n_updates, uint64_t seed,
+                              uint32_t chain0, uint32_t update0, uint32_t *d_cluster_sites, void *d_work, void *stream);
 int mlmcpi_lattice_state_size(const mlmcpi_lattice_action *act, uint32_t *n); /* Action::sample_size */
 int mlmcpi_lattice_evaluate(const mlmcpi_lattice_action *act, const double *d_phi, uint32_t B, double *d_S,
                             void *stream);

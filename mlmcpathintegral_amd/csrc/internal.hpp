@@ -50,6 +50,8 @@ struct Tuning {
   int or_heat_wide = 0;                          // MLMCPI_OR_HEAT=wide|narrow: 1024-thread workgroups for the fused launch (+1 / -1; 0: by the number of tiles)
   bool random_sweep_global = false;               // MLMCPI_RANDOM_SWEEP_HOME=global: the random-order sweep keeps the state in global memory whatever the lattice
   uint32_t random_sweep_chunk = 0;                // MLMCPI_RANDOM_SWEEP_CHUNK=k: rounds scheduled per pass of the random-order sweep (0: 254)
+  int sigma_cluster_team = 0;                     // MLMCPI_SIGMA_CLUSTER_TEAM=wave|block: lanes that share a chain in the sigma-model Wolff update (1 / 2; 0: by the batch)
+  bool sigma_cluster_map_global = false;          // MLMCPI_SIGMA_CLUSTER_BITMAP=global: its membership bitmap in the workspace whatever the lattice
 };
 Tuning tuning();  // a copy taken under the lock: callers snapshot it once per call
 

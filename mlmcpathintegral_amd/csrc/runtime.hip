@@ -111,11 +111,20 @@ bool apply_option(Tuning &t, const char *name, const char *value) {
     }
     return false;
   }
+  if (n == "MLMCPI_SIGMA_CLUSTER_TEAM") {
+    t.sigma_cluster_team = v == "wave" ? 1 : v == "block" ? 2 : 0;
+    return v.empty() || v == "auto" || v == "wave" || v == "block";
+  }
+  if (n == "MLMCPI_SIGMA_CLUSTER_BITMAP") {
+    t.sigma_cluster_map_global = v == "global";
+    return v.empty() || v == "global" || v == "lds";
+  }
   return false;
 }
 void load_tuning_locked() {
   if (g_tuning_loaded) return;
-  for (const char *name : {"MLMCPI_SWEEP_TILE", "MLMCPI_OR_KERNEL", "MLMCPI_OR_HEAT", "MLMCPI_RANDOM_SWEEP_HOME", "MLMCPI_RANDOM_SWEEP_CHUNK"})
+  for (const char *name : {"MLMCPI_SWEEP_TILE", "MLMCPI_OR_KERNEL", "MLMCPI_OR_HEAT", "MLMCPI_RANDOM_SWEEP_HOME", "MLMCPI_RANDOM_SWEEP_CHUNK",
+                           "MLMCPI_SIGMA_CLUSTER_TEAM", "MLMCPI_SIGMA_CLUSTER_BITMAP"})
     if (const char *e = getenv(name)) apply_option(g_tuning, name, e);
   g_tuning_loaded = true;
 }

@@ -1,0 +1,250 @@
+// sigma_cluster.hip -- the Wolff single-cluster update of the O(3) nonlinear sigma model (gfx950, wave64).
+//
+// NOT the reference's ClusterSampler for this action: ClusterSampler::single_cluster_update (sampler/clustersampler.cc:52-89)
+// walks the eight entries of Lattice2D::neighbour_vertices (lattice2d.cc:135-155), the action couples four of them
+// (nonlinearsigmaaction.hh:416-419); bonds across diagonals that carry no energy sample another model.  This is
+// the same walk over the four links per vertex the action has, with the action's own new_reflection / S_ell / flip
+// (nonlinearsigmaaction.cc:166-208).
+//
+// The update, restated (tests/sigma_cluster_model.py).  Vertex l = Mt j + i; link (l, 0) joins l to its +i
+// neighbour, link (l, 1) to its +j neighbour (2 N links; on an extent of 2 the two links between a pair are two links).  With
+// r the reflection normal and a_l = r . sigma_l of the field BEFORE the update, link (x, y) is bonded iff its uniform
+// < 1 - exp(min(0, -2 beta (a_x a_y)))  (the walk evaluates S_ell with one end already flipped: r . sigma' = -r . sigma).  The
+// cluster is the connected component of the seed vertex in the graph of bonded links; every vertex of it is reflected once,
+// sigma' = sigma - 2 a r, and stored in the canonical form (sigma2d.hip).  Every decision is a function of (link, chain,
+// update counter, field before the update): the result does not depend on the order of the traversal.
+//
+// RNG contract, step = global update counter:
+//   P_SIGMA_REFLECT  site 0, sub 0: (u, v) -> r_z = 1 - 2 u, azimuth 2 pi v - pi;  sub 1: u -> seed vertex min(floor(u N), N - 1)
+//   P_SIGMA_BOND     site l, sub 0: u decides link (l, 0), v decides link (l, 1)
+#include <mutex>
+
+#include "internal.hpp"
+
+#include "sigma_device.hpp"  // fp contraction is off from here on
+
+namespace mlmcpi {
+
+constexpr uint32_t kScWaveChains = 4;          // team = wave: chains per workgroup of 256 threads
+constexpr uint32_t kScWaveLdsWords = 2048;     // team = wave: bitmap in LDS up to 8 KiB per chain (65 536 vertices)
+constexpr uint32_t kScBlockLdsWords = 32768;   // team = workgroup: bitmap in LDS up to 128 KiB (2^20 vertices)
+constexpr uint32_t kScBlockThreads = 1024;
+
+// What orders one phase of a team behind the one before it: the phase's stores (state, queue, bitmap) drained and, for a
+// team of several waves, the barrier.  A team of one wave runs in lockstep and needs the drain only.
+template <bool BLOCK>
+__device__ __forceinline__ void team_sync() {
+  __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");
+  if (BLOCK) __syncthreads();
+  else __builtin_amdgcn_wave_barrier();
+}
+
+__device__ __forceinline__ double reflect_dot(const V3 &r, const V3 &s) { return (r.x * s.x + r.y * s.y) + r.z * s.z; }
+
+// n_updates updates of every chain, in place.  A chain belongs to a team of lanes: one wave (BLOCK = false, kScWaveChains
+// chains per workgroup) or the whole workgroup (BLOCK = true).  Growth by frontier expansion: the vertices of the cluster
+// are queued in the order they join, (vertex, a) pairs in the workspace; a level is the range [head, tail) of the queue.  A
+// lane takes one (frontier vertex, direction) task: if the neighbour is not a member yet and the link is bonded, it claims
+// the neighbour with an atomic OR on the membership bitmap, and the lane that set the bit appends it (one atomic add on the
+// team's tail counter per wave and round).  Reflections are applied from the queue once growth has ended, so every bond test
+// reads the field before the update; the same pass clears the bitmap words of the members.  Work per update is
+// proportional to the cluster and its boundary; the bitmap is zeroed once per launch.
+// The frontier loop ends after at most N levels (a vertex joins once, a level without a new member is the last one); `level <
+// N` states that cap explicitly.  Queue positions are < N for the same reason; the store is guarded all the same.
+template <bool BLOCK, bool LDS_MAP>
+__global__ void __launch_bounds__(BLOCK ? kScBlockThreads : kScWaveChains * kWave)
+    sigma_cluster_kernel(double2 *phi_all, uint32_t Mt, uint32_t Mx, double beta2, uint32_t B, uint32_t n_updates, RngKey key0,
+                         uint32_t *queue_vertex, double *queue_a, uint32_t *map_all, uint32_t words, uint32_t *cluster_sites) {
+  extern __shared__ uint32_t lds_map[];
+  __shared__ uint32_t s_tail[kScWaveChains];
+  const uint32_t T = BLOCK ? blockDim.x : (uint32_t)kWave;
+  const uint32_t lane = BLOCK ? threadIdx.x : threadIdx.x & (kWave - 1);
+  const uint32_t wave_lane = threadIdx.x & (kWave - 1);
+  const uint32_t slot = BLOCK ? 0 : threadIdx.x >> 6;
+  const uint32_t b = BLOCK ? blockIdx.x : blockIdx.x * kScWaveChains + slot;
+  if (b >= B) return;                                    // team uniform (BLOCK: the grid has B workgroups)
+  const uint32_t N = Mt * Mx;
+  double2 *phi = phi_all + (size_t)b * N;
+  uint32_t *qv = queue_vertex + (size_t)b * N;
+  double *qa = queue_a + (size_t)b * N;
+  uint32_t *map = LDS_MAP ? lds_map + slot * words : map_all + (size_t)b * words;
+  for (uint32_t w = lane; w < words; w += T) map[w] = 0;
+  RngKey key = key0;
+  key.chain = key0.chain + b;
+  uint32_t total = 0;
+  team_sync<BLOCK>();
+
+  for (uint32_t n = 0; n < n_updates; ++n, ++key.step) {
+    double u, v, us, unused;
+    rng_uniforms(key, 0, P_SIGMA_REFLECT, 0, u, v);
+    rng_uniforms(key, 0, P_SIGMA_REFLECT, 1, us, unused);
+    const double rz = 1.0 - 2.0 * u, t = 1.0 - rz * rz, rho = t > 0.0 ? sqrt(t) : 0.0;
+    double sa, ca;
+    sincos(kTwoPi * v - kPi, &sa, &ca);
+    const V3 r{rho * ca, rho * sa, rz};
+    uint32_t seed = (uint32_t)(us * (double)N);
+    seed = seed < N ? seed : N - 1;
+    if (lane == 0) {
+      qv[0] = seed;
+      qa[0] = reflect_dot(r, sigma_of(phi[seed]));
+      map[seed >> 5] = 1u << (seed & 31u);
+      s_tail[slot] = 1;
+    }
+    team_sync<BLOCK>();
+
+    uint32_t head = 0, tail = 1;
+    for (uint32_t level = 0; level < N && head < tail; ++level) {
+      for (uint32_t base = head; base < tail; base += T / 4) {  // team uniform trip count: the ballot below sees whole waves
+        const uint32_t q = base + (lane >> 2), d = lane & 3u;
+        bool add = false;
+        uint32_t y = 0;
+        double ay = 0.0;
+        if (q < tail) {
+          const uint32_t x = qv[q];
+          const double ax = qa[q];
+          const uint32_t i = x % Mt, j = x / Mt;
+          if (d == 0) y = i + 1 == Mt ? x - i : x + 1;
+          else if (d == 1) y = i == 0 ? x + (Mt - 1) : x - 1;
+          else if (d == 2) y = j + 1 == Mx ? i : x + Mt;
+          else y = j == 0 ? x + (Mx - 1) * Mt : x - Mt;
+          const uint32_t bit = 1u << (y & 31u);
+          // a relaxed atomic load: other lanes set bits meanwhile; a stale 0 costs a test, the atomic OR below decides
+          if (!(__hip_atomic_load(&map[y >> 5], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP) & bit)) {
+            ay = reflect_dot(r, sigma_of(phi[y]));
+            const double prod = ax * ay;
+            if (prod > 0.0) {                            // else p = 0: never bonded, no random number
+              const double p = 1.0 - exp(fmin(0.0, -(beta2 * prod)));
+              // +i: link (x, 0), -i: link (y, 0), +j: link (x, 1), -j: link (y, 1)
+              const U4 w = philox4x32_10((d & 1u) ? y : x, key.chain, key.step, (uint32_t)P_SIGMA_BOND << 24, key.k0, key.k1);
+              const double uni = (d & 2u) ? u01(w.z, w.w) : u01(w.x, w.y);
+              if (uni < p) add = !(atomicOr(&map[y >> 5], bit) & bit);
+            }
+          }
+        }
+        const unsigned long long joiners = __ballot(add);
+        if (joiners) {                                   // wave uniform
+          const uint32_t leader = (uint32_t)__builtin_ctzll(joiners);
+          uint32_t first = 0;
+          if (wave_lane == leader) first = atomicAdd(&s_tail[slot], (uint32_t)__builtin_popcountll(joiners));
+          first = __shfl(first, leader);
+          const uint32_t pos = first + (uint32_t)__builtin_popcountll(joiners & ((1ull << wave_lane) - 1ull));
+          if (add && pos < N) {
+            qv[pos] = y;
+            qa[pos] = ay;
+          }
+        }
+      }
+      team_sync<BLOCK>();
+      head = tail;
+      tail = s_tail[slot];
+      if (BLOCK) __syncthreads();                        // nobody appends to the next level before everybody has read the tail
+    }
+
+    for (uint32_t q = lane; q < tail; q += T) {
+      const uint32_t x = qv[q];
+      const double c = 2.0 * qa[q];
+      const V3 s = sigma_of(phi[x]);
+      phi[x] = angles_of(V3{s.x - c * r.x, s.y - c * r.y, s.z - c * r.z});
+      map[x >> 5] = 0;                                   // every bit of the word that is set belongs to a member
+    }
+    total += tail;
+    // the next update reads what this one stored (other lanes, other waves of the team): drain the stores first
+    team_sync<BLOCK>();
+  }
+  if (cluster_sites && lane == 0) cluster_sites[b] += total;
+}
+
+namespace {
+
+struct ScPlan {
+  bool block, lds_map;
+  uint32_t threads, words, grid;
+  size_t lds_bytes;
+};
+
+// Launch plan.  A team is one wave when there are enough chains to give every SIMD of the device a wave
+// (B >= 4 x kComputeUnits), the workgroup otherwise; the bitmap sits in LDS where it fits.  Knobs (bit-identical results):
+// MLMCPI_SIGMA_CLUSTER_TEAM=wave|block, MLMCPI_SIGMA_CLUSTER_BITMAP=global|lds.
+ScPlan sc_plan(uint32_t N, uint32_t B, const Tuning &tune) {
+  ScPlan p;
+  p.words = (N + 31) / 32;
+  p.block = tune.sigma_cluster_team ? tune.sigma_cluster_team == 2 : B < 4 * kComputeUnits;
+  p.lds_map = !tune.sigma_cluster_map_global && p.words <= (p.block ? kScBlockLdsWords : kScWaveLdsWords);
+  p.threads = p.block ? (N >= 16384 ? kScBlockThreads : 256u) : kScWaveChains * kWave;
+  p.grid = p.block ? B : (B + kScWaveChains - 1) / kScWaveChains;
+  p.lds_bytes = p.lds_map ? (size_t)p.words * sizeof(uint32_t) * (p.block ? 1 : kScWaveChains) : 0;
+  return p;
+}
+
+std::mutex g_sc_attr_mutex;
+bool g_sc_attr_set[64] = {false};
+
+int sc_init_attrs() {
+  int dev = 0;
+  MLMCPI_HIP_TRY(hipGetDevice(&dev));
+  if (dev < 0 || dev >= 64) return fail(MLMCPI_ERR_INVALID, "device index %d out of range", dev);
+  std::lock_guard<std::mutex> lock(g_sc_attr_mutex);
+  if (g_sc_attr_set[dev]) return MLMCPI_OK;
+  MLMCPI_HIP_TRY(hipFuncSetAttribute((const void *)sigma_cluster_kernel<true, true>, hipFuncAttributeMaxDynamicSharedMemorySize,
+                                     kScBlockLdsWords * sizeof(uint32_t)));
+  g_sc_attr_set[dev] = true;
+  return MLMCPI_OK;
+}
+
+int sc_check(const mlmcpi_lattice_action *act, const char *what) {
+  if (!act) return fail(MLMCPI_ERR_INVALID, "action is NULL");
+  if (act->kind != MLMCPI_NONLINEAR_SIGMA)
+    return fail(MLMCPI_ERR_UNSUPPORTED, "%s: the Wolff single-cluster update is built for the O(3) nonlinear sigma model only "
+                "(action kind %d)", what, act->kind);
+  if (int rc = check_lattice(act)) return rc;
+  if (!(act->beta > 0.0)) return fail(MLMCPI_ERR_INVALID, "beta must be positive");
+  return MLMCPI_OK;
+}
+
+// workspace sections: queue a [B N] double, queue vertex [B N] uint32, bitmap [B words] uint32
+size_t sc_section_a(uint32_t N, uint32_t B) { return align256((size_t)B * N * sizeof(double)); }
+size_t sc_section_v(uint32_t N, uint32_t B) { return align256((size_t)B * N * sizeof(uint32_t)); }
+size_t sc_section_map(uint32_t N, uint32_t B) { return align256((size_t)B * ((N + 31) / 32) * sizeof(uint32_t)); }
+
+}  // namespace
+}  // namespace mlmcpi
+
+using namespace mlmcpi;
+
+extern "C" {
+
+int mlmcpi_sigma_cluster_workspace_bytes(const mlmcpi_lattice_action *act, uint32_t B, size_t *bytes) {
+  if (int rc = sc_check(act, "mlmcpi_sigma_cluster_workspace_bytes")) return rc;
+  MLMCPI_REQUIRE(bytes && B > 0, "bad arguments");
+  const uint32_t N = act->Mt * act->Mx;
+  *bytes = sc_section_a(N, B) + sc_section_v(N, B) + sc_section_map(N, B);
+  return MLMCPI_OK;
+}
+
+int mlmcpi_sigma_cluster_draw(const mlmcpi_lattice_action *act, double *d_phi, uint32_t B, uint32_t n_updates, uint64_t seed,
+                              uint32_t chain0, uint32_t update0, uint32_t *d_cluster_sites, void *d_work, void *stream) {
+  if (int rc = sc_check(act, "mlmcpi_sigma_cluster_draw")) return rc;
+  MLMCPI_REQUIRE(d_phi && d_work && B > 0, "bad arguments");
+  MLMCPI_REQUIRE((uint64_t)update0 + n_updates <= 0xFFFFFFFFull, "update counter overflows");
+  if (int rc = sc_init_attrs()) return rc;
+  const uint32_t N = act->Mt * act->Mx;
+  const ScPlan p = sc_plan(N, B, tuning());
+  char *w = (char *)d_work;
+  double *qa = (double *)w;
+  uint32_t *qv = (uint32_t *)(w + sc_section_a(N, B));
+  uint32_t *map = (uint32_t *)(w + sc_section_a(N, B) + sc_section_v(N, B));
+  const RngKey key = make_key(seed, chain0, update0);
+  const hipStream_t st = as_stream(stream);
+#define MLMCPI_SC_LAUNCH(BLOCK, LDS)                                                                                           \
+  hipLaunchKernelGGL((sigma_cluster_kernel<BLOCK, LDS>), dim3(p.grid), dim3(p.threads), p.lds_bytes, st, (double2 *)d_phi, act->Mt, \
+                     act->Mx, 2.0 * act->beta, B, n_updates, key, qv, qa, map, p.words, d_cluster_sites)
+  if (p.block && p.lds_map) MLMCPI_SC_LAUNCH(true, true);
+  else if (p.block) MLMCPI_SC_LAUNCH(true, false);
+  else if (p.lds_map) MLMCPI_SC_LAUNCH(false, true);
+  else MLMCPI_SC_LAUNCH(false, false);
+#undef MLMCPI_SC_LAUNCH
+  MLMCPI_LAUNCH_CHECK("sigma_cluster_kernel");
+  return MLMCPI_OK;
+}
+
+}  // extern "C"

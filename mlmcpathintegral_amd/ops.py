@@ -342,6 +342,26 @@ def lattice_random_sweep_draw(act, phi, n_overrelax, n_heatbath, seed, chain0, s
              _p(work), _stream())
 
 
+def sigma_cluster_workspace(act, B, device="cuda"):
+    """workspace of sigma_cluster_draw for B chains (uint8 tensor)"""
+    nbytes = C.c_size_t(0)
+    abi.call("mlmcpi_sigma_cluster_workspace_bytes", C.byref(act), B, C.byref(nbytes))
+    return torch.empty(nbytes.value, dtype=torch.uint8, device=device)
+
+
+def sigma_cluster_draw(act, x, n_updates, seed, chain0, update0, count=True, work=None):
+    """Wolff single-cluster updates of the O(3) sigma model (mlmcpi_sigma_cluster_draw): n_updates updates of every chain of
+    x [B, 2 Mt Mx], in place, update counters update0 + k; returns the flipped sites per chain of this call (int32 [B]; None
+    with count=False)"""
+    _check_state(x, lattice_size(act))
+    if work is None:
+        work = sigma_cluster_workspace(act, x.shape[0], x.device)
+    sites = torch.zeros(x.shape[0], dtype=torch.int32, device=x.device) if count else None
+    abi.call("mlmcpi_sigma_cluster_draw", C.byref(act), _p(x), x.shape[0], n_updates, seed, chain0, update0, _p(sites), _p(work),
+             _stream())
+    return sites
+
+
 def lattice_random_sweep_order(act, B, seed, chain0, sweep, rounds=True, device="cuda"):
     """the visiting order (int32 [B, n]) and the round of every index (int32 [B, n], or None) of that sweep"""
     n = (2 if act.kind == abi.SCHWINGER else 1) * act.Mt * act.Mx
