@@ -28,7 +28,7 @@
  *     MLMCPI_OR_KERNEL=block (which makes BOTH actions sweep by sweep) -- differ in the last bits
  *     (<= 4e-14 Schwinger at K = 10, <= 2e-15 rotor).  A heat-bath accept/reject decision that sits on
  *     such a difference flips, after which two chains diverge: compare, checkpoint and resume runs under
- *     one launch plan, and record it (K per launch: bench.py's config.overrelaxation_launches).  The
+ *     one launch plan, and record it (mlmcpi_lattice_sweep_plan: every launch of a draw, its kernel and depth K).  The
  *     sweep-by-sweep kernels (GFF and the sigma model always) agree bit for bit whatever the plan.  A QoI fused into the last launch of a
  *     draw (mlmcpi_lattice_sweep_draw_qoi*) sums per-tile partials in the tile order of that launch: under another plan
  *     (MLMCPI_OR_HEAT=split, MLMCPI_OR_KERNEL=block) it agrees to rounding (1e-13).  Spelled out in DESIGN.md 3 / 9.
@@ -375,6 +375,37 @@ int mlmcpi_lattice_sweep_draw_qoi_record(const mlmcpi_lattice_action *act, const
                                          uint32_t B, uint32_t n_overrelax, uint32_t n_heatbath, uint64_t seed, uint32_t chain0,
                                          uint32_t sweep0, uint32_t fuse, int32_t qoi_kind, double *d_qoi, double *d_acc,
                                          int32_t *result_in, void *stream);
+/* The launch plan of a draw: the launches mlmcpi_lattice_sweep_draw* issues for (act, B, n_overrelax, n_heatbath, fuse) under
+ * the options in force (mlmcpi_set_option), in order -- from the very planner the draws run, without touching a device.
+ * Kernels (namespace mlmcpi) and the template arguments a record fixes: */
+enum mlmcpi_sweep_kernel {
+  MLMCPI_K_SCHWINGER_SWEEP = 0,     /* schwinger_sweep_kernel<n_heatbath != 0, threads, TWC, THC, step>; TWC x THC = tile_w x tile_h
+                                     * with fixed_tile, else 0 x 0 */
+  MLMCPI_K_GFF_SWEEP = 1,           /* gff_sweep_kernel<n_heatbath != 0, threads, TWC, THC> */
+  MLMCPI_K_SCHWINGER_OR_BLOCK = 2,  /* schwinger_or_block_kernel<n_overrelax> */
+  MLMCPI_K_GFF_OR_BLOCK = 3,        /* gff_or_block_kernel<n_overrelax, tile_w> */
+  MLMCPI_K_GFF_OR_HEAT = 4,         /* gff_or_heat_kernel<n_overrelax, tile_w> */
+  MLMCPI_K_SCHWINGER_PERM = 5,      /* schwinger_perm_kernel<tile_h> */
+  MLMCPI_K_SCHWINGER_PERM_HEAT = 6, /* schwinger_perm_heat_kernel<threads, step> */
+  MLMCPI_K_SIGMA_SWEEP = 7          /* sigma_sweep_kernel<threads> */
+};
+typedef struct mlmcpi_sweep_launch {
+  uint32_t kernel;                  /* enum mlmcpi_sweep_kernel */
+  uint32_t n_overrelax, n_heatbath; /* the sweeps the launch covers, overrelaxation first (the depth K of the fused kernels) */
+  uint32_t grid_x, threads;         /* workgroups per chain (grid.y = B) and threads per workgroup */
+  uint32_t lds_bytes;               /* dynamic LDS */
+  uint32_t tile_w, tile_h, tiles_x; /* owned tile and tiles per row of tiles */
+  uint32_t fixed_tile;              /* 1: the tile extents are template arguments of the generic kernels */
+  uint32_t step;                    /* 1: Schwinger heat bath from the step envelope (2 beta <= 16), 0: wrapped Cauchy */
+  uint32_t planes;                  /* closed-form kernels: the plane is built in one piece or two (else 0) */
+  uint32_t pool_cap;                /* schwinger_sweep_kernel heat bath: entries of the list of open cells */
+  uint32_t kinds;                   /* generic kernels: bit q set = sweep q of the launch is a heat-bath sweep */
+} mlmcpi_sweep_launch;
+/* Same argument checks as the draws (even extents, square GFF lattice, B > 0).  Writes min(*count, capacity) records to `out`
+ * and the number of launches to *count; MLMCPI_ERR_INVALID, with *count set, when capacity is too small (call with
+ * capacity 0 to ask).  Record this beside a checkpoint: see BIT REPRODUCIBILITY ACROSS LAUNCH PLANS above. */
+int mlmcpi_lattice_sweep_plan(const mlmcpi_lattice_action *act, uint32_t B, uint32_t n_overrelax, uint32_t n_heatbath,
+                              uint32_t fuse, mlmcpi_sweep_launch *out, uint32_t capacity, uint32_t *count);
 /* Action::copy_from_fine / copy_from_coarse between a lattice and its next-coarser level, coarsening
  * factors rt, rx in {1, 2} in the temporal / spatial direction (CoarsenBoth = 2,2; CoarsenTemporal = 2,1;
  * CoarsenSpatial = 1,2; lattice/lattice2d.cc:24-47).  `fine` describes the FINE lattice.

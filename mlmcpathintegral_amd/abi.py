@@ -34,6 +34,12 @@ class LatticeAction(C.Structure):
                 ("mass", C.c_double)]
 
 
+class SweepLaunch(C.Structure):
+    """mlmcpi_sweep_launch"""
+    _fields_ = [(n, C.c_uint32) for n in ("kernel", "n_overrelax", "n_heatbath", "grid_x", "threads", "lds_bytes", "tile_w", "tile_h",
+                                          "tiles_x", "fixed_tile", "step", "planes", "pool_cap", "kinds")]
+
+
 _vp, _u32, _u64, _i, _d, _sz = C.c_void_p, C.c_uint32, C.c_uint64, C.c_int, C.c_double, C.c_size_t
 _PA, _LA = C.POINTER(PathAction), C.POINTER(LatticeAction)
 
@@ -107,6 +113,7 @@ SIGNATURES = {
     "mlmcpi_lattice_sweep_draw_from": (_i, [_LA, _vp, _vp, _vp, _u32, _u32, _u32, _u64, _u32, _u32, _u32, _vp, _vp]),
     "mlmcpi_lattice_sweep_draw_pingpong": (_i, [_LA, _vp, _vp, _u32, _u32, _u32, _u64, _u32, _u32, _u32,
                                                 C.POINTER(C.c_int32), _vp]),
+    "mlmcpi_lattice_sweep_plan": (_i, [_LA, _u32, _u32, _u32, _u32, C.POINTER(SweepLaunch), _u32, C.POINTER(_u32)]),
     "mlmcpi_qoi_phi_squared": (_i, [_vp, _u32, _u32, _vp, _vp]),
     "mlmcpi_qoi_avg_plaquette": (_i, [_vp, _u32, _u32, _u32, _vp, _vp]),
     "mlmcpi_qoi_2d_susceptibility": (_i, [_vp, _u32, _u32, _u32, _vp, _vp]),

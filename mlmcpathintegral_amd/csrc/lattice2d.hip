@@ -9,7 +9,8 @@
 // RNG makes those recomputations bit-identical.  Per sweep HBM sees ~(1 + halo overhead) reads and
 // one write of every entry -- instead of the 4-5 passes of one-kernel-per-colour -- and k fused
 // sweeps divide that by k.
-// This file is the sweep path only: the kernels, the launch plan (sweep_draw_impl) and the site-at-a-time updates.
+// This file is the sweep path only: the kernels, the launch plan (make_sweep_plan, next_launch), its executor
+// (sweep_draw_impl, the launchers) and the site-at-a-time updates.
 // Reductions, force and HMC, level transfers and the two-level step, and the exact GFF sampler are in lattice_reduce.hip,
 // lattice_hmc.hip, lattice_twolevel.hip and gff_exact.hip.
 #include <algorithm>
@@ -1773,97 +1774,6 @@ __global__ void __launch_bounds__(64)
 }
 
 // ---- host dispatch ----------------------------------------------------------------------------------------
-struct SweepGeom {
-  TileGeom tg;
-  uint32_t tiles_y, NT;
-  size_t lds_bytes;
-  bool overridden;  // MLMCPI_SWEEP_TILE given: use the generic kernels with that geometry
-};
-
-// Tile shape and workgroup size for a launch of `nsweeps` fused sweeps.  Default: 64 x 32 owned sites,
-// 256 threads (4 workgroups per CU at one sweep).  MLMCPI_SWEEP_TILE=TWxTHxNT overrides (tuning knob;
-// results never depend on it).
-static SweepGeom choose_geometry(const Tuning &tune, uint32_t Mt, uint32_t Mx, uint32_t nsweeps, uint32_t bytes_per_cell) {
-  uint32_t TW = 64, TH = 32, NT = 256;
-  bool overridden = false;
-  if (tune.tile_w) {
-    TW = tune.tile_w; TH = tune.tile_h; NT = tune.tile_nt;
-    overridden = true;
-  }
-  SweepGeom g;
-  g.overridden = overridden;
-  g.tg.TW = Mt < TW ? Mt : TW;
-  g.tg.TH = Mx < TH ? Mx : TH;
-  g.tg.tiles_x = (Mt + g.tg.TW - 1) / g.tg.TW;
-  g.tiles_y = (Mx + g.tg.TH - 1) / g.tg.TH;
-  g.NT = NT;
-  g.lds_bytes = (size_t)(g.tg.TW + 4 * nsweeps) * (g.tg.TH + 4 * nsweeps) * bytes_per_cell;
-  return g;
-}
-
-template <bool SCHW, bool HEAT, int NT>
-static int launch_sweep_nt(const SweepGeom &g, dim3 grid, hipStream_t st, uint32_t Mt, uint32_t Mx, double coupling,
-                            const double *src, double *dst, uint32_t n, uint32_t kinds, RngKey key, int qoi_op = 0,
-                            double *qoi_partial = nullptr) {
-  if (SCHW) {
-    // heat-bath launches: room for the tables and the list of open cells in front of the tile image, as many entries as still keep the workgroup's
-    // LDS footprint within a quarter of the CU's 160 KiB (4 workgroups per CU), at least one wave's worth
-    const bool fixed = HEAT && NT == 256 && n == 1 && !g.overridden && g.tg.TW == 64 && g.tg.TH == 32 && Mt % 64 == 0 &&
-                       Mx % 32 == 0 && Mt >= 128 && Mx >= 64;  // compile-time tile geometry (bit-identical results)
-    const bool step = HEAT && 2. * coupling <= kVsKappaMax;      // which sampler: a property of the action, not a knob
-    uint32_t cap = 0;
-    size_t lds = g.lds_bytes;
-    const uint32_t *vs_table = nullptr;
-    if (step)
-      if (int rc = vs_table_device(2. * coupling, &vs_table)) return rc;
-    if (HEAT) {
-      const size_t quarter = 40 * 1024 - 64;  // (the kernel's static LDS: the QoI reduction scratch)
-      const size_t entry = step ? (fixed ? sizeof(uint16_t) : sizeof(uint32_t)) : 24, fixed_part = (step ? kVsTableBytes + 16 : 8) + 16;
-      cap = 64;
-      if (lds + fixed_part + entry * cap <= quarter) cap = (uint32_t)((quarter - lds - fixed_part) / entry) & ~7u;
-      if (cap > (step ? 256u : 1024u)) cap = step ? 256u : 1024u;
-      lds = g.lds_bytes + sweep_pool_bytes(step, fixed && step, cap);
-      if (lds > 160 * 1024 - 256) { cap = 0; lds = g.lds_bytes + sweep_pool_bytes(step, fixed && step, 0); }
-    }
-    if (fixed && step)
-      hipLaunchKernelGGL((schwinger_sweep_kernel<HEAT, NT, 64, 32, HEAT>), grid, dim3(NT), lds, st, Mt, Mx, coupling,
-                         (const double2 *)src, (double2 *)dst, g.tg, n, kinds, key, cap, qoi_op, qoi_partial, vs_table);
-    else if (fixed)
-      hipLaunchKernelGGL((schwinger_sweep_kernel<HEAT, NT, 64, 32>), grid, dim3(NT), lds, st, Mt, Mx, coupling,
-                         (const double2 *)src, (double2 *)dst, g.tg, n, kinds, key, cap, qoi_op, qoi_partial, vs_table);
-    else if (step)
-      hipLaunchKernelGGL((schwinger_sweep_kernel<HEAT, NT, 0, 0, HEAT>), grid, dim3(NT), lds, st, Mt, Mx, coupling,
-                         (const double2 *)src, (double2 *)dst, g.tg, n, kinds, key, cap, qoi_op, qoi_partial, vs_table);
-    else
-      hipLaunchKernelGGL((schwinger_sweep_kernel<HEAT, NT>), grid, dim3(NT), lds, st, Mt, Mx, coupling,
-                         (const double2 *)src, (double2 *)dst, g.tg, n, kinds, key, cap, qoi_op, qoi_partial, vs_table);
-  }
-  else
-  if (HEAT && NT == 256 && n == 1 && (kinds & 1u) && !g.overridden && g.tg.TW == 64 && g.tg.TH == 32 && Mt % 64 == 0 &&
-      Mx % 32 == 0 && Mt >= 128 && Mx >= 64)  // single heat-bath sweep: compile-time geometry (bit-identical results)
-    hipLaunchKernelGGL((gff_sweep_kernel<HEAT, NT, 64, 32>), grid, dim3(NT), g.lds_bytes, st, Mt, Mx, coupling, src, dst, g.tg,
-                       n, kinds, key, qoi_op, qoi_partial);
-  else
-    hipLaunchKernelGGL((gff_sweep_kernel<HEAT, NT>), grid, dim3(NT), g.lds_bytes, st, Mt, Mx, coupling, src, dst, g.tg, n,
-                       kinds, key, qoi_op, qoi_partial);
-  return MLMCPI_OK;
-}
-
-template <bool SCHW, bool HEAT>
-static int launch_sweep(const SweepGeom &g, dim3 grid, hipStream_t st, uint32_t Mt, uint32_t Mx, double coupling,
-                        const double *src, double *dst, uint32_t n, uint32_t kinds, RngKey key, int qoi_op = 0,
-                        double *qoi_partial = nullptr) {
-  int rc;
-  switch (g.NT) {
-    case 1024: rc = launch_sweep_nt<SCHW, HEAT, 1024>(g, grid, st, Mt, Mx, coupling, src, dst, n, kinds, key, qoi_op, qoi_partial); break;
-    case 512: rc = launch_sweep_nt<SCHW, HEAT, 512>(g, grid, st, Mt, Mx, coupling, src, dst, n, kinds, key, qoi_op, qoi_partial); break;
-    default: rc = launch_sweep_nt<SCHW, HEAT, 256>(g, grid, st, Mt, Mx, coupling, src, dst, n, kinds, key, qoi_op, qoi_partial);
-  }
-  if (rc) return rc;
-  MLMCPI_LAUNCH_CHECK("lattice sweep kernel");
-  return MLMCPI_OK;
-}
-
 template <bool HEAT, int NT>
 static int allow_full_lds() {
   // tiles with deep halos may use the whole 160 KiB of LDS
@@ -1923,6 +1833,281 @@ static int init_sweep_kernels() {
   return MLMCPI_OK;
 }
 
+// ---- launch plan: the per-draw constants; next_launch is the only place that chooses kernels.  No HIP call in here. ----
+struct SweepPlan {
+  int32_t kind;
+  uint32_t Mt, Mx, B, n_overrelax, n_heatbath;
+  double coupling;                   // beta; GFF: mu2
+  Tuning tune;                       // ONE snapshot per draw: mlmcpi_set_option on another thread cannot split a launch plan
+  uint32_t tile_w, tile_h, tile_nt;  // generic tile kernels and the sigma model: 64 x 32 owned sites, 256 threads (4 workgroups
+                                     // per CU at one sweep); MLMCPI_SWEEP_TILE=TWxTHxNT overrides (results never depend on it)
+  bool schw, or_blocks, gff_blocks32, perm, perm64, step;  // step: the heat bath's sampler, a property of the action, not a knob
+  int gff_T;                         // the GFF register-block tile (0: the generic kernels)
+  uint32_t perm_th;
+  uint32_t fuse, fuse_arg;           // sweeps per launch in effect / as the caller gave it
+};
+
+// sigma model (profiles/sigma_fuse_tile.json, 1024^2 x 32, 10 + 1 sweeps): 64 x 32 tiles of 256 threads, 2 sweeps
+// per launch -- 8.78 ms per draw against 9.94 ms at fuse = 1 and 10.25 ms on 32 x 32 tiles; the kernel is issue-bound, so
+// deeper fusion buys little (fuse 3: 8.75 ms) and at fuse 4 the 92 KB tile leaves one workgroup per CU
+constexpr uint32_t kSigmaFuse = 2;
+static size_t sigma_lds_bytes(const SweepPlan &p, uint32_t K) {  // three planes of tile + halo
+  return (size_t)(p.tile_w + 4 * K) * (p.tile_h + 4 * K) * 3 * sizeof(double); }
+
+// The argument checks every draw makes, then the constants.  `fuse` = 0: the library default.
+static int make_sweep_plan(const mlmcpi_lattice_action *act, uint32_t B, uint32_t n_overrelax, uint32_t n_heatbath, uint32_t fuse,
+                           const Tuning &tune, SweepPlan *out) {
+  if (int rc = check_lattice(act)) return rc;
+  MLMCPI_REQUIRE(B > 0, "bad arguments");
+  MLMCPI_REQUIRE(act->Mt % 2 == 0 && act->Mx % 2 == 0, "multicolour sweeps need even Mt, Mx (got %u x %u)", act->Mt, act->Mx);
+  SweepPlan &p = *out;
+  const uint32_t Mt = act->Mt, Mx = act->Mx;
+  p = SweepPlan{act->kind, Mt, Mx, B, n_overrelax, n_heatbath, act->beta, tune};
+  p.tile_w = tune.tile_w ? tune.tile_w : 64;
+  p.tile_h = tune.tile_w ? tune.tile_h : 32;
+  p.tile_nt = tune.tile_w && (tune.tile_nt == 1024 || tune.tile_nt == 512) ? tune.tile_nt : 256;
+  p.fuse_arg = fuse;
+  if (act->kind == MLMCPI_NONLINEAR_SIGMA) {
+    p.fuse = std::min(fuse ? fuse : kSigmaFuse, kMaxFuse);
+    while (p.fuse > 1 && sigma_lds_bytes(p, p.fuse) > kSigmaLdsMax) --p.fuse;
+    if (sigma_lds_bytes(p, p.fuse) > kSigmaLdsMax)
+      return fail(MLMCPI_ERR_INVALID, "sigma sweep tile %u x %u does not fit in LDS", p.tile_w, p.tile_h);
+    return MLMCPI_OK;
+  }
+  const bool schw = p.schw = act->kind == MLMCPI_SCHWINGER;
+  p.coupling = schw ? act->beta : gff_mu2(*act);
+  p.step = schw && 2. * act->beta <= kVsKappaMax;
+  // 4 x 4 register-block overrelaxation on 64 x 64 tiles where they divide the lattice: the GFF default; for the Schwinger
+  // action the sweep-by-sweep plan (MLMCPI_OR_KERNEL=block, lattices the closed form does not take)
+  p.or_blocks = !tune.tile_w && Mt % 64 == 0 && Mx % 64 == 0;
+  // GFF lattices that 32 x 32 tiles divide and 64 x 64 ones do not (or that are below 128, where the 64-tile fused launch
+  // does not apply): the register-block kernels on 32 x 32 tiles, same launch plan
+  // (r05: also lattices no tile divides -- edge tiles computed whole and written in part -- unless the padding would more
+  // than double the work)
+  const uint32_t g32_tx = (Mt + 31) / 32, g32_ty = (Mx + 31) / 32;
+  p.gff_blocks32 = !schw && !tune.tile_w && Mt >= 64 && Mx >= 64 && !(p.or_blocks && Mt >= 128 && Mx >= 128) &&
+                   (uint64_t)g32_tx * g32_ty * 1024 <= (uint64_t)2 * Mt * Mx + (uint64_t)Mt * Mx / 5;
+  // 64 only on lattices of at least 128 x 128 (else gff_blocks32)
+  p.gff_T = schw ? 0 : p.gff_blocks32 ? 32 : p.or_blocks ? 64 : 0;
+  // Schwinger overrelaxation in closed form (schwinger_perm_kernel, schwinger_perm_heat_kernel): the default;
+  // MLMCPI_OR_KERNEL=block selects the sweep-by-sweep kernels
+  // r05: any even lattice of at least one tile.  Tiles on the upper / right edge of a lattice the tiles do not divide reach
+  // beyond it; what lies there are periodic images of vertices other tiles own (the plane wraps as often as needed):
+  // computed like any halo, not written.  64 x 64 tiles where they divide Mx and wherever the fused launch applies (both
+  // extents >= 128: its image must not wrap onto itself), else 64 x 32 (the heat bath is then a launch of its own);
+  // lattices that would more than double the work through padding stay with the sweep-by-sweep kernels.
+  const bool perm_shape = schw && Mt >= 64 && Mx >= 32 && (uint64_t)Mt * Mx < (1ull << 28);   // (32-bit byte offsets)
+  p.perm64 = perm_shape && (Mx % 64 == 0 || (Mt >= 128 && Mx >= 128));
+  p.perm_th = p.perm64 ? 64 : 32;
+  const uint32_t perm_tx = (Mt + 63) / 64, perm_ty = (Mx + p.perm_th - 1) / p.perm_th;
+  p.perm = perm_shape && !tune.or_block && !tune.tile_w &&
+           (uint64_t)perm_tx * 64 * perm_ty * p.perm_th <= (uint64_t)2 * Mt * Mx + (uint64_t)Mt * Mx / 5;
+  // library default: best measured whole-step time (DESIGN.md section 7) -- up to 6 sweeps per launch where the 4 x 4
+  // register-block kernels apply, 4 otherwise
+  p.fuse = std::min(fuse ? fuse : (p.or_blocks || p.gff_blocks32) ? 6u : 4u, kMaxFuse);
+  return MLMCPI_OK;
+}
+
+// The launch that begins at sweep s < n_overrelax + n_heatbath of the draw.  Stateless; allocates nothing.
+// Overrelaxation sweeps are fused: they are bound by the passes over the state, and a fused launch trades halo
+// recomputation (cheap for them) for passes.  A heat-bath sweep is bound by its sampler arithmetic, which a wider halo
+// would only multiply: no sweep follows it inside a launch.  As the LAST sweep of an overrelaxation launch it needs no
+// halo of its own beyond the two rings it reads (schwinger_perm_heat_kernel, gff_or_heat_kernel); otherwise it gets a
+// launch to itself.  (The sigma model's kernel takes both kinds of sweep, up to `fuse` of them.)
+static int next_launch(const SweepPlan &p, uint32_t s, SweepLaunch *out) {
+  SweepLaunch &l = *out;
+  l = {};
+  const uint32_t Mt = p.Mt, Mx = p.Mx, rem = s < p.n_overrelax ? p.n_overrelax - s : 0;
+  auto tiles = [&](uint32_t TW, uint32_t TH) {  // the owned tile and the workgroups per chain
+    l.tile_w = TW, l.tile_h = TH, l.tiles_x = (Mt + TW - 1) / TW;
+    l.grid_x = l.tiles_x * ((Mx + TH - 1) / TH);
+  };
+  if (p.kind == MLMCPI_NONLINEAR_SIGMA) {
+    const uint32_t K = std::min(p.n_overrelax + p.n_heatbath - s, p.fuse);
+    l.kernel = MLMCPI_K_SIGMA_SWEEP;
+    l.n_overrelax = std::min(rem, K);
+    l.n_heatbath = K - l.n_overrelax;
+    l.threads = p.tile_nt;
+    tiles(p.tile_w, p.tile_h);
+    l.lds_bytes = (uint32_t)sigma_lds_bytes(p, K);
+    return MLMCPI_OK;
+  }
+  if (p.perm && rem) {
+    // as few launches as kPermMaxK (or the caller's `fuse`) allows, of equal depth
+    const uint32_t kmax = p.fuse_arg ? std::min(p.fuse_arg, kPermMaxK) : kPermMaxK;
+    const uint32_t launches = (rem + kmax - 1) / kmax, K = (rem + launches - 1) / launches;
+    l.n_overrelax = K;
+    tiles(64, p.perm_th);
+    if (p.perm64 && !p.tune.or_heat_split && K == rem && p.n_heatbath >= 1 && Mt >= 128 && Mx >= 128) {
+      // the last overrelaxation launch takes the heat-bath sweep behind it along, and the QoI if that ends the draw
+      // at most one workgroup per CU: sixteen waves (MLMCPI_OR_HEAT=wide|narrow forces)
+      const bool wide = p.tune.or_heat_wide ? p.tune.or_heat_wide > 0 : (uint64_t)l.grid_x * p.B <= kComputeUnits;
+      using PHG = PermHeatGeom<512, true>;
+      // one plane for all 68 rows where it fits: beside a second workgroup (narrow) or in the whole LDS (wide)
+      const size_t lds_max = wide ? (size_t)156 * 1024 : HeatImageGeom::hb_bytes;
+      l.planes = PHG::lds_bytes(K, 1) <= lds_max ? 1 : 2;
+      if (PHG::lds_bytes(K, l.planes) > lds_max) return fail(MLMCPI_ERR_INVALID, "closed-form plane of %u sweeps does not fit", K);
+      l.kernel = MLMCPI_K_SCHWINGER_PERM_HEAT;
+      l.n_heatbath = 1;
+      l.threads = wide ? 1024 : 512;
+      l.step = p.step;
+      l.lds_bytes = (uint32_t)PHG::lds_bytes(K, l.planes);
+    } else {
+      l.kernel = MLMCPI_K_SCHWINGER_PERM;
+      l.threads = 512;
+      l.planes = (p.perm64 ? PermGeom<512, 0, 64>::plane_bytes(K, 1) : PermGeom<512, 0, 32>::plane_bytes(K, 1)) <= kPermPlaneMax ? 1 : 2;
+      l.lds_bytes = (uint32_t)(p.perm64 ? perm_lds_bytes<64>(K, l.planes) : perm_lds_bytes<32>(K, l.planes));
+    }
+    return MLMCPI_OK;
+  }
+  // register blocks: as few launches as `fuse` allows, of equal depth (10 sweeps, fuse 6: 5 + 5, not 6 + 4)
+  const uint32_t launches = (rem + p.fuse - 1) / p.fuse;
+  uint32_t n = !rem ? 1 : (p.or_blocks || p.gff_blocks32) ? (rem + launches - 1) / launches : std::min(rem, p.fuse);
+  const bool heat = !rem, overridden = p.tune.tile_w != 0;  // a heat-bath sweep is a launch of its own: n == 1
+  // the generic tile: Schwinger two link angles per site; GFF heat bath field + parked normal per site
+  const uint32_t TW = std::min(Mt, p.tile_w), TH = std::min(Mx, p.tile_h), bytes_per_cell = (p.schw || heat) ? 16 : 8;
+  auto tile_lds = [&](uint32_t k) { return (size_t)(TW + 4 * k) * (TH + 4 * k) * bytes_per_cell; };
+  while (n > 1 && tile_lds(n) > 160 * 1024 - 256) --n;  // shrink the fused count until the tile + halo fits in LDS
+  if (!heat && !overridden && n <= 6 && (p.schw ? p.or_blocks : p.gff_T != 0)) {
+    // 4 x 4 register blocks, sweep by sweep.  Schwinger: 64 x 64 tiles (bit-identical to the generic kernel and the closed
+    // form).  GFF: gff_T x gff_T tiles; the last overrelaxation launch of the draw takes the heat-bath sweep behind it
+    // along (and the QoI, if that ends the draw): gff_or_heat_kernel, bit-identical to the two launches (MLMCPI_OR_HEAT=split)
+    const uint32_t T = p.schw ? 64 : (uint32_t)p.gff_T;
+    const bool fused = !p.schw && !p.tune.or_heat_split && n == rem && p.n_heatbath >= 1 && n <= 5;
+    l.kernel = p.schw ? MLMCPI_K_SCHWINGER_OR_BLOCK : fused ? MLMCPI_K_GFF_OR_HEAT : MLMCPI_K_GFF_OR_BLOCK;
+    l.n_overrelax = n;
+    l.n_heatbath = fused;
+    tiles(T, T);
+    with_depth<6>(n, [&](auto kc) {
+      constexpr int K = decltype(kc)::value, KH = K < 5 ? K : 5;  // (fused: n <= 5)
+      auto size = [&](uint32_t nt, size_t lds) { l.threads = nt, l.lds_bytes = (uint32_t)lds; };
+      if (p.schw) size(OrBlockGeom<K>::NT, OrBlockGeom<K>::lds_bytes);
+      else if (fused && T == 32) size(GffHeatGeom<KH, 32>::NT, GffHeatGeom<KH, 32>::lds_bytes);
+      else if (fused) size(GffHeatGeom<KH, 64>::NT, GffHeatGeom<KH, 64>::lds_bytes);
+      else if (T == 32) size(GffBlockGeom<K, 32>::NT, GffBlockGeom<K, 32>::lds_bytes);
+      else size(GffBlockGeom<K, 64>::NT, GffBlockGeom<K, 64>::lds_bytes);
+      return 0;
+    });
+    return MLMCPI_OK;
+  }
+  // the generic tile kernels; launches without a heat-bath sweep use the lean instantiation (no sampler code, fewer VGPRs)
+  l.kernel = p.schw ? MLMCPI_K_SCHWINGER_SWEEP : MLMCPI_K_GFF_SWEEP;
+  l.n_overrelax = heat ? 0 : n;
+  l.n_heatbath = l.kinds = heat;
+  l.threads = p.tile_nt;
+  tiles(TW, TH);
+  // single heat-bath sweep on a lattice the default tiles divide: compile-time tile geometry (bit-identical results)
+  l.fixed_tile = heat && !overridden && Mt % 64 == 0 && Mx % 32 == 0 && Mt >= 128 && Mx >= 64;
+  l.step = heat && p.step;
+  size_t lds = tile_lds(n);
+  if (p.schw && heat) {
+    // room for the tables and the list of open cells in front of the tile image, as many entries as still keep the workgroup's
+    // LDS footprint within a quarter of the CU's 160 KiB (4 workgroups per CU), at least one wave's worth
+    const bool step = l.step, fixed = l.fixed_tile;
+    const size_t quarter = 40 * 1024 - 64;  // (the kernel's static LDS: the QoI reduction scratch)
+    const size_t entry = step ? (fixed ? sizeof(uint16_t) : sizeof(uint32_t)) : 24, fixed_part = (step ? kVsTableBytes + 16 : 8) + 16;
+    uint32_t cap = 64;
+    if (lds + fixed_part + entry * cap <= quarter) cap = (uint32_t)((quarter - lds - fixed_part) / entry) & ~7u;
+    if (cap > (step ? 256u : 1024u)) cap = step ? 256u : 1024u;
+    if (lds + sweep_pool_bytes(step, fixed && step, cap) > 160 * 1024 - 256) cap = 0;
+    l.pool_cap = cap;
+    lds += sweep_pool_bytes(step, fixed && step, cap);
+  }
+  l.lds_bytes = (uint32_t)lds;
+  return MLMCPI_OK;
+}
+
+// ---- launchers: one SweepLaunch each --------------------------------------------------------------------------------
+struct SweepArgs {  // what a launch needs beside its SweepLaunch
+  uint32_t Mt, Mx, B;
+  double coupling;
+  const double *src;
+  double *dst;
+  RngKey key;                             // of the launch's heat-bath sweep (generic kernels: of its first sweep)
+  int qoi_op; double *qoi_partial;        // op != 0: the launch ends the draw and sums the QoI into qoi_partial[b * grid.x + tile]
+  const uint32_t *vs_table;
+  hipStream_t st;
+};
+
+template <bool HEAT, int NT>
+static void launch_tile_sweep_nt(const SweepLaunch &l, const SweepArgs &a) {
+  const dim3 grid(l.grid_x, a.B);
+  const TileGeom tg{l.tile_w, l.tile_h, l.tiles_x};
+  const uint32_t n = l.n_overrelax + l.n_heatbath;
+#define MLMCPI_SCHW_SWEEP(...)                                                                                                       \
+  hipLaunchKernelGGL((schwinger_sweep_kernel<__VA_ARGS__>), grid, dim3(NT), l.lds_bytes, a.st, a.Mt, a.Mx, a.coupling, (const double2 *)a.src, \
+                     (double2 *)a.dst, tg, n, l.kinds, a.key, l.pool_cap, a.qoi_op, a.qoi_partial, a.vs_table)
+#define MLMCPI_GFF_SWEEP(...)                                                                                               \
+  hipLaunchKernelGGL((gff_sweep_kernel<__VA_ARGS__>), grid, dim3(NT), l.lds_bytes, a.st, a.Mt, a.Mx, a.coupling, a.src, a.dst, \
+                     tg, n, l.kinds, a.key, a.qoi_op, a.qoi_partial)
+  if (l.kernel == MLMCPI_K_SCHWINGER_SWEEP) {
+    if (l.fixed_tile && l.step) MLMCPI_SCHW_SWEEP(HEAT, NT, 64, 32, HEAT);
+    else if (l.fixed_tile) MLMCPI_SCHW_SWEEP(HEAT, NT, 64, 32);
+    else if (l.step) MLMCPI_SCHW_SWEEP(HEAT, NT, 0, 0, HEAT);
+    else MLMCPI_SCHW_SWEEP(HEAT, NT);
+  } else if (l.fixed_tile) MLMCPI_GFF_SWEEP(HEAT, NT, 64, 32);
+  else MLMCPI_GFF_SWEEP(HEAT, NT);
+#undef MLMCPI_SCHW_SWEEP
+#undef MLMCPI_GFF_SWEEP
+}
+
+static int launch_tile_sweep(const SweepLaunch &l, const SweepArgs &a) {
+  const bool heat = l.n_heatbath != 0;
+  switch (l.threads) {
+    case 1024: heat ? launch_tile_sweep_nt<true, 1024>(l, a) : launch_tile_sweep_nt<false, 1024>(l, a); break;
+    case 512: heat ? launch_tile_sweep_nt<true, 512>(l, a) : launch_tile_sweep_nt<false, 512>(l, a); break;
+    default: heat ? launch_tile_sweep_nt<true, 256>(l, a) : launch_tile_sweep_nt<false, 256>(l, a);
+  }
+  MLMCPI_LAUNCH_CHECK("lattice sweep kernel");
+  return MLMCPI_OK;
+}
+
+// schwinger_or_block_kernel, gff_or_block_kernel, gff_or_heat_kernel: the depth is the launch's overrelaxation count
+template <int T>
+static int launch_blocks(const SweepLaunch &l, const SweepArgs &a) {
+  const dim3 grid(l.grid_x, a.B);
+  if (l.kernel == MLMCPI_K_GFF_OR_HEAT)
+    return with_depth<5>(l.n_overrelax, [&](auto kc) -> int {
+      constexpr int K = decltype(kc)::value;
+      hipLaunchKernelGGL((gff_or_heat_kernel<K, T>), grid, dim3(l.threads), l.lds_bytes, a.st, a.Mt, a.Mx, a.coupling, a.src, a.dst,
+                         l.tiles_x, a.key, a.qoi_op, a.qoi_partial);
+      MLMCPI_LAUNCH_CHECK("gff_or_heat_kernel");
+      return MLMCPI_OK;
+    });
+  return with_depth<6>(l.n_overrelax, [&](auto kc) -> int {
+    constexpr int K = decltype(kc)::value;
+    if (l.kernel == MLMCPI_K_GFF_OR_BLOCK)
+      hipLaunchKernelGGL((gff_or_block_kernel<K, T>), grid, dim3(l.threads), l.lds_bytes, a.st, a.Mt, a.Mx, a.coupling, a.src, a.dst,
+                         l.tiles_x);
+    else if constexpr (T == 64)
+      hipLaunchKernelGGL(schwinger_or_block_kernel<K>, grid, dim3(l.threads), l.lds_bytes, a.st, a.Mt, a.Mx, (const double2 *)a.src,
+                         (double2 *)a.dst, l.tiles_x);
+    MLMCPI_LAUNCH_CHECK("register-block overrelaxation kernel");
+    return MLMCPI_OK;
+  });
+}
+
+static int launch_perm(const SweepLaunch &l, const SweepArgs &a) {
+  const dim3 grid(l.grid_x, a.B);
+  const double2 *in = (const double2 *)a.src;
+  double2 *out = (double2 *)a.dst;
+#define MLMCPI_PERM_HEAT(NT, STEP)                                                                                           \
+  hipLaunchKernelGGL((schwinger_perm_heat_kernel<NT, STEP>), grid, dim3(NT), l.lds_bytes, a.st, a.Mt, a.Mx, a.coupling, in, out, \
+                     l.tiles_x, l.n_overrelax, l.planes, a.key, a.qoi_op, a.qoi_partial, a.vs_table)
+  if (l.kernel == MLMCPI_K_SCHWINGER_PERM_HEAT) {
+    if (l.threads == 1024 && l.step) MLMCPI_PERM_HEAT(1024, true);
+    else if (l.threads == 1024) MLMCPI_PERM_HEAT(1024, false);
+    else if (l.step) MLMCPI_PERM_HEAT(512, true);
+    else MLMCPI_PERM_HEAT(512, false);
+  } else if (l.tile_h == 64)
+    hipLaunchKernelGGL(schwinger_perm_kernel<64>, grid, dim3(512), l.lds_bytes, a.st, a.Mt, a.Mx, in, out, l.tiles_x, l.n_overrelax, l.planes);
+  else
+    hipLaunchKernelGGL(schwinger_perm_kernel<32>, grid, dim3(512), l.lds_bytes, a.st, a.Mt, a.Mx, in, out, l.tiles_x, l.n_overrelax, l.planes);
+#undef MLMCPI_PERM_HEAT
+  MLMCPI_LAUNCH_CHECK("schwinger closed-form kernel");
+  return MLMCPI_OK;
+}
+
 }  // namespace mlmcpi
 
 using namespace mlmcpi;
@@ -1932,222 +2117,80 @@ extern "C" {
 // The launches read `src` and write `dst`; after each one src <- dst and dst <- the other work buffer.  d_phi is only
 // read unless it is also d_w1.  result_in (may be NULL: then the result is copied into d_phi, which must be writable):
 // 0 -> the result is in d_w0, 1 -> in d_w1, -1 -> no sweep was run (result is the input).
-// qoi_kind != 0 (1 average plaquette, 2 Q^2 / 4 pi^2): the QoI of the final state, summed inside the last launch (which
-// has to be a launch of schwinger_sweep_kernel, i.e. the draw must end with a heat-bath sweep), into d_qoi[b].
+// qoi_kind != 0 (1 average plaquette, 2 Q^2 / 4 pi^2, 3 phi^2, 4 chi_m): the QoI of the final state, summed inside the last
+// launch (so the draw must end with a heat-bath sweep) into d_qoi[b].
 static int sweep_draw_impl(const mlmcpi_lattice_action *act, double *d_phi, double *d_w0, double *d_w1, uint32_t B,
                            uint32_t n_overrelax, uint32_t n_heatbath, uint64_t seed, uint32_t chain0, uint32_t sweep0,
                            uint32_t fuse, int32_t *result_in, void *stream, int qoi_kind = 0, double *d_qoi = nullptr,
                            double *d_acc = nullptr) {
-  if (int rc = check_lattice(act)) return rc;
+  SweepPlan p;
+  if (int rc = make_sweep_plan(act, B, n_overrelax, n_heatbath, fuse, tuning(), &p)) return rc;
+  const bool sigma = act->kind == MLMCPI_NONLINEAR_SIGMA;
   if (qoi_kind) {
     MLMCPI_REQUIRE(d_qoi && qoi_kind >= 1 && qoi_kind <= 4, "bad QoI arguments");
-    const int own = act->kind == MLMCPI_GFF ? 3 : act->kind == MLMCPI_NONLINEAR_SIGMA ? 4 : 0;
+    const int own = act->kind == MLMCPI_GFF ? 3 : sigma ? 4 : 0;
     if (own ? qoi_kind != own : qoi_kind > 2)
       return fail(MLMCPI_ERR_UNSUPPORTED, "fused QoI %d does not belong to this action", qoi_kind);
     if (n_heatbath == 0) return fail(MLMCPI_ERR_UNSUPPORTED, "the fused QoI needs a draw that ends with a heat-bath sweep");
   }
-  MLMCPI_REQUIRE(d_phi && d_w0 && d_w1 && d_phi != d_w0 && d_w0 != d_w1 && B > 0, "bad arguments");
-  MLMCPI_REQUIRE(act->Mt % 2 == 0 && act->Mx % 2 == 0, "multicolour sweeps need even Mt, Mx (got %u x %u)", act->Mt,
-                 act->Mx);
-  if (act->kind == MLMCPI_NONLINEAR_SIGMA)
-    return sigma_sweep_draw(act, d_phi, d_w0, d_w1, B, n_overrelax, n_heatbath, seed, chain0, sweep0, fuse, result_in,
-                            as_stream(stream), qoi_kind, d_qoi, d_acc);
-  const uint32_t Mt = act->Mt, Mx = act->Mx;
-  const Tuning tune = tuning();  // ONE snapshot per draw: mlmcpi_set_option on another thread cannot split a launch plan
-  const bool schw = act->kind == MLMCPI_SCHWINGER;
-  // 4 x 4 register-block overrelaxation on 64 x 64 tiles where they divide the lattice: the GFF default; for the Schwinger
-  // action the sweep-by-sweep plan (MLMCPI_OR_KERNEL=block, lattices the closed form does not take)
-  const bool or_blocks = !tune.tile_w && Mt % 64 == 0 && Mx % 64 == 0;
-  // GFF lattices that 32 x 32 tiles divide and 64 x 64 ones do not (or that are below 128, where the 64-tile fused launch
-  // does not apply): the register-block kernels on 32 x 32 tiles, same launch plan
-  // (r05: also lattices no tile divides -- edge tiles computed whole and written in part -- unless the padding would more
-  // than double the work)
-  const uint32_t g32_tx = (Mt + 31) / 32, g32_ty = (Mx + 31) / 32;
-  const bool gff_blocks32 = !schw && !tune.tile_w && Mt >= 64 && Mx >= 64 && !(or_blocks && Mt >= 128 && Mx >= 128) &&
-                            (uint64_t)g32_tx * g32_ty * 1024 <= (uint64_t)2 * Mt * Mx + (uint64_t)Mt * Mx / 5;
-  // the GFF register-block tile (0: the generic kernels); 64 only on lattices of at least 128 x 128 (else gff_blocks32)
-  const int gff_T = schw ? 0 : gff_blocks32 ? 32 : or_blocks ? 64 : 0;
-  // Schwinger overrelaxation in closed form (schwinger_perm_kernel, schwinger_perm_heat_kernel): the default;
-  // MLMCPI_OR_KERNEL=block selects the sweep-by-sweep kernels
-  // r05: any even lattice of at least one tile.  Tiles on the upper / right edge of a lattice the tiles do not divide reach
-  // beyond it; what lies there are periodic images of vertices other tiles own (the plane wraps as often as needed):
-  // computed like any halo, not written.  64 x 64 tiles where they divide Mx and wherever the fused launch applies (both
-  // extents >= 128: its image must not wrap onto itself), else 64 x 32 (the heat bath is then a launch of its own);
-  // lattices that would more than double the work through padding stay with the sweep-by-sweep kernels.
-  const bool perm_shape = schw && Mt >= 64 && Mx >= 32 && (uint64_t)Mt * Mx < (1ull << 28);   // (32-bit byte offsets)
-  const bool perm64 = perm_shape && (Mx % 64 == 0 || (Mt >= 128 && Mx >= 128));
-  const uint32_t perm_th = perm64 ? 64 : 32, perm_tx = (Mt + 63) / 64, perm_ty = (Mx + perm_th - 1) / perm_th;
-  const bool perm = perm_shape && !tune.or_block && !tune.tile_w &&
-                    (uint64_t)perm_tx * 64 * perm_ty * perm_th <= (uint64_t)2 * Mt * Mx + (uint64_t)Mt * Mx / 5;
-  // library default: best measured whole-step time (DESIGN.md section 7) -- up to 6 sweeps per launch where the 4 x 4
-  // register-block kernels apply, 4 otherwise
-  const uint32_t fuse_arg = fuse;
-  if (fuse == 0) fuse = (or_blocks || gff_blocks32) ? 6 : 4;
-  if (fuse > kMaxFuse) fuse = kMaxFuse;
-  hipStream_t st = as_stream(stream);
+  MLMCPI_REQUIRE(d_phi && d_w0 && d_w1 && d_phi != d_w0 && d_w0 != d_w1, "bad arguments");
+  if (int rc = sigma ? sigma_init_sweep_kernels() : init_sweep_kernels()) return rc;
+  const hipStream_t st = as_stream(stream);
   const uint32_t total = n_overrelax + n_heatbath;
-  const size_t state_bytes = (size_t)B * Mt * Mx * (schw ? 16 : 8);
-  if (int rc = init_sweep_kernels()) return rc;
-  double *src = d_phi, *dst = d_w0;
-  auto advance = [&]() {  // the buffer just written becomes the input; the next output is the other work buffer
-    src = dst;
-    dst = (dst == d_w0) ? d_w1 : d_w0;
-  };
-  // A launch whose last sweep is the heat-bath sweep number h of the draw, `tiles` workgroups per chain:
-  // launch(key of sweep h, op, partial) sums the QoI into partial[b * tiles + tile] if that sweep ends the draw (op != 0),
-  // and this finishes the sum into d_qoi.
   const int qoi_op = qoi_kind == 1 ? (int)L_PLAQ : qoi_kind == 2 ? (int)L_CHARGE : (int)L_PHI2;
-  auto heat_launch = [&](uint32_t h, uint32_t tiles, auto &&launch) -> int {
-    const bool with_qoi = qoi_kind && h + 1 == total;
-    void *partial = nullptr;
-    if (with_qoi)
-      if (int rc = scratch((size_t)B * tiles * sizeof(double), &partial, st)) return rc;
-    if (int rc = launch(make_key(seed, chain0, sweep0 + h), with_qoi ? qoi_op : 0, (double *)partial)) return rc;
-    if (with_qoi)
-      return lattice_finish((const double *)partial, tiles, B, qoi_op, 1.0 / ((double)Mx * Mt), d_qoi, d_acc, st);
-    return MLMCPI_OK;
-  };
-  uint32_t s = 0;
-  while (s < total) {
-    // Overrelaxation sweeps are fused: they are bound by the passes over the state, and a fused launch trades halo
-    // recomputation (cheap for them) for passes.  A heat-bath sweep is bound by its sampler arithmetic, which a wider halo
-    // would only multiply: no sweep follows it inside a launch.  As the LAST sweep of an overrelaxation launch it needs no
-    // halo of its own beyond the two rings it reads (schwinger_perm_heat_kernel, gff_or_heat_kernel); otherwise it gets a
-    // launch to itself.
-    const double2 *in2 = (const double2 *)src;
-    double2 *out2 = (double2 *)dst;
-    if (perm && s < n_overrelax) {
-      // as few launches as kPermMaxK (or the caller's `fuse`) allows, of equal depth
-      const uint32_t rem = n_overrelax - s, kmax = fuse_arg ? std::min(fuse_arg, kPermMaxK) : kPermMaxK;
-      const uint32_t launches = (rem + kmax - 1) / kmax, K = (rem + launches - 1) / launches;
-      const dim3 bgrid(perm_tx * perm_ty, B);
-      if (perm64 && !tune.or_heat_split && s + K == n_overrelax && n_heatbath >= 1 && Mt >= 128 && Mx >= 128) {
-        // the last overrelaxation launch takes the heat-bath sweep behind it along, and the QoI if that ends the draw
-        const bool step = 2. * act->beta <= kVsKappaMax;   // which sampler: a property of the action (device_common.hpp)
-        const uint32_t *vs_table = nullptr;
-        if (step)
-          if (int rc = vs_table_device(2. * act->beta, &vs_table)) return rc;
-        // at most one workgroup per CU: sixteen waves (MLMCPI_OR_HEAT=wide|narrow forces)
-        const bool wide = tune.or_heat_wide ? tune.or_heat_wide > 0 : (uint64_t)bgrid.x * B <= kComputeUnits;
-        using PHG = PermHeatGeom<512, true>;
-        // one plane for all 68 rows where it fits: beside a second workgroup (narrow) or in the whole LDS (wide)
-        const size_t lds_max = wide ? (size_t)156 * 1024 : HeatImageGeom::hb_bytes;
-        const uint32_t NB = PHG::lds_bytes(K, 1) <= lds_max ? 1 : 2;
-        const size_t lds = PHG::lds_bytes(K, NB);
-        if (lds > lds_max) return fail(MLMCPI_ERR_INVALID, "closed-form plane of %u sweeps does not fit", K);
-        if (int rc = heat_launch(s + K, bgrid.x, [&](RngKey hkey, int op, double *partial) -> int {
-              auto go = [&](auto nt, auto stp) -> int {
-                constexpr int NT = decltype(nt)::value;
-                hipLaunchKernelGGL((schwinger_perm_heat_kernel<NT, decltype(stp)::value>), bgrid, dim3(NT), lds, st, Mt, Mx,
-                                   act->beta, in2, out2, perm_tx, K, NB, hkey, op, partial, vs_table);
-                MLMCPI_LAUNCH_CHECK("schwinger_perm_heat_kernel");
-                return MLMCPI_OK;
-              };
-              using Wide = std::integral_constant<int, 1024>;
-              using Narrow = std::integral_constant<int, 512>;
-              return wide ? (step ? go(Wide(), std::true_type()) : go(Wide(), std::false_type()))
-                          : (step ? go(Narrow(), std::true_type()) : go(Narrow(), std::false_type()));
-            }))
-          return rc;
-        advance();
-        s += K + 1;
-        continue;
-      }
-      if (perm64) {
-        using PG0 = PermGeom<512, 0, 64>;
-        const uint32_t NB = PG0::plane_bytes(K, 1) <= kPermPlaneMax ? 1 : 2;
-        hipLaunchKernelGGL(schwinger_perm_kernel<64>, bgrid, dim3(512), perm_lds_bytes<64>(K, NB), st, Mt, Mx, in2, out2, perm_tx, K, NB);
-      } else {
-        using PG0 = PermGeom<512, 0, 32>;
-        const uint32_t NB = PG0::plane_bytes(K, 1) <= kPermPlaneMax ? 1 : 2;
-        hipLaunchKernelGGL(schwinger_perm_kernel<32>, bgrid, dim3(512), perm_lds_bytes<32>(K, NB), st, Mt, Mx, in2, out2, perm_tx, K, NB);
-      }
-      MLMCPI_LAUNCH_CHECK("schwinger_perm_kernel");
-      advance();
-      s += K;
-      continue;
-    }
-    uint32_t n = 1;
-    if (s < n_overrelax) {
-      const uint32_t rem = n_overrelax - s;
-      n = rem < fuse ? rem : fuse;
-      if (or_blocks || gff_blocks32) {  // as few launches as `fuse` allows, of equal depth (10 sweeps, fuse 6: 5 + 5, not 6 + 4)
-        const uint32_t launches = (rem + fuse - 1) / fuse;
-        n = (rem + launches - 1) / launches;
-      }
-    }
-    SweepGeom g;
-    uint32_t kinds = 0;
-    for (;;) {  // shrink the fused count until the tile + halo fits in LDS
-      kinds = 0;
-      for (uint32_t q = 0; q < n; ++q)
-        if (s + q >= n_overrelax) kinds |= 1u << q;
-      // Schwinger: two link angles per site; GFF heat bath: field + parked normal per site
-      g = choose_geometry(tune, Mt, Mx, n, (schw || kinds) ? 16 : 8);
-      if (g.lds_bytes <= 160 * 1024 - 256 || n == 1) break;
-      --n;
-    }
-    const dim3 grid(g.tg.tiles_x * g.tiles_y, B);
-    uint32_t swept = n;
+  double *src = d_phi, *dst = d_w0;
+  for (uint32_t s = 0; s < total;) {
+    SweepLaunch l;
+    if (int rc = next_launch(p, s, &l)) return rc;
+    const uint32_t sweeps = l.n_overrelax + l.n_heatbath;
+    const bool with_qoi = qoi_kind && s + sweeps == total;  // the launch ends the draw: it sums the QoI per tile
     int rc;
-    if (schw && !kinds && !g.overridden && or_blocks && n <= 6) {
-      // 4 x 4 register blocks on 64 x 64 tiles, sweep by sweep (bit-identical to the generic kernel and the closed form)
-      const dim3 bgrid((Mt / 64) * (Mx / 64), B);
-      rc = with_depth<6>(n, [&](auto kc) -> int {
-        constexpr int K = decltype(kc)::value;
-        hipLaunchKernelGGL(schwinger_or_block_kernel<K>, bgrid, dim3(OrBlockGeom<K>::NT), OrBlockGeom<K>::lds_bytes, st, Mt, Mx,
-                           in2, out2, Mt / 64);
-        MLMCPI_LAUNCH_CHECK("schwinger_or_block_kernel");
-        return MLMCPI_OK;
-      });
-    } else if (gff_T && !kinds && !g.overridden && n <= 6) {
-      // GFF, 4 x 4 register blocks on gff_T x gff_T tiles.  The last overrelaxation launch of the draw takes the heat-bath
-      // sweep behind it along (and the QoI, if that ends the draw): gff_or_heat_kernel, bit-identical to the two launches
-      // (MLMCPI_OR_HEAT=split)
-      const bool fused = !tune.or_heat_split && s + n == n_overrelax && n_heatbath >= 1 && n <= 5;
-      const double mu2 = gff_mu2(*act);
-      auto gff_blocks = [&](auto tc) -> int {
-        constexpr int T = decltype(tc)::value;
-        const uint32_t tiles_x = (Mt + T - 1) / T;
-        const dim3 bgrid(tiles_x * ((Mx + T - 1) / T), B);
-        if (fused)
-          return heat_launch(s + n, bgrid.x, [&](RngKey hkey, int op, double *partial) -> int {
-            return with_depth<5>(n, [&](auto kc) -> int {
-              constexpr int K = decltype(kc)::value;
-              hipLaunchKernelGGL((gff_or_heat_kernel<K, T>), bgrid, dim3((GffHeatGeom<K, T>::NT)), (GffHeatGeom<K, T>::lds_bytes),
-                                 st, Mt, Mx, mu2, (const double *)src, dst, tiles_x, hkey, op, partial);
-              MLMCPI_LAUNCH_CHECK("gff_or_heat_kernel");
-              return MLMCPI_OK;
-            });
-          });
-        return with_depth<6>(n, [&](auto kc) -> int {
-          constexpr int K = decltype(kc)::value;
-          hipLaunchKernelGGL((gff_or_block_kernel<K, T>), bgrid, dim3((GffBlockGeom<K, T>::NT)), (GffBlockGeom<K, T>::lds_bytes),
-                             st, Mt, Mx, mu2, (const double *)src, dst, tiles_x);
-          MLMCPI_LAUNCH_CHECK("gff_or_block_kernel");
-          return MLMCPI_OK;
-        });
-      };
-      rc = gff_T == 32 ? gff_blocks(std::integral_constant<int, 32>()) : gff_blocks(std::integral_constant<int, 64>());
-      if (fused) swept = n + 1;
-    } else if (kinds) {  // a heat-bath sweep (a launch of its own: n == 1), with the QoI if it ends the draw
-      rc = heat_launch(s, grid.x, [&](RngKey key, int op, double *partial) -> int {
-        return schw ? launch_sweep<true, true>(g, grid, st, Mt, Mx, act->beta, src, dst, n, kinds, key, op, partial)
-                    : launch_sweep<false, true>(g, grid, st, Mt, Mx, gff_mu2(*act), src, dst, n, kinds, key, op, partial);
-      });
-    } else {  // launches without a heat-bath sweep use the lean instantiation (no sampler code, fewer VGPRs)
-      const RngKey key = make_key(seed, chain0, sweep0 + s);
-      rc = schw ? launch_sweep<true, false>(g, grid, st, Mt, Mx, act->beta, src, dst, n, kinds, key)
-                : launch_sweep<false, false>(g, grid, st, Mt, Mx, gff_mu2(*act), src, dst, n, kinds, key);
+    if (sigma) rc = sigma_sweep_launch(act, l, B, src, dst, make_key(seed, chain0, sweep0 + s), with_qoi, d_qoi, d_acc, st);
+    else {
+      const uint32_t *vs_table = nullptr;
+      void *partial = nullptr;
+      if (l.step && (rc = vs_table_device(2. * act->beta, &vs_table))) return rc;
+      if (with_qoi && (rc = scratch((size_t)B * l.grid_x * sizeof(double), &partial, st))) return rc;
+      const SweepArgs a = {p.Mt, p.Mx, B, p.coupling, src, dst, make_key(seed, chain0, sweep0 + s + (l.n_heatbath ? l.n_overrelax : 0)),
+                           with_qoi ? qoi_op : 0, (double *)partial, vs_table, st};
+      switch (l.kernel) {
+        case MLMCPI_K_SCHWINGER_PERM:
+        case MLMCPI_K_SCHWINGER_PERM_HEAT: rc = launch_perm(l, a); break;
+        case MLMCPI_K_SCHWINGER_OR_BLOCK: rc = launch_blocks<64>(l, a); break;
+        case MLMCPI_K_GFF_OR_BLOCK:
+        case MLMCPI_K_GFF_OR_HEAT: rc = l.tile_w == 32 ? launch_blocks<32>(l, a) : launch_blocks<64>(l, a); break;
+        default: rc = launch_tile_sweep(l, a);
+      }
+      if (!rc && with_qoi)
+        rc = lattice_finish(a.qoi_partial, l.grid_x, B, qoi_op, 1.0 / ((double)p.Mx * p.Mt), d_qoi, d_acc, st);
     }
     if (rc) return rc;
-    advance();
-    s += swept;
+    src = dst;  // the buffer just written becomes the input; the next output is the other work buffer
+    dst = (dst == d_w0) ? d_w1 : d_w0;
+    s += sweeps;
   }
   if (result_in)
     *result_in = total == 0 ? -1 : (src == d_w0 ? 0 : 1);
   else if (src != d_phi)
-    MLMCPI_HIP_TRY(hipMemcpyAsync(d_phi, src, state_bytes, hipMemcpyDeviceToDevice, st));
+    MLMCPI_HIP_TRY(hipMemcpyAsync(d_phi, src, (size_t)B * p.Mt * p.Mx * (act->kind == MLMCPI_GFF ? 8 : 16), hipMemcpyDeviceToDevice, st));
+  return MLMCPI_OK;
+}
+
+// The launches of that draw, in order, without touching a device: same argument checks, same planner.
+int mlmcpi_lattice_sweep_plan(const mlmcpi_lattice_action *act, uint32_t B, uint32_t n_overrelax, uint32_t n_heatbath,
+                              uint32_t fuse, mlmcpi_sweep_launch *out, uint32_t capacity, uint32_t *count) {
+  SweepPlan p;
+  if (int rc = make_sweep_plan(act, B, n_overrelax, n_heatbath, fuse, tuning(), &p)) return rc;
+  MLMCPI_REQUIRE(count && (out || capacity == 0), "bad arguments");
+  uint32_t n = 0;
+  for (uint32_t s = 0; s < n_overrelax + n_heatbath; ++n) {
+    SweepLaunch l;
+    if (int rc = next_launch(p, s, &l)) return rc;
+    if (n < capacity) out[n] = l;
+    s += l.n_overrelax + l.n_heatbath;
+  }
+  *count = n;
+  if (n > capacity) return fail(MLMCPI_ERR_INVALID, "the plan has %u launches, capacity is %u", n, capacity);
   return MLMCPI_OK;
 }
 

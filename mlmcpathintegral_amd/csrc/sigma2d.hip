@@ -233,30 +233,10 @@ __global__ void __launch_bounds__(64) sigma_site_update_kernel(uint32_t Mt, uint
 // ---- host side ----------------------------------------------------------------------------------------------------
 namespace {
 
-constexpr uint32_t kSigmaLdsMax = 160 * 1024 - 512;  // dynamic LDS a workgroup may take (static: the 3 x NT/64 reduction)
-// default plan (profiles/sigma_fuse_tile.json, 1024^2 x 32, 10 + 1 sweeps): 64 x 32 tiles of 256 threads,
-// 2 sweeps per launch -- 8.78 ms per draw against 9.94 ms at fuse = 1 and 10.25 ms on 32 x 32 tiles; the kernel is
-// issue-bound, so deeper fusion buys little (fuse 3: 8.75 ms) and at fuse 4 the 92 KB tile leaves one workgroup per CU
-constexpr uint32_t kSigmaTileW = 64, kSigmaTileH = 32;
-constexpr uint32_t kSigmaFuse = 2;
-
 uint32_t sigma_blocks(uint32_t N, uint32_t B) { return row_blocks((N + 255) / 256, B); }  // workgroups of 256 per chain
 
 std::mutex g_sigma_attr_mutex;
 bool g_sigma_attr_set[64] = {false};
-
-int sigma_init_attrs() {
-  int dev = 0;
-  MLMCPI_HIP_TRY(hipGetDevice(&dev));
-  if (dev < 0 || dev >= 64) return fail(MLMCPI_ERR_INVALID, "device index %d out of range", dev);
-  std::lock_guard<std::mutex> lock(g_sigma_attr_mutex);
-  if (g_sigma_attr_set[dev]) return MLMCPI_OK;
-  MLMCPI_HIP_TRY(hipFuncSetAttribute((const void *)sigma_sweep_kernel<256>, hipFuncAttributeMaxDynamicSharedMemorySize, kSigmaLdsMax));
-  MLMCPI_HIP_TRY(hipFuncSetAttribute((const void *)sigma_sweep_kernel<512>, hipFuncAttributeMaxDynamicSharedMemorySize, kSigmaLdsMax));
-  MLMCPI_HIP_TRY(hipFuncSetAttribute((const void *)sigma_sweep_kernel<1024>, hipFuncAttributeMaxDynamicSharedMemorySize, kSigmaLdsMax));
-  g_sigma_attr_set[dev] = true;
-  return MLMCPI_OK;
-}
 
 template <int OP>
 int sigma_reduce(uint32_t Mt, uint32_t Mx, const double *d_phi, uint32_t B, double scale, double *d_out, hipStream_t st) {
@@ -272,6 +252,19 @@ int sigma_reduce(uint32_t Mt, uint32_t Mx, const double *d_phi, uint32_t B, doub
 }
 
 }  // namespace
+
+int sigma_init_sweep_kernels() {  // once per draw: the sweep kernel may take the whole LDS (of the current device)
+  int dev = 0;
+  MLMCPI_HIP_TRY(hipGetDevice(&dev));
+  if (dev < 0 || dev >= 64) return fail(MLMCPI_ERR_INVALID, "device index %d out of range", dev);
+  std::lock_guard<std::mutex> lock(g_sigma_attr_mutex);
+  if (g_sigma_attr_set[dev]) return MLMCPI_OK;
+  MLMCPI_HIP_TRY(hipFuncSetAttribute((const void *)sigma_sweep_kernel<256>, hipFuncAttributeMaxDynamicSharedMemorySize, kSigmaLdsMax));
+  MLMCPI_HIP_TRY(hipFuncSetAttribute((const void *)sigma_sweep_kernel<512>, hipFuncAttributeMaxDynamicSharedMemorySize, kSigmaLdsMax));
+  MLMCPI_HIP_TRY(hipFuncSetAttribute((const void *)sigma_sweep_kernel<1024>, hipFuncAttributeMaxDynamicSharedMemorySize, kSigmaLdsMax));
+  g_sigma_attr_set[dev] = true;
+  return MLMCPI_OK;
+}
 
 int sigma_evaluate(const mlmcpi_lattice_action *act, const double *d_phi, uint32_t B, double *d_S, hipStream_t st) {
   return sigma_reduce<0>(act->Mt, act->Mx, d_phi, B, -act->beta, d_S, st);
@@ -299,63 +292,27 @@ int sigma_site_updates(const mlmcpi_lattice_action *act, double *d_state, uint32
   return MLMCPI_OK;
 }
 
-// the sweeps of mlmcpi_lattice_sweep_draw* (argument checks done by the caller): launches of up to `fuse` sweeps, read
-// `src`, write `dst`, then src <- dst and dst <- the other work buffer (lattice2d.hip's convention); qoi_kind 4 sums the
-// magnetisation in the last launch and finishes chi_m (and the record_sample moments with d_acc) in one more.
-int sigma_sweep_draw(const mlmcpi_lattice_action *act, double *d_phi, double *d_w0, double *d_w1, uint32_t B, uint32_t n_overrelax,
-                     uint32_t n_heatbath, uint64_t seed, uint32_t chain0, uint32_t sweep0, uint32_t fuse, int32_t *result_in,
-                     hipStream_t st, int qoi_kind, double *d_qoi, double *d_acc) {
-  if (int rc = sigma_init_attrs()) return rc;
+// one launch of a draw of mlmcpi_lattice_sweep_draw* (lattice2d.hip plans the draw and runs the loop): reads `src`, writes
+// `dst`; `key` is that of the launch's first sweep.  with_qoi (the launch ends the draw): it sums the magnetisation, and one
+// more launch finishes chi_m into d_qoi (and the record_sample moments with d_acc).
+int sigma_sweep_launch(const mlmcpi_lattice_action *act, const SweepLaunch &l, uint32_t B, const double *src, double *dst, RngKey key,
+                       bool with_qoi, double *d_qoi, double *d_acc, hipStream_t st) {
   const uint32_t Mt = act->Mt, Mx = act->Mx;
-  const Tuning tune = tuning();
-  const uint32_t TW = tune.tile_w ? tune.tile_w : kSigmaTileW, TH = tune.tile_h ? tune.tile_h : kSigmaTileH;
-  const uint32_t NT = tune.tile_w ? tune.tile_nt : 256;
-  uint32_t kmax = fuse ? fuse : kSigmaFuse;
-  if (kmax > kMaxFuse) kmax = kMaxFuse;
-  auto lds_bytes = [&](uint32_t K) { return (size_t)(TW + 4 * K) * (TH + 4 * K) * 3 * sizeof(double); };
-  while (kmax > 1 && lds_bytes(kmax) > kSigmaLdsMax) --kmax;
-  if (lds_bytes(kmax) > kSigmaLdsMax) return fail(MLMCPI_ERR_INVALID, "sigma sweep tile %u x %u does not fit in LDS", TW, TH);
-  const uint32_t tiles_t = (Mt + TW - 1) / TW, tiles = tiles_t * ((Mx + TH - 1) / TH);
-  const uint32_t total = n_overrelax + n_heatbath;
-  const size_t state_bytes = (size_t)B * 2 * Mt * Mx * sizeof(double);
-  double *part = nullptr;
-  if (qoi_kind) {
-    void *p = nullptr;
-    if (int rc = scratch((size_t)B * tiles * 3 * sizeof(double), &p, st)) return rc;
-    part = (double *)p;
-  }
-  double *src = d_phi, *dst = d_w0;
-  for (uint32_t s = 0; s < total;) {
-    const uint32_t K = total - s < kmax ? total - s : kmax;
-    const uint32_t k_heat = s >= n_overrelax ? 0 : (n_overrelax - s < K ? n_overrelax - s : K);
-    const bool last = s + K == total;
-    const RngKey key = make_key(seed, chain0, sweep0 + s);
-    const dim3 grid(tiles, B);
-    const size_t lds = lds_bytes(K);
-    double *pp = last ? part : nullptr;
-    if (NT == 1024)
-      hipLaunchKernelGGL(sigma_sweep_kernel<1024>, grid, dim3(1024), lds, st, Mt, Mx, act->beta, (const double2 *)src, (double2 *)dst,
-                         TW, TH, tiles_t, K, k_heat, key, pp);
-    else if (NT == 512)
-      hipLaunchKernelGGL(sigma_sweep_kernel<512>, grid, dim3(512), lds, st, Mt, Mx, act->beta, (const double2 *)src, (double2 *)dst,
-                         TW, TH, tiles_t, K, k_heat, key, pp);
-    else
-      hipLaunchKernelGGL(sigma_sweep_kernel<256>, grid, dim3(256), lds, st, Mt, Mx, act->beta, (const double2 *)src, (double2 *)dst,
-                         TW, TH, tiles_t, K, k_heat, key, pp);
-    MLMCPI_LAUNCH_CHECK("sigma_sweep_kernel");
-    src = dst;
-    dst = dst == d_w0 ? d_w1 : d_w0;
-    s += K;
-  }
-  if (qoi_kind) {
-    hipLaunchKernelGGL(sigma_finish_kernel<1>, dim3(B), dim3(256), 0, st, (const double *)part, tiles, 1.0 / ((double)Mt * Mx), d_qoi,
+  void *part = nullptr;
+  if (int rc = with_qoi ? scratch((size_t)B * l.grid_x * 3 * sizeof(double), &part, st) : 0) return rc;
+#define MLMCPI_SIGMA_SWEEP(NT)                                                                                                 \
+  hipLaunchKernelGGL(sigma_sweep_kernel<NT>, dim3(l.grid_x, B), dim3(NT), l.lds_bytes, st, Mt, Mx, act->beta, (const double2 *)src, \
+                     (double2 *)dst, l.tile_w, l.tile_h, l.tiles_x, l.n_overrelax + l.n_heatbath, l.n_overrelax, key, (double *)part)
+  if (l.threads == 1024) MLMCPI_SIGMA_SWEEP(1024);
+  else if (l.threads == 512) MLMCPI_SIGMA_SWEEP(512);
+  else MLMCPI_SIGMA_SWEEP(256);
+#undef MLMCPI_SIGMA_SWEEP
+  MLMCPI_LAUNCH_CHECK("sigma_sweep_kernel");
+  if (with_qoi) {
+    hipLaunchKernelGGL(sigma_finish_kernel<1>, dim3(B), dim3(256), 0, st, (const double *)part, l.grid_x, 1.0 / ((double)Mt * Mx), d_qoi,
                        d_acc);
     MLMCPI_LAUNCH_CHECK("sigma_finish_kernel");
   }
-  if (result_in)
-    *result_in = total == 0 ? -1 : (src == d_w0 ? 0 : 1);
-  else if (src != d_phi)
-    MLMCPI_HIP_TRY(hipMemcpyAsync(d_phi, src, state_bytes, hipMemcpyDeviceToDevice, st));
   return MLMCPI_OK;
 }
 

@@ -325,6 +325,37 @@ def lattice_sweep_draw(act, phi, scratch, n_overrelax, n_heatbath, seed, chain0,
              seed, chain0, sweep0, fuse, _stream())
 
 
+# enum mlmcpi_sweep_kernel -> the instantiation a record names, as a demangler prints it
+_SWEEP_KERNELS = [
+    lambda l: "schwinger_sweep_kernel<%s, %d, %d, %d, %s>" % (_b(l["n_heatbath"]), l["threads"], l["tile_w"] * l["fixed_tile"],
+                                                               l["tile_h"] * l["fixed_tile"], _b(l["step"])),
+    lambda l: "gff_sweep_kernel<%s, %d, %d, %d>" % (_b(l["n_heatbath"]), l["threads"], l["tile_w"] * l["fixed_tile"],
+                                                     l["tile_h"] * l["fixed_tile"]),
+    lambda l: "schwinger_or_block_kernel<%d>" % l["n_overrelax"],
+    lambda l: "gff_or_block_kernel<%d, %d>" % (l["n_overrelax"], l["tile_w"]),
+    lambda l: "gff_or_heat_kernel<%d, %d>" % (l["n_overrelax"], l["tile_w"]),
+    lambda l: "schwinger_perm_kernel<%d>" % l["tile_h"],
+    lambda l: "schwinger_perm_heat_kernel<%d, %s>" % (l["threads"], _b(l["step"])),
+    lambda l: "sigma_sweep_kernel<%d>" % l["threads"],
+]
+
+
+def _b(v):
+    return "true" if v else "false"
+
+
+def lattice_sweep_plan(act, B, n_overrelax, n_heatbath, fuse=0):
+    """The launches of lattice_sweep_draw* for these arguments under the options in force (mlmcpi_lattice_sweep_plan; no
+    device needed): one dict per launch with the fields of mlmcpi_sweep_launch and "instantiation", the kernel it names."""
+    count, capacity = C.c_uint32(0), max(1, n_overrelax + n_heatbath)   # a launch covers at least one sweep
+    recs = (abi.SweepLaunch * capacity)()
+    abi.call("mlmcpi_lattice_sweep_plan", C.byref(act), B, n_overrelax, n_heatbath, fuse, recs, capacity, C.byref(count))
+    plan = [{n: getattr(r, n) for n, _ in abi.SweepLaunch._fields_} for r in recs[:count.value]]
+    for l in plan:
+        l["instantiation"] = _SWEEP_KERNELS[l["kernel"]](l)
+    return plan
+
+
 def lattice_random_sweep_workspace(act, B, device="cuda"):
     """workspace of lattice_random_sweep_draw for B chains (uint8 tensor)"""
     nbytes = C.c_size_t(0)

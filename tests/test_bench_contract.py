@@ -183,7 +183,7 @@ def test_bench_refuses_a_rank_count_it_did_not_run():
 
 
 def test_overrelaxation_launch_plan_mirrors_the_library():
-    """bench.or_plan restates sweep_draw_impl's launch depths (lattice2d.hip): register-block kernels take up to `fuse`
+    """bench.or_plan restates next_launch's launch depths (lattice2d.hip): register-block kernels take up to `fuse`
     sweeps per launch in launches of equal depth, the others launches of `fuse` and a remainder."""
     import bench
     assert bench.or_plan(10, 6, True) == [(5, 2)]
@@ -202,6 +202,22 @@ def test_overrelaxation_launch_plan_mirrors_the_library():
             for blocks in (False, True):
                 plan = bench.or_plan(n, fuse, blocks)
                 assert sum(d * k for d, k in plan) == n and all(1 <= d <= fuse for d, _ in plan)
+
+
+def test_overrelaxation_launch_plan_equals_the_librarys():
+    """the same (n, fuse, blocks) triples against the planner itself (mlmcpi_lattice_sweep_plan; no device needed): GFF 128^2
+    takes the register-block kernels, GFF 32^2 the generic ones, Schwinger 128^2 the closed form (fuse 10)"""
+    import bench
+    from mlmcpathintegral_amd import abi, ops
+    gff = {True: abi.lattice_action(abi.GFF, 128, 128, mass=3.0), False: abi.lattice_action(abi.GFF, 32, 32, mass=3.0)}
+    schw = abi.lattice_action(abi.SCHWINGER, 128, 128, beta=1.0)
+    triples = [(10, 6, True), (12, 6, True), (7, 6, True), (10, 4, True), (10, 4, False), (3, 4, False), (0, 6, True),
+               (10, 10, True), (13, 10, True), (23, 10, True)]
+    triples += [(n, fuse, blocks) for n in range(0, 40) for fuse in (1, 2, 4, 6) for blocks in (False, True)]
+    for n, fuse, blocks in triples:
+        depths = [l["n_overrelax"] for l in ops.lattice_sweep_plan(schw if fuse == 10 else gff[blocks], 2, n, 0, fuse)]
+        grouped = [(d, depths.count(d)) for d in sorted(set(depths), reverse=True)]   # (depths never rise along a draw)
+        assert depths == sorted(depths, reverse=True) and grouped == bench.or_plan(n, fuse, blocks), (n, fuse, blocks, depths)
 
 
 def test_default_line_says_what_the_headline_number_is():
