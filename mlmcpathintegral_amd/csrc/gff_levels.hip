@@ -136,7 +136,9 @@ static bool coarsening(uint32_t Mt, uint32_t Mx, int32_t ctype, int32_t level, b
     case 2: rx = 2; break;                                          // CoarsenSpatial
     case 3: (level % 2 == 0 ? rt : rx) = 2; break;                  // CoarsenAlternate
     case 4:                                                         // CoarsenRotate
-      if (rotated) { rt = rx = 2; ok = !((Mt % 2) || (Mx % 2)); }
+      // either way the coarser lattice needs even extents: it is rotated (lattice2d.cc:13-15) or has half of them
+      ok = !((Mt % 2) || (Mx % 2));
+      if (rotated) rt = rx = 2;
       break;
     default: ok = false;
   }

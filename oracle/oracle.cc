@@ -1805,7 +1805,7 @@ struct GffLevelO {
       case 1: rt = 2; break;
       case 2: rx = 2; break;
       case 3: (level % 2 == 0 ? rt : rx) = 2; break;
-      case 4: if (g.rotated) { rt = rx = 2; ok = !((Mt % 2) || (Mx % 2)); } break;
+      case 4: ok = !((Mt % 2) || (Mx % 2)); if (g.rotated) rt = rx = 2; break;  // lattice2d.cc:13-15: no rotated lattice with odd extents
       default: ok = false;
     }
     unsigned mt = Mt, mx = Mx;

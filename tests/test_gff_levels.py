@@ -26,6 +26,10 @@ class Level:
         n, nc, mtc, mxc, mu2 = C.c_uint32(), C.c_uint32(), C.c_uint32(), C.c_uint32(), C.c_double()
         abi.call("mlmcpi_gff_level_info", self.h, C.byref(n), C.byref(nc), C.byref(mtc), C.byref(mxc), C.byref(mu2))
         self.N, self.n_coarse, self.Mt_c, self.mu2 = n.value, nc.value, mtc.value, mu2.value
+        self.Mt, self.n_gibbs, self.rotated = Mt, n_gibbs, ctype == ROTATE and level % 2 == 1
+
+    def nb(self):
+        return _neighbours(self.Mt, self.rotated)
 
     def tables(self):
         pairs = np.zeros(2 * self.n_coarse, dtype=np.uint32)
@@ -80,11 +84,14 @@ def test_vertex_lists_match_compiled_reference(compiled_ref, orc, Mt, ctype, lev
         assert np.array_equal(pairs, want_p) and np.array_equal(fineonly, want_f)
 
 
-@pytest.mark.parametrize("Mt,level,n_gibbs,omega", [(4, 0, 2, 1.0), (4, 1, 2, 1.0), (8, 1, 2, 1.0), (8, 1, 1, 1.3), (8, 0, 3, 0.8), (8, 1, 0, 1.0)])
+@pytest.mark.parametrize("Mt,level,n_gibbs,omega", [(4, 0, 2, 1.0), (4, 1, 2, 1.0), (8, 1, 2, 1.0), (8, 1, 1, 1.3), (8, 0, 3, 0.8), (8, 1, 0, 1.0),
+                                                    (24, 1, 2, 1.0), (17, 0, 1, 1.0)])
 def test_dense_matrices_match_oracle(orc, Mt, level, n_gibbs, omega):
     """Qhat of gffaction.cc:126-173 and the factor of the exact sampler: the library (Cholesky-based inverses) against the
-    oracle (Gauss-Jordan), independent constructions of the same dense algebra"""
-    a, b = Level(Mt, ROTATE, level, 10.0, n_gibbs, omega), OLevel(orc, Mt, ROTATE, level, 10.0, n_gibbs, omega)
+    oracle (Gauss-Jordan), independent constructions of the same dense algebra.  (24, level 1) is the 288-vertex level the
+    GPU cases beyond one workgroup pass rest on; 17 x 17 has odd extents, which only CoarsenBoth level 0 may have.)"""
+    ctype = BOTH if Mt % 2 else ROTATE
+    a, b = Level(Mt, ctype, level, 10.0, n_gibbs, omega), OLevel(orc, Mt, ctype, level, 10.0, n_gibbs, omega)
     for which in (0, 1):
         A, Bm = a.matrix(which), b.matrix(which)
         assert np.max(np.abs(A - Bm)) < 1e-11 * np.max(np.abs(Bm)), which
@@ -374,3 +381,305 @@ def test_gff_two_level_chain_samples_the_fine_distribution(gpu_ops, orc):
     zcheck("GFF two-level chain 16^2: acceptance vs the reference author's matrices", p_acc,
            math.sqrt(p_acc * (1.0 - p_acc) / (n * B)) * 3.0, want["mean"], want["error"])   # (x 3: successive steps of a chain are correlated)
     assert p_acc > 0.5
+
+
+# ---- beyond one workgroup pass ----------------------------------------------------------------------------------------------
+# Every kernel of gff_levels.hip runs 256 threads over a chain with a stride loop.  The cases above have at most 256
+# vertices per chain, so no loop there takes a second pass, no accumulator a second term, no copy a second block.  The
+# shapes here are the smallest at which each loop does something new:
+#   24 x 24 level 0   576 = 2 * 256 + 64 vertices: three passes, the last one ragged; three blocks in the copy / accept kernels
+#   24 x 24 level 1   288 = 256 + 32 (rotated): two passes, ragged
+#   32 x 32 level 1   512 (rotated), coarse level 256: exact multiples of the block, both levels dense
+#   17 x 17           289, odd, not coarsenable (CoarsenBoth level 0): the odd tail of the normals on the 145th pair
+#   3 x 3             9: the odd tail inside one pass
+# held to the long-double restatement (tests/gff_level_reference.py) and to the oracle.  Dense levels above 1024 vertices
+# (kMaxDense = 4096) stay untested.
+import functools
+
+import gff_level_reference as ref
+
+MASS = 10.0
+BIG = [(24, ROTATE, 0), (24, ROTATE, 1), (32, ROTATE, 1)]
+ODD = [(17, BOTH, 0), (3, BOTH, 0)]
+
+
+@functools.lru_cache(maxsize=None)
+def _pair(Mt, ctype, level, n_gibbs, omega=1.0):
+    """library and oracle handles of one level, made once per session (the dense set-up of 576 vertices takes 0.7 s each)"""
+    import oracle
+    return Level(Mt, ctype, level, MASS, n_gibbs, omega), OLevel(oracle, Mt, ctype, level, MASS, n_gibbs, omega)
+
+
+def _ref_energy(lv):
+    if lv.n_gibbs == 0:
+        nb = lv.nb()
+        return lambda phi: ref.stencil_energy(phi, nb, lv.mu2)
+    Q = lv.matrix(0)
+    return lambda phi: ref.dense_energy(phi, Q)
+
+
+def _ptr(t):
+    return C.c_void_p(t.data_ptr())
+
+
+def test_coarsen_rotate_with_odd_extents_has_no_coarse_level():
+    """An unrotated CoarsenRotate level coarsens to a rotated lattice, which needs even extents (lattice2d.cc:13-15).  A
+    17 x 17 level used to report the 145 vertices with i + j even as coarse vertices -- mapped onto 128 distinct indices of
+    a coarse lattice that cannot exist, next to a coarse buffer of 17 * 17 / 2 = 144 entries.  Now it has no coarse level,
+    and the copies refuse before any launch (host checks only: no device is touched)."""
+    from mlmcpathintegral_amd import abi
+    lv = Level(17, ROTATE, 0, 1.0)
+    assert lv.N == 289 and lv.n_coarse == 0 and lv.Mt_c == 0
+    dummy = np.zeros(289)
+    p = dummy.ctypes.data_as(C.c_void_p)
+    for name in ("mlmcpi_gff_copy_from_fine", "mlmcpi_gff_copy_from_coarse"):
+        with pytest.raises(abi.MlmcpiError, match="the lattice has no coarse level"):
+            abi.call(name, lv.h, p, p, 1, None)
+    with pytest.raises(abi.MlmcpiError, match="the lattice has no coarse level"):
+        abi.call("mlmcpi_gff_cfa_fill", lv.h, p, 1, 1, 0, 0, p, None)
+    nbytes = C.c_size_t()
+    with pytest.raises(abi.MlmcpiError):
+        abi.call("mlmcpi_gff_twolevel_workspace_bytes", lv.h, 1, C.byref(nbytes))
+    # even extents coarsen as before; CoarsenBoth with odd extents never did
+    assert Level(18, ROTATE, 0, 1.0).n_coarse == 162 and Level(17, BOTH, 0, 1.0).n_coarse == 0
+
+
+def _eval_cases():
+    out = [(Mt, ct, lv, ng) for Mt, ct, lv in BIG for ng in (0, 2)]
+    return out + [(Mt, ct, lv, ng) for Mt, ct, lv in ODD for ng in (0, 1)]
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("Mt,ctype,level,n_gibbs", _eval_cases())
+def test_level_evaluate_beyond_one_pass(gpu_ops, Mt, ctype, level, n_gibbs):
+    """mlmcpi_gff_level_evaluate, table kernel (n_gibbs = 0) and dense kernel: four seeded fields that no draw made, and one
+    that is non-zero at a single vertex of the last pass, whose action is 1/2 Q_ll v^2 (a kernel that stops after the first
+    pass returns 0)."""
+    import torch
+    from mlmcpathintegral_amd import abi
+    a, b = _pair(Mt, ctype, level, n_gibbs)
+    n = a.N
+    phi = np.zeros((5, n))
+    phi[:4] = 0.3 * np.random.default_rng(n + n_gibbs).normal(size=(4, n))
+    l, v = n - 7, 1.5
+    assert n <= 256 or l >= 256
+    phi[4, l] = v
+    d = torch.tensor(phi, device="cuda")
+    S = torch.full((5,), -1.0, dtype=torch.float64, device="cuda")
+    abi.call("mlmcpi_gff_level_evaluate", a.h, _ptr(d), 5, _ptr(S), None)
+    got, want = S.cpu().numpy(), _ref_energy(a)(phi)
+    single = 0.5 * (4.0 + a.mu2 if n_gibbs == 0 else a.matrix(0)[l, l]) * v * v
+    assert single > 1.0 and abs(float(want[4]) - single) < 1e-13 * single
+    for c in range(5):
+        print(f"evaluate {Mt} level {level} n_gibbs {n_gibbs} field {c}: S = {got[c]:.15g}, device - reference = {float(got[c] - want[c]):.2e}")
+        assert abs(got[c] - want[c]) < 1e-10 * max(1.0, abs(float(want[c])))
+        wo = b.L.orc_gff_level_evaluate(b.h, phi[c])
+        assert abs(got[c] - wo) < 1e-10 * max(1.0, abs(wo))
+
+
+def _draw_want(a, b, orc, seed, chains, step, n_gibbs, omega):
+    """reference and oracle draws of the given chains: ([len(chains), N] long double, the same from the oracle)"""
+    n, m = a.N, (a.N + 1) // 2
+    psi = np.stack([ref.pair_normals(ref.oracle_random(orc, seed, c, step, ref.P_GFF_EXACT, 0, m), n) for c in chains])
+    gibbs = np.zeros((n_gibbs, len(chains), n), dtype=ref.LD)
+    for k in range(n_gibbs):
+        for i, c in enumerate(chains):
+            gibbs[k, i] = ref.pair_normals(ref.oracle_random(orc, seed, c, step, ref.P_GFF_GIBBS, k, m), n)
+    want = ref.level_draw(psi, a.matrix(1), a.nb(), a.mu2, omega, gibbs)
+    wo = np.zeros((len(chains), n))
+    for i, c in enumerate(chains):
+        b.L.orc_gff_level_dev_draw(b.h, wo[i], seed, c, step)
+    return want, wo
+
+
+def _draw_cases():
+    out = []
+    for Mt, ct, lv in BIG + ODD:
+        ng = 2 if (Mt, ct, lv) in BIG else 1
+        out += [(Mt, ct, lv, 0, 1.0), (Mt, ct, lv, ng, 1.0), (Mt, ct, lv, ng, 1.3)]
+    return out
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("Mt,ctype,level,n_gibbs,omega", _draw_cases())
+def test_level_draw_beyond_one_pass(gpu_ops, orc, Mt, ctype, level, n_gibbs, omega):
+    """mlmcpi_gff_level_draw: white noise over more than 128 pairs (and an odd last one), the triangular product with more
+    than one row per thread, Gibbs sweeps over the whole level; chain0 != 0; every vertex of every chain."""
+    import torch
+    from mlmcpathintegral_amd import abi
+    a, b = _pair(Mt, ctype, level, n_gibbs, omega)
+    B, seed, chain0, step = 5, 31, 3, 7
+    phi = torch.full((B, a.N), 99.0, dtype=torch.float64, device="cuda")
+    abi.call("mlmcpi_gff_level_draw", a.h, _ptr(phi), B, seed, chain0, step, None)
+    got = phi.cpu().numpy()
+    want, wo = _draw_want(a, b, orc, seed, range(chain0, chain0 + B), step, n_gibbs, omega)
+    for c in range(B):
+        scale = max(1.0, float(np.abs(want[c]).max()))
+        print(f"draw {Mt} level {level} n_gibbs {n_gibbs} omega {omega} chain {c}: device - reference = "
+              f"{float(np.max(np.abs(got[c] - want[c]))):.2e}, max|phi| = {scale:.3f}")
+        assert np.max(np.abs(got[c] - want[c])) < 1e-11 * scale
+        assert np.max(np.abs(got[c] - wo[c])) < 1e-11 * scale
+
+
+@pytest.mark.gpu
+def test_level_draw_chain_index_past_a_byte(gpu_ops, orc):
+    """300 chains in one launch (key.chain += b with b > 255), 8 x 8 rotated level with two Gibbs sweeps"""
+    import torch
+    from mlmcpathintegral_amd import abi
+    a, b = _pair(8, ROTATE, 1, 2)
+    B, seed, chain0, step = 300, 31, 3, 2
+    phi = torch.full((B, a.N), 99.0, dtype=torch.float64, device="cuda")
+    abi.call("mlmcpi_gff_level_draw", a.h, _ptr(phi), B, seed, chain0, step, None)
+    got = phi.cpu().numpy()
+    spots = [0, 1, 255, 256, 299]
+    want, wo = _draw_want(a, b, orc, seed, [chain0 + c for c in spots], step, 2, 1.0)
+    for i, c in enumerate(spots):
+        scale = max(1.0, float(np.abs(want[i]).max()))
+        assert np.max(np.abs(got[c] - want[i])) < 1e-11 * scale and np.max(np.abs(got[c] - wo[i])) < 1e-11 * scale
+    assert not np.any(got == 99.0)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("Mt,ctype,level", BIG)
+def test_copies_and_fill_in_beyond_one_block(gpu_ops, orc, Mt, ctype, level):
+    """mlmcpi_gff_copy_from_fine / copy_from_coarse / cfa_fill / cfa_evaluate as calls of their own: copies bit for bit (more
+    than 256 pairs: a second block of gff_pairs_copy_kernel), vertices that a call must not write left as they were"""
+    import torch
+    from mlmcpathintegral_amd import abi
+    ng = 0 if level == 0 else 2
+    a, b = _pair(Mt, ctype, level, ng)
+    nb, (pairs, fineonly) = a.nb(), a.tables()
+    fidx, n, nc, B = pairs[0::2], a.N, a.n_coarse, 3
+    assert len(fineonly) == n - nc and (nc > 256 or (Mt, level) != (24, 0))   # 288 pairs at 24 x 24 level 0: a second block
+    rng = np.random.default_rng(n)
+    fine0, coarse0 = rng.normal(size=(B, n)), rng.normal(size=(B, nc))
+    # fine -> coarse
+    dc = torch.full((B, nc), -7.25, dtype=torch.float64, device="cuda")
+    abi.call("mlmcpi_gff_copy_from_fine", a.h, _ptr(torch.tensor(fine0, device="cuda")), _ptr(dc), B, None)
+    got = dc.cpu().numpy()
+    assert np.array_equal(got, ref.copy_from_fine(fine0, pairs, nc))
+    for c in range(B):
+        want = np.zeros(nc)
+        b.L.orc_gff_copy(b.h, fine0[c].copy(), want, 1)
+        assert np.array_equal(got[c], want)
+    # coarse -> fine: the fine-only vertices keep their sentinel
+    df = torch.full((B, n), -7.25, dtype=torch.float64, device="cuda")
+    abi.call("mlmcpi_gff_copy_from_coarse", a.h, _ptr(torch.tensor(coarse0, device="cuda")), _ptr(df), B, None)
+    got = df.cpu().numpy()
+    assert np.array_equal(got, ref.copy_from_coarse(coarse0, pairs, np.full((B, n), -7.25)))
+    assert np.all(got[:, fineonly] == -7.25) and not np.any(got[:, fidx] == -7.25)
+    # fill-in: coarse vertices untouched, fine-only ones and S_cfa against the reference and the oracle
+    seed, chain0, step = 77, 2, 9
+    state0 = 0.3 * rng.normal(size=(B, n))
+    ds = torch.tensor(state0, device="cuda")
+    S = torch.full((B,), -1.0, dtype=torch.float64, device="cuda")
+    abi.call("mlmcpi_gff_cfa_fill", a.h, _ptr(ds), B, seed, chain0, step, _ptr(S), None)
+    got, gotS = ds.cpu().numpy(), S.cpu().numpy()
+    assert np.array_equal(got[:, fidx], state0[:, fidx])
+    normals = np.stack([ref.oracle_random(orc, seed, chain0 + c, step, ref.P_FILLIN, 0, n)[:, 2] for c in range(B)])
+    want, wantS = ref.cfa_fill(state0, nb, fineonly, a.mu2, normals)
+    for c in range(B):
+        assert np.max(np.abs(got[c] - want[c])) < 1e-11 * max(1.0, float(np.abs(want[c]).max()))
+        assert abs(gotS[c] - wantS[c]) < 1e-10 * max(1.0, float(wantS[c]))
+        wo = state0[c].copy()
+        So = b.L.orc_gff_cfa_dev_fill(b.h, wo, seed, chain0 + c, step)
+        assert np.max(np.abs(got[c] - wo)) < 1e-11 * max(1.0, np.abs(wo).max()) and abs(gotS[c] - So) < 1e-10 * max(1.0, So)
+    # conditioned fine action of a state that no fill-in made
+    abi.call("mlmcpi_gff_cfa_evaluate", a.h, _ptr(torch.tensor(state0, device="cuda")), B, _ptr(S), None)
+    gotS, wantS = S.cpu().numpy(), ref.cfa_action(state0, nb, fineonly, a.mu2)
+    for c in range(B):
+        assert abs(gotS[c] - wantS[c]) < 1e-10 * max(1.0, float(wantS[c]))
+        assert abs(gotS[c] - b.L.orc_gff_cfa_evaluate(b.h, state0[c])) < 1e-10 * max(1.0, float(wantS[c]))
+
+
+@functools.lru_cache(maxsize=None)
+def _twolevel_case(Mt, level):
+    """Inputs of the two-level cases and what the oracle makes of them.  Current fine states: chains 0-3 are samples of the
+    fine level's plain stencil (numpy normals through the library's host matrix), chains 4-7 seeded normals of amplitude 3
+    (far from a sample).  Coarse proposals: for the even chains the coarse vertices of the current state plus noise of 1e-3
+    (the step then only replaces the fill-in), for the odd ones rough, unit-variance noise -- the construction of
+    test_twolevel_step_matches_oracle for the paths.  The Gaussian fill-in is exact and the smoothed coarse action close to
+    the marginal, so a step from a sample is accepted nearly always; the steps from the far states supply the rejections."""
+    B, seed, chain0, step = 8, 78, 2, 9   # (seed 77 accepts all eight chains of 24 x 24 level 0)
+    fine, ofine = _pair(Mt, ROTATE, level, 0 if level == 0 else 2)
+    coarse, ocoarse = _pair(fine.Mt_c, ROTATE, level + 1, 2)
+    pairs, _ = fine.tables()
+    rng = np.random.default_rng(100 * Mt + level)
+    theta0 = rng.normal(size=(B, fine.N))
+    theta0[:4] = theta0[:4] @ np.tril(fine.matrix(1))
+    theta0[4:] *= 3.0
+    phic0 = ref.copy_from_fine(theta0, pairs, coarse.N)
+    phic0[0::2] += 1e-3 * rng.normal(size=phic0[0::2].shape)
+    phic0[1::2] = rng.normal(size=phic0[1::2].shape)
+    want, terms, acc = theta0.copy(), np.zeros((B, 3)), np.zeros(B, dtype=np.int32)
+    for c in range(B):
+        acc[c] = ofine.L.orc_gff_dev_twolevel_draw(ofine.h, ocoarse.h, np.ascontiguousarray(phic0[c]), want[c], seed, chain0 + c, step, terms[c])
+    return dict(B=B, seed=seed, chain0=chain0, step=step, fine=fine, coarse=coarse, theta0=theta0, phic0=phic0, want=want, terms=terms,
+                acc=acc)
+
+
+TWOLEVEL = [(24, 0), (24, 1), (32, 1)]
+
+
+@pytest.mark.parametrize("Mt,level", TWOLEVEL)
+def test_twolevel_inputs_give_both_outcomes_and_the_reference_agrees(orc, Mt, level):
+    """CPU: the oracle accepts some chains of each case and rejects others (a condition of the GPU test, not a measurement),
+    and the long-double restatement gives the same action differences, decisions and states."""
+    k = _twolevel_case(Mt, level)
+    assert set(k["acc"].tolist()) == {0, 1}, k["acc"]
+    fine, B = k["fine"], k["B"]
+    pairs, fineonly = fine.tables()
+    normals = np.stack([ref.oracle_random(orc, k["seed"], k["chain0"] + c, k["step"], ref.P_FILLIN, 0, fine.N)[:, 2] for c in range(B)])
+    prime, terms = ref.twolevel_step(k["theta0"], k["phic0"], fine.nb(), pairs, fineonly, fine.mu2, normals, _ref_energy(fine),
+                                     _ref_energy(k["coarse"]))
+    u = np.array([ref.oracle_random(orc, k["seed"], k["chain0"] + c, k["step"], ref.P_ACCEPT2, 0, 1)[0, 0] for c in range(B)])
+    assert np.array_equal(ref.accepts(terms, u), k["acc"] == 1)
+    for c in range(B):
+        assert np.max(np.abs(terms[c] - k["terms"][c])) < 1e-10 * max(1.0, np.abs(k["terms"][c]).max())
+        assert np.max(np.abs((prime[c] if k["acc"][c] else k["theta0"][c]) - k["want"][c])) < 1e-12
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("Mt,level", TWOLEVEL)
+def test_twolevel_step_beyond_one_block(gpu_ops, orc, Mt, level):
+    """mlmcpi_gff_twolevel_draw with more than 256 fine vertices: gff_twolevel_accept_kernel runs two or three blocks per
+    chain, of which only the first writes the flag while all of them copy.  Accepted chains hold the whole trial state
+    (bit for bit the one in the workspace, vertices >= 256 included), rejected ones their input, bit for bit."""
+    import torch
+    from mlmcpathintegral_amd import abi
+    k = _twolevel_case(Mt, level)
+    fine, coarse, B, acc_o = k["fine"], k["coarse"], k["B"], k["acc"]
+    assert set(acc_o.tolist()) == {0, 1} and fine.N > 256
+    nbytes = C.c_size_t()
+    abi.call("mlmcpi_gff_twolevel_workspace_bytes", fine.h, B, C.byref(nbytes))
+    phic = torch.tensor(k["phic0"], device="cuda")
+
+    def run(with_outputs):
+        theta = torch.tensor(k["theta0"], device="cuda")
+        work = torch.zeros(nbytes.value, dtype=torch.uint8, device="cuda")
+        acc = torch.full((B,), -5, dtype=torch.int32, device="cuda")
+        terms = torch.zeros((B, 3), dtype=torch.float64, device="cuda")
+        abi.call("mlmcpi_gff_twolevel_draw", fine.h, coarse.h, _ptr(phic), _ptr(theta), B, k["seed"], k["chain0"], k["step"], _ptr(work),
+                 _ptr(acc) if with_outputs else None, _ptr(terms) if with_outputs else None, None)
+        prime = work[:B * fine.N * 8].view(torch.float64).reshape(B, fine.N)   # workspace: theta' [B N_f] first
+        return theta.cpu().numpy(), prime.cpu().numpy(), acc.cpu().numpy(), terms.cpu().numpy()
+
+    got, prime, acc, terms = run(True)
+    pairs, fineonly = fine.tables()
+    normals = np.stack([ref.oracle_random(orc, k["seed"], k["chain0"] + c, k["step"], ref.P_FILLIN, 0, fine.N)[:, 2] for c in range(B)])
+    rprime, rterms = ref.twolevel_step(k["theta0"], k["phic0"], fine.nb(), pairs, fineonly, fine.mu2, normals, _ref_energy(fine),
+                                       _ref_energy(coarse))
+    for c in range(B):
+        scale = max(1.0, float(np.abs(k["terms"][c]).max()))
+        print(f"two-level {Mt} level {level} chain {c}: terms {terms[c]}, device - reference {np.max(np.abs(terms[c] - rterms[c])):.2e}, accept {acc[c]}")
+        assert np.max(np.abs(terms[c] - rterms[c])) < 1e-10 * scale and np.max(np.abs(terms[c] - k["terms"][c])) < 1e-10 * scale
+        assert acc[c] == acc_o[c]
+        assert np.max(np.abs(prime[c] - rprime[c])) < 1e-11 * max(1.0, float(np.abs(rprime[c]).max()))
+        if acc_o[c]:
+            assert np.array_equal(got[c], prime[c]) and np.array_equal(got[c, 256:], prime[c, 256:])
+            assert np.max(np.abs(got[c] - k["want"][c])) < 1e-11 * max(1.0, np.abs(k["want"][c]).max())
+        else:
+            assert np.array_equal(got[c], k["theta0"][c])
+    # d_accept = NULL and d_terms = NULL: the same step, nothing reported
+    got2, _, acc2, terms2 = run(False)
+    assert np.array_equal(got2, got) and np.all(acc2 == -5) and np.all(terms2 == 0.0)

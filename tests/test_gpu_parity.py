@@ -1207,6 +1207,92 @@ def test_gff_exact_sampler_matches_oracle(gpu_ops, orc, Mt, mass, B):
         gpu_ops.GFFExactSampler(abi.lattice_action(4, 8, 8, beta=1.0), 1)
 
 
+# ---- the exact GFF sampler beyond powers of two, one stride and one chunk (reference: tests/gff_level_reference.py) ----------
+def _exact_rows(gpu_ops, chain, step, sub, n):
+    """rows (u, v, n0, n1) of the modes 0 .. n - 1 from the device's generator (pinned to the oracle's by
+    test_random_streams_match_oracle), P_EXACT"""
+    import gff_level_reference as ref
+    return gpu_ops.test_random(SEED, chain, step, ref.P_EXACT, sub, n).cpu().numpy()
+
+
+@pytest.mark.parametrize("Mt", [12, 20, 34, 17])
+def test_gff_exact_sampler_mixed_radix_lengths(gpu_ops, orc, Mt):
+    """hipFFT lengths that are no power of two: 12 = 4 x 3, 20 = 4 x 5, 34 = 2 x 17, and the odd prime 17 (check_lattice
+    admits odd GFF extents); against the oracle's direct sum and against ifft2 of the oracle's normals"""
+    import gff_level_reference as ref
+    mass, B = 3.0, 3
+    act, A = make_lattice(orc, "gff", Mt, Mt, mass=mass)
+    s = gpu_ops.GFFExactSampler(act, B, seed=SEED, chain0=2)
+    n, mu2 = Mt * Mt, ref.mu2_of(Mt, False, mass)
+    for step in range(2):
+        phi = s.draw().cpu().numpy()
+        for b in range(B):
+            want = np.zeros(n)
+            orc.lib().orc_dev_gff_exact_draw(A.h, want, SEED, 2 + b, step)
+            scale = float(np.max(np.abs(want)))
+            assert_close(phi[b], want, tol=1e-12, scale=scale, what=f"GFF exact draw {Mt}, step {step} chain {b}, oracle")
+            fft = ref.spectral_fft(ref.oracle_random(orc, SEED, 2 + b, step, ref.P_EXACT, 0, n), Mt, Mt, mu2)
+            assert_close(phi[b], fft, tol=1e-12, scale=scale, what=f"GFF exact draw {Mt}, step {step} chain {b}, ifft2")
+
+
+def test_gff_exact_sampler_grid_stride_loops(gpu_ops):
+    """576 x 576 = 331 776 sites > 262 144: gff_spectrum_kernel and gff_real_part_kernel run 1024 blocks whose threads take a
+    second stride; the last 69 632 sites are written by that second iteration only.  Every site against ifft2 (double) of
+    the same noise, whose own distance from the long-double sum is 2e-16 max|phi|
+    (tests/test_gff_level_reference.py); 64 sites against that sum itself."""
+    import gff_level_reference as ref
+    Mt, mass, B = 576, 10.0, 2
+    n, mu2 = Mt * Mt, ref.mu2_of(Mt, False, mass)
+    act = gpu_ops.abi.lattice_action(gpu_ops.abi.GFF, Mt, Mt, mass=mass)
+    phi = gpu_ops.GFFExactSampler(act, B, seed=SEED, chain0=2).draw().cpu().numpy()
+    sites = np.concatenate([[0, n - 1, 262143, 262144], np.random.default_rng(2).integers(0, n, 60)])
+    for b in range(B):
+        rows = _exact_rows(gpu_ops, 2 + b, 0, 0, n)
+        want = ref.spectral_fft(rows, Mt, Mt, mu2)
+        scale = float(np.max(np.abs(want)))
+        print(f"GFF exact 576 chain {b}: device - ifft2 = {np.max(np.abs(phi[b] - want)) / scale:.2e} max|phi|")
+        assert_close(phi[b], want, tol=1e-12, scale=scale, what=f"GFF exact draw 576 chain {b}")
+        assert_close(phi[b, 262144:], want[262144:], tol=1e-12, scale=scale, what=f"GFF exact draw 576 chain {b}, second stride")
+        assert np.count_nonzero(phi[b, 262144:]) == 69632
+        direct = ref.spectral_direct(rows, Mt, Mt, mu2, sites=sites).astype(np.float64)
+        assert_close(phi[b, sites], direct, tol=1e-12, scale=scale, what=f"GFF exact draw 576 chain {b}, direct sum")
+    assert not np.array_equal(phi[0], phi[1])
+
+
+def test_gff_exact_sampler_replans(gpu_ops, orc):
+    """the cached hipFFT plan is remade when (Mt, Mx, B) changes and made again when the first shape returns"""
+    def draw(Mt, B):
+        act, A = make_lattice(orc, "gff", Mt, Mt, mass=2.0)
+        phi = gpu_ops.GFFExactSampler(act, B, seed=SEED, chain0=2).draw().cpu().numpy()
+        for b in range(B):
+            want = np.zeros(Mt * Mt)
+            orc.lib().orc_dev_gff_exact_draw(A.h, want, SEED, 2 + b, 0)
+            assert_close(phi[b], want, tol=1e-12, scale=float(np.max(np.abs(want))), what=f"GFF exact draw {Mt} x {B} chain {b}")
+        return phi
+    first, _, third, fourth = draw(16, 2), draw(20, 3), draw(16, 2), draw(16, 5)
+    assert np.array_equal(third, first)
+    assert_close(fourth[:2], first, tol=1e-12, scale=float(np.max(np.abs(first))), what="first chains of a larger batch")
+
+
+def test_gff_initialise_runs_a_second_chunk(gpu_ops):
+    """GFFAction::initialise_state at 1024 x 1024 with 17 chains: 16 MiB of scratch per chain, so the 256 MiB scratch takes
+    16 chains and the 17th is a chunk of its own (chain0 + b0).  Chains 0, 15 and 16 against ifft2 (double) of the sub = 1
+    noise of chains chain0 + b (its own distance from the long-double sum: 2e-16 max|phi|,
+    tests/test_gff_level_reference.py)."""
+    import gff_level_reference as ref
+    Mt, mass, B, chain0 = 1024, 10.0, 17, 5
+    n, mu2 = Mt * Mt, ref.mu2_of(Mt, False, mass)
+    act = gpu_ops.abi.lattice_action(gpu_ops.abi.GFF, Mt, Mt, mass=mass)
+    phi = gpu_ops.lattice_initialise(act, B, SEED, chain0=chain0)
+    got = {b: phi[b].cpu().numpy() for b in (0, 15, 16)}
+    for b, g in got.items():
+        want = ref.spectral_fft(_exact_rows(gpu_ops, chain0 + b, 0, 1, n), Mt, Mt, mu2)
+        scale = float(np.max(np.abs(want)))
+        print(f"GFF initialise 1024 chain {b}: device - ifft2 = {np.max(np.abs(g - want)) / scale:.2e} max|phi|")
+        assert_close(g, want, tol=1e-12, scale=scale, what=f"GFF initialise 1024 chain {b}")
+    assert np.max(np.abs(got[16] - got[0])) > 0.1 * np.max(np.abs(got[0]))
+
+
 # ---- the device's angle samplers against the analytic law, with no oracle in between ---------------------------------
 # (VERDICT r03 weak #1: oracle.cc::dev_vonmises_table was written in lockstep with device_common.hpp, so device == oracle is
 # close to a self-comparison there.  Here 2 10^5 DEVICE draws per case go straight against the quadrature CDF of
