@@ -13,6 +13,8 @@
 //          (O(3) sigma model: singlelevel and throughput with the heat-bath sampler only)
 //   driver --action nonlinearsigma --Mt_lat 16 --beta 1.5 --sampler wolff --n_updates 10 --n_samples 20000
 //          (Wolff single-cluster updates over the four links per vertex; prints chi_m and the mean cluster size)
+//   driver --action nonlinearsigma --Mt_lat 16 --beta 1.5 --sampler swendsenwang --n_updates 1 --n_samples 20000
+//          (Swendsen-Wang multi-cluster updates; prints chi_m, its cluster-improved estimator and the clusters per update)
 //   driver --action rotor --M_lat 256 --T_final 25.6 --m0 0.25 --sampler cluster --n_updates 10 --n_samples 20000
 //          (cluster samplers: rotor and schwinger; also --coarsesampler cluster for twolevel / hierarchical rotor runs)
 //   driver --method throughput --action schwinger --Mt_lat 1024 --sampler heatbath --batch 32 --n_samples 20
@@ -90,6 +92,16 @@ int main(int argc, char **argv) {
   if (o["coarsesampler"] == "wolff")
     fatal(" --coarsesampler wolff is not supported: the wolff sampler is a single-level sampler of the nonlinear sigma model, "
           "and no hierarchical or two-level run exists for that action (DESIGN.md 8)");
+  // --sampler swendsenwang: the multi-cluster sampler of the sigma model (sampler.hh SwendsenWangSampler)
+  if (o["sampler"] == "swendsenwang" && a != "nonlinearsigma")
+    fatal(" swendsenwang sampler not supported for chosen action: it is built for nonlinearsigma only (the rotor and schwinger have "
+          "--sampler cluster; the other actions have no reflection the bond form is symmetric under)");
+  if (o["sampler"] == "swendsenwang" && o["method"] != "singlelevel")
+    fatal("nonlinearsigma: --sampler swendsenwang runs --method singlelevel only, not " + o["method"] + " (two-level and multilevel "
+          "are not built for this action, DESIGN.md 8; the throughput loop is the heat-bath sampler's)");
+  if (o["coarsesampler"] == "swendsenwang")
+    fatal(" --coarsesampler swendsenwang is not supported: the swendsenwang sampler is a single-level sampler of the nonlinear sigma "
+          "model, and no hierarchical or two-level run exists for that action (DESIGN.md 8)");
   if (a == "harmonicoscillator" || a == "quarticoscillator" || a == "rotor") {
     auto lat = std::make_shared<Lattice1D>((unsigned)num("M_lat"), num("T_final"));
     if (a == "harmonicoscillator") {
@@ -115,8 +127,8 @@ int main(int argc, char **argv) {
     }
   } else if (a == "nonlinearsigma") {  // driver_qft.cc:159-166, 241-246
     auto lat = std::make_shared<Lattice2D>((unsigned)num("Mt_lat"), (unsigned)num("Mt_lat"), coarsenings.at(o["coarsening"]));
-    if (o["sampler"] != "heatbath" && o["sampler"] != "wolff")
-      fatal("nonlinearsigma: only --sampler heatbath and --sampler wolff are supported (HMC: the reference's force omits the sin theta of the measure "
+    if (o["sampler"] != "heatbath" && o["sampler"] != "wolff" && o["sampler"] != "swendsenwang")
+      fatal("nonlinearsigma: only --sampler heatbath, --sampler wolff and --sampler swendsenwang are supported (HMC: the reference's force omits the sin theta of the measure "
             "in (theta, phi) coordinates and would sample the wrong law; DESIGN.md 8)");
     if (o["method"] != "singlelevel" && o["method"] != "throughput")
       fatal("nonlinearsigma: --method " + o["method"] + " is not supported, only singlelevel and throughput (the reference's "
@@ -158,6 +170,11 @@ int main(int argc, char **argv) {
       ClusterParameters cp;
       cp.n_burnin = (unsigned)num("n_burnin"); cp.n_updates = (unsigned)num("n_updates"); cp.batch = batch;
       return std::make_shared<WolffClusterSamplerFactory>(cp);
+    }
+    if (name == "swendsenwang") {
+      ClusterParameters cp;
+      cp.n_burnin = (unsigned)num("n_burnin"); cp.n_updates = (unsigned)num("n_updates"); cp.batch = batch;
+      return std::make_shared<SwendsenWangSamplerFactory>(cp);
     }
     if (name != "heatbath") fatal("unknown sampler " + name);
     OverrelaxedHeatBathParameters hb;

@@ -613,5 +613,101 @@ private:
   const ClusterParameters param;
 };
 
+/** The Swendsen-Wang multi-cluster sampler of the O(3) nonlinear sigma model (mlmcpi_sigma_sw_draw): the
+ *  multi-cluster form of WolffClusterSampler's embedding, the project's own sampler like that one.  One draw = n_updates
+ *  updates of every chain, then the copy out; it runs its own update counter, which advances by n_updates per draw; set_state
+ *  is a no-op.  Every draw also returns the clusters and the improved estimator of chi_m (3 sum_C A_C^2 / N of the field
+ *  before each update): the sampler keeps, since the last reset_improved(), the mean over draws of the per-draw value (the
+ *  mean over the draw's updates and over the chains) and its standard error over the draws. */
+class SwendsenWangSampler : public Sampler {
+public:
+  SwendsenWangSampler(const std::shared_ptr<Action> action_, const ClusterParameters p)
+      : Sampler(), action(std::dynamic_pointer_cast<NonlinearSigmaAction>(action_)), n_updates(p.n_updates), B(p.batch),
+        clusters(p.batch, sizeof(uint32_t)), improved(p.batch) {
+    if (!action) fatal(" swendsenwang sampler not supported for chosen action: it is built for the nonlinear sigma model only.");
+    if (n_updates == 0) fatal("SwendsenWangSampler: n_updates must be positive.");
+    // the device adds the clusters of one call to a uint32 per chain: n_updates updates of at most N clusters each
+    if ((uint64_t)n_updates * (action->sample_size() / 2) > 0xFFFFFFFFull)
+      fatal("SwendsenWangSampler: n_updates x vertices must stay below 2^32 (the per-chain counter of one draw).");
+    size_t bytes = 0;
+    check(mlmcpi_sigma_sw_workspace_bytes(&action->abi_action(), B, &bytes), "sigma_sw_workspace_bytes");
+    work = std::make_shared<DeviceBuffer>(bytes);
+    phi_state_cur = std::make_shared<SampleState>(action->sample_size(), B);
+    action->initialise_state(phi_state_cur);
+    std::shared_ptr<SampleState> tmp = std::make_shared<SampleState>(action->sample_size(), B);
+    for (unsigned int i = 0; i < p.n_burnin; ++i) draw(tmp);
+    check(mlmcpi_stream_synchronize(nullptr), "sync");
+    const auto t0 = std::chrono::steady_clock::now();
+    for (unsigned int k = 0; k < p.n_meas; ++k) draw(tmp);
+    check(mlmcpi_stream_synchronize(nullptr), "sync");
+    cost_per_sample_ = 1.E6 * std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count() / (p.n_meas ? p.n_meas : 1);
+    reset_stats();
+    reset_improved();
+  }
+  void draw(std::shared_ptr<SampleState> phi_state) override {
+    if (update_counter > 0xFFFFFFFFu - n_updates) fatal("SwendsenWangSampler: the 32-bit update counter of the Philox contract is used up.");
+    check(mlmcpi_memset(clusters.ptr(), 0, B * sizeof(uint32_t), nullptr), "mlmcpi_memset");
+    check(mlmcpi_memset(improved.ptr(), 0, B * sizeof(double), nullptr), "mlmcpi_memset");
+    check(mlmcpi_sigma_sw_draw(&action->abi_action(), phi_state_cur->device_mutable(), B, n_updates, action->get_seed(),
+                               action->get_chain0(), update_counter, nullptr, (uint32_t *)clusters.ptr(), (double *)improved.ptr(),
+                               work->p, nullptr),
+          "sigma_sw_draw");
+    update_counter += n_updates;
+    double c = 0.0, v = 0.0;
+    for (uint32_t x : clusters.download<uint32_t>()) c += x;
+    for (double x : improved.download<double>()) v += x;
+    v /= (double)B * n_updates;                          // this draw's value: the mean over its updates and the chains
+    clusters_total += c / B;
+    improved_sum += v;
+    improved_sum2 += v * v;
+    ++draws_counted;
+    n_total_samples += n_updates;
+    n_accepted_samples += n_updates;
+    phi_state->data = phi_state_cur->data;
+    accept = true;
+  }
+  void set_state(std::shared_ptr<SampleState>) override {}
+  double cost_per_sample() override { return cost_per_sample_; }
+  /** forget the clusters and improved values recorded so far (the constructor does, after burn-in and timing draws) */
+  void reset_improved() { clusters_total = improved_sum = improved_sum2 = 0.0; draws_counted = 0; }
+  /** clusters per update, averaged over the chains and the updates since the last reset */
+  double mean_clusters_per_update() const { return draws_counted ? clusters_total / ((double)draws_counted * n_updates) : 0.0; }
+  /** improved estimator of chi_m, averaged over the chains and the updates since the last reset */
+  double improved_mean() const { return draws_counted ? improved_sum / draws_counted : 0.0; }
+  /** its standard error over the draws, each draw contributing the mean of its updates */
+  double improved_error() const {
+    if (draws_counted < 2) return 0.0;
+    const double n = (double)draws_counted, m = improved_sum / n, var = std::max(0.0, (improved_sum2 - n * m * m) / (n - 1.0));
+    return std::sqrt(var / n);
+  }
+  void show_stats() override {
+    std::cout << std::setprecision(3) << std::fixed << "  cluster updates per draw = " << n_updates << std::endl
+              << std::setprecision(6) << "  improved chi_m = " << improved_mean() << " +/- " << improved_error() << std::endl
+              << std::setprecision(3) << "  mean clusters per update = " << mean_clusters_per_update() << std::endl;
+  }
+
+private:
+  const std::shared_ptr<NonlinearSigmaAction> action;
+  const unsigned int n_updates, B;
+  std::shared_ptr<SampleState> phi_state_cur;
+  std::shared_ptr<DeviceBuffer> work;
+  DeviceVector clusters;  // uint32 per chain: the clusters of the draw at hand
+  DeviceVector improved;  // double per chain: the improved values of the draw at hand, summed over its updates
+  double clusters_total = 0.0, improved_sum = 0.0, improved_sum2 = 0.0;
+  uint64_t draws_counted = 0;
+  uint32_t update_counter = 0;
+  double cost_per_sample_ = 0.0;
+};
+
+class SwendsenWangSamplerFactory : public SamplerFactory {
+public:
+  explicit SwendsenWangSamplerFactory(const ClusterParameters p) : param(p) {}
+  std::shared_ptr<Sampler> get(std::shared_ptr<Action> action) override {
+    return std::make_shared<SwendsenWangSampler>(action, param);  // fatal unless the action is the nonlinear sigma model
+  }
+private:
+  const ClusterParameters param;
+};
+
 }  // namespace mlmcpi
 #endif

@@ -291,6 +291,36 @@ int mlmcpi_schwinger_cluster_links(const mlmcpi_lattice_action *act, const doubl
 int mlmcpi_sigma_cluster_workspace_bytes(const mlmcpi_lattice_action *act, uint32_t B, size_t *bytes);
 int mlmcpi_sigma_cluster_draw(const mlmcpi_lattice_action *act, double *d_phi, uint32_t B, uint32_t n_updates, uint64_t seed,
                               uint32_t chain0, uint32_t update0, uint32_t *d_cluster_sites, void *d_work, void *stream);
+/* Swendsen-Wang multi-cluster update of the O(3) nonlinear sigma model (sigma_sw.hip): n_updates updates of
+ * every chain of d_phi [B][2 Mt Mx], in place.  The multi-cluster form of the embedding of mlmcpi_sigma_cluster_draw, the
+ * project's own sampler (the reference has none): one update tests all 2 N links once, labels every connected component of
+ * the bonded links and reflects each component with probability 1/2.  Vertex l = Mt j + i; link (l, 0) joins l to its +i
+ * neighbour, link (l, 1) to its +j neighbour (periodic; on an extent of 2 the two links between a pair of vertices are two
+ * links with a uniform each).  Update k of this call has the counter update0 + k.  Philox purposes: 21, site 0, sub 0: (u, v)
+ * -> the reflection normal r, r_z = 1 - 2 u, azimuth 2 pi v - pi; 22, site l, sub 0: u decides link (l, 0), v link (l, 1):
+ * with a_l = r . sigma_l of the field BEFORE the update a link (x, y) is bonded iff a_x a_y > 0 and its uniform < 1 - exp(min(0,
+ * -2 beta (a_x a_y))) (the product first); 23, site = the root of a cluster = its smallest vertex index, sub 0: the cluster
+ * is reflected iff u < 0.5 (a vertex without a bond is a cluster of one and takes its own coin).  Every vertex of a reflected
+ * cluster becomes sigma' = sigma - 2 a r, stored in the canonical form theta = atan2(sqrt(sx^2 + sy^2), sz), phi = atan2(sy,
+ * sx).  Every decision is a function of (link or root, global chain index, counter, field before the update): the state is
+ * bit-identical under every launch plan, tile size, batch split and chain0, and ten updates in one call equal 5 + 5.
+ * Outputs, each an optional [B] array that is ADDED to, per chain:
+ *   d_flipped   uint32: the vertices this call's updates reflected (32 bits: it wraps)
+ *   d_clusters  uint32: the clusters of this call's updates (roots; 32 bits: it wraps)
+ *   d_improved  double: per update 3 sum_C A_C^2 / N, A_C = sum of a_l over cluster C, an unbiased estimator of chi_m =
+ *               <|M|^2> / N evaluated on the field before the update; A_C is summed in 64-bit fixed point (llrint(a 2^32),
+ *               integer atomics) and the squares over the roots in one reduction of fixed configuration, so the value does not
+ *               depend on the launch plan; it is added update by update, so 10 updates equal 5 + 5 to the bit
+ *   d_work      _workspace_bytes (21 B per vertex and chain + 256 B); its content at entry is ignored
+ * The call returns after its launches have finished: it reads back the status word the labelling loops set if one of them
+ * ran into its iteration cap (MLMCPI_ERR_HIP; it cannot by construction, and it is an error, not a hang).
+ * MLMCPI_NONLINEAR_SIGMA only: MLMCPI_ERR_UNSUPPORTED otherwise, and when MLMCPI_SIGMA_SW_PLAN=chain is forced on a lattice
+ * beyond that plan's LDS bound.  MLMCPI_ERR_INVALID: Mt or Mx < 2, Mt Mx > 2^30, no workspace, update0 + n_updates beyond 32
+ * bits. */
+int mlmcpi_sigma_sw_workspace_bytes(const mlmcpi_lattice_action *act, uint32_t B, size_t *bytes);
+int mlmcpi_sigma_sw_draw(const mlmcpi_lattice_action *act, double *d_phi, uint32_t B, uint32_t n_updates, uint64_t seed,
+                         uint32_t chain0, uint32_t update0, uint32_t *d_flipped, uint32_t *d_clusters, double *d_improved,
+                         void *d_work, void *stream);
 int mlmcpi_lattice_state_size(const mlmcpi_lattice_action *act, uint32_t *n); /* Action::sample_size */
 int mlmcpi_lattice_evaluate(const mlmcpi_lattice_action *act, const double *d_phi, uint32_t B, double *d_S,
                             void *stream);

@@ -142,6 +142,8 @@ SIGNATURES = {
     "mlmcpi_lattice_random_sweep_order": (_i, [_LA, _u32, _u64, _u32, _u32, _vp, _vp, _vp]),
     "mlmcpi_sigma_cluster_workspace_bytes": (_i, [_LA, _u32, C.POINTER(_sz)]),
     "mlmcpi_sigma_cluster_draw": (_i, [_LA, _vp, _u32, _u32, _u64, _u32, _u32, _vp, _vp, _vp]),
+    "mlmcpi_sigma_sw_workspace_bytes": (_i, [_LA, _u32, C.POINTER(_sz)]),
+    "mlmcpi_sigma_sw_draw": (_i, [_LA, _vp, _u32, _u32, _u64, _u32, _u32, _vp, _vp, _vp, _vp, _vp]),
 }
 
 # functions whose int return value is a status code

@@ -52,6 +52,8 @@ struct Tuning {
   uint32_t random_sweep_chunk = 0;                // MLMCPI_RANDOM_SWEEP_CHUNK=k: rounds scheduled per pass of the random-order sweep (0: 254)
   int sigma_cluster_team = 0;                     // MLMCPI_SIGMA_CLUSTER_TEAM=wave|block: lanes that share a chain in the sigma-model Wolff update (1 / 2; 0: by the batch)
   bool sigma_cluster_map_global = false;          // MLMCPI_SIGMA_CLUSTER_BITMAP=global: its membership bitmap in the workspace whatever the lattice
+  int sigma_sw_plan = 0;                          // MLMCPI_SIGMA_SW_PLAN=chain|tiled: launch plan of the sigma-model Swendsen-Wang update (1 / 2; 0: by lattice and batch)
+  uint32_t sigma_sw_tile_w = 0, sigma_sw_tile_h = 0;  // MLMCPI_SIGMA_SW_TILE=WxH: tile of its tiled plan, W, H in {8, 16, 32, 64} (0: 64x32)
 };
 Tuning tuning();  // a copy taken under the lock: callers snapshot it once per call
 

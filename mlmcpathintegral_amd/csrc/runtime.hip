@@ -119,12 +119,28 @@ bool apply_option(Tuning &t, const char *name, const char *value) {
     t.sigma_cluster_map_global = v == "global";
     return v.empty() || v == "global" || v == "lds";
   }
+  if (n == "MLMCPI_SIGMA_SW_PLAN") {
+    t.sigma_sw_plan = v == "chain" ? 1 : v == "tiled" ? 2 : 0;
+    return v.empty() || v == "auto" || v == "chain" || v == "tiled";
+  }
+  if (n == "MLMCPI_SIGMA_SW_TILE") {
+    unsigned a = 0, b = 0;
+    char rest = 0;
+    t.sigma_sw_tile_w = t.sigma_sw_tile_h = 0;
+    if (v.empty()) return true;
+    auto extent = [](unsigned e) { return e == 8 || e == 16 || e == 32 || e == 64; };
+    if (sscanf(v.c_str(), "%ux%u%c", &a, &b, &rest) == 2 && extent(a) && extent(b)) {
+      t.sigma_sw_tile_w = a; t.sigma_sw_tile_h = b;
+      return true;
+    }
+    return false;
+  }
   return false;
 }
 void load_tuning_locked() {
   if (g_tuning_loaded) return;
   for (const char *name : {"MLMCPI_SWEEP_TILE", "MLMCPI_OR_KERNEL", "MLMCPI_OR_HEAT", "MLMCPI_RANDOM_SWEEP_HOME", "MLMCPI_RANDOM_SWEEP_CHUNK",
-                           "MLMCPI_SIGMA_CLUSTER_TEAM", "MLMCPI_SIGMA_CLUSTER_BITMAP"})
+                           "MLMCPI_SIGMA_CLUSTER_TEAM", "MLMCPI_SIGMA_CLUSTER_BITMAP", "MLMCPI_SIGMA_SW_PLAN", "MLMCPI_SIGMA_SW_TILE"})
     if (const char *e = getenv(name)) apply_option(g_tuning, name, e);
   g_tuning_loaded = true;
 }

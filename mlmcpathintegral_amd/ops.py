@@ -393,6 +393,31 @@ def sigma_cluster_draw(act, x, n_updates, seed, chain0, update0, count=True, wor
     return sites
 
 
+def sigma_sw_workspace(act, B, device="cuda"):
+    """workspace of sigma_sw_draw for B chains (uint8 tensor)"""
+    nbytes = C.c_size_t(0)
+    abi.call("mlmcpi_sigma_sw_workspace_bytes", C.byref(act), B, C.byref(nbytes))
+    return torch.empty(nbytes.value, dtype=torch.uint8, device=device)
+
+
+def sigma_sw_draw(act, x, n_updates, seed, chain0, update0, outputs=True, work=None):
+    """Swendsen-Wang multi-cluster updates of the O(3) sigma model (mlmcpi_sigma_sw_draw): n_updates updates of every chain of
+    x [B, 2 Mt Mx], in place, update counters update0 + k; returns, per chain and summed over this call's updates, (flipped
+    vertices int32 [B], clusters int32 [B], improved chi_m float64 [B]), or None with outputs=False"""
+    _check_state(x, lattice_size(act))
+    B = x.shape[0]
+    if work is None:
+        work = sigma_sw_workspace(act, B, x.device)
+    flipped = clusters = improved = None
+    if outputs:
+        flipped = torch.zeros(B, dtype=torch.int32, device=x.device)
+        clusters = torch.zeros(B, dtype=torch.int32, device=x.device)
+        improved = torch.zeros(B, dtype=torch.float64, device=x.device)
+    abi.call("mlmcpi_sigma_sw_draw", C.byref(act), _p(x), B, n_updates, seed, chain0, update0, _p(flipped), _p(clusters), _p(improved),
+             _p(work), _stream())
+    return (flipped, clusters, improved) if outputs else None
+
+
 def lattice_random_sweep_order(act, B, seed, chain0, sweep, rounds=True, device="cuda"):
     """the visiting order (int32 [B, n]) and the round of every index (int32 [B, n], or None) of that sweep"""
     n = (2 if act.kind == abi.SCHWINGER else 1) * act.Mt * act.Mx
