@@ -10,7 +10,9 @@
 //   driver --method multilevel --action schwinger --Mt_lat 16 --beta 2 --coarsening both --coarsesampler heatbath
 //          --sampler hierarchical --n_level 2 --epsilon 0.005
 //   driver --action nonlinearsigma --Mt_lat 16 --beta 1 --sampler heatbath --n_samples 20000
-//          (O(3) sigma model: singlelevel and throughput with the heat-bath sampler only)
+//          (O(3) sigma model: heat-bath sampler; twolevel and hierarchical with --coarsening rotate, never multilevel: DESIGN.md 4.4a, 8)
+//   driver --action nonlinearsigma --Mt_lat 16 --beta 1 --coarsening rotate --method twolevel --coarsesampler heatbath
+//   driver --action nonlinearsigma --Mt_lat 16 --beta 1 --coarsening rotate --sampler hierarchical --coarsesampler heatbath --n_level 3
 //   driver --action nonlinearsigma --Mt_lat 16 --beta 1.5 --sampler wolff --n_updates 10 --n_samples 20000
 //          (Wolff single-cluster updates over the four links per vertex; prints chi_m and the mean cluster size)
 //   driver --action nonlinearsigma --Mt_lat 16 --beta 1.5 --sampler swendsenwang --n_updates 1 --n_samples 20000
@@ -87,21 +89,21 @@ int main(int argc, char **argv) {
     fatal(" wolff sampler not supported for chosen action: it is built for nonlinearsigma only (the rotor and schwinger have "
           "--sampler cluster; the other actions have no reflection the bond form is symmetric under)");
   if (o["sampler"] == "wolff" && o["method"] != "singlelevel")
-    fatal("nonlinearsigma: --sampler wolff runs --method singlelevel only, not " + o["method"] + " (two-level and multilevel are "
-          "not built for this action, DESIGN.md 8; the throughput loop is the heat-bath sampler's)");
+    fatal("nonlinearsigma: --sampler wolff runs --method singlelevel only, not " + o["method"] + " (the two-level step of this action "
+          "takes the heat-bath sampler on its coarse level, DESIGN.md 4.4a; the throughput loop is the heat-bath sampler's)");
   if (o["coarsesampler"] == "wolff")
     fatal(" --coarsesampler wolff is not supported: the wolff sampler is a single-level sampler of the nonlinear sigma model, "
-          "and no hierarchical or two-level run exists for that action (DESIGN.md 8)");
+          "whose hierarchical and two-level runs sample the coarse level with --coarsesampler heatbath (DESIGN.md 4.4a)");
   // --sampler swendsenwang: the multi-cluster sampler of the sigma model (sampler.hh SwendsenWangSampler)
   if (o["sampler"] == "swendsenwang" && a != "nonlinearsigma")
     fatal(" swendsenwang sampler not supported for chosen action: it is built for nonlinearsigma only (the rotor and schwinger have "
           "--sampler cluster; the other actions have no reflection the bond form is symmetric under)");
   if (o["sampler"] == "swendsenwang" && o["method"] != "singlelevel")
-    fatal("nonlinearsigma: --sampler swendsenwang runs --method singlelevel only, not " + o["method"] + " (two-level and multilevel "
-          "are not built for this action, DESIGN.md 8; the throughput loop is the heat-bath sampler's)");
+    fatal("nonlinearsigma: --sampler swendsenwang runs --method singlelevel only, not " + o["method"] + " (the two-level step of this "
+          "action takes the heat-bath sampler on its coarse level, DESIGN.md 4.4a; the throughput loop is the heat-bath sampler's)");
   if (o["coarsesampler"] == "swendsenwang")
     fatal(" --coarsesampler swendsenwang is not supported: the swendsenwang sampler is a single-level sampler of the nonlinear sigma "
-          "model, and no hierarchical or two-level run exists for that action (DESIGN.md 8)");
+          "model, whose hierarchical and two-level runs sample the coarse level with --coarsesampler heatbath (DESIGN.md 4.4a)");
   if (a == "harmonicoscillator" || a == "quarticoscillator" || a == "rotor") {
     auto lat = std::make_shared<Lattice1D>((unsigned)num("M_lat"), num("T_final"));
     if (a == "harmonicoscillator") {
@@ -127,14 +129,28 @@ int main(int argc, char **argv) {
     }
   } else if (a == "nonlinearsigma") {  // driver_qft.cc:159-166, 241-246
     auto lat = std::make_shared<Lattice2D>((unsigned)num("Mt_lat"), (unsigned)num("Mt_lat"), coarsenings.at(o["coarsening"]));
-    if (o["sampler"] != "heatbath" && o["sampler"] != "wolff" && o["sampler"] != "swendsenwang")
-      fatal("nonlinearsigma: only --sampler heatbath, --sampler wolff and --sampler swendsenwang are supported (HMC: the reference's force omits the sin theta of the measure "
+    if (o["sampler"] != "heatbath" && o["sampler"] != "wolff" && o["sampler"] != "swendsenwang" && o["sampler"] != "hierarchical")
+      fatal("nonlinearsigma: only --sampler heatbath, --sampler wolff, --sampler swendsenwang and --sampler hierarchical are supported (HMC: the reference's force omits the sin theta of the measure "
             "in (theta, phi) coordinates and would sample the wrong law; DESIGN.md 8)");
-    if (o["method"] != "singlelevel" && o["method"] != "throughput")
-      fatal("nonlinearsigma: --method " + o["method"] + " is not supported, only singlelevel and throughput (the reference's "
-            "driver refuses multilevel for this action; the two-level fill-in is an open question, DESIGN.md 8)");
+    // driver_qft.cc:406-410: the reference refuses multilevel for this action; its two-level method and hierarchical sampler run
+    if (o["method"] == "multilevel")
+      fatal("nonlinearsigma: --method multilevel is not supported (the reference's driver refuses multilevel for this action, "
+            "driver_qft.cc:406-410); --method twolevel and --sampler hierarchical run with --coarsening rotate");
+    const bool levels = o["method"] == "twolevel" || o["sampler"] == "hierarchical";
+    if (o["method"] != "singlelevel" && o["method"] != "throughput" && o["method"] != "twolevel")
+      fatal("nonlinearsigma: --method " + o["method"] + " is not supported, only singlelevel, throughput and twolevel");
+    if (levels && o["coarsening"] != "rotate")
+      fatal("nonlinearsigma: " + std::string(o["method"] == "twolevel" ? "--method twolevel" : "--sampler hierarchical") +
+            " needs --coarsening rotate, not " + o["coarsening"] + ": this action coarsens by rotate only (nonlinearsigmaaction.hh:143-149)");
+    if (levels && o["coarsesampler"] != "heatbath")
+      fatal("nonlinearsigma: the coarse level of a twolevel or hierarchical run is sampled by --coarsesampler heatbath only, not " +
+            o["coarsesampler"]);
+    if (o["renormalisation"] == "exact" && levels)
+      fatal("nonlinearsigma: non-perturbative renormalisation not implemented for non-linear sigma model.");
     action = std::make_shared<NonlinearSigmaAction>(lat, nullptr, renorm, num("beta"));
     qoi = std::make_shared<QoI2DMagneticSusceptibility>(lat);
+    qoi_factory = std::make_shared<QoI2DMagneticSusceptibilityFactory>();
+    cfa_factory = std::make_shared<NonlinearSigmaConditionedFineActionFactory>();
   } else if (a == "schwinger" || a == "gff") {
     auto lat = std::make_shared<Lattice2D>((unsigned)num("Mt_lat"), (unsigned)num("Mt_lat"), coarsenings.at(o["coarsening"]));
     if (a == "schwinger") {

@@ -504,32 +504,102 @@ private:
 
 /** action/qft/nonlinearsigmaaction.hh: the O(3) nonlinear sigma model, (theta, phi) per vertex.  Heat-bath and
  *  overrelaxation updates (the index set is the vertices: site_updates takes a vertex index), sweeps, evaluate, force and
- *  initialise_state run on the device.  Not built: coarse_action / copy_from_* (the reference's driver refuses
- *  multilevel for this action) and HMC (the reference's force misses the sin theta of the measure). */
+ *  initialise_state run on the device.  The action coarsens by CoarsenRotate only (nonlinearsigmaaction.hh:143-149), so every
+ *  second level of a hierarchy lives on a ROTATED lattice: evaluate, initialise_state and the sweeps of a rotated level and
+ *  copy_from_* of every level go through the level ABI (mlmcpi_sigma_level_*).  Not built: HMC
+ *  (the reference's force misses the sin theta of the measure), force and site-at-a-time updates on rotated levels. */
 class NonlinearSigmaAction : public QFTAction {
 public:
   NonlinearSigmaAction(const std::shared_ptr<Lattice2D> lattice_, const std::shared_ptr<Lattice2D> fine_lattice_,
                        const RenormalisationType r, const double beta_)
       : QFTAction(lattice_, fine_lattice_, r, MLMCPI_NONLINEAR_SIGMA, beta_, 0.0), beta(beta_) {
-    if (lattice->is_rotated()) fatal("nonlinear sigma action is only built for unrotated lattices");
     // nonlinearsigmaaction.hh: the heat-bath index set is the vertices (an update changes both angles of one vertex)
     heatbath_indexset.resize(lattice->getNvertices());
     for (unsigned int l = 0; l < heatbath_indexset.size(); ++l) heatbath_indexset[l] = l;
   }
   unsigned int sample_size() const override { return 2 * lattice->getNvertices(); }
   double getbeta() const { return beta; }
+  bool rotated() const { return lattice->is_rotated(); }
+  /** this level as the level ABI describes it */
+  mlmcpi_sigma_level level() const { return level_of(lattice); }
+  /** nonlinearsigmaaction.hh:151-166 with RenormalisedNonlinearSigmaParameters::beta_coarse
+   *  (nonlinearsigmarenormalisation.hh:58-76): beta, or beta - 1/2 log 2 / (2 pi); nonperturbative is refused, as there */
   std::shared_ptr<Action> coarse_action() override {
-    fatal("nonlinear sigma action: multilevel / two-level methods are not supported (DESIGN.md 8)");
+    if (lattice->get_coarsening_type() != CoarsenRotate)
+      fatal("nonlinear sigma action can only be coarsened with --coarsening rotate (nonlinearsigmaaction.hh:143-149)");
+    std::shared_ptr<Lattice2D> coarse_lattice = lattice->get_coarse_lattice();
+    if (!coarse_lattice)
+      fatal("cannot coarsen 2d lattice with M_{t,lat} = " + std::to_string(lattice->getMt_lat()) + " , M_{x,lat} = " + std::to_string(lattice->getMx_lat()) + ".");
+    if (renormalisation == RenormalisationNonperturbative)
+      fatal("non-perturbative renormalisation not implemented for non-linear sigma model.");
+    const double beta_c = renormalisation == RenormalisationPerturbative ? beta - 0.5 * std::log(2.) / (2. * M_PI) : beta;
+    return std::make_shared<NonlinearSigmaAction>(coarse_lattice, lattice, renormalisation, beta_c);
   }
-  void copy_from_coarse(const std::shared_ptr<SampleState>, std::shared_ptr<SampleState>) override {
-    fatal("nonlinear sigma action: copy_from_coarse is not supported (DESIGN.md 8)");
+  std::vector<double> evaluate_batch(const std::shared_ptr<SampleState> phi) const override {
+    if (!rotated()) return QFTAction::evaluate_batch(phi);
+    const mlmcpi_sigma_level lv = level();
+    DeviceVector out(phi->batch());
+    check(mlmcpi_sigma_level_evaluate(&lv, phi->device(), phi->batch(), (double *)out.ptr(), nullptr), "sigma_level_evaluate");
+    return out.download<double>();
   }
-  void copy_from_fine(const std::shared_ptr<SampleState>, std::shared_ptr<SampleState>) override {
-    fatal("nonlinear sigma action: copy_from_fine is not supported (DESIGN.md 8)");
+  void initialise_state(std::shared_ptr<SampleState> phi) const override {
+    if (!rotated()) return QFTAction::initialise_state(phi);
+    const mlmcpi_sigma_level lv = level();
+    check(mlmcpi_sigma_level_initialise(&lv, phi->device_overwrite(), phi->batch(), seed, chain0, nullptr), "sigma_level_initialise");
   }
-  std::string info_string() const override { return QFTAction::info_string() + ", beta = " + std::to_string(beta); }
+  void force(const std::shared_ptr<SampleState> phi, std::shared_ptr<SampleState> p) const override {
+    if (rotated()) fatal("force of the nonlinear sigma action is only built for the unrotated level");
+    QFTAction::force(phi, p);
+  }
+  void site_updates(std::shared_ptr<SampleState> phi, const uint32_t *d_sites, unsigned int n, unsigned int ell, bool heat) override {
+    if (rotated()) fatal(std::string(heat ? "heat bath" : "overrelaxation") + " update of single sites is only built for the unrotated level of the nonlinear sigma action");
+    QFTAction::site_updates(phi, d_sites, n, ell, heat);
+  }
+  void random_sweep_draw(std::shared_ptr<SampleState> phi, unsigned int n_or, unsigned int n_hb, uint32_t sweep0) override {
+    if (rotated()) fatal("the random-order sweep of the nonlinear sigma action is only built for the unrotated level");
+    QFTAction::random_sweep_draw(phi, n_or, n_hb, sweep0);
+  }
+  void sweep(std::shared_ptr<SampleState> phi, std::shared_ptr<SampleState> scratch, unsigned n_or, unsigned n_hb, uint32_t sweep0) override {
+    if (!rotated()) return QFTAction::sweep(phi, scratch, n_or, n_hb, sweep0);
+    const mlmcpi_sigma_level lv = level();
+    check(mlmcpi_sigma_level_sweep_draw(&lv, phi->device_mutable(), scratch->device_overwrite(), phi->batch(), n_or, n_hb, seed, chain0, sweep0,
+                                        nullptr), "sigma_level_sweep_draw");
+  }
+  /** rotated level: the sweeps run in place on d_w0 (a copy of d_src) with d_w1 as their scratch; the result is in d_w0 */
+  int sweep_from(const double *d_src, double *d_w0, double *d_w1, unsigned batch, unsigned n_or, unsigned n_hb, uint32_t sweep0) override {
+    if (!rotated()) return QFTAction::sweep_from(d_src, d_w0, d_w1, batch, n_or, n_hb, sweep0);
+    const mlmcpi_sigma_level lv = level();
+    check(mlmcpi_copy_d2d(d_w0, d_src, (size_t)batch * sample_size() * sizeof(double), nullptr), "copy_d2d");
+    check(mlmcpi_sigma_level_sweep_draw(&lv, d_w0, d_w1, batch, n_or, n_hb, seed, chain0, sweep0, nullptr), "sigma_level_sweep_draw");
+    return 0;
+  }
+  int sweep_from_qoi(const double *d_src, double *d_w0, double *d_w1, unsigned batch, unsigned n_or, unsigned n_hb, uint32_t sweep0,
+                     int qoi_kind, double *d_q, double *d_acc = nullptr) override {
+    if (rotated()) return -1;  // the caller evaluates the QoI on its own
+    return QFTAction::sweep_from_qoi(d_src, d_w0, d_w1, batch, n_or, n_hb, sweep0, qoi_kind, d_q, d_acc);
+  }
+  /** nonlinearsigmaaction.cc:113-139: `this` is the level being written to */
+  void copy_from_coarse(const std::shared_ptr<SampleState> phi_coarse, std::shared_ptr<SampleState> phi_state) override {
+    if (lattice->get_coarsening_type() != CoarsenRotate || phi_coarse->size() != sample_size() / 2 || phi_state->size() != sample_size())
+      fatal("cannot copy from coarse lattice.");
+    const mlmcpi_sigma_level lv = level();
+    check(mlmcpi_sigma_level_copy_from_coarse(&lv, phi_coarse->device(), phi_state->device_mutable(), phi_state->batch(), nullptr),
+          "sigma_level_copy_from_coarse");
+  }
+  void copy_from_fine(const std::shared_ptr<SampleState> phi_fine, std::shared_ptr<SampleState> phi_state) override {
+    if (!fine_lattice || phi_fine->size() != 2 * sample_size() || phi_state->size() != sample_size()) fatal("cannot copy from fine lattice.");
+    const mlmcpi_sigma_level lv = level_of(fine_lattice);
+    check(mlmcpi_sigma_level_copy_from_fine(&lv, phi_fine->device(), phi_state->device_overwrite(), phi_state->batch(), nullptr),
+          "sigma_level_copy_from_fine");
+  }
+  std::string info_string() const override {
+    return QFTAction::info_string() + (rotated() ? " (rotated)" : "") + ", beta = " + std::to_string(beta);
+  }
 
 private:
+  mlmcpi_sigma_level level_of(const std::shared_ptr<Lattice2D> l) const {
+    return mlmcpi_sigma_level{l->getMt_lat(), l->getMx_lat(), l->is_rotated() ? 1 : 0, beta};
+  }
   const double beta;
 };
 

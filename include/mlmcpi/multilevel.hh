@@ -167,6 +167,38 @@ public:
   }
 };
 
+/** action/qft/nonlinearsigmaconditionedfineaction.{hh,cc}: every fine-only vertex of a CoarsenRotate level has its four
+ *  neighbours among the coarse vertices, so the fill is one independent heat-bath draw per fine-only vertex and evaluate is minus
+ *  the log of its density; both run inside mlmcpi_sigma_twolevel_draw, and are exposed here for direct use. */
+class NonlinearSigmaConditionedFineAction : public ConditionedFineAction {
+public:
+  explicit NonlinearSigmaConditionedFineAction(const std::shared_ptr<NonlinearSigmaAction> action_) : action(action_) {}
+  std::shared_ptr<Action> fine_action() const override { return action; }
+  void fill_fine_points(std::shared_ptr<SampleState> phi_state, uint32_t step = 0) const {
+    const mlmcpi_sigma_level lv = action->level();
+    check(mlmcpi_sigma_cfa_fill(&lv, phi_state->device_mutable(), phi_state->batch(), action->get_seed() ^ 0x115147ull, action->get_chain0(),
+                                step, nullptr), "sigma_cfa_fill");
+  }
+  double evaluate(const std::shared_ptr<SampleState> phi_state) const {
+    const mlmcpi_sigma_level lv = action->level();
+    DeviceVector S(phi_state->batch());
+    check(mlmcpi_sigma_cfa_evaluate(&lv, phi_state->device(), phi_state->batch(), (double *)S.ptr(), nullptr), "sigma_cfa_evaluate");
+    return S.download<double>()[0];
+  }
+
+private:
+  const std::shared_ptr<NonlinearSigmaAction> action;
+};
+
+class NonlinearSigmaConditionedFineActionFactory : public ConditionedFineActionFactory {
+public:
+  std::shared_ptr<ConditionedFineAction> get(std::shared_ptr<Action> action) override {
+    auto sigma = std::dynamic_pointer_cast<NonlinearSigmaAction>(action);
+    if (!sigma) fatal("nonlinear sigma conditioned fine action needs a NonlinearSigmaAction");
+    return std::make_shared<NonlinearSigmaConditionedFineAction>(sigma);
+  }
+};
+
 /** twolevelmetropolisstep.{hh,cc}: draws a fine-level sample from a coarse-level proposal. */
 class TwoLevelMetropolisStep : public MCMCStep {
 public:
@@ -176,11 +208,16 @@ public:
       : MCMCStep(), coarse(coarse_action_), fine(fine_action_), qm_coarse(std::dynamic_pointer_cast<QMAction>(coarse_action_)),
         qm_fine(std::dynamic_pointer_cast<QMAction>(fine_action_)), qft_coarse(std::dynamic_pointer_cast<QFTAction>(coarse_action_)),
         qft_fine(std::dynamic_pointer_cast<QFTAction>(fine_action_)), gff_coarse(std::dynamic_pointer_cast<GFFAction>(coarse_action_)),
-        gff_fine(std::dynamic_pointer_cast<GFFAction>(fine_action_)), cfa(conditioned_fine_action_), B(batch),
+        gff_fine(std::dynamic_pointer_cast<GFFAction>(fine_action_)), sigma_coarse(std::dynamic_pointer_cast<NonlinearSigmaAction>(coarse_action_)),
+        sigma_fine(std::dynamic_pointer_cast<NonlinearSigmaAction>(fine_action_)), cfa(conditioned_fine_action_), B(batch),
         accept_flags(batch, sizeof(int32_t)), cost_per_sample_(0.0) {
     if (!cfa || !((qm_coarse && qm_fine) || (qft_coarse && qft_fine))) fatal("TwoLevelMetropolisStep: actions have no device implementation");
     size_t bytes = 0;
     if (gff_fine && gff_coarse) check(mlmcpi_gff_twolevel_workspace_bytes(gff_fine->level_handle(), B, &bytes), "gff_twolevel_workspace_bytes");
+    else if (sigma_fine && sigma_coarse) {
+      const mlmcpi_sigma_level lv = sigma_fine->level();
+      check(mlmcpi_sigma_twolevel_workspace_bytes(&lv, B, &bytes), "sigma_twolevel_workspace_bytes");
+    }
     else if (qm_fine) check(mlmcpi_path_twolevel_workspace_bytes(&qm_fine->abi_action(), B, &bytes), "twolevel_workspace_bytes");
     else check(mlmcpi_lattice_twolevel_workspace_bytes(&qft_fine->abi_action(), &qft_coarse->abi_action(), B, &bytes), "twolevel_workspace_bytes");
     check(mlmcpi_malloc(&work, bytes), "mlmcpi_malloc");
@@ -203,7 +240,11 @@ public:
       check(mlmcpi_gff_twolevel_draw(gff_fine->level_handle(), gff_coarse->level_handle(), phi_coarse_state->device(),
                                      theta_fine->device_mutable(), B, level_seed(), fine->get_chain0(), step++, work,
                                      (int32_t *)accept_flags.ptr(), nullptr, nullptr), "gff_twolevel_draw");
-    else if (qm_fine)
+    else if (sigma_fine && sigma_coarse) {
+      const mlmcpi_sigma_level lf = sigma_fine->level(), lc = sigma_coarse->level();
+      check(mlmcpi_sigma_twolevel_draw(&lf, &lc, phi_coarse_state->device(), theta_fine->device_mutable(), B, level_seed(), fine->get_chain0(),
+                                       step++, work, (int32_t *)accept_flags.ptr(), nullptr, nullptr), "sigma_twolevel_draw");
+    } else if (qm_fine)
       check(mlmcpi_path_twolevel_draw(&qm_fine->abi_action(), &qm_coarse->abi_action(), phi_coarse_state->device(),
                                       theta_fine->device_mutable(), B, level_seed(), fine->get_chain0(), step++, work,
                                       (int32_t *)accept_flags.ptr(), nullptr, nullptr), "path_twolevel_draw");
@@ -232,6 +273,7 @@ private:
   const std::shared_ptr<QMAction> qm_coarse, qm_fine;
   const std::shared_ptr<QFTAction> qft_coarse, qft_fine;
   const std::shared_ptr<GFFAction> gff_coarse, gff_fine;
+  const std::shared_ptr<NonlinearSigmaAction> sigma_coarse, sigma_fine;
   const std::shared_ptr<ConditionedFineAction> cfa;
   const unsigned int B;
   std::shared_ptr<SampleState> theta_fine;
@@ -729,6 +771,7 @@ public:
 typedef QFTQoIFactory<QoI2DSusceptibility> QoI2DSusceptibilityFactory;
 typedef QFTQoIFactory<QoIAvgPlaquette> QoIAvgPlaquetteFactory;
 typedef QFTQoIFactory<QoI2DPhiSquared> QoI2DPhiSquaredFactory;
+typedef QFTQoIFactory<QoI2DMagneticSusceptibility> QoI2DMagneticSusceptibilityFactory;
 
 }  // namespace mlmcpi
 #endif

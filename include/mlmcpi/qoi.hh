@@ -101,17 +101,24 @@ private:
   const unsigned int M_lat;
 };
 
-/** qoi/qft/qoi2dmagneticsusceptibility.cc:7-21: |sum_n sigma_n|^2 / N of the O(3) sigma model */
+/** qoi/qft/qoi2dmagneticsusceptibility.cc:7-21: |sum_n sigma_n|^2 / N of the O(3) sigma model, on any level of its hierarchy
+ *  (N = the vertices of the level; rotated levels through mlmcpi_sigma_level_magnetic_susceptibility) */
 class QoI2DMagneticSusceptibility : public QoI {
 public:
-  explicit QoI2DMagneticSusceptibility(const std::shared_ptr<Lattice2D> lattice) : Mt_lat(lattice->getMt_lat()), Mx_lat(lattice->getMx_lat()) {}
+  explicit QoI2DMagneticSusceptibility(const std::shared_ptr<Lattice2D> lattice)
+      : Mt_lat(lattice->getMt_lat()), Mx_lat(lattice->getMx_lat()), n_vertices(lattice->getNvertices()), rotated(lattice->is_rotated()) {}
   int fused_kind() const override { return 4; }
   void evaluate_device(const std::shared_ptr<SampleState> phi, double *d_out) override {
-    if (phi->size() != 2 * Mt_lat * Mx_lat) fatal("Evaluating QoI2DMagneticSusceptibility on state of wrong size.");
-    check(mlmcpi_qoi_magnetic_susceptibility(phi->device(), Mt_lat, Mx_lat, phi->batch(), d_out, nullptr), "qoi_magnetic_susceptibility");
+    if (phi->size() != 2 * n_vertices) fatal("Evaluating QoI2DMagneticSusceptibility on state of wrong size.");
+    if (rotated) {
+      const mlmcpi_sigma_level lv{Mt_lat, Mx_lat, 1, 0.0};
+      check(mlmcpi_sigma_level_magnetic_susceptibility(&lv, phi->device(), phi->batch(), d_out, nullptr), "sigma_level_magnetic_susceptibility");
+    } else
+      check(mlmcpi_qoi_magnetic_susceptibility(phi->device(), Mt_lat, Mx_lat, phi->batch(), d_out, nullptr), "qoi_magnetic_susceptibility");
   }
 private:
-  const unsigned int Mt_lat, Mx_lat;
+  const unsigned int Mt_lat, Mx_lat, n_vertices;
+  const bool rotated;
 };
 
 }  // namespace mlmcpi

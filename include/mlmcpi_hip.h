@@ -60,10 +60,14 @@ enum mlmcpi_action_kind {
   MLMCPI_GFF = 3,       /* action/qft/gffaction.{hh,cc} (n_gibbs_smooth = 0) */
   MLMCPI_SCHWINGER = 4, /* action/qft/quenchedschwingeraction.{hh,cc} */
   MLMCPI_NONLINEAR_SIGMA = 5 /* action/qft/nonlinearsigmaaction.{hh,cc}: O(3) spins as (theta, phi) per vertex; uses `beta`.
-                              * Sweeps, evaluate, force, initialise, site updates and QoI 4; NOT HMC (the reference's force
-                              * samples exp(-S) dtheta dphi, without the sin theta of the measure), copy_from_* or the two-level
-                              * step: MLMCPI_ERR_UNSUPPORTED.  Sweeps are bit-identical whatever the launch plan:
-                              * every update reads spins recomputed from the stored angles. */
+                              * Through mlmcpi_lattice_*: sweeps, evaluate, force, initialise, site updates and QoI 4 on the
+                              * unrotated lattice; NOT HMC (the reference's force samples exp(-S) dtheta dphi, without the sin
+                              * theta of the measure), and NOT mlmcpi_lattice_copy_from_* / mlmcpi_lattice_twolevel_*, whose
+                              * (rt, rx) describe unrotated coarsenings: MLMCPI_ERR_UNSUPPORTED.  The action coarsens by
+                              * CoarsenRotate only (nonlinearsigmaaction.hh:143-149); its rotated levels, the transfers, the
+                              * conditioned fine action and the two-level step are mlmcpi_sigma_level_* / mlmcpi_sigma_cfa_* /
+                              * mlmcpi_sigma_twolevel_* below.  Sweeps are bit-identical whatever
+                              * the launch plan: every update reads spins recomputed from the stored angles. */
 };
 
 /* 1-D path action: lattice/lattice1d.hh:60-101 (M_lat, T_final, a = T_final/M_lat) + the action's
@@ -520,6 +524,65 @@ int mlmcpi_gff_twolevel_workspace_bytes(const mlmcpi_gff_level *fine, uint32_t B
 int mlmcpi_gff_twolevel_draw(mlmcpi_gff_level *fine, mlmcpi_gff_level *coarse, const double *d_phi_coarse, double *d_theta,
                              uint32_t B, uint64_t seed, uint32_t chain0, uint32_t step, void *d_work, int32_t *d_accept,
                              double *d_terms, void *stream);
+
+/* ---- O(3) nonlinear sigma model: levels of the CoarsenRotate hierarchy and the two-level step ---------
+ * A level by value: (Mt, Mx) are the extents of the Cartesian frame of Lattice2D, both even and >= 2 (Mt Mx <= 2^30);
+ * rotated = 0: the Mt Mx vertices of mlmcpi_lattice_action, l = Mt j + i; rotated != 0: the Mt Mx / 2 vertices with (i + j)
+ * even in the reference's order (lattice2d.hh:230-268), two planes of Mt/2 x Mx/2, the even-even plane E then the odd-odd plane
+ * O, index p (Mt Mx / 4) + (Mt/2) b + a = vertex (2 a + p, 2 b + p).  State [B][2 n]: (theta, phi) of vertex l at 2 l, 2 l + 1.
+ * Rotated neighbours in the reference's order (+1,+1), (+1,-1), (-1,+1), (-1,-1): E(a, b): O(a, b), O(a, b-1), O(a-1, b),
+ * O(a-1, b-1); O(a, b): E(a+1, b+1), E(a+1, b), E(a, b+1), E(a, b) (periodic).  The coarse partner of the unrotated (Mt, Mx)
+ * is the rotated (Mt, Mx); that of the rotated (Mt, Mx) is the unrotated (Mt/2, Mx/2) (lattice2d.cc:83-108). */
+typedef struct mlmcpi_sigma_level {
+  uint32_t Mt, Mx;
+  int32_t rotated;
+  double beta;
+} mlmcpi_sigma_level;
+/* _state_size: 2 n.  _initialise: the map of mlmcpi_lattice_initialise over the level's 2 n entries.  _evaluate: S = -1/2 beta
+ * sum_n sigma_n . Delta_n; rotated: as the bond sum -beta sum_E sigma_E . Delta_E; unrotated: mlmcpi_lattice_evaluate.
+ * _magnetic_susceptibility: |sum_n sigma_n|^2 / n with the level's n.
+ * _sweep_draw: OverrelaxedHeatBathSampler::draw on the level, d_state in place, d_scratch of the same size; unrotated:
+ * mlmcpi_lattice_sweep_draw (fuse 0).  Rotated: a sweep is phase E then phase O; heat bath of vertex l in sweep s = ONE Philox
+ * call (site l = the level's vertex index, chain, step sweep0 + s, purpose 14); the canonical form of the unrotated kernel, so a
+ * draw is bit-identical whatever MLMCPI_SIGMA_LEVEL_PLAN=TWxTHxNTxK (mlmcpi_set_option: tile of plane cells, TW, TH in 1..128,
+ * workgroup NT in {256, 512, 1024}, K in 1..16 sweeps fused per launch, within the LDS) and whatever the batch split.
+ * _copy_from_fine / _copy_from_coarse (NonlinearSigmaAction::copy_from_*, nonlinearsigmaaction.cc:113-139): `fine` is the FINE
+ * level, the other state lives on its coarse partner; _copy_from_coarse leaves the fine-only entries untouched. */
+int mlmcpi_sigma_level_state_size(const mlmcpi_sigma_level *level, uint32_t *n);
+int mlmcpi_sigma_level_initialise(const mlmcpi_sigma_level *level, double *d_state, uint32_t B, uint64_t seed, uint32_t chain0,
+                                  void *stream);
+int mlmcpi_sigma_level_evaluate(const mlmcpi_sigma_level *level, const double *d_state, uint32_t B, double *d_S, void *stream);
+int mlmcpi_sigma_level_magnetic_susceptibility(const mlmcpi_sigma_level *level, const double *d_state, uint32_t B, double *d_out,
+                                               void *stream);
+int mlmcpi_sigma_level_sweep_draw(const mlmcpi_sigma_level *level, double *d_state, double *d_scratch, uint32_t B,
+                                  uint32_t n_overrelax, uint32_t n_heatbath, uint64_t seed, uint32_t chain0, uint32_t sweep0,
+                                  void *stream);
+int mlmcpi_sigma_level_copy_from_fine(const mlmcpi_sigma_level *fine, const double *d_fine, double *d_coarse, uint32_t B,
+                                      void *stream);
+int mlmcpi_sigma_level_copy_from_coarse(const mlmcpi_sigma_level *fine, const double *d_coarse, double *d_fine, uint32_t B,
+                                        void *stream);
+/* NonlinearSigmaConditionedFineAction (nonlinearsigmaconditionedfineaction.cc:7-44) on a level.  Every fine-only vertex (the
+ * (i + j) odd ones of an unrotated level, the O plane of a rotated one) has coarse neighbours only, so the fill is a product of
+ * independent heat-bath laws and _evaluate is minus the log of its density.
+ *   _fill      every fine-only vertex l <- the heat-bath draw from its four neighbours, all at once, ONE Philox call each (site l
+ *              = its index on the fine level, chain, step, purpose 24); a vertex whose neighbour sum is 0 keeps its entry
+ *   _evaluate  d_S[b] = -sum_X log p(z_X; s_X), s = beta |Delta|, z = sigma . Delta / |Delta|, log p = s (z - 1) + log s -
+ *              log(1 - exp(-2 s)); Delta = 0 contributes log 2 */
+int mlmcpi_sigma_cfa_fill(const mlmcpi_sigma_level *fine, double *d_state, uint32_t B, uint64_t seed, uint32_t chain0,
+                          uint32_t step, void *stream);
+int mlmcpi_sigma_cfa_evaluate(const mlmcpi_sigma_level *fine, const double *d_state, uint32_t B, double *d_S, void *stream);
+/* TwoLevelMetropolisStep::draw (twolevelmetropolisstep.cc:35-89) between a level and its coarse partner (`coarse` must be that
+ * partner: MLMCPI_ERR_INVALID otherwise; coarse->beta is the caller's).  One pass, with no intermediate state in HBM beyond the trial (neighbours are re-read through the cache), builds the trial (the coarse proposal on the
+ * coarse vertices, the fill of purpose 24 on the fine-only ones; a fine-only vertex whose neighbour sum is 0 takes the entry of
+ * d_theta) and sums the terms of the trial and of the current state; a per-chain launch decides (u = Philox site 0, purpose 8,
+ * as mlmcpi_lattice_twolevel_draw); a masked copy writes the accepted trials into d_theta.  Arguments as
+ * mlmcpi_lattice_twolevel_draw; d_terms[b] = (dS_fine, dS_coarse, dS_trial).  The sums are formed in a fixed order (groups of
+ * 256 vertices, then the groups in order), so accept, terms and states do not depend on MLMCPI_SIGMA_TWOLEVEL_GROUPS=g (groups
+ * per workgroup, 1..64) or on the batch split. */
+int mlmcpi_sigma_twolevel_workspace_bytes(const mlmcpi_sigma_level *fine, uint32_t B, size_t *bytes);
+int mlmcpi_sigma_twolevel_draw(const mlmcpi_sigma_level *fine, const mlmcpi_sigma_level *coarse, const double *d_phi_coarse,
+                               double *d_theta, uint32_t B, uint64_t seed, uint32_t chain0, uint32_t step, void *d_work,
+                               int32_t *d_accept, double *d_terms, void *stream);
 
 /* QoI2DPhiSquared (qoi/qft/qoi2dphisquared.cc:8-15), QoIAvgPlaquette (qoi/qft/qoiavgplaquette.cc:8-27),
  * QoI2DSusceptibility (qoi/qft/qoi2dsusceptibility.cc:8-27); d_out[b]. */

@@ -34,6 +34,20 @@ class LatticeAction(C.Structure):
                 ("mass", C.c_double)]
 
 
+class SigmaLevel(C.Structure):
+    """mlmcpi_sigma_level: a level of the sigma model's CoarsenRotate hierarchy"""
+    _fields_ = [("Mt", C.c_uint32), ("Mx", C.c_uint32), ("rotated", C.c_int32), ("beta", C.c_double)]
+
+    @property
+    def n_vertices(self):
+        return self.Mt * self.Mx // 2 if self.rotated else self.Mt * self.Mx
+
+    def coarse(self, beta=None):
+        """the coarse partner under CoarsenRotate (lattice2d.cc:83-108), with the caller's coarse beta (default: the same)"""
+        b = self.beta if beta is None else beta
+        return SigmaLevel(self.Mt // 2, self.Mx // 2, 0, b) if self.rotated else SigmaLevel(self.Mt, self.Mx, 1, b)
+
+
 class SweepLaunch(C.Structure):
     """mlmcpi_sweep_launch"""
     _fields_ = [(n, C.c_uint32) for n in ("kernel", "n_overrelax", "n_heatbath", "grid_x", "threads", "lds_bytes", "tile_w", "tile_h",
@@ -42,6 +56,7 @@ class SweepLaunch(C.Structure):
 
 _vp, _u32, _u64, _i, _d, _sz = C.c_void_p, C.c_uint32, C.c_uint64, C.c_int, C.c_double, C.c_size_t
 _PA, _LA = C.POINTER(PathAction), C.POINTER(LatticeAction)
+_SL = C.POINTER(SigmaLevel)
 
 # name -> (restype, argtypes); must list EVERY symbol of include/mlmcpi_hip.h (tests check this)
 SIGNATURES = {
@@ -144,6 +159,17 @@ SIGNATURES = {
     "mlmcpi_sigma_cluster_draw": (_i, [_LA, _vp, _u32, _u32, _u64, _u32, _u32, _vp, _vp, _vp]),
     "mlmcpi_sigma_sw_workspace_bytes": (_i, [_LA, _u32, C.POINTER(_sz)]),
     "mlmcpi_sigma_sw_draw": (_i, [_LA, _vp, _u32, _u32, _u64, _u32, _u32, _vp, _vp, _vp, _vp, _vp]),
+    "mlmcpi_sigma_level_state_size": (_i, [_SL, C.POINTER(_u32)]),
+    "mlmcpi_sigma_level_initialise": (_i, [_SL, _vp, _u32, _u64, _u32, _vp]),
+    "mlmcpi_sigma_level_evaluate": (_i, [_SL, _vp, _u32, _vp, _vp]),
+    "mlmcpi_sigma_level_magnetic_susceptibility": (_i, [_SL, _vp, _u32, _vp, _vp]),
+    "mlmcpi_sigma_level_sweep_draw": (_i, [_SL, _vp, _vp, _u32, _u32, _u32, _u64, _u32, _u32, _vp]),
+    "mlmcpi_sigma_level_copy_from_fine": (_i, [_SL, _vp, _vp, _u32, _vp]),
+    "mlmcpi_sigma_level_copy_from_coarse": (_i, [_SL, _vp, _vp, _u32, _vp]),
+    "mlmcpi_sigma_cfa_fill": (_i, [_SL, _vp, _u32, _u64, _u32, _u32, _vp]),
+    "mlmcpi_sigma_cfa_evaluate": (_i, [_SL, _vp, _u32, _vp, _vp]),
+    "mlmcpi_sigma_twolevel_workspace_bytes": (_i, [_SL, _u32, C.POINTER(_sz)]),
+    "mlmcpi_sigma_twolevel_draw": (_i, [_SL, _SL, _vp, _vp, _u32, _u64, _u32, _u32, _vp, _vp, _vp, _vp]),
 }
 
 # functions whose int return value is a status code
@@ -184,6 +210,10 @@ def path_action(kind, M, T_final, m0=1.0, mu2=1.0, lam=0.0, x0=0.0):
 
 def lattice_action(kind, Mt, Mx, beta=0.0, mass=0.0):
     return LatticeAction(kind, Mt, Mx, beta, mass)
+
+
+def sigma_level(Mt, Mx, rotated, beta):
+    return SigmaLevel(Mt, Mx, 1 if rotated else 0, beta)
 
 
 def set_option(name, value=""):

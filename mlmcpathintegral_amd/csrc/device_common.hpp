@@ -209,6 +209,8 @@ enum Purpose : uint32_t {
                            // by the map of purpose 19 sub 0
   P_SIGMA_SW_BOND = 22,    // Swendsen-Wang update, site = vertex l, sub 0: u decides link (l, 0), v decides link (l, 1)
   P_SIGMA_SW_FLIP = 23,    // Swendsen-Wang update, site = the root (smallest vertex) of a cluster, sub 0: reflected iff u < 0.5
+  P_SIGMA_FILLIN = 24,     // sigma-model two-level step (sigma_twolevel.hip), site = the fine-only vertex's index on the fine level, sub 0:
+                           // (u, v) of its heat-bath draw from the four coarse neighbours
 };
 
 struct RngKey {

@@ -135,12 +135,36 @@ bool apply_option(Tuning &t, const char *name, const char *value) {
     }
     return false;
   }
+  if (n == "MLMCPI_SIGMA_LEVEL_PLAN") {
+    unsigned a = 0, b = 0, c = 0, k = 0;
+    char rest = 0;
+    t.sigma_level_tw = t.sigma_level_th = t.sigma_level_nt = t.sigma_level_fuse = 0;
+    if (v.empty()) return true;
+    if (sscanf(v.c_str(), "%ux%ux%ux%u%c", &a, &b, &c, &k, &rest) == 4 && a >= 1 && a <= 128 && b >= 1 && b <= 128 &&
+        (c == 256 || c == 512 || c == 1024) && k >= 1 && k <= kMaxFuse && (size_t)(a + 2 * k) * (b + 2 * k) * 48 <= kSigmaLdsMax) {
+      t.sigma_level_tw = a; t.sigma_level_th = b; t.sigma_level_nt = c; t.sigma_level_fuse = k;
+      return true;
+    }
+    return false;
+  }
+  if (n == "MLMCPI_SIGMA_TWOLEVEL_GROUPS") {
+    unsigned g = 0;
+    char rest = 0;
+    t.sigma_twolevel_groups = 0;
+    if (v.empty()) return true;
+    if (sscanf(v.c_str(), "%u%c", &g, &rest) == 1 && g >= 1 && g <= 64) {
+      t.sigma_twolevel_groups = g;
+      return true;
+    }
+    return false;
+  }
   return false;
 }
 void load_tuning_locked() {
   if (g_tuning_loaded) return;
   for (const char *name : {"MLMCPI_SWEEP_TILE", "MLMCPI_OR_KERNEL", "MLMCPI_OR_HEAT", "MLMCPI_RANDOM_SWEEP_HOME", "MLMCPI_RANDOM_SWEEP_CHUNK",
-                           "MLMCPI_SIGMA_CLUSTER_TEAM", "MLMCPI_SIGMA_CLUSTER_BITMAP", "MLMCPI_SIGMA_SW_PLAN", "MLMCPI_SIGMA_SW_TILE"})
+                           "MLMCPI_SIGMA_CLUSTER_TEAM", "MLMCPI_SIGMA_CLUSTER_BITMAP", "MLMCPI_SIGMA_SW_PLAN", "MLMCPI_SIGMA_SW_TILE", "MLMCPI_SIGMA_LEVEL_PLAN",
+                           "MLMCPI_SIGMA_TWOLEVEL_GROUPS"})
     if (const char *e = getenv(name)) apply_option(g_tuning, name, e);
   g_tuning_loaded = true;
 }

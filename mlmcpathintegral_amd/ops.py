@@ -418,6 +418,98 @@ def sigma_sw_draw(act, x, n_updates, seed, chain0, update0, outputs=True, work=N
     return (flipped, clusters, improved) if outputs else None
 
 
+# ---- O(3) sigma model: levels of the CoarsenRotate hierarchy and the two-level step ---------------------------------
+def sigma_level_size(level):
+    n = C.c_uint32(0)
+    abi.call("mlmcpi_sigma_level_state_size", C.byref(level), C.byref(n))
+    return n.value
+
+
+def sigma_level_initialise(level, B, seed, chain0=0, device="cuda"):
+    x = torch.empty((B, sigma_level_size(level)), dtype=torch.float64, device=device)
+    abi.call("mlmcpi_sigma_level_initialise", C.byref(level), _p(x), B, seed, chain0, _stream())
+    return x
+
+
+def sigma_level_evaluate(level, x):
+    _check_state(x, sigma_level_size(level))
+    out = torch.empty(x.shape[0], dtype=torch.float64, device=x.device)
+    abi.call("mlmcpi_sigma_level_evaluate", C.byref(level), _p(x), x.shape[0], _p(out), _stream())
+    return out
+
+
+def sigma_level_magnetic_susceptibility(level, x):
+    _check_state(x, sigma_level_size(level))
+    out = torch.empty(x.shape[0], dtype=torch.float64, device=x.device)
+    abi.call("mlmcpi_sigma_level_magnetic_susceptibility", C.byref(level), _p(x), x.shape[0], _p(out), _stream())
+    return out
+
+
+def sigma_level_sweep_draw(level, x, scratch, n_overrelax, n_heatbath, seed, chain0, sweep0):
+    """OverrelaxedHeatBathSampler::draw on a level, in place"""
+    _check_state(x, sigma_level_size(level))
+    assert scratch.shape == x.shape and scratch.dtype == x.dtype
+    abi.call("mlmcpi_sigma_level_sweep_draw", C.byref(level), _p(x), _p(scratch), x.shape[0], n_overrelax, n_heatbath, seed, chain0,
+             sweep0, _stream())
+    return x
+
+
+def sigma_level_copy_from_fine(fine_level, fine):
+    _check_state(fine, sigma_level_size(fine_level))
+    coarse = _f64(fine.shape[0], sigma_level_size(fine_level) // 2, fine)   # half of the vertices are coarse
+    abi.call("mlmcpi_sigma_level_copy_from_fine", C.byref(fine_level), _p(fine), _p(coarse), fine.shape[0], _stream())
+    return coarse
+
+
+def sigma_level_copy_from_coarse(fine_level, coarse, fine):
+    _check_state(fine, sigma_level_size(fine_level))
+    _check_state(coarse, sigma_level_size(fine_level) // 2)
+    abi.call("mlmcpi_sigma_level_copy_from_coarse", C.byref(fine_level), _p(coarse), _p(fine), fine.shape[0], _stream())
+    return fine
+
+
+def sigma_cfa_fill(fine_level, x, seed, chain0, step):
+    """NonlinearSigmaConditionedFineAction::fill_fine_points, in place"""
+    _check_state(x, sigma_level_size(fine_level))
+    abi.call("mlmcpi_sigma_cfa_fill", C.byref(fine_level), _p(x), x.shape[0], seed, chain0, step, _stream())
+    return x
+
+
+def sigma_cfa_evaluate(fine_level, x):
+    _check_state(x, sigma_level_size(fine_level))
+    out = torch.empty(x.shape[0], dtype=torch.float64, device=x.device)
+    abi.call("mlmcpi_sigma_cfa_evaluate", C.byref(fine_level), _p(x), x.shape[0], _p(out), _stream())
+    return out
+
+
+class SigmaTwoLevelStep:
+    """TwoLevelMetropolisStep between a sigma-model level and its CoarsenRotate partner, B device chains."""
+
+    def __init__(self, fine, coarse, B, seed=1, chain0=0, device="cuda"):
+        self.fine, self.coarse, self.B, self.seed, self.chain0 = fine, coarse, B, seed, chain0
+        nbytes = C.c_size_t(0)
+        abi.call("mlmcpi_sigma_twolevel_workspace_bytes", C.byref(fine), B, C.byref(nbytes))
+        self.work = torch.empty(nbytes.value, dtype=torch.uint8, device=device)
+        self.accept = torch.zeros(B, dtype=torch.int32, device=device)
+        self.terms = torch.zeros((B, 3), dtype=torch.float64, device=device)
+        self.theta = torch.zeros((B, sigma_level_size(fine)), dtype=torch.float64, device=device)  # current fine state
+        self.step = 0
+
+    def set_state(self, x):
+        self.theta.copy_(x)
+
+    def trial(self):
+        """the trial state of the last draw (a view of the workspace)"""
+        return self.work[:self.theta.numel() * 8].view(torch.float64).view(self.theta.shape)
+
+    def draw(self, phi_coarse):
+        _check_state(phi_coarse, sigma_level_size(self.coarse))
+        abi.call("mlmcpi_sigma_twolevel_draw", C.byref(self.fine), C.byref(self.coarse), _p(phi_coarse), _p(self.theta), self.B,
+                 self.seed, self.chain0, self.step, _p(self.work), _p(self.accept), _p(self.terms), _stream())
+        self.step += 1
+        return self.accept
+
+
 def lattice_random_sweep_order(act, B, seed, chain0, sweep, rounds=True, device="cuda"):
     """the visiting order (int32 [B, n]) and the round of every index (int32 [B, n], or None) of that sweep"""
     n = (2 if act.kind == abi.SCHWINGER else 1) * act.Mt * act.Mx
