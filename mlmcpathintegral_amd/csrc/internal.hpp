@@ -69,12 +69,7 @@ int sigma_force(const mlmcpi_lattice_action *act, const double *d_phi, double *d
 int sigma_initialise(const mlmcpi_lattice_action *act, double *d_phi, uint32_t B, uint64_t seed, uint32_t chain0, hipStream_t st);
 int sigma_site_updates(const mlmcpi_lattice_action *act, double *d_state, uint32_t B, const uint32_t *d_sites, uint32_t n,
                        uint32_t site, int32_t heat, uint64_t seed, uint32_t chain0, uint32_t step, hipStream_t st);
-// one launch of a draw, as lattice2d.hip's planner describes it (include/mlmcpi_hip.h: what mlmcpi_lattice_sweep_plan reports)
-using SweepLaunch = mlmcpi_sweep_launch;
 constexpr uint32_t kSigmaLdsMax = 160 * 1024 - 512;  // dynamic LDS a workgroup of sigma_sweep_kernel may take (static: the 3 x NT/64 reduction)
-int sigma_init_sweep_kernels();
-int sigma_sweep_launch(const mlmcpi_lattice_action *act, const SweepLaunch &l, uint32_t B, const double *src, double *dst, RngKey key,
-                       bool with_qoi, double *d_qoi, double *d_acc, hipStream_t st);
 
 inline double gff_mu2(const mlmcpi_lattice_action &A) {  // gffaction.hh:174-181 (unrotated lattice)
   const double a_lat = 1. / A.Mt;

@@ -1,4 +1,4 @@
-// lattice_reduce.hip -- the streaming side of the GFF and Schwinger lattices (lattice2d.hip holds the sweeps): per-chain
+// lattice_reduce.hip -- the streaming side of the GFF and Schwinger lattices (lattice2d.hip and its kernel units hold the sweeps): per-chain
 // reductions over a state (action, phi^2, average plaquette, topological charge), the final sum of per-tile partials,
 // start states, the per-chain statistics, and the argument checks every lattice entry point shares.
 #include "internal.hpp"

@@ -14,7 +14,7 @@
 // (u, v); initialise: P_INIT, one uniform per state entry (entry 2l -> cos theta = 1 - 2u, 2l + 1 -> phi = 2 pi u - pi).
 #include <mutex>
 
-#include "internal.hpp"
+#include "lattice_sweep.hpp"
 
 #include "sigma_device.hpp"  // fp contraction is off from here on
 
@@ -292,25 +292,24 @@ int sigma_site_updates(const mlmcpi_lattice_action *act, double *d_state, uint32
   return MLMCPI_OK;
 }
 
-// one launch of a draw of mlmcpi_lattice_sweep_draw* (lattice2d.hip plans the draw and runs the loop): reads `src`, writes
-// `dst`; `key` is that of the launch's first sweep.  with_qoi (the launch ends the draw): it sums the magnetisation, and one
-// more launch finishes chi_m into d_qoi (and the record_sample moments with d_acc).
-int sigma_sweep_launch(const mlmcpi_lattice_action *act, const SweepLaunch &l, uint32_t B, const double *src, double *dst, RngKey key,
-                       bool with_qoi, double *d_qoi, double *d_acc, hipStream_t st) {
-  const uint32_t Mt = act->Mt, Mx = act->Mx;
+// one launch of a draw of mlmcpi_lattice_sweep_draw* (lattice2d.hip plans the draw and runs the loop): reads a.src, writes
+// a.dst; a.key is that of the launch's first sweep.  a.qoi_op != 0 (the launch ends the draw): it sums the magnetisation, and one
+// more launch finishes chi_m into a.d_qoi (and the record_sample moments with a.d_acc).
+int sigma_sweep_launch(const SweepLaunch &l, const SweepArgs &a) {
   void *part = nullptr;
-  if (int rc = with_qoi ? scratch((size_t)B * l.grid_x * 3 * sizeof(double), &part, st) : 0) return rc;
-#define MLMCPI_SIGMA_SWEEP(NT)                                                                                                 \
-  hipLaunchKernelGGL(sigma_sweep_kernel<NT>, dim3(l.grid_x, B), dim3(NT), l.lds_bytes, st, Mt, Mx, act->beta, (const double2 *)src, \
-                     (double2 *)dst, l.tile_w, l.tile_h, l.tiles_x, l.n_overrelax + l.n_heatbath, l.n_overrelax, key, (double *)part)
+  if (int rc = a.qoi_op ? scratch((size_t)a.B * l.grid_x * 3 * sizeof(double), &part, a.st) : 0) return rc;
+#define MLMCPI_SIGMA_SWEEP(NT)                                                                                                    \
+  hipLaunchKernelGGL(sigma_sweep_kernel<NT>, dim3(l.grid_x, a.B), dim3(NT), l.lds_bytes, a.st, a.Mt, a.Mx, a.coupling,            \
+                     (const double2 *)a.src, (double2 *)a.dst, l.tile_w, l.tile_h, l.tiles_x, l.n_overrelax + l.n_heatbath, l.n_overrelax, \
+                     a.key, (double *)part)
   if (l.threads == 1024) MLMCPI_SIGMA_SWEEP(1024);
   else if (l.threads == 512) MLMCPI_SIGMA_SWEEP(512);
   else MLMCPI_SIGMA_SWEEP(256);
 #undef MLMCPI_SIGMA_SWEEP
   MLMCPI_LAUNCH_CHECK("sigma_sweep_kernel");
-  if (with_qoi) {
-    hipLaunchKernelGGL(sigma_finish_kernel<1>, dim3(B), dim3(256), 0, st, (const double *)part, l.grid_x, 1.0 / ((double)Mt * Mx), d_qoi,
-                       d_acc);
+  if (a.qoi_op) {
+    hipLaunchKernelGGL(sigma_finish_kernel<1>, dim3(a.B), dim3(256), 0, a.st, (const double *)part, l.grid_x,
+                       1.0 / ((double)a.Mt * a.Mx), a.d_qoi, a.d_acc);
     MLMCPI_LAUNCH_CHECK("sigma_finish_kernel");
   }
   return MLMCPI_OK;
