@@ -656,7 +656,7 @@ __device__ __forceinline__ void heatbath_cells(uint32_t total, const RngKey &key
 // the exact test -- a Philox call, an fp64 logarithm and cosine behind a function call: measured at 8 % of the fused
 // sweep launch.)  Random numbers: the same Philox calls (word pair = one attempt), fields: bit 0 sign, bits 1..22 leading
 // bits of u2, bits 23..57 position inside the bin (35 bits: 2 10^-11 rad), bits 58..63 selector.
-// host rule (lattice2d.hip / path1d.hip; the oracle applies the same): this sampler where the action's largest concentration,
+// host rule (lattice2d.hip / rotor_sweeps.hip; the oracle applies the same): this sampler where the action's largest concentration,
 // 2 beta or 2 m0 / a, is <= kVsKappaMax; the wrapped-Cauchy sampler beyond.  r05: 16 (4 until then).  The eight classes split
 // [0, scale] by sin(2 pi c / 32), so they get wider in kappa with the scale and a table, built for the smallest
 // concentration of its class, fits the largest one less well: acceptance per attempt 0.78 on average at scale 2, 0.74 at 4,

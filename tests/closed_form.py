@@ -39,7 +39,7 @@ def schwinger_overrelax_closed_form(theta, Mt, Mx, K):
 
 def rotor_overrelax_closed_form(x, K):
     """K even / odd overrelaxation sweeps of the rotor path x (rotoraction.cc:40-56: x_j <- x_{j-1} + x_{j+1} - x_j), as
-    rotor_sweep_kernel computes them (path1d.hip): the update exchanges the differences d_j = x_{j+1} - x_j on either side
+    rotor_sweep_kernel computes them (rotor_sweeps.hip): the update exchanges the differences d_j = x_{j+1} - x_j on either side
     of the site, a sweep moves the difference at an even index two down and the one at an odd index two up, and with
     de[i] = d(2 i), do[i] = d(2 i + 1) the pair of sites (2 p, 2 p + 1) receives X - S and X' - S, S = sum_{s<K} do[p - 1 - s],
     X = sum_{s<K} de[p + s], X' = X - de[p] + de[p + K]."""

@@ -271,6 +271,57 @@ def test_hmc_run_equals_repeated_draws(gpu_ops, orc, name, p, nt, dt, n_rep):
         assert_close(xa.cpu().numpy(), xo, tol=1e-9, what="state vs oracle")
 
 
+@pytest.mark.parametrize("name,M,dt", [
+    # dt chosen with the oracle (chains 0..47, 63 and 2099 of this start state, nt = 6, n_rep = 2, three draws) so that the
+    # batch holds chains with every draw accepted and chains with fewer; accepted draws per chain 0/1/2/3 of those 50 chains:
+    ("quartic", 128, 0.34),    # 0 / 5 / 18 / 27   (0.36 is past the leapfrog's stability limit at a = 1/8: nothing accepted)
+    ("quartic", 256, 0.30),    # 0 / 0 / 1 / 49
+    ("quartic", 512, 0.34),    # 0 / 2 / 17 / 31
+    ("quartic", 1024, 0.34),   # 0 / 0 / 9 / 41
+    ("rotor", 512, 0.45),      # 0 / 11 / 25 / 14
+])
+def test_hmc_run_one_wave_chains_equal_repeated_draws(gpu_ops, orc, name, M, dt):
+    """mlmcpi_path_hmc_run where one wave holds a chain (B = 2100: R = M / 64, NT = 64, boundary values by DPP rotation, no
+    LDS exchange) against repeated mlmcpi_path_hmc_draw + QoI calls: the assertions of test_hmc_run_equals_repeated_draws,
+    and chains of the batch against the oracle."""
+    import ctypes as C
+    from mlmcpathintegral_amd import abi
+    p = dict(M=M, T_final=M / 8.0, m0=0.25) if name == "rotor" else dict(M=M, T_final=M / 8.0, m0=1.0, mu2=1.0, lam=1.0, x0=1.0)
+    act, A = make_path(orc, name, p)
+    B, nt, n_draws, n_rep = 2100, 6, 3, 2
+    qoi_kind = 2 if name == "rotor" else 1
+    layout = C.c_int32(0)
+    abi.call("mlmcpi_path_hmc_run_layout", C.byref(act), B, nt, C.byref(layout))
+    assert layout.value == 1, "chain-major: the single-launch kernel runs"
+    g = torch.Generator().manual_seed(M)
+    x0 = torch.rand((B, M), generator=g, dtype=torch.float64) * 2 - 1
+    xa, xb = x0.cuda(), x0.cuda()
+    run = gpu_ops.PathHMC(act, B, nt, dt, n_rep=n_rep, seed=SEED, chain0=0)
+    q, cnt = gpu_ops.path_hmc_run(run, xa, n_draws, qoi_kind)
+    ref = gpu_ops.PathHMC(act, B, nt, dt, n_rep=n_rep, seed=SEED, chain0=0)
+    qs, total = [], torch.zeros(B, dtype=torch.int32, device="cuda")
+    for d in range(n_draws):
+        total += ref.draw(xb)
+        qs.append(gpu_ops.qoi_susceptibility(xb, p["T_final"]) if qoi_kind == 2 else gpu_ops.qoi_xsquared(xb))
+    assert torch.equal(cnt, total), (cnt, total)
+    assert_close(xa.cpu().numpy(), xb.cpu().numpy(), tol=1e-12, what="state after n_draws")
+    assert_close(q.cpu().numpy(), torch.stack(qs, dim=1).cpu().numpy(), tol=1e-13, what="per-draw QoIs")
+    counts = cnt.cpu().numpy()
+    assert not (counts == 0).all() and not (counts == n_draws).all(), "the batch should see both outcomes"
+    got = xa.cpu().numpy()
+    for b in (0, 63, 2099):
+        xo, n_acc = x0[b].numpy().copy(), 0
+        for d in range(n_draws):
+            a = 0
+            for r in range(n_rep):
+                if a:
+                    break
+                a, _, _ = A.dev_hmc_trajectory(xo, nt, dt, SEED, b, d * n_rep + r)
+            n_acc += a
+        assert counts[b] == n_acc, f"accepted draws of chain {b}"
+        assert_close(got[b], xo, tol=1e-10, what=f"chain {b} vs oracle")
+
+
 def test_hmc_n_rep_short_circuit(gpu_ops, orc):
     """hmcsampler.cc:10-12: `accept = accept or single_step()` stops integrating after the first
     accepted repetition; repetition r uses Philox step traj0 + r."""

@@ -3,6 +3,8 @@
 Schwinger closed-form launches of every depth, 64 x 64 and 64 x 32 tiles, GFF register-block launches on 64 x 64 and 32 x 32
 tiles, with and without the heat bath and the QoI -- and, under MLMCPI_OR_KERNEL=block, the Schwinger sweep-by-sweep plan
 (lines starting "block": state hashes, and the QoI values themselves, which two builds may sum in different tile orders).
+Behind them the 1-D paths: HMC draws and whole-chain runs on every launch geometry, rotor sweeps with both heat-bath samplers,
+the two-level step of the three actions and the exact harmonic-oscillator draw.
    MLMCPI_LIB_VARIANT=r04 python tools/exp_variant_hash.py > a.txt; python tools/exp_variant_hash.py > b.txt
    python tools/exp_variant_hash.py --compare a.txt b.txt   (other lines equal; block lines: states equal, QoI to 1e-13)"""
 import hashlib, sys
@@ -77,3 +79,51 @@ try:
             print(line, flush=True)
 finally:
     abi.set_option("MLMCPI_OR_KERNEL", "")
+
+# ---- the 1-D paths: HMC draws and whole-chain runs, rotor sweeps, the two-level step, the exact HO draw
+def path_act(name, M, m0=None):
+    if name == "rotor":
+        return abi.path_action(2, M, M / 8.0, 0.25 if m0 is None else m0)
+    return abi.path_action(0 if name == "harmonic" else 1, M, M / 8.0, 1.0, 1.0, 0.0 if name == "harmonic" else 1.0,
+                           0.0 if name == "harmonic" else 1.0)
+
+
+def path_start(M, B):
+    g = torch.Generator().manual_seed(M + B)
+    return (torch.rand((B, M), generator=g, dtype=torch.float64) * 2 - 1).cuda()
+
+
+for name, M, B, nt, dt in (("harmonic", 128, 4, 20, 0.05), ("quartic", 1000, 2, 12, 0.08), ("quartic", 1024, 2100, 6, 0.34),
+                           ("rotor", 512, 2100, 6, 0.45), ("rotor", 65536, 2, 6, 0.05)):
+    act, x = path_act(name, M), path_start(M, B)
+    hmc = ops.PathHMC(act, B, nt, dt, n_rep=2, seed=SEED, chain0=3)
+    for d in range(3):
+        acc = hmc.draw(x)
+        print(f"hmc_draw {name} M={M} B={B} draw {d}: {h(x)} {h(acc)} {h(hmc.energies)}", flush=True)
+    for qoi_kind in (1, 2):
+        x = path_start(M, B)
+        run = ops.PathHMC(act, B, nt, dt, n_rep=2, seed=SEED, chain0=3)
+        q, cnt = ops.path_hmc_run(run, x, 3, qoi_kind)
+        print(f"hmc_run {name} M={M} B={B} qoi {qoi_kind}: {h(x)} {h(q)} {h(cnt)}", flush=True)
+
+for m0 in (0.25, 2.0):   # 2 m0 / a = 4 and 32: step envelope and wrapped Cauchy (kVsKappaMax = 16)
+    for M in (64, 4096, 10000):
+        act, x0 = path_act("rotor", M, m0), path_start(M, 3) * 3.0
+        for n_or, n_hb in ((10, 1), (3, 0), (0, 2)):
+            x = x0.clone()
+            ops.path_sweep_draw(act, x, torch.empty_like(x), n_or, n_hb, SEED, 0, 5)
+            a, w, q = ops.path_sweep_draw_qoi(act, x0.clone(), torch.empty_like(x0), torch.empty_like(x0), n_or, n_hb, SEED, 0, 5)
+            print(f"rotor_sweep M={M} m0={m0} ({n_or},{n_hb}): {h(x)} qoi {h(a)} {h(q)}", flush=True)
+
+for name in ("harmonic", "quartic", "rotor"):
+    for M in (64, 4096):
+        fine, coarse = path_act(name, M), path_act(name, M // 2)
+        coarse.T_final = fine.T_final
+        step = ops.PathTwoLevelStep(fine, coarse, 3, seed=SEED, chain0=1)
+        step.set_state(path_start(M, 3))
+        xc = path_start(M // 2, 3)
+        for d in range(2):
+            acc = step.draw(xc)
+            print(f"twolevel {name} M={M} step {d}: {h(step.theta)} {h(acc)} {h(step.terms)}", flush=True)
+
+print(f"ho_exact M=128 B=32: {h(ops.HOExactSampler(path_act('harmonic', 128), 32, seed=SEED, chain0=2).draw())}", flush=True)
