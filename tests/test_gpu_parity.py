@@ -1108,12 +1108,15 @@ def test_schwinger_twolevel_step_matches_oracle(gpu_ops, orc, Mt, Mx, rt, rx, be
         # lattices) or a lot (mostly rejected)
         base = gpu_ops.lattice_copy_from_fine(fine, rt, rx, dev(theta)).cpu().numpy()
         pc = base + rng.normal(0, 0.02 if t % 2 == 0 else 1.5, base.shape)
+        before = step.theta.clone()
         acc = step.draw(dev(pc)).cpu().numpy()
         terms = step.terms.cpu().numpy()
         for b in range(B):
             a, want = F.dev_lattice_twolevel_draw(Cc, pc[b], theta[b], SEED, 4 + b, t)
             assert_close(terms[b], want, tol=2e-10, scale=max(1.0, float(np.max(np.abs(want)))), what=f"action differences t={t} b={b}")
             assert acc[b] == a, (t, b, want)
+            if not a:   # a refused draw writes no link
+                assert torch.equal(step.theta[b].view(torch.int64), before[b].view(torch.int64)), f"refused draw t={t} b={b} changed the state"
             seen.add(int(a))
         assert_angles_close(step.theta.cpu().numpy(), theta, tol=1e-10, what=f"fine state after draw {t}")
         theta = step.theta.cpu().numpy().copy()   # resync (angle wrap at +-pi may differ by 2 pi)
