@@ -60,7 +60,7 @@ struct Tuning {
 Tuning tuning();  // a copy taken under the lock: callers snapshot it once per call
 
 // Table of the step-envelope heat-bath sampler for an action of the given scale (2 beta, 2 m0 / a), in the memory of the
-// current device: built and uploaded on first use (device_common.hpp, runtime.hip).
+// current device: built and uploaded on first use (step_envelope.hpp, runtime.hip).
 int vs_table_device(double scale, const uint32_t **d_table);
 
 // the O(3) nonlinear sigma model (sigma2d.hip); arguments checked by the lattice entry points that dispatch here

@@ -23,6 +23,7 @@
 #include <stdlib.h>
 
 #include "lattice_sweep.hpp"
+#include "step_envelope.hpp"
 
 namespace mlmcpi {
 

@@ -6,6 +6,9 @@
 #include <type_traits>
 
 #include "internal.hpp"
+#include "site_update.hpp"
+#include "step_envelope.hpp"
+#include "vonmises.hpp"
 
 namespace mlmcpi {
 
@@ -78,7 +81,7 @@ __device__ __forceinline__ uint32_t wrap_add(uint32_t base, uint32_t off, uint32
 // Same arithmetic and the same random numbers -- Philox (site, chain, step) -- as the sweep kernels, so the sites of a
 // colour class visited in any order with the sweep's step reproduce that colour phase of the sweep.
 // One template, two launching units: <false> belongs to lattice2d.hip (mlmcpi_lattice_site_updates), <true> to
-// schwinger_sweeps.hip (schwinger_site_updates).  vs_exact_pair (device_common.hpp) is not inlined, and without relocatable
+// schwinger_sweeps.hip (schwinger_site_updates).  vs_exact_pair (step_envelope.hpp) is not inlined, and without relocatable
 // device code the compiler specialises it for the callers it has in a unit: the Schwinger sweep kernels hand it the table in
 // LDS, this kernel in global memory.  Only with both in one unit are the function and the sweep kernels generated as
 // tools/kernel_digest.py records them (EXPERIMENTS.md 0.9).

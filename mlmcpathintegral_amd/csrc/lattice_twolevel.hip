@@ -3,7 +3,9 @@
 #include <cmath>
 #include <mutex>
 
+#include "fillin.hpp"
 #include "internal.hpp"
+#include "vonmises.hpp"
 
 // =================================================================================================
 // Transfers between lattice levels: Action::copy_from_fine / copy_from_coarse for the 2-D actions.

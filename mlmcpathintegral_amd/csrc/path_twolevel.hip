@@ -1,5 +1,6 @@
 // path_twolevel.hip -- the two-level Metropolis step of the 1-D paths, one launch per step.
 #include "path_common.hpp"
+#include "vonmises.hpp"
 
 namespace mlmcpi {
 

@@ -26,6 +26,8 @@
 #include <mutex>
 
 #include "internal.hpp"
+#include "site_update.hpp"
+#include "step_envelope.hpp"
 
 #include "sigma_device.hpp"  // fp contraction is off from here on (this file adds no floating-point arithmetic of its own)
 

@@ -2,6 +2,8 @@
 // segments, with both heat-bath samplers, and its site-at-a-time updates.  Both kernels stay in this unit: each reaches
 // the step-envelope sampler's device functions that are not inlined, and the compiler specialises those for the callers a unit has.
 #include "path_common.hpp"
+#include "step_envelope.hpp"
+#include "vonmises.hpp"
 
 namespace mlmcpi {
 
@@ -12,7 +14,7 @@ namespace mlmcpi {
 // the neighbours' writes otherwise).  kinds bit s = 1 -> sweep s is a heat-bath sweep.
 // rotoraction.cc:20-56, rotoraction.hh:195-213.
 // HEAT = false: overrelaxation-only instantiation (no sampler code, few registers).  STEP: heat-bath draws from the step
-// envelope (2 m0 / a <= kVsKappaMax, device_common.hpp) instead of the wrapped-Cauchy one; pool_cap then counts VsPool entries.
+// envelope (2 m0 / a <= kVsKappaMax, step_envelope.hpp) instead of the wrapped-Cauchy one; pool_cap then counts VsPool entries.
 #ifndef MLMCPI_ROTOR_LEAN
 #define MLMCPI_ROTOR_LEAN 2
 #endif
@@ -248,7 +250,7 @@ static int path_sweep_impl(const mlmcpi_path_action *act, double *d_x, double *d
     owned += owned & 1;  // keep segment starts even
     const uint32_t nseg2 = (P.M + owned - 1) / owned;
     const size_t lds = (size_t)(owned + 2 * halo) * sizeof(double);
-    // retry pool of the heat-bath phases (device_common.hpp); which sampler: a property of the action (2 m0 / a), not a knob
+    // retry pool of the heat-bath phases (vonmises.hpp, step_envelope.hpp); which sampler: a property of the action (2 m0 / a), not a knob
     const bool step = 2.0 * P.m0 / P.a <= kVsKappaMax;
     const uint32_t pool_cap = 256;
     const uint32_t *vs_table = nullptr;

@@ -11,6 +11,8 @@
 #include <vector>
 
 #include "internal.hpp"
+#include "step_envelope.hpp"
+#include "vonmises.hpp"
 
 namespace mlmcpi {
 
@@ -176,7 +178,7 @@ Tuning tuning() {
   return g_tuning;
 }
 
-// ---- tables of the step-envelope sampler (device_common.hpp, "tabulated step envelope") -----------------------------------
+// ---- tables of the step-envelope sampler (step_envelope.hpp) -----------------------------------
 // For the action's scale (kappa = scale |cos(.)| <= scale <= kVsKappaMax) and each of the kVsClasses ranges of kappa: the
 // proposal probabilities q_k / 64 of the eight bins, as a 64-entry selector, and log2 of the acceptance factors.
 // q[c][k] selector values for bin k of class c, lw[c][k] = log2 of its acceptance factor
@@ -221,7 +223,7 @@ void vs_build_tables(double scale, int *q_out, float *lw) {
   }
 }
 
-// the device image (device_common.hpp, "Device image of the tables"): code | scr | lw | fin | consts
+// the device image (step_envelope.hpp, "Device image of the tables"): code | scr | lw | fin | consts
 static void vs_device_image(double scale, uint32_t *image) {
   int q[kVsClasses * kVsBins];
   float lw[kVsClasses * kVsBins];

@@ -7,6 +7,8 @@
 #include <stdlib.h>
 
 #include "lattice_sweep.hpp"
+#include "step_envelope.hpp"
+#include "vonmises.hpp"
 
 namespace mlmcpi {
 
@@ -70,7 +72,7 @@ __device__ __forceinline__ void heatbath_region(uint32_t nr, uint32_t nc, const 
                         commit);
 }
 
-// the same for the step-envelope sampler (device_common.hpp): cells are addressed by their LDS offset
+// the same for the step-envelope sampler (step_envelope.hpp): cells are addressed by their LDS offset
 // r0 * bw + c0 + (row step) * bw * ri + (column step) * ci
 template <int NT, int S, bool DIRECT, class E, class Setup, class KappaExact, class Commit>
 __device__ __forceinline__ void heatbath_region_step(uint32_t nr, uint32_t nc, uint32_t origin, uint32_t row_stride,
@@ -109,7 +111,7 @@ __device__ __forceinline__ void heatbath_region_step(uint32_t nr, uint32_t nc, u
 // (Mt >= TWC + 4, Mx >= THC + 4): tile and buffer extents are compile-time constants (index arithmetic folds, cell
 // coordinates come from divisions by constants) and a buffer coordinate wraps around the lattice at most once.  Same
 // updates in the same order as the generic instantiation (TWC = THC = 0): bit-identical results.
-// STEP: the heat-bath phases draw from the step envelope (2 beta <= kVsKappaMax; device_common.hpp) instead of the
+// STEP: the heat-bath phases draw from the step envelope (2 beta <= kVsKappaMax; step_envelope.hpp) instead of the
 // wrapped-Cauchy one; pool_cap then counts entries of VsPool.
 template <bool HEAT, int NT, int TWC = 0, int THC = 0, bool STEP = false>
 __global__ void __launch_bounds__(NT, HEAT ? (NT == 256 ? 4 : NT == 512 ? 2 : 1) : 1)

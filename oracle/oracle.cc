@@ -164,7 +164,7 @@ double expcos_draw(Src &src, double beta, double x_p, double x_m) {
 // for every concentration.  Equality in distribution with the reference's samplers is a test
 // (tests/test_distributions.py), not an assumption.
 //
-// Arithmetic and random-number layout follow the device (mlmcpathintegral_amd/csrc/device_common.hpp, "heat-bath angle
+// Arithmetic and random-number layout follow the device (mlmcpathintegral_amd/csrc/vonmises.hpp, "heat-bath angle
 // draws"): Best & Fisher's r = (1 + rho^2)/(2 rho) equals (1 + s)/(2 kappa), s = sqrt(1 + 4 kappa^2); with
 // R = kappa r = (1 + s)/2:  z = cos(pi u1), f = cos(theta) = (kappa + R z)/(R + kappa z), c = R - kappa f, accept when
 // u2 <= c exp(1 - c).  One Philox call (word 3 = P_VONMISES << 24 | sub0 | t) feeds attempts 2t (words 0, 1) and 2t + 1
@@ -202,7 +202,7 @@ inline double dev_vonmises(const DevRng &rng, uint32_t site, double kappa, uint3
 }
 
 // Device-order angle sampler for moderate concentrations (sweeps of actions with kappa_max = scale <= kVsKappaMax;
-// device: device_common.hpp, "tabulated step envelope").  Same von Mises law p(x) ~ exp(kappa cos x), piecewise-constant
+// device: step_envelope.hpp).  Same von Mises law p(x) ~ exp(kappa cos x), piecewise-constant
 // envelope: |x| falls into one of eight bins with edges (0, 1, 2, 3, 4, 6, 8, 12, 16) pi/16, bin k proposed with
 // probability q_k / 64, |x| uniform inside the bin, accepted with probability
 //     exp(kappa (cos x - 1)) (w_k / q_k) / max_j (H_j w_j / q_j),      H_j = exp(kappa_min (cos(edge_j) - 1)),
@@ -214,7 +214,7 @@ inline double dev_vonmises(const DevRng &rng, uint32_t site, double kappa, uint3
 // of u2 from the refine call); of the 52 bits above them the top six select the bin (selector value s belongs to bin k
 // when q_0 + ... + q_{k-1} <= s < q_0 + ... + q_k) and the other 46 are the position inside it.  The test is taken in
 // logarithms, exactly as the device's exact path does.
-constexpr double kVsKappaMax = 16.0;   // (round 5; 4 before: the device's rule, device_common.hpp)
+constexpr double kVsKappaMax = 16.0;   // (round 5; 4 before: the device's rule, step_envelope.hpp)
 constexpr int kVsClasses = 8, kVsBins = 8, kVsSel = 64;
 struct VsTables {
   int q[kVsClasses][kVsBins];

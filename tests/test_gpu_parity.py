@@ -90,7 +90,7 @@ def test_expcos_draws_match_oracle(gpu_ops, orc):
 
 
 def test_step_envelope_draws_match_oracle(gpu_ops, orc):
-    """The sampler of the heat-bath sweeps at moderate concentrations (device_common.hpp, "tabulated step envelope";
+    """The sampler of the heat-bath sweeps at moderate concentrations (step_envelope.hpp;
     oracle dev_vonmises_table): the accepted angle is a linear function of random bits, so device and oracle agree to
     rounding wherever they take the same accept / reject decisions -- i.e. everywhere."""
     rng = np.random.default_rng(3)
@@ -1348,7 +1348,7 @@ def test_gff_initialise_runs_a_second_chunk(gpu_ops):
 
 
 # ---- the device's angle samplers against the analytic law, with no oracle in between ---------------------------------
-# (oracle.cc::dev_vonmises_table was written in lockstep with device_common.hpp, so device == oracle is
+# (oracle.cc::dev_vonmises_table was written in lockstep with step_envelope.hpp, so device == oracle is
 # close to a self-comparison there.  Here 2 10^5 DEVICE draws per case go straight against the quadrature CDF of
 # p(x) ~ exp(kappa cos(x - centre)) (expcosdistribution.cc:7-21) and the closed form <cos> = I1 / I0.)
 def _vonmises_cdf(kappa):
