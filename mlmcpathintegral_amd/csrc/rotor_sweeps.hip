@@ -57,7 +57,7 @@ __global__ void __launch_bounds__(256, HEAT && STEP ? MLMCPI_ROTOR_WAVES : 1)
   //     x_{j+1} += X' - S,                                                           X' = X - de[p] + de[p + K]
   // with the differences of the path the launch started from, split by parity (de[i] = d(2 i), do[i] = d(2 i + 1): every
   // sum is a run of consecutive LDS words, consecutive lanes read consecutive words).  The same map as K sweeps to the
-  // rounding of 2 K additions (the 2-D counterpart: schwinger_sweeps.hip, schwinger_perm_kernel); exact where the sweeps are
+  // rounding of 2 K additions (the 2-D counterpart: schwinger_perm.hpp, schwinger_perm_kernel); exact where the sweeps are
   // (buffer sites [2 K, L - 2 K)), the edge sites keep their values as they do under the sweeps' creeping halo.
   if (n_closed) {
     const uint32_t H2 = L / 2, K = n_closed;   // L is even (owned lengths, halos and M are) and at most 2048: <= 4 pairs per thread

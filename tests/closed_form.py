@@ -1,5 +1,5 @@
 """K multicolour overrelaxation sweeps of the quenched Schwinger action in closed form (numpy), as
-mlmcpathintegral_amd/csrc/schwinger_sweeps.hip (schwinger_perm_kernel) computes them: test infrastructure.
+mlmcpathintegral_amd/csrc/schwinger_perm.hpp (perm_sweeps, schwinger_perm_kernel) computes them: test infrastructure.
 
 With P(i, j) = theta_0(i, j) + theta_1(i+1, j) - theta_0(i, j+1) - theta_1(i, j) the overrelaxation update of a link
 (/root/reference/src/action/qft/quenchedschwingeraction.cc:57-65) adds the difference of its two plaquettes to the link and

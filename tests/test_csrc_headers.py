@@ -12,7 +12,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "mlmcpathintegral_amd", "csrc")
 SAMPLER_HEADERS = {"vonmises.hpp", "step_envelope.hpp", "site_update.hpp", "fillin.hpp"}
 UNITS_WITHOUT_SAMPLER = ("path1d", "path_hmc", "ho_exact", "lattice_reduce", "lattice_hmc", "gff_exact", "gff_levels", "cluster",
-                         "sigma_cluster", "sigma_sw", "sigma_levels", "sigma_twolevel")
+                         "sigma_cluster", "sigma_sw", "sigma_levels", "sigma_twolevel", "schwinger_or_block")
 
 
 def _hipcc():

@@ -2,7 +2,7 @@
 cover: every task / cell of the region is taken by exactly one (wave, lane, slot), none outside it.  The kernels'
 results do not depend on which lane computes what (GPU tests: bit-identical states over 134 hashed draws against the
 linear hand-out), but a hole or a double in a map would be a silent wrong answer on the device, so the arithmetic of
-schwinger_sweeps.hip `PermTasks::task` and of the `kMapped` phases of `schwinger_image_heat` is pinned here.
+schwinger_perm.hpp `PermTasks::task` and of the `kMapped` phases of `schwinger_image_heat` (schwinger_sweeps.hip) is pinned here.
 (Reference semantics of what is mapped: quenchedschwingeraction.cc:46-65; the map itself has no counterpart there.)"""
 import itertools
 
