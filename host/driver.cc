@@ -15,6 +15,10 @@
 //   driver --action nonlinearsigma --Mt_lat 16 --beta 1 --coarsening rotate --sampler hierarchical --coarsesampler heatbath --n_level 3
 //   driver --action nonlinearsigma --Mt_lat 16 --beta 1.5 --sampler wolff --n_updates 10 --n_samples 20000
 //          (Wolff single-cluster updates over the four links per vertex; prints chi_m and the mean cluster size)
+//   driver --action nonlinearsigma --Mt_lat 16 --beta 1.5 --coarsening rotate --sampler hierarchical --coarsesampler levelwolff
+//          --n_level 2 --n_updates 40
+//          (the Wolff sampler on the coarsest level of a hierarchical or --method twolevel run, n_updates cluster updates per coarse
+//           draw: the rotated level with --n_level 2, the unrotated M/2 level with --n_level 3)
 //   driver --action nonlinearsigma --Mt_lat 16 --beta 1.5 --sampler swendsenwang --n_updates 1 --n_samples 20000
 //          (Swendsen-Wang multi-cluster updates; prints chi_m, its cluster-improved estimator and the clusters per update)
 //   driver --action rotor --M_lat 256 --T_final 25.6 --m0 0.25 --sampler cluster --n_updates 10 --n_samples 20000
@@ -94,6 +98,22 @@ int main(int argc, char **argv) {
   if (o["coarsesampler"] == "wolff")
     fatal(" --coarsesampler wolff is not supported: the wolff sampler is a single-level sampler of the nonlinear sigma model, "
           "whose hierarchical and two-level runs sample the coarse level with --coarsesampler heatbath (DESIGN.md 4.4a)");
+  // --coarsesampler levelwolff: the same sampler on the coarsest level of a two-level or hierarchical sigma-model run, whichever
+  // orientation that level has (mlmcpi_sigma_level_cluster_draw)
+  if (o["sampler"] == "levelwolff")
+    fatal(" --sampler levelwolff is not supported: levelwolff names the Wolff sampler as a coarse sampler (--coarsesampler levelwolff "
+          "with --method twolevel or --sampler hierarchical); the single-level sampler is --sampler wolff");
+  if (o["coarsesampler"] == "levelwolff") {
+    if (a != "nonlinearsigma")
+      fatal(" --coarsesampler levelwolff is not supported for chosen action: the Wolff cluster update is built for nonlinearsigma only "
+            "(the rotor has --coarsesampler cluster)");
+    if (o["method"] == "throughput" || (o["method"] != "twolevel" && o["sampler"] != "hierarchical"))
+      fatal("nonlinearsigma: --coarsesampler levelwolff needs --method twolevel or --sampler hierarchical (and not --method throughput): "
+            "with --method " + o["method"] + " --sampler " + o["sampler"] + " no coarse level is sampled; the single-level sampler is --sampler wolff");
+    if (o["coarsening"] != "rotate")
+      fatal("nonlinearsigma: --coarsesampler levelwolff needs --coarsening rotate, not " + o["coarsening"] +
+            ": this action coarsens by rotate only (nonlinearsigmaaction.hh:143-149)");
+  }
   // --sampler swendsenwang: the multi-cluster sampler of the sigma model (sampler.hh SwendsenWangSampler)
   if (o["sampler"] == "swendsenwang" && a != "nonlinearsigma")
     fatal(" swendsenwang sampler not supported for chosen action: it is built for nonlinearsigma only (the rotor and schwinger have "
@@ -142,9 +162,9 @@ int main(int argc, char **argv) {
     if (levels && o["coarsening"] != "rotate")
       fatal("nonlinearsigma: " + std::string(o["method"] == "twolevel" ? "--method twolevel" : "--sampler hierarchical") +
             " needs --coarsening rotate, not " + o["coarsening"] + ": this action coarsens by rotate only (nonlinearsigmaaction.hh:143-149)");
-    if (levels && o["coarsesampler"] != "heatbath")
+    if (levels && o["coarsesampler"] != "heatbath" && o["coarsesampler"] != "levelwolff")
       fatal("nonlinearsigma: the coarse level of a twolevel or hierarchical run is sampled by --coarsesampler heatbath only, not " +
-            o["coarsesampler"]);
+            o["coarsesampler"] + " (or by --coarsesampler levelwolff: Wolff cluster updates on that level)");
     if (o["renormalisation"] == "exact" && levels)
       fatal("nonlinearsigma: non-perturbative renormalisation not implemented for non-linear sigma model.");
     action = std::make_shared<NonlinearSigmaAction>(lat, nullptr, renorm, num("beta"));
@@ -182,7 +202,7 @@ int main(int argc, char **argv) {
       cp.n_burnin = (unsigned)num("n_burnin"); cp.n_updates = (unsigned)num("n_updates"); cp.batch = batch;
       return std::make_shared<ClusterSamplerFactory>(cp);
     }
-    if (name == "wolff") {
+    if (name == "wolff" || name == "levelwolff") {  // levelwolff: on whatever level the hierarchy hands it (checked above)
       ClusterParameters cp;
       cp.n_burnin = (unsigned)num("n_burnin"); cp.n_updates = (unsigned)num("n_updates"); cp.batch = batch;
       return std::make_shared<WolffClusterSamplerFactory>(cp);

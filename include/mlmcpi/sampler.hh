@@ -524,7 +524,10 @@ private:
   const ClusterParameters param;
 };
 
-/** The Wolff single-cluster sampler of the O(3) nonlinear sigma model (mlmcpi_sigma_cluster_draw).  It is NOT
+/** The Wolff single-cluster sampler of the O(3) nonlinear sigma model on either kind of lattice (mlmcpi_sigma_level_cluster_draw
+ *  with the action's level: the unrotated lattice delegates to mlmcpi_sigma_cluster_draw, the same bits; the rotated level of
+ *  the CoarsenRotate hierarchy runs sigma_level_cluster.hip, so the sampler can be the coarse sampler of a two-level or
+ *  hierarchical run; everything is sized by the level's n = sample_size / 2 vertices).  It is NOT
  *  the reference's ClusterSampler for this action: single_cluster_update (clustersampler.cc:52-89) bonds all eight entries of
  *  Lattice2D::neighbour_vertices while the action couples four, which samples another model; this is the same
  *  walk over the four links per vertex the action has.  One draw = n_updates updates of every chain in one launch, then the
@@ -539,7 +542,8 @@ public:
     if ((uint64_t)n_updates * (action->sample_size() / 2) > 0xFFFFFFFFull)
       fatal("WolffClusterSampler: n_updates x vertices must stay below 2^32 (the per-chain counter of one draw).");
     size_t bytes = 0;
-    check(mlmcpi_sigma_cluster_workspace_bytes(&action->abi_action(), B, &bytes), "sigma_cluster_workspace_bytes");
+    const mlmcpi_sigma_level lv = action->level();
+    check(mlmcpi_sigma_level_cluster_workspace_bytes(&lv, B, &bytes), "sigma_level_cluster_workspace_bytes");
     work = std::make_shared<DeviceBuffer>(bytes);
     // an update flips at most N = sample_size / 2 vertices: fold before 2^31 could have been added to a chain's counter
     fold_period = std::max<uint64_t>(1, std::min<uint64_t>(1024, (1ull << 32) / ((uint64_t)std::max(1u, n_updates) * action->sample_size())));
@@ -559,9 +563,10 @@ public:
   }
   void draw(std::shared_ptr<SampleState> phi_state) override {
     if (update_counter > 0xFFFFFFFFu - n_updates) fatal("WolffClusterSampler: the 32-bit update counter of the Philox contract is used up.");
-    check(mlmcpi_sigma_cluster_draw(&action->abi_action(), phi_state_cur->device_mutable(), B, n_updates, action->get_seed(),
-                                    action->get_chain0(), update_counter, (uint32_t *)sites.ptr(), work->p, nullptr),
-          "sigma_cluster_draw");
+    const mlmcpi_sigma_level lv = action->level();
+    check(mlmcpi_sigma_level_cluster_draw(&lv, phi_state_cur->device_mutable(), B, n_updates, action->get_seed(),
+                                          action->get_chain0(), update_counter, (uint32_t *)sites.ptr(), work->p, nullptr),
+          "sigma_level_cluster_draw");
     update_counter += n_updates;
     updates_counted += n_updates;
     if (++draws_unfolded >= fold_period) fold_sites();

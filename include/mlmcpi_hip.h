@@ -561,6 +561,22 @@ int mlmcpi_sigma_level_copy_from_fine(const mlmcpi_sigma_level *fine, const doub
                                       void *stream);
 int mlmcpi_sigma_level_copy_from_coarse(const mlmcpi_sigma_level *fine, const double *d_coarse, double *d_fine, uint32_t B,
                                         void *stream);
+/* The Wolff single-cluster update on a level (sigma_level_cluster.hip): n_updates updates of every chain of
+ * d_state [B][2 n], in place.  Unrotated: mlmcpi_sigma_cluster_* on (Mt, Mx, beta), the same bits.  Rotated: the level is
+ * bipartite, every link has one E end; its 2 n links are (e, d), e an E vertex (e < n / 2), d its direction in the order above;
+ * from O(a, b), direction d' crosses link (neighbour, 3 - d').  Where a plane extent is 1 several neighbours of a vertex
+ * coincide: distinct links, a uniform each.  Philox, step = update0 + k: purpose 19 site 0 sub 0 (u, v) -> r (r_z = 1 - 2 u,
+ * azimuth 2 pi v - pi), sub 1 u -> seed vertex min(floor(u n), n - 1); purpose 20 site e sub d >> 1: u decides link (e, d) for
+ * d even, v for d odd.  With a_l = r . sigma_l BEFORE the update, link (x, y) is bonded iff (a_x a_y) > 0 and its uniform <
+ * 1 - exp(min(0, -2 beta (a_x a_y))); the component of the seed is reflected, sigma' = sigma - 2 a r, canonical form.  The
+ * state does not depend on launch plan (MLMCPI_SIGMA_CLUSTER_TEAM / _BITMAP govern this kernel too), batch split, chain0
+ * or call split.  Workspace: 12 B per vertex and chain (the queue) plus a bit per vertex; its content at entry is ignored.
+ * d_cluster_sites (uint32 [B], may be NULL) is ADDED to.  MLMCPI_ERR_INVALID: NULL level, odd or zero extents, Mt Mx > 2^30,
+ * beta <= 0, no workspace, B = 0, update0 + n_updates beyond 32 bits. */
+int mlmcpi_sigma_level_cluster_workspace_bytes(const mlmcpi_sigma_level *level, uint32_t B, size_t *bytes);
+int mlmcpi_sigma_level_cluster_draw(const mlmcpi_sigma_level *level, double *d_state, uint32_t B, uint32_t n_updates,
+                                    uint64_t seed, uint32_t chain0, uint32_t update0, uint32_t *d_cluster_sites,
+                                    void *d_work, void *stream);
 /* NonlinearSigmaConditionedFineAction (nonlinearsigmaconditionedfineaction.cc:7-44) on a level.  Every fine-only vertex (the
  * (i + j) odd ones of an unrotated level, the O plane of a rotated one) has coarse neighbours only, so the fill is a product of
  * independent heat-bath laws and _evaluate is minus the log of its density.

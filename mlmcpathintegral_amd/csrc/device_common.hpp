@@ -229,9 +229,10 @@ enum Purpose : uint32_t {
   P_SWEEP_ORDER = 18,      // random-order sweep (random_sweep.hip), site l >> 2, step = the sweep's counter, sub 0: word l & 3 of the
                            // call is the 32-bit key of index l; the sweep visits the indices of a chain in ascending (key, l)
   P_SIGMA_REFLECT = 19,    // sigma-model Wolff update (sigma_cluster.hip), site 0, step = update counter: sub 0 (u, v) -> normal r with
-                           // r_z = 1 - 2 u, azimuth 2 pi v - pi; sub 1 u -> seed vertex min(floor(u N), N - 1)
+                           // r_z = 1 - 2 u, azimuth 2 pi v - pi; sub 1 u -> seed vertex min(floor(u N), N - 1) (N: the level's vertices)
   P_SIGMA_BOND = 20,       // sigma-model Wolff update, site = vertex l, step = update counter, sub 0: u decides link (l, 0) (to the +i
-                           // neighbour), v decides link (l, 1) (to the +j neighbour)
+                           // neighbour), v decides link (l, 1) (to the +j neighbour).  On a rotated level (sigma_level_cluster.hip):
+                           // site = the E vertex e of the link, sub d >> 1 (0 or 1): u decides link (e, d) for d even, v for d odd
   P_SIGMA_SW_REFLECT = 21, // sigma-model Swendsen-Wang update (sigma_sw.hip), site 0, step = update counter, sub 0: (u, v) -> normal r
                            // by the map of purpose 19 sub 0
   P_SIGMA_SW_BOND = 22,    // Swendsen-Wang update, site = vertex l, sub 0: u decides link (l, 0), v decides link (l, 1)

@@ -468,6 +468,26 @@ def sigma_level_copy_from_coarse(fine_level, coarse, fine):
     return fine
 
 
+def sigma_level_cluster_workspace(level, B, device="cuda"):
+    """workspace of sigma_level_cluster_draw for B chains (uint8 tensor)"""
+    nbytes = C.c_size_t(0)
+    abi.call("mlmcpi_sigma_level_cluster_workspace_bytes", C.byref(level), B, C.byref(nbytes))
+    return torch.empty(nbytes.value, dtype=torch.uint8, device=device)
+
+
+def sigma_level_cluster_draw(level, x, n_updates, seed, chain0, update0, count=True, work=None):
+    """Wolff single-cluster updates on a level, rotated or not (mlmcpi_sigma_level_cluster_draw): n_updates updates of every
+    chain of x [B, 2 n], in place, update counters update0 + k; returns the flipped vertices per chain of this call (int32 [B];
+    None with count=False)"""
+    _check_state(x, sigma_level_size(level))
+    if work is None:
+        work = sigma_level_cluster_workspace(level, x.shape[0], x.device)
+    sites = torch.zeros(x.shape[0], dtype=torch.int32, device=x.device) if count else None
+    abi.call("mlmcpi_sigma_level_cluster_draw", C.byref(level), _p(x), x.shape[0], n_updates, seed, chain0, update0, _p(sites),
+             _p(work), _stream())
+    return sites
+
+
 def sigma_cfa_fill(fine_level, x, seed, chain0, step):
     """NonlinearSigmaConditionedFineAction::fill_fine_points, in place"""
     _check_state(x, sigma_level_size(fine_level))
