@@ -431,7 +431,7 @@ typedef struct mlmcpi_sweep_launch {
   uint32_t tile_w, tile_h, tiles_x; /* owned tile and tiles per row of tiles */
   uint32_t fixed_tile;              /* 1: the tile extents are template arguments of the generic kernels */
   uint32_t step;                    /* 1: Schwinger heat bath from the step envelope (2 beta <= 16), 0: wrapped Cauchy */
-  uint32_t planes;                  /* closed-form kernels: the plane is built in one piece or two (else 0) */
+  uint32_t planes;                  /* closed-form kernels: builds of the plane of plaquettes per workgroup, 1 since the plane is packed to its read set (else 0) */
   uint32_t pool_cap;                /* schwinger_sweep_kernel heat bath: entries of the list of open cells */
   uint32_t kinds;                   /* generic kernels: bit q set = sweep q of the launch is a heat-bath sweep */
 } mlmcpi_sweep_launch;

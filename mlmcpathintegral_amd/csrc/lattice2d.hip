@@ -151,21 +151,18 @@ static int next_launch(const SweepPlan &p, uint32_t s, SweepLaunch *out) {
       // the last overrelaxation launch takes the heat-bath sweep behind it along, and the QoI if that ends the draw
       // at most one workgroup per CU: sixteen waves (MLMCPI_OR_HEAT=wide|narrow forces)
       const bool wide = p.tune.or_heat_wide ? p.tune.or_heat_wide > 0 : (uint64_t)l.grid_x * p.B <= kComputeUnits;
-      using PHG = PermHeatGeom<512, true>;
-      // one plane for all 68 rows where it fits: beside a second workgroup (narrow) or in the whole LDS (wide)
-      const size_t lds_max = wide ? (size_t)156 * 1024 : HeatImageGeom::hb_bytes;
-      l.planes = PHG::lds_bytes(K, 1) <= lds_max ? 1 : 2;
-      if (PHG::lds_bytes(K, l.planes) > lds_max) return fail(MLMCPI_ERR_INVALID, "closed-form plane of %u sweeps does not fit", K);
+      // (the packed plane of either workgroup size lies inside the image's LDS at every depth: one build, planes = 1)
+      l.planes = 1;
       l.kernel = MLMCPI_K_SCHWINGER_PERM_HEAT;
       l.n_heatbath = 1;
       l.threads = wide ? 1024 : 512;
       l.step = p.step;
-      l.lds_bytes = (uint32_t)PHG::lds_bytes(K, l.planes);
+      l.lds_bytes = (uint32_t)PermHeatGeom<512, true>::lds_bytes;
     } else {
       l.kernel = MLMCPI_K_SCHWINGER_PERM;
       l.threads = 512;
-      l.planes = (p.perm64 ? PermGeom<512, 0, 64>::plane_bytes(K, 1) : PermGeom<512, 0, 32>::plane_bytes(K, 1)) <= kPermPlaneMax ? 1 : 2;
-      l.lds_bytes = (uint32_t)(p.perm64 ? perm_lds_bytes<64>(K, l.planes) : perm_lds_bytes<32>(K, l.planes));
+      l.planes = 1;
+      l.lds_bytes = (uint32_t)(p.perm64 ? perm_lds_bytes<64>() : perm_lds_bytes<32>());
     }
     return MLMCPI_OK;
   }

@@ -137,9 +137,9 @@ template <int NT, bool STEP>
 struct PermHeatGeom {
   using PG = PermGeom<NT, 2>;
   using OH = HeatImageGeom;
-  static constexpr size_t lds_bytes(uint32_t K, uint32_t NB) {
-    return OH::pool_bytes + (PG::plane_bytes(K, NB) > OH::image_bytes ? PG::plane_bytes(K, NB) : OH::image_bytes);
-  }
+  // (the packed plane of every depth is smaller than the image: one build, one LDS size)
+  static constexpr size_t lds_bytes = OH::pool_bytes + (PG::plane_bytes > OH::image_bytes ? PG::plane_bytes : OH::image_bytes);
+  static_assert(PG::plane_bytes <= OH::image_bytes, "the plane lies where the image follows it");
 };
 
 // ---- launchers: one SweepLaunch each --------------------------------------------------------------------------------

@@ -59,34 +59,44 @@ __device__ unsigned long long g_stamps[16 * 65536];
 // U + 1 rows in flight per thread.  W + 1 <= Mt and rows + 1 <= Mx are not required: columns and rows wrap as often as
 // needed (a 64 x 64 lattice is its own halo).
 #ifndef MLMCPI_PERM_U
-#define MLMCPI_PERM_U 0    // rows in flight per thread in the first plane build; 0 = all of a thread's rows at the deepest launch (19 at 512 threads; r05: one round trip to HBM instead of two, 10 + 9 rows: -4.2 % on the launch, same-box A/B)
+#define MLMCPI_PERM_U 0    // rows in flight per thread in the plane build; 0 = all of a thread's rows at the deepest launch (r05: one round trip to HBM instead of two: -4.2 % on the launch, same-box A/B)
 #endif
 
 // The plane in LDS.  Every stream of the closed form walks a diagonal of the plaquettes of ONE parity class: column and
 // row parity do not change along it, the column moves by 2 e_c and the row by +-2 per step s.  So the plane is kept as four
-// quadrants by (column parity, row parity), each Rh = rows / 2 rows of Wh = WP / 2 values, with the ODD index mirrored:
-//     column C -> u = C / 2 (C even),  Wh - 1 - (C - 1) / 2 (C odd);      row R -> v = R / 2,  Rh - 1 - (R - 1) / 2 likewise.
+// quadrants by (column parity, row parity) with the ODD index mirrored, and -- an even index only grows along a stream, an
+// odd one only falls -- each quadrant holds only the columns and rows of its parity that some task reads (PermGeom: the
+// read set, col_first .. col_last, row_first .. row_last):
+//     column C -> u = (C - col_first(K, 0)) / 2 (C even),  (col_last(K, 1) - C) / 2 (C odd);      row R -> v likewise.
 // A step of any stream of any task is then (u, v) -> (u + 1, v + 1): ONE byte stride, kStep, for all of them -- whatever
-// the parities, mu = 0 or 1 -- and with the pitch WP a compile-time constant (the width of the deepest launch, kPermMaxK
-// sweeps; a shallower one leaves columns unused) the K reads of a stream are K immediate offsets from one address.  (The
-// row-major plane this replaces cost 6.6 integer instructions of address arithmetic per read: a third of the launch's
-// vector instructions outside the heat bath.)  Same values, same order of additions: results are bit for bit those of the
-// row-major form.
-template <int WP>
+// the parities, mu = 0 or 1 -- and with the pitch and the quadrant size compile-time constants (the extents of the deepest
+// launch, kPermMaxK sweeps; a shallower one leaves columns and rows unused) the K reads of a stream are K immediate
+// offsets from one address, and the address of a task's first read does not depend on K: in output coordinates (c, r)
+// the read set begins where the tasks do.  (The row-major plane this replaces cost 6.6 integer instructions of address
+// arithmetic per read; the four full quadrants of (OW / 2 + 2 K) x (HR / 2 + 2 K) after it held a third more plaquettes than
+// anybody reads and did not fit for both halves at once beyond K = 6.)  Same values, same order of additions: results are
+// bit for bit those of the row-major form.
+template <class PG>
 struct PermPlane {
-  static constexpr int Wh = WP / 2, kRow = Wh * 8, kStep = kRow + 8;   // bytes
-  uint32_t Rh, QB;                                                      // rows per quadrant; bytes per quadrant
-  __device__ __forceinline__ explicit PermPlane(uint32_t rows) : Rh(rows / 2), QB((rows / 2) * (uint32_t)kRow) {}
-  // byte offset of plaquette (C, R) = col(C) + row(R)
-  __device__ __forceinline__ uint32_t col(uint32_t C) const { return (C & 1u) ? QB + (uint32_t)(Wh - 1 - (int)(C >> 1)) * 8u : (C >> 1) * 8u; }
-  __device__ __forceinline__ uint32_t row(uint32_t R) const { return (R & 1u) ? 2u * QB + (Rh - 1u - (R >> 1)) * (uint32_t)kRow : (R >> 1) * (uint32_t)kRow; }
+  static constexpr int kRow = PG::kPitch * 8, kStep = kRow + 8;        // bytes
+  static constexpr uint32_t QB = (uint32_t)PG::kQRows * kRow;          // bytes per quadrant
+  static_assert(kStep == (int)PG::kStep * 8, "the stride of a stream");
+  uint32_t K;
+  __device__ __forceinline__ explicit PermPlane(uint32_t K_) : K(K_) {}
+  // is column C / row R of the plane in the read set?  (C < width(K), R < rows(K))
+  __device__ __forceinline__ bool has_col(uint32_t C) const { return (C & 1u) ? C <= PG::col_last(K, 1) : C >= PG::col_first(K, 0) && C <= PG::col_last(K, 0); }
+  __device__ __forceinline__ bool has_row(uint32_t R) const { return (R & 1u) ? R <= PG::row_last(K, 1) : R >= PG::row_first(K, 0) && R <= PG::row_last(K, 0); }
+  // byte offset of plaquette (C, R) of the read set = col(C) + row(R)
+  __device__ __forceinline__ uint32_t col(uint32_t C) const { return (C & 1u) ? QB + PG::col_u(K, C) * 8u : PG::col_u(K, C) * 8u; }
+  __device__ __forceinline__ uint32_t row(uint32_t R) const { return (R & 1u) ? 2u * QB + PG::row_v(K, R) * (uint32_t)kRow : PG::row_v(K, R) * (uint32_t)kRow; }
 };
 
 // where a thread stands in a build: its theta column, its rows [r, rend) of the `rows`, whether it owns a plaquette column
 struct PermBuildPos {
   uint32_t c, r, rend, row_off, gj;   // row_off = gj Mt: the lattice row of build row r, in vertices (< 2^32: check_lattice)
   uint32_t cb;                        // PermPlane::col of the plaquette column
-  const double2 *p;                   // src + the lattice column
+  const double2 *src;                 // the chain (uniform: with the scalar row offset the base of a row's loads) ...
+  uint32_t col;                       // ... and the thread's lattice column
   bool active, owns;
 };
 template <int NT, class PP>
@@ -101,13 +111,18 @@ __device__ __forceinline__ PermBuildPos perm_build_pos(const PP &P, const double
   static_assert(((NT / kWave) & (NT / kWave - 1)) == 0, "waves per workgroup: a power of two (shifts for divisions)");
   const uint32_t rpg = groups == 4 ? (rows + 3) >> 2 : groups == 8 ? (rows + 7) >> 3 : (rows + groups - 1) / groups;
   q.c = 63 * cw + lane;                                                // theta column; the plaquette column of lanes 0 .. 62
-  q.r = g * rpg;
-  q.rend = g < groups ? min(rows, q.r + rpg) : 0;
-  q.active = q.r < q.rend && q.c <= W;   // (not: whole waves, or the lanes beyond theta column W, which nobody reads)
-  q.owns = lane < 63 && q.c < W;
+  // (rows and row offsets are the same for a whole wave; said so explicitly, so that the conditions on them below are scalar
+  // branches: behind a vector condition every load of the chunk waits for the one before it)
+  q.r = __builtin_amdgcn_readfirstlane(g * rpg);
+  q.rend = __builtin_amdgcn_readfirstlane(g < groups ? min(rows, q.r + rpg) : 0);
+  q.active = q.r < q.rend;               // (wave-uniform: not the waves without rows)
+  q.owns = lane < 63 && q.c < W && P.has_col(q.c);   // (a wing column is loaded for its neighbour's theta_1 and owns nothing)
   q.cb = P.col(q.c);
-  q.p = src + wrap_add(gi0, q.c, Mt);
-  q.gj = wrap_add(gj0, q.r, Mx);
+  // (the lanes beyond theta column W, which nobody reads, load column W again: a lane condition on the loads would make
+  // vector branches of the scalar ones around them, and every load would wait for the one before it)
+  q.src = src;
+  q.col = wrap_add(gi0, min(q.c, W), Mt);
+  q.gj = __builtin_amdgcn_readfirstlane(wrap_add(gj0, q.r, Mx));
   q.row_off = q.gj * Mt;
   return q;
 }
@@ -115,38 +130,46 @@ __device__ __forceinline__ PermBuildPos perm_build_pos(const PP &P, const double
 template <int U>
 __device__ __forceinline__ void perm_rows_load(PermBuildPos &q, uint32_t Mt, uint32_t Mx, bool first, double2 &cur, double2 (&nxt)[U]) {
   if (!q.active) return;
-  if (first) cur = q.p[q.row_off];
+  if (first) cur = (q.src + q.row_off)[q.col];
 #pragma unroll
   for (int u = 0; u < U; ++u) {
     q.gj = q.gj + 1 == Mx ? 0 : q.gj + 1;
     q.row_off = q.gj == 0 ? 0 : q.row_off + Mt;
-    if (q.r + u < q.rend) nxt[u] = q.p[q.row_off];
+    if (q.r + u < q.rend) nxt[u] = (q.src + q.row_off)[q.col];
   }
 }
-// their plaquettes into the plane (build row 0 = plane row R0); cur <- the last row, for the next chunk
+// their plaquettes into the plane, those of the read set; cur <- the last row, for the next chunk
 template <int U, class PP>
-__device__ __forceinline__ void perm_rows_store(PermBuildPos &q, const PP &P, double *plane, uint32_t R0, double2 &cur, const double2 (&nxt)[U]) {
+__device__ __forceinline__ void perm_rows_store(PermBuildPos &q, const PP &P, double *plane, double2 &cur, const double2 (&nxt)[U]) {
   if (!q.active) return;
   char *const pb = reinterpret_cast<char *>(plane) + q.cb;
 #pragma unroll
   for (int u = 0; u < U; ++u)
     if (q.r + u < q.rend) {
       const double right = wave_rotate_down(cur.y);   // theta_1 of the next column
-      if (q.owns) *reinterpret_cast<double *>(pb + P.row(R0 + q.r + u)) = ((cur.x + right) - nxt[u].x) - cur.y;   // (the row part is scalar)
+      if (q.owns && P.has_row(q.r + u)) *reinterpret_cast<double *>(pb + P.row(q.r + u)) = ((cur.x + right) - nxt[u].x) - cur.y;   // (the row part is scalar)
       cur = nxt[u];
     }
   q.r += U;
 }
-template <int NT, int U, class PP>
+// ONCE: U covers a thread's rows at every depth -- no loop, whose back edge would make every load of a chunk wait for the
+// loads of the chunk before (their registers are the ones it is about to fill)
+template <int NT, int U, bool ONCE, class PP>
 __device__ __forceinline__ void perm_build_rows(const PP &P, double *plane, const double2 *__restrict__ src, uint32_t Mt, uint32_t Mx,
                                                 uint32_t gi0, uint32_t gj0, uint32_t W, uint32_t rows) {
   PermBuildPos q = perm_build_pos<NT>(P, src, Mt, Mx, gi0, gj0, W, rows);
   double2 cur = make_double2(0., 0.);
+  if (ONCE) {
+    double2 nxt[U];
+    perm_rows_load<U>(q, Mt, Mx, true, cur, nxt);
+    perm_rows_store<U>(q, P, plane, cur, nxt);
+    return;
+  }
   bool first = true;
   while (__builtin_amdgcn_readfirstlane(q.r) < __builtin_amdgcn_readfirstlane(q.rend)) {   // (uniform per wave)
     double2 nxt[U];
     perm_rows_load<U>(q, Mt, Mx, first, cur, nxt);
-    perm_rows_store<U>(q, P, plane, 0u, cur, nxt);
+    perm_rows_store<U>(q, P, plane, cur, nxt);
     first = false;
   }
 }
@@ -257,16 +280,16 @@ __device__ __forceinline__ void perm_gather1(uint32_t pa, uint32_t px, uint32_t 
 // res[h][k] = the new angles of the two links of task k of half h
 template <int NT, int RING, int TH = 64>
 __device__ __forceinline__ void perm_sweeps(double *plane, const double2 *__restrict__ src, uint32_t Mt, uint32_t Mx, uint32_t i0,
-                                            uint32_t j0, uint32_t K, uint32_t NB, double2 (&res)[2][PermGeom<NT, RING, TH>::NV]) {
+                                            uint32_t j0, uint32_t K, double2 (&res)[2][PermGeom<NT, RING, TH>::NV]) {
   using PG = PermGeom<NT, RING, TH>;
-  using PP = PermPlane<PG::WP>;
+  using PP = PermPlane<PG>;
   constexpr int HR = PG::HR, NV = PG::NV;
-  // all of a thread's rows at the deepest launch: (HR + 4 kPermMaxK) rows over (NT / 64) / 2 row groups (W > 63: two column waves)
+  // all of a thread's rows at the deepest launch: (2 HR + 4 kPermMaxK) rows over (NT / 64) / 2 row groups (W > 63: two column waves)
   constexpr int kGroups = NT / kWave / 2;
-  constexpr int U = MLMCPI_PERM_U ? MLMCPI_PERM_U : (HR + 4 * (int)kPermMaxK + kGroups - 1) / kGroups, UB = (HR + kGroups - 1) / kGroups;   // rows in flight per thread: first build (nothing else is live yet), new rows of the second
-  const uint32_t W = PG::width(K), rows = PG::rows(K, NB), H = RING + 2 * K;
-  const PP P(rows);
-  // lattice coordinates of plane (0, 0) of the first build, and of output vertex (0, 0)
+  constexpr int U = MLMCPI_PERM_U ? MLMCPI_PERM_U : (2 * HR + 4 * (int)kPermMaxK + kGroups - 1) / kGroups;   // rows in flight per thread (nothing else is live yet)
+  const uint32_t W = PG::width(K), rows = PG::rows(K), H = RING + 2 * K;
+  const PP P(K);
+  // lattice coordinates of plane (0, 0), and of output vertex (0, 0)
   // (x - h) mod n for x < n: a comparison where h <= n -- the rule; the two modulo operations of the general form are ~80
   // instructions each in front of the first load of the workgroup
   auto back = [](uint32_t x, uint32_t h, uint32_t n) { return h <= n ? (x >= h ? x - h : x + n - h) : (x + n - h % n) % n; };
@@ -307,30 +330,30 @@ __device__ __forceinline__ void perm_sweeps(double *plane, const double2 *__rest
   };
   // what K sweeps add to them
   auto gather = [&](int h, double2 (&d)[NV]) {
-    const uint32_t row_off = 2 * K + (NB == 2 ? 0 : h * HR);  // plane row of output row 0 of this half (even)
     const uint32_t lds0 = (uint32_t)(uintptr_t)plane;   // the LDS byte address of the plane (lds_read_f64)
 #pragma unroll
     for (int k = 0; k < NV; ++k) {
       if (!tasks.valid(k)) continue;
       uint32_t r, c;
       tasks.coords(k, r, c);
-      // the shared stream, the first of the two others and the second, at s = 0 (plane coordinates C = c + 2 K, R = r + row_off):
+      // the shared stream, the first of the two others and the second, at s = 0 (plane coordinates C = c + 2 K, R = r + h HR + 2 K):
       //   mu = 0 (R even): A_s = P(C + 2 s e_C, R - 1 - 2 s), B_s = P(C + 2 s e_C, R + 2 s), B'_s two rows above B_s;
       //   mu = 1 (C even): D_s = P(C - 1 - 2 s, J_s), J_s = R + 2 (s + 1) e_R, C_s = P(C + 2 s, J_s), C'_s two columns on;
-      // in quadrant coordinates every one of them advances by (1, 1) per s
-      const uint32_t C = c + 2 * K, R = r + row_off, Rq = R >> 1;
+      // in quadrant coordinates every one of them advances by (1, 1) per s, and where it starts does not depend on K: the
+      // read set begins at the tasks (PermGeom::col_u, row_v with C = c + 2 K, R = ro + 2 K written out in c and ro)
+      const uint32_t ro = r + (uint32_t)(h * HR), cq = c >> 1, rq = ro >> 1;
       uint32_t a, x, x2;
       if (!tasks.is_mu1(k)) {
-        const uint32_t cb = P.col(C);
-        x = cb + Rq * (uint32_t)PP::kRow;                       // row R, even: v = R / 2
+        const uint32_t cb = (c & 1u) ? PP::QB + ((uint32_t)(PG::OW / 2 - 1) - cq) * 8u : cq * 8u;   // = P.col(C)
+        x = cb + rq * (uint32_t)PP::kRow;                                             // row R, even: v = ro / 2
         x2 = x + (uint32_t)PP::kRow;
-        a = cb + 2u * P.QB + (P.Rh - Rq) * (uint32_t)PP::kRow;  // row R - 1, odd: v = Rh - 1 - (R / 2 - 1)
+        a = cb + 2u * PP::QB + ((uint32_t)(HR - 1) - rq) * (uint32_t)PP::kRow;        // row R - 1, odd: v = OH / 2 - 1 - ro / 2
       } else {
-        // J_0 = R + 2 (v = R / 2 + 1) for even R, R - 2 (v = Rh - 1 - ((R - 1) / 2 - 1)) for odd R
-        const uint32_t rb = (R & 1u) ? 2u * P.QB + (P.Rh - Rq) * (uint32_t)PP::kRow : (Rq + 1u) * (uint32_t)PP::kRow;
-        x = rb + (C >> 1) * 8u;                                  // column C, even: u = C / 2
+        // J_0 = R + 2 (v = ro / 2 + 1) for even R, R - 2 (v = OH / 2 - 1 - (ro - 1) / 2) for odd R
+        const uint32_t rb = (ro & 1u) ? 2u * PP::QB + ((uint32_t)(HR - 1) - rq) * (uint32_t)PP::kRow : (rq + 1u) * (uint32_t)PP::kRow;
+        x = rb + cq * 8u;                                                             // column C, even: u = c / 2
         x2 = x + 8u;
-        a = rb + P.QB + ((uint32_t)PP::Wh - (C >> 1)) * 8u;      // column C - 1, odd: u = Wh - 1 - (C / 2 - 1)
+        a = rb + PP::QB + ((uint32_t)(PG::OW / 2) - cq) * 8u;                         // column C - 1, odd: u = OW / 2 - c / 2
       }
       uint32_t pa = lds0 + a, px = lds0 + x, px2 = lds0 + x2;
       double S = 0.0, X = 0.0, X2 = 0.0;
@@ -356,61 +379,18 @@ __device__ __forceinline__ void perm_sweeps(double *plane, const double2 *__rest
       if (tasks.valid(k)) d[k] = make_double2(mod_2pi_fast(th[k].x + d[k].x), mod_2pi_fast(th[k].y + d[k].y));
   };
 
-  perm_build_rows<NT, U>(P, plane, src, Mt, Mx, gi0, gj0, W, rows);
+  perm_build_rows<NT, U, MLMCPI_PERM_U == 0>(P, plane, src, Mt, Mx, gi0, gj0, W, rows);
+  // one plane: first half (its angles are in flight across the barrier and the first reads of the plane), second half
   double2 th[NV];
-  if (NB == 1) {
-    // one plane: first half (its angles are in flight across the barrier and the first reads of the plane), second half
-    load_theta(0, th);
-    __syncthreads();
-    MLMCPI_STAMP(1);  // plane built
-    gather(0, res[0]);
-    finish(th, res[0]);
-    MLMCPI_STAMP(2);  // first half gathered
-    load_theta(1, th);
-    gather(1, res[1]);
-    finish(th, res[1]);
-    return;
-  }
-  // NB = 2: the HR new rows of the second plane are loaded while the first half is gathered (at most UB rows per thread:
-  // HR / 4 row groups); the angles of the first half only after it, so that the gather has the registers
-  PermBuildPos qb = perm_build_pos<NT>(P, src, Mt, Mx, gi0, wrap_add(gj0, rows, Mx), W, HR);
-  double2 curb = make_double2(0., 0.), vb[UB];
+  load_theta(0, th);
   __syncthreads();
   MLMCPI_STAMP(1);  // plane built
-  perm_rows_load<UB>(qb, Mt, Mx, true, curb, vb);
   gather(0, res[0]);
+  finish(th, res[0]);
   MLMCPI_STAMP(2);  // first half gathered
-  // rows [HR, rows) of the plane become rows [0, rows - HR), the HR new rows go on top.  HR is even: a row keeps its parity
-  // and moves by HR / 2 quadrant rows -- down in the quadrants of the even rows, up (mirrored) in those of the odd rows
-  constexpr int NC = (4 * 2 * (int)kPermMaxK * PP::Wh + NT - 1) / NT;   // 4 quadrants x (rows - HR) / 2 = 2 K quadrant rows
-  const uint32_t nkeep = (rows - HR) / 2 * (uint32_t)PP::Wh, shift = (uint32_t)(HR / 2) * (uint32_t)PP::kRow;
-  {
-    double keep[NC];
-    char *const pbw = reinterpret_cast<char *>(plane);
-    // (a thread reads what it moves as soon as its own gather is done -- reads beside the reads of the gathers still running
-    // -- and ONE barrier separates every read of the old plane, the gathers' and these, from the writes; the barrier that
-    // used to stand in front of these reads as well was worth 0.1 % of the launch, same-box A/B)
-#pragma unroll
-    for (int q = 0; q < NC; ++q) {
-      const uint32_t idx = threadIdx.x + q * NT, e = idx >> 2, qd = idx & 3u;
-      if (e < nkeep) keep[q] = *reinterpret_cast<const double *>(pbw + qd * P.QB + e * 8u + ((qd & 2u) ? 0u : shift));
-    }
-    __syncthreads();  // the first half has read its plane, and so have the threads that move its rows
-#pragma unroll
-    for (int q = 0; q < NC; ++q) {
-      const uint32_t idx = threadIdx.x + q * NT, e = idx >> 2, qd = idx & 3u;
-      if (e < nkeep) *reinterpret_cast<double *>(pbw + qd * P.QB + e * 8u + ((qd & 2u) ? shift : 0u)) = keep[q];
-    }
-  }
-  perm_rows_store<UB>(qb, P, plane, rows - HR, curb, vb);
-  load_theta(0, th);   // (earlier -- before the rows move, or before they are stored -- costs a spill or gains nothing: EXPERIMENTS 0.1, 0.6)
-  double2 th1[NV];
-  load_theta(1, th1);
-  __syncthreads();
-  MLMCPI_STAMP(10);  // second plane built
-  finish(th, res[0]);   // (behind the gather instead: 48 bytes of spills)
+  load_theta(1, th);
   gather(1, res[1]);
-  finish(th1, res[1]);
+  finish(th, res[1]);
 }
 
 // the angles of perm_sweeps into the planes th0, th1 of an OW x 2 HR image (the caller puts barriers around it)

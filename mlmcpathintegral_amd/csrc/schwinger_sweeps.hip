@@ -437,11 +437,11 @@ __device__ __forceinline__ void schwinger_image_heat(double *th0, double *th1, V
   MLMCPI_STAMP(9);
 }
 
-// K <= kPermMaxK overrelaxation sweeps of a 64 x TH tile per workgroup; lds = perm_lds_bytes<TH>(K, NB)
+// K <= kPermMaxK overrelaxation sweeps of a 64 x TH tile per workgroup; lds = perm_lds_bytes<TH>()
 template <int TH>
 __global__ void __launch_bounds__(512, 4)
     schwinger_perm_kernel(uint32_t Mt, uint32_t Mx, const double2 *__restrict__ in, double2 *__restrict__ out, uint32_t tiles_x,
-                          uint32_t K, uint32_t NB) {
+                          uint32_t K) {
   constexpr int NT = 512;
   using PG = PermGeom<NT, 0, TH>;
   extern __shared__ double lds[];
@@ -449,7 +449,7 @@ __global__ void __launch_bounds__(512, 4)
   const uint32_t ty = tile / tiles_x, tx = tile - ty * tiles_x;
   const uint32_t i0 = tx * 64, j0 = ty * TH;
   double2 res[2][PG::NV];
-  perm_sweeps<NT, 0, TH>(lds, in + (size_t)b * Mt * Mx, Mt, Mx, i0, j0, K, NB, res);
+  perm_sweeps<NT, 0, TH>(lds, in + (size_t)b * Mt * Mx, Mt, Mx, i0, j0, K, res);
   double *th0 = lds, *th1 = lds + 64 * TH;
   __syncthreads();  // the plane is dead: the image takes its place
   perm_store_image<NT, 0, TH>(th0, th1, res);
@@ -469,7 +469,7 @@ __global__ void __launch_bounds__(512, 4)
 template <int NT, bool STEP>
 __global__ void __launch_bounds__(NT, 4)
     schwinger_perm_heat_kernel(uint32_t Mt, uint32_t Mx, double beta, const double2 *__restrict__ in, double2 *__restrict__ out,
-                               uint32_t tiles_x, uint32_t K, uint32_t NB, RngKey key0, int qoi_op, double *__restrict__ qoi_partial,
+                               uint32_t tiles_x, uint32_t K, RngKey key0, int qoi_op, double *__restrict__ qoi_partial,
                                const uint32_t *__restrict__ vs_table) {
   using PH = PermHeatGeom<NT, STEP>;
   using PG = typename PH::PG;
@@ -490,7 +490,7 @@ __global__ void __launch_bounds__(NT, 4)
   HbPool hpool = HbPool::carve(lds, STEP ? 0u : OH::hb_pool_cap);
   double *th0 = lds + OH::pool_bytes / sizeof(double), *th1 = th0 + IW * IH;
   double2 res[2][PG::NV];
-  perm_sweeps<NT, 2>(th0, in + (size_t)b * Mt * Mx, Mt, Mx, i0, j0, K, NB, res);
+  perm_sweeps<NT, 2>(th0, in + (size_t)b * Mt * Mx, Mt, Mx, i0, j0, K, res);
   MLMCPI_STAMP(3);  // K sweeps done
   VsPool<uint32_t> vpool = VsPool<uint32_t>::carve(lds, OH::pool_cap, nullptr);
   if (STEP) {
@@ -566,16 +566,16 @@ static int launch_perm(const SweepLaunch &l, const SweepArgs &a) {
   double2 *out = (double2 *)a.dst;
 #define MLMCPI_PERM_HEAT(NT, STEP)                                                                                           \
   hipLaunchKernelGGL((schwinger_perm_heat_kernel<NT, STEP>), grid, dim3(NT), l.lds_bytes, a.st, a.Mt, a.Mx, a.coupling, in, out, \
-                     l.tiles_x, l.n_overrelax, l.planes, a.key, a.qoi_op, a.qoi_partial, a.vs_table)
+                     l.tiles_x, l.n_overrelax, a.key, a.qoi_op, a.qoi_partial, a.vs_table)
   if (l.kernel == MLMCPI_K_SCHWINGER_PERM_HEAT) {
     if (l.threads == 1024 && l.step) MLMCPI_PERM_HEAT(1024, true);
     else if (l.threads == 1024) MLMCPI_PERM_HEAT(1024, false);
     else if (l.step) MLMCPI_PERM_HEAT(512, true);
     else MLMCPI_PERM_HEAT(512, false);
   } else if (l.tile_h == 64)
-    hipLaunchKernelGGL(schwinger_perm_kernel<64>, grid, dim3(512), l.lds_bytes, a.st, a.Mt, a.Mx, in, out, l.tiles_x, l.n_overrelax, l.planes);
+    hipLaunchKernelGGL(schwinger_perm_kernel<64>, grid, dim3(512), l.lds_bytes, a.st, a.Mt, a.Mx, in, out, l.tiles_x, l.n_overrelax);
   else
-    hipLaunchKernelGGL(schwinger_perm_kernel<32>, grid, dim3(512), l.lds_bytes, a.st, a.Mt, a.Mx, in, out, l.tiles_x, l.n_overrelax, l.planes);
+    hipLaunchKernelGGL(schwinger_perm_kernel<32>, grid, dim3(512), l.lds_bytes, a.st, a.Mt, a.Mx, in, out, l.tiles_x, l.n_overrelax);
 #undef MLMCPI_PERM_HEAT
   MLMCPI_LAUNCH_CHECK("schwinger closed-form kernel");
   return MLMCPI_OK;

@@ -49,27 +49,60 @@ constexpr uint32_t kPermMaxK = 10;  // sweeps per launch
 
 // K sweeps for the (64 + 2 RING) x (TH + 2 RING) vertices around a 64 x TH tile (RING = 0: the tile; RING = 2: what the heat
 // bath behind the sweeps reads; TH = 32: lattices that 64 x 32 tiles divide and 64 x 64 ones do not), in two halves of
-// HR = TH / 2 + RING rows.  NB = 1: one plane of 2 HR + 4 K rows serves both; NB = 2 (K
-// sweeps reach 2 K rows up and down: beyond K = 6 the whole plane does not fit beside a second workgroup): a plane of
-// HR + 4 K rows; for the second half its upper HR + 4 K - HR rows move down and HR new rows are built on top.
+// HR = TH / 2 + RING rows that share ONE plane of plaquettes.
 // Tasks of a half: (HR / 2) x OW column pairs (mu = 0), then HR x (OW / 2) row pairs (mu = 1); thread t takes t, t + NT, ...
+//
+// The read set.  Plane coordinates: output vertex (c, r), 0 <= c < OW, 0 <= r < OH = 2 HR, is plane (C, R) = (c + 2 K, r + 2 K);
+// all of 2 K, OW, HR and the tile origins are even, so plane, output and lattice parities agree.  From the two sums of
+// schwinger_perm.hpp, with s = 0 .. K - 1:
+//   mu = 0 task at (C, R), R even:   P(C + 2 s e_C, R - 1 - 2 s),  P(C + 2 s e_C, R + 2 s),  P(C + 2 s e_C, R + 2 + 2 s)
+//   mu = 1 task at (C, R), C even:   P(C - 1 - 2 s, J_s),  P(C + 2 s, J_s),  P(C + 2 + 2 s, J_s),   J_s = R + 2 (s + 1) e_R.
+// An index that is read at an even value only ever grows from where a task stands, one that is read at an odd value only falls:
+//   even columns:  mu = 0, C even: C .. C + 2 K - 2;  mu = 1: C .. C + 2 K                ->  [2 K, OW + 4 K - 2]
+//   odd columns:   mu = 0, C odd:  C - 2 K + 2 .. C;  mu = 1: C - 2 K + 1 .. C - 1         ->  [1, OW + 2 K - 1]
+//   even rows:     mu = 0: R .. R + 2 K;              mu = 1, R even: R + 2 .. R + 2 K    ->  [2 K, OH + 4 K - 2]
+//   odd rows:      mu = 0: R - 2 K + 1 .. R - 1;      mu = 1, R odd:  R - 2 K .. R - 2    ->  [1, OH + 2 K - 3]
+// (C over [2 K, 2 K + OW), R over [2 K, 2 K + OH) of the task's parity).  That is OW / 2 + K columns of either parity and
+// OH / 2 + K even, OH / 2 + K - 1 odd rows: each of the four (column parity, row parity) quadrants of the plane is read over
+// about (OW / 2 + K) x (OH / 2 + K) plaquettes instead of the (OW / 2 + 2 K) x (OH / 2 + 2 K) of the rectangle around them.
+// Packed (PermPlane) every quadrant is kQRows rows of kPitch values, the extents of the deepest launch: the four of them
+// fit the LDS of the image that follows them at every depth, so one build serves both halves.
 template <int NT, int RING, int TH = 64>
 struct PermGeom {
-  static constexpr int OW = 64 + 2 * RING, HR = TH / 2 + RING, NTASK = HR * OW, NV = (NTASK + NT - 1) / NT;
-  static constexpr int WP = OW + 4 * (int)kPermMaxK;   // the plane's pitch (PermPlane): the width of the deepest launch
-  static_assert(HR % 2 == 0 && OW % 2 == 0, "parities of the output = parities of the lattice; the halves move by whole quadrant rows");
+  static constexpr int OW = 64 + 2 * RING, HR = TH / 2 + RING, OH = 2 * HR, NTASK = HR * OW, NV = (NTASK + NT - 1) / NT;
+  static_assert(HR % 2 == 0 && OW % 2 == 0, "parities of the output = parities of the lattice");
+  // the plaquettes a build has to cover: columns [0, width), rows [0, rows) around the read set
   static __host__ __device__ constexpr uint32_t width(uint32_t K) { return OW + 4 * K; }
-  static __host__ __device__ constexpr uint32_t rows(uint32_t K, uint32_t NB) { return (NB == 2 ? HR : 2 * HR) + 4 * K; }
-  static __host__ __device__ constexpr size_t plane_bytes(uint32_t K, uint32_t NB) { return (size_t)WP * rows(K, NB) * sizeof(double); }
+  static __host__ __device__ constexpr uint32_t rows(uint32_t K) { return OH + 4 * K; }
+  // first and last column / row of parity `par` that any task reads
+  static __host__ __device__ constexpr uint32_t col_first(uint32_t K, uint32_t par) { return par ? 1 : 2 * K; }
+  static __host__ __device__ constexpr uint32_t col_last(uint32_t K, uint32_t par) { return par ? OW + 2 * K - 1 : OW + 4 * K - 2; }
+  static __host__ __device__ constexpr uint32_t row_first(uint32_t K, uint32_t par) { return par ? 1 : 2 * K; }
+  static __host__ __device__ constexpr uint32_t row_last(uint32_t K, uint32_t par) { return par ? OH + 2 * K - 3 : OH + 4 * K - 2; }
+  static __host__ __device__ constexpr uint32_t col_count(uint32_t K, uint32_t par) { return (col_last(K, par) - col_first(K, par)) / 2 + 1; }
+  static __host__ __device__ constexpr uint32_t row_count(uint32_t K, uint32_t par) { return (row_last(K, par) - row_first(K, par)) / 2 + 1; }
+  // a quadrant: kQRows rows of kPitch values (odd rows: one row of padding); the plane: four quadrants, whatever K
+  static constexpr int kPitch = OW / 2 + (int)kPermMaxK, kQRows = OH / 2 + (int)kPermMaxK;
+  static_assert(col_count(kPermMaxK, 0) == kPitch && col_count(kPermMaxK, 1) == kPitch, "the pitch: the columns of a parity at the deepest launch");
+  static_assert(row_count(kPermMaxK, 0) == kQRows && row_count(kPermMaxK, 1) == kQRows - 1, "the rows of a quadrant at the deepest launch");
+  static constexpr size_t plane_bytes = (size_t)4 * kQRows * kPitch * sizeof(double);
+  // the value index of plaquette (C, R) of the read set of a launch of K sweeps: the odd index mirrored, so that a step of
+  // any stream is (u, v) -> (u + 1, v + 1)
+  static __host__ __device__ constexpr uint32_t col_u(uint32_t K, uint32_t C) { return (C & 1u) ? (col_last(K, 1) - C) / 2 : (C - col_first(K, 0)) / 2; }
+  static __host__ __device__ constexpr uint32_t row_v(uint32_t K, uint32_t R) { return (R & 1u) ? (row_last(K, 1) - R) / 2 : (R - row_first(K, 0)) / 2; }
+  static __host__ __device__ constexpr uint32_t offset(uint32_t K, uint32_t C, uint32_t R) {
+    return ((R & 1u) * 2 + (C & 1u)) * (uint32_t)(kQRows * kPitch) + row_v(K, R) * (uint32_t)kPitch + col_u(K, C);
+  }
+  static constexpr uint32_t kStep = kPitch + 1;   // values per step of a stream
 };
 
 // dynamic LDS of schwinger_perm_kernel<TH>
 constexpr size_t kPermPlaneMax = 80 * 1024;  // two workgroups per CU
 template <int TH>
-__host__ __device__ constexpr size_t perm_lds_bytes(uint32_t K, uint32_t NB) {   // the plane; then the tile's image in its place
-  return PermGeom<512, 0, TH>::plane_bytes(K, NB) > 2 * 64 * TH * sizeof(double) ? PermGeom<512, 0, TH>::plane_bytes(K, NB)
-                                                                                   : 2 * 64 * TH * sizeof(double);
+__host__ __device__ constexpr size_t perm_lds_bytes() {   // the plane; then the tile's image in its place
+  return PermGeom<512, 0, TH>::plane_bytes > 2 * 64 * TH * sizeof(double) ? PermGeom<512, 0, TH>::plane_bytes : 2 * 64 * TH * sizeof(double);
 }
+static_assert(perm_lds_bytes<64>() <= kPermPlaneMax && perm_lds_bytes<32>() <= kPermPlaneMax, "the packed plane fits at every depth");
 
 // ---- GFF overrelaxation, 4 x 4 register blocks on 64 x 64 tiles ------------------------------------------------
 // The construction of schwinger_or_block_kernel for the scalar field: a thread keeps 16 sites for all K sweeps, LDS

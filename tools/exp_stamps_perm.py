@@ -10,7 +10,7 @@ from mlmcpathintegral_amd import abi, ops
 lib = abi.load()
 SEED = 7
 ORDER = [0, 1, 2, 10, 3, 4, 5, 6, 7, 8, 9]
-NAMES = ["theta_0 loads + plane A", "gather A", "plane B", "gather B", "image down", "HB mu=0 even", "HB mu=0 odd", "HB mu=1 even", "HB mu=1 odd", "write-out + QoI"]
+NAMES = ["theta_0 loads + plane (A)", "gather A", "plane B (two builds only)", "gather B", "image down", "HB mu=0 even", "HB mu=0 odd", "HB mu=1 even", "HB mu=1 odd", "write-out + QoI"]
 n_or = int(sys.argv[1]) if len(sys.argv) > 1 else 10
 for B in (32, 1):
     act = abi.lattice_action(abi.SCHWINGER, 1024, 1024, beta=1.0)
@@ -25,7 +25,7 @@ for B in (32, 1):
     rc = lib.mlmcpi_debug_read_stamps(buf.ctypes.data_as(C.c_void_p), C.c_uint32(n))
     assert rc == 0
     t = buf[:, ORDER].astype(np.int64)
-    if n_or <= 7:  # one plane: no stamp 10
+    if not buf[:, 10].any():  # one build of the plane (every depth since the plane is packed to its read set): no stamp 10
         t[:, 3] = t[:, 2]
     t0 = t[:, 0].min()
     seg = (t[:, 1:] - t[:, :-1]) * 0.01  # us (100 MHz)
