@@ -11,20 +11,18 @@ namespace mlmcpi {
 // ---- standalone evaluate / force / QoI ------------------------------------------------------------
 
 // grid (nsplit, B); partial[b*nsplit + s] = sum over the split's sites of the site term
-// `stride` > 1 evaluates on every stride-th entry of a longer path (the coarse points of a fine path,
-// action/qm/qmaction.cc:16-24, without materialising the copy)
 template <int KIND, int OP>
 __global__ void __launch_bounds__(256) path_reduce_kernel(PathP P, const double *__restrict__ x,
-                                                          double *__restrict__ partial, uint32_t stride, double scale,
+                                                          double *__restrict__ partial, double scale,
                                                           double *__restrict__ out) {
   __shared__ double red[4];
   const uint32_t b = blockIdx.y, M = P.M;
-  const double *xb = x + (size_t)b * M * stride;
+  const double *xb = x + (size_t)b * M;
   const uint32_t per = (M + gridDim.x - 1) / gridDim.x;
   const uint32_t lo = blockIdx.x * per, hi = min(M, lo + per);
   double acc[1] = {0.0};
   for (uint32_t j = lo + threadIdx.x; j < hi; j += blockDim.x) {
-    const double xj = xb[(size_t)j * stride], xl = xb[(size_t)(j == 0 ? M - 1 : j - 1) * stride];
+    const double xj = xb[j], xl = xb[j == 0 ? M - 1 : j - 1];
     if (OP == R_ENERGY) acc[0] += site_energy<KIND>(P, xj, xl);
     if (OP == R_XSQUARED) acc[0] += xj * xj;
     if (OP == R_WINDING) acc[0] += mod_2pi(xj - xl);
@@ -113,26 +111,25 @@ uint32_t choose_split(uint32_t sites, uint32_t B) {
 }
 
 template <int OP>
-static int launch_reduce(const PathP &P, const double *d_x, uint32_t B, double scale, double *d_out, hipStream_t st,
-                         uint32_t stride = 1) {
+static int launch_reduce(const PathP &P, const double *d_x, uint32_t B, double scale, double *d_out, hipStream_t st) {
   const uint32_t nsplit = choose_split(P.M, B);
   void *ws = nullptr;
   int rc = scratch((size_t)B * nsplit * sizeof(double), &ws, st);
   if (rc) return rc;
   dim3 grid(nsplit, B), block(256);
   dispatch_kind(P.kind, [&](auto K) {
-    hipLaunchKernelGGL((path_reduce_kernel<decltype(K)::value, OP>), grid, block, 0, st, P, d_x, (double *)ws, stride, scale, d_out);
+    hipLaunchKernelGGL((path_reduce_kernel<decltype(K)::value, OP>), grid, block, 0, st, P, d_x, (double *)ws, scale, d_out);
   });
   MLMCPI_LAUNCH_CHECK("path_reduce_kernel");
   if (nsplit == 1) return MLMCPI_OK;
   return path_finish((const double *)ws, nsplit, B, OP, scale, d_out, nullptr, st);
 }
 
-int path_reduce(int op, const PathP &P, const double *d_x, uint32_t B, double scale, double *d_out, hipStream_t st, uint32_t stride) {
+int path_reduce(int op, const PathP &P, const double *d_x, uint32_t B, double scale, double *d_out, hipStream_t st) {
   switch (op) {
-    case R_ENERGY: return launch_reduce<R_ENERGY>(P, d_x, B, scale, d_out, st, stride);
-    case R_XSQUARED: return launch_reduce<R_XSQUARED>(P, d_x, B, scale, d_out, st, stride);
-    default: return launch_reduce<R_WINDING>(P, d_x, B, scale, d_out, st, stride);
+    case R_ENERGY: return launch_reduce<R_ENERGY>(P, d_x, B, scale, d_out, st);
+    case R_XSQUARED: return launch_reduce<R_XSQUARED>(P, d_x, B, scale, d_out, st);
+    default: return launch_reduce<R_WINDING>(P, d_x, B, scale, d_out, st);
   }
 }
 

@@ -90,8 +90,8 @@ enum ReduceOp { R_ENERGY = 0, R_XSQUARED = 1, R_WINDING = 2 };
 // path1d.hip
 int check_action(const mlmcpi_path_action *act);
 uint32_t choose_split(uint32_t sites, uint32_t B);  // workgroups per chain of the kernels that stride over sites
-// d_out[b] = finish(sum over the sites of chain b of the site term of `op`), on the library's scratch; stride: see path_reduce_kernel
-int path_reduce(int op, const PathP &P, const double *d_x, uint32_t B, double scale, double *d_out, hipStream_t st, uint32_t stride = 1);
+// d_out[b] = finish(sum over the sites of chain b of the site term of `op`), on the library's scratch
+int path_reduce(int op, const PathP &P, const double *d_x, uint32_t B, double scale, double *d_out, hipStream_t st);
 // partial[b * nsplit + s] summed over s in a fixed order -> d_out[b] (op R_WINDING: its square / 4 pi^2 times scale; else
 // scale * sum); d_acc != NULL: the value recorded there as well (mlmcpi_stats_accumulate's sums)
 int path_finish(const double *partial, uint32_t nsplit, uint32_t B, int op, double scale, double *d_out, double *d_acc, hipStream_t st);

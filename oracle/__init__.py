@@ -105,6 +105,7 @@ _SIGS = {
     "orc_stats_record": (None, [_vp, _dp, _u32]),
     "orc_stats_reset": (None, [_vp, _i]),
     "orc_stats_get": (None, [_vp, _dp]),
+    "orc_stats_sums": (None, [_vp, _dp]),
     "orc_gff_level_new": (_vp, [_u32, _u32, _i, _i, _d, _i, _d]),
     "orc_gff_level_free": (None, [_vp]),
     "orc_gff_level_size": (_u32, [_vp]),
@@ -215,6 +216,7 @@ class Action:
 
 class Statistics:
     def __init__(self, k_max):
+        self.k_max = k_max
         self.h = lib().orc_stats_new(k_max)
 
     def __del__(self):
@@ -233,3 +235,9 @@ class Statistics:
         out = np.zeros(6)
         lib().orc_stats_get(self.h, out)
         return dict(zip(("average", "variance", "variance_error", "tau_int", "error", "samples"), out))
+
+    def sums(self):
+        """(samples, running average, [S_0 .. S_{k_max-1}]) of the long series"""
+        out = np.zeros(2 + self.k_max)
+        lib().orc_stats_sums(self.h, out)
+        return out[0], out[1], out[2:]

@@ -2466,6 +2466,12 @@ void orc_stats_get(void *h, double *out) {
   out[0] = s->avg; out[1] = s->variance(); out[2] = s->variance_error(); out[3] = s->tau_int();
   out[4] = s->error(); out[5] = (double)s->n;
 }
+// out [2 + k_max]: samples of the long series, its running average a1, the running averages S_0 .. S_{k_max-1} of Q_j Q_{j-k}
+void orc_stats_sums(void *h, double *out) {
+  StatsO *s = (StatsO *)h;
+  out[0] = (double)s->n_long; out[1] = s->a1;
+  for (unsigned k = 0; k < s->k_max; ++k) out[2 + k] = s->S[k];
+}
 
 // mpi/mpi_random.cc:5-29: seeds of the ranks' engines = the sorted set {seed} + outputs of minstd_rand(seed) until it
 // holds `world` distinct values (std::set iterates in ascending order; rank r takes the r-th smallest).
