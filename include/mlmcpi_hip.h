@@ -167,6 +167,7 @@ int mlmcpi_path_hmc_run_layout(const mlmcpi_path_action *act, uint32_t B, uint32
  * n_overrelax sweeps of RotorAction::overrelaxation_update (rotoraction.cc:40-56) then n_heatbath
  * sweeps of heatbath_update (:20-37), even sites then odd sites within each sweep.  Sweep s of
  * this call uses Philox step sweep0 + s.  d_x is updated in place; d_scratch is B*M doubles.
+ * At most 65535 chains per call (they are one grid dimension of every launch; _from and _qoi too): more is an error.
  * Up to 16 overrelaxation sweeps of a launch are applied in closed form (more: launches of equal depth);
  * MLMCPI_OR_KERNEL=block sweeps one by one, 8 per launch.  The two agree to <= 2e-15 without a heat bath
  * behind (the same map, other rounding), NOT bit for bit: see "bit reproducibility across launch plans"

@@ -216,6 +216,8 @@ static int path_sweep_impl(const mlmcpi_path_action *act, double *d_x, double *d
     return fail(MLMCPI_ERR_UNSUPPORTED, "heat bath / overrelaxation update not implemented for this action");
   MLMCPI_REQUIRE(d_x && d_w0 && d_w1 && d_x != d_w0 && d_w0 != d_w1 && B > 0, "bad arguments");
   MLMCPI_REQUIRE(act->M % 2 == 0, "even/odd sweeps need an even number of sites (M_lat = %u)", act->M);
+  // the chains are gridDim.y of every launch below
+  MLMCPI_REQUIRE(B <= 65535, "at most 65535 chains per call (B = %u): split the batch", B);
   PathP P = make_params(*act);
   hipStream_t st = as_stream(stream);
   const uint32_t total = n_overrelax + n_heatbath;
