@@ -21,6 +21,10 @@
 //           draw: the rotated level with --n_level 2, the unrotated M/2 level with --n_level 3)
 //   driver --action nonlinearsigma --Mt_lat 16 --beta 1.5 --sampler swendsenwang --n_updates 1 --n_samples 20000
 //          (Swendsen-Wang multi-cluster updates; prints chi_m, its cluster-improved estimator and the clusters per update)
+//   driver --action nonlinearsigma --Mt_lat 16 --beta 1.5 --coarsening rotate --sampler hierarchical --coarsesampler levelsw
+//          --n_level 2 --n_updates 4
+//          (the Swendsen-Wang sampler on the coarsest level of a hierarchical or --method twolevel run, n_updates updates per coarse
+//           draw: the rotated level with --n_level 2, the unrotated M/2 level with --n_level 3)
 //   driver --action rotor --M_lat 256 --T_final 25.6 --m0 0.25 --sampler cluster --n_updates 10 --n_samples 20000
 //          (cluster samplers: rotor and schwinger; also --coarsesampler cluster for twolevel / hierarchical rotor runs)
 //   driver --method throughput --action schwinger --Mt_lat 1024 --sampler heatbath --batch 32 --n_samples 20
@@ -124,6 +128,22 @@ int main(int argc, char **argv) {
   if (o["coarsesampler"] == "swendsenwang")
     fatal(" --coarsesampler swendsenwang is not supported: the swendsenwang sampler is a single-level sampler of the nonlinear sigma "
           "model, whose hierarchical and two-level runs sample the coarse level with --coarsesampler heatbath (DESIGN.md 4.4a)");
+  // --coarsesampler levelsw: the same sampler on the coarsest level of a two-level or hierarchical sigma-model run, whichever
+  // orientation that level has (mlmcpi_sigma_level_sw_draw)
+  if (o["sampler"] == "levelsw")
+    fatal(" --sampler levelsw is not supported: levelsw names the Swendsen-Wang sampler as a coarse sampler (--coarsesampler levelsw "
+          "with --method twolevel or --sampler hierarchical); the single-level sampler is --sampler swendsenwang");
+  if (o["coarsesampler"] == "levelsw") {
+    if (a != "nonlinearsigma")
+      fatal(" --coarsesampler levelsw is not supported for chosen action: the Swendsen-Wang update is built for nonlinearsigma only "
+            "(the rotor has --coarsesampler cluster)");
+    if (o["method"] == "throughput" || (o["method"] != "twolevel" && o["sampler"] != "hierarchical"))
+      fatal("nonlinearsigma: --coarsesampler levelsw needs --method twolevel or --sampler hierarchical (and not --method throughput): "
+            "with --method " + o["method"] + " --sampler " + o["sampler"] + " no coarse level is sampled; the single-level sampler is --sampler swendsenwang");
+    if (o["coarsening"] != "rotate")
+      fatal("nonlinearsigma: --coarsesampler levelsw needs --coarsening rotate, not " + o["coarsening"] +
+            ": this action coarsens by rotate only (nonlinearsigmaaction.hh:143-149)");
+  }
   if (a == "harmonicoscillator" || a == "quarticoscillator" || a == "rotor") {
     auto lat = std::make_shared<Lattice1D>((unsigned)num("M_lat"), num("T_final"));
     if (a == "harmonicoscillator") {
@@ -162,9 +182,10 @@ int main(int argc, char **argv) {
     if (levels && o["coarsening"] != "rotate")
       fatal("nonlinearsigma: " + std::string(o["method"] == "twolevel" ? "--method twolevel" : "--sampler hierarchical") +
             " needs --coarsening rotate, not " + o["coarsening"] + ": this action coarsens by rotate only (nonlinearsigmaaction.hh:143-149)");
-    if (levels && o["coarsesampler"] != "heatbath" && o["coarsesampler"] != "levelwolff")
+    if (levels && o["coarsesampler"] != "heatbath" && o["coarsesampler"] != "levelwolff" && o["coarsesampler"] != "levelsw")
       fatal("nonlinearsigma: the coarse level of a twolevel or hierarchical run is sampled by --coarsesampler heatbath only, not " +
-            o["coarsesampler"] + " (or by --coarsesampler levelwolff: Wolff cluster updates on that level)");
+            o["coarsesampler"] + " (or by --coarsesampler levelwolff: Wolff cluster updates on that level; --coarsesampler levelsw is "
+            "also allowed: Swendsen-Wang updates on that level)");
     if (o["renormalisation"] == "exact" && levels)
       fatal("nonlinearsigma: non-perturbative renormalisation not implemented for non-linear sigma model.");
     action = std::make_shared<NonlinearSigmaAction>(lat, nullptr, renorm, num("beta"));
@@ -207,7 +228,7 @@ int main(int argc, char **argv) {
       cp.n_burnin = (unsigned)num("n_burnin"); cp.n_updates = (unsigned)num("n_updates"); cp.batch = batch;
       return std::make_shared<WolffClusterSamplerFactory>(cp);
     }
-    if (name == "swendsenwang") {
+    if (name == "swendsenwang" || name == "levelsw") {  // levelsw: on whatever level the hierarchy hands it (checked above)
       ClusterParameters cp;
       cp.n_burnin = (unsigned)num("n_burnin"); cp.n_updates = (unsigned)num("n_updates"); cp.batch = batch;
       return std::make_shared<SwendsenWangSamplerFactory>(cp);

@@ -618,7 +618,10 @@ private:
   const ClusterParameters param;
 };
 
-/** The Swendsen-Wang multi-cluster sampler of the O(3) nonlinear sigma model (mlmcpi_sigma_sw_draw): the
+/** The Swendsen-Wang multi-cluster sampler of the O(3) nonlinear sigma model on either kind of lattice
+ *  (mlmcpi_sigma_level_sw_draw with the action's level: the unrotated lattice delegates to mlmcpi_sigma_sw_draw, the same bits;
+ *  the rotated level of the CoarsenRotate hierarchy runs sigma_level_sw.hip, so the sampler can be the coarse sampler of a
+ *  two-level or hierarchical run; everything is sized by the level's n = sample_size / 2 vertices): the
  *  multi-cluster form of WolffClusterSampler's embedding, the project's own sampler like that one.  One draw = n_updates
  *  updates of every chain, then the copy out; it runs its own update counter, which advances by n_updates per draw; set_state
  *  is a no-op.  Every draw also returns the clusters and the improved estimator of chi_m (3 sum_C A_C^2 / N of the field
@@ -635,7 +638,8 @@ public:
     if ((uint64_t)n_updates * (action->sample_size() / 2) > 0xFFFFFFFFull)
       fatal("SwendsenWangSampler: n_updates x vertices must stay below 2^32 (the per-chain counter of one draw).");
     size_t bytes = 0;
-    check(mlmcpi_sigma_sw_workspace_bytes(&action->abi_action(), B, &bytes), "sigma_sw_workspace_bytes");
+    const mlmcpi_sigma_level lv = action->level();
+    check(mlmcpi_sigma_level_sw_workspace_bytes(&lv, B, &bytes), "sigma_level_sw_workspace_bytes");
     work = std::make_shared<DeviceBuffer>(bytes);
     phi_state_cur = std::make_shared<SampleState>(action->sample_size(), B);
     action->initialise_state(phi_state_cur);
@@ -653,10 +657,11 @@ public:
     if (update_counter > 0xFFFFFFFFu - n_updates) fatal("SwendsenWangSampler: the 32-bit update counter of the Philox contract is used up.");
     check(mlmcpi_memset(clusters.ptr(), 0, B * sizeof(uint32_t), nullptr), "mlmcpi_memset");
     check(mlmcpi_memset(improved.ptr(), 0, B * sizeof(double), nullptr), "mlmcpi_memset");
-    check(mlmcpi_sigma_sw_draw(&action->abi_action(), phi_state_cur->device_mutable(), B, n_updates, action->get_seed(),
-                               action->get_chain0(), update_counter, nullptr, (uint32_t *)clusters.ptr(), (double *)improved.ptr(),
-                               work->p, nullptr),
-          "sigma_sw_draw");
+    const mlmcpi_sigma_level lv = action->level();
+    check(mlmcpi_sigma_level_sw_draw(&lv, phi_state_cur->device_mutable(), B, n_updates, action->get_seed(),
+                                     action->get_chain0(), update_counter, nullptr, (uint32_t *)clusters.ptr(),
+                                     (double *)improved.ptr(), work->p, nullptr),
+          "sigma_level_sw_draw");
     update_counter += n_updates;
     double c = 0.0, v = 0.0;
     for (uint32_t x : clusters.download<uint32_t>()) c += x;

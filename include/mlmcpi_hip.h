@@ -578,6 +578,31 @@ int mlmcpi_sigma_level_cluster_workspace_bytes(const mlmcpi_sigma_level *level, 
 int mlmcpi_sigma_level_cluster_draw(const mlmcpi_sigma_level *level, double *d_state, uint32_t B, uint32_t n_updates,
                                     uint64_t seed, uint32_t chain0, uint32_t update0, uint32_t *d_cluster_sites,
                                     void *d_work, void *stream);
+/* The Swendsen-Wang multi-cluster update on a level (sigma_level_sw.hip): n_updates updates of every chain of
+ * d_state [B][2 n], in place.  Unrotated: mlmcpi_sigma_sw_* on (Mt, Mx, beta), the same bits and the same workspace size.
+ * Rotated: n = Mt Mx / 2 vertices, plane E then plane O of ht x hx = Mt/2 x Mx/2 each, index p ht hx + ht b + a; the links are
+ * named as the level Wolff update names them: (e, d), e an E vertex (e < n / 2), d in 0..3, E(a, b) -> O(a, b), O(a, b-1),
+ * O(a-1, b), O(a-1, b-1); from O(a, b), direction d' crosses link (neighbour, 3 - d').  Where a plane extent is 1 coinciding
+ * neighbours are distinct links with a uniform each.  Philox, step = update0 + k, the purposes of mlmcpi_sigma_sw_draw with
+ * the level's indices: purpose 21 site 0 sub 0 (u, v) -> r (r_z = 1 - 2 u, azimuth 2 pi v - pi); purpose 22 site e sub d >> 1:
+ * u decides link (e, d) for d even, v for d odd; purpose 23 site = the root of a cluster = its smallest LEVEL index (also for a
+ * lone O vertex), sub 0: reflected iff u < 0.5.  With a_l = r . sigma_l BEFORE the update, link (x, y) is bonded iff (a_x a_y) >
+ * 0 and its uniform < 1 - exp(min(0, -2 beta (a_x a_y))), the product formed first; every component of the bonded links is
+ * labelled, a flipped cluster is reflected, sigma' = sigma - 2 a r, canonical form, no fp contraction.  Improved estimator of
+ * chi_m: 3 sum_C A_C^2 / n, A_C summed as llrint(a 2^32) by integer atomics, the squares summed over the roots in one fixed
+ * configuration (1024 threads, thread t takes t, t + 1024, .., then a fixed tree), ADDED to d_improved update by update.
+ * The state and all three outputs are the same bits under every launch plan, tile, batch split, chain0 and call split
+ * (10 = 5 + 5).  MLMCPI_SIGMA_SW_PLAN=chain|tiled and MLMCPI_SIGMA_SW_TILE=WxH (W, H in {8, 16, 32, 64}, here in plane cells;
+ * default 32x32) govern this update too; chain forced on a level of more than 7552 vertices: MLMCPI_ERR_UNSUPPORTED.
+ * Workspace: 256 B (status word) + 20.5 B per vertex and chain (label 4, q(a) 8, root slot 8, four bond bits per E vertex);
+ * its content at entry is ignored.  d_flipped, d_clusters (uint32 [B]) and d_improved (double [B]) may each be NULL and are
+ * ADDED to.  The draw reads the status word back after its launches (it synchronises the stream); a labelling loop that hit
+ * its iteration cap: MLMCPI_ERR_HIP.  MLMCPI_ERR_INVALID: NULL level, odd or zero extents, Mt Mx > 2^30, beta <= 0, no
+ * workspace, B = 0, update0 + n_updates beyond 32 bits. */
+int mlmcpi_sigma_level_sw_workspace_bytes(const mlmcpi_sigma_level *level, uint32_t B, size_t *bytes);
+int mlmcpi_sigma_level_sw_draw(const mlmcpi_sigma_level *level, double *d_state, uint32_t B, uint32_t n_updates, uint64_t seed,
+                               uint32_t chain0, uint32_t update0, uint32_t *d_flipped, uint32_t *d_clusters, double *d_improved,
+                               void *d_work, void *stream);
 /* NonlinearSigmaConditionedFineAction (nonlinearsigmaconditionedfineaction.cc:7-44) on a level.  Every fine-only vertex (the
  * (i + j) odd ones of an unrotated level, the O plane of a rotated one) has coarse neighbours only, so the fill is a product of
  * independent heat-bath laws and _evaluate is minus the log of its density.

@@ -235,8 +235,11 @@ enum Purpose : uint32_t {
                            // site = the E vertex e of the link, sub d >> 1 (0 or 1): u decides link (e, d) for d even, v for d odd
   P_SIGMA_SW_REFLECT = 21, // sigma-model Swendsen-Wang update (sigma_sw.hip), site 0, step = update counter, sub 0: (u, v) -> normal r
                            // by the map of purpose 19 sub 0
-  P_SIGMA_SW_BOND = 22,    // Swendsen-Wang update, site = vertex l, sub 0: u decides link (l, 0), v decides link (l, 1)
-  P_SIGMA_SW_FLIP = 23,    // Swendsen-Wang update, site = the root (smallest vertex) of a cluster, sub 0: reflected iff u < 0.5
+  P_SIGMA_SW_BOND = 22,    // Swendsen-Wang update, site = vertex l, sub 0: u decides link (l, 0), v decides link (l, 1).  On a rotated
+                           // level (sigma_level_sw.hip): site = the E vertex e of the link, sub d >> 1: u decides link (e, d) for d even,
+                           // v for d odd
+  P_SIGMA_SW_FLIP = 23,    // Swendsen-Wang update, site = the root (smallest vertex; on a rotated level the smallest LEVEL index) of a
+                           // cluster, sub 0: reflected iff u < 0.5
   P_SIGMA_FILLIN = 24,     // sigma-model two-level step (sigma_twolevel.hip), site = the fine-only vertex's index on the fine level, sub 0:
                            // (u, v) of its heat-bath draw from the four coarse neighbours
 };

@@ -1,0 +1,171 @@
+"""numpy restatement of the Swendsen-Wang multi-cluster update of the O(3) sigma model on a level of its CoarsenRotate
+hierarchy (mlmcpathintegral_amd/csrc/sigma_level_sw.hip): the contract's second statement.
+
+An unrotated Level calls through to tests/sigma_sw_model.py, so that the two stay one definition.  A rotated Level is table
+driven from sigma_level_model.Level (L.nbr, L.n), with the link naming of tests/sigma_level_cluster_model.py: n = Mt Mx / 2
+vertices, plane E (indices < n / 2) then plane O; the 2 n links are (e, d), e an E vertex, d its direction in the order of L.nbr
+(E(a, b) -> O(a, b), O(a, b-1), O(a-1, b), O(a-1, b-1)); from an O vertex direction d' crosses link (L.nbr[x, d'], 3 - d').  Where a
+plane extent is 1 several neighbours of a vertex coincide: they are distinct links with a uniform each.
+
+Random numbers, Philox (site, chain, step, purpose << 24 | sub) keyed by the seed, step = update counter:
+  P_SIGMA_SW_REFLECT = 21  site 0, sub 0: (u, v) -> normal r, r_z = 1 - 2 u, azimuth 2 pi v - pi
+  P_SIGMA_SW_BOND    = 22  site e, sub d >> 1: u decides link (e, d) for d even, v for d odd
+  P_SIGMA_SW_FLIP    = 23  site = root of a cluster (its smallest LEVEL index), sub 0: reflected iff u < 0.5
+With a_l = r . sigma_l before the update, link (x, y) is bonded iff a_x a_y > 0 and its uniform < 1 - exp(min(0, -(2 beta (a_x
+a_y)))).  Improved estimator of chi_m: 3 sum_C A_C^2 / n, A_C = sum of q(a_l) = rint(a_l 2^32) over the cluster, as integers.
+"""
+import numpy as np
+
+import sigma_sw_model as swm
+from sigma_cluster_model import _dots
+from sigma_level_cluster_model import _bonds, link_tables
+from sigma_model import angles_of, sigma_of, uniforms
+from sigma_sw_model import FIX, P_SIGMA_SW_BOND, P_SIGMA_SW_FLIP, P_SIGMA_SW_REFLECT, coins, improved_of, normal
+
+
+def plane_link(L, e, d):
+    """the kernels' plane arithmetic: the O end of link (e, d) of a rotated level, E(a, b) -> O(a - (d >> 1), b - (d & 1))"""
+    ht, hx = L.Mt // 2, L.Mx // 2
+    b, a = divmod(e, ht)
+    oa = (ht - 1 if a == 0 else a - 1) if d & 2 else a
+    ob = (hx - 1 if b == 0 else b - 1) if d & 1 else b
+    return ht * hx + ob * ht + oa
+
+
+def link_uniforms(seed, chain, step, nE):
+    """U [nE, 4]: the uniform of link (e, d)"""
+    e = np.arange(nE, dtype=np.uint64)
+    u0, v0 = uniforms(seed, chain, step, e, P_SIGMA_SW_BOND, 0)
+    u1, v1 = uniforms(seed, chain, step, e, P_SIGMA_SW_BOND, 1)
+    return np.stack([u0, v0, u1, v1], axis=-1)
+
+
+def labels_of(L, bonded):
+    """label [.., n]: the smallest level index of the component of every vertex in the graph of the bonded links (bonded
+    [.., nE, 4]); plain propagation of the minimum along bonds with pointer jumping, until nothing changes"""
+    site, which = link_tables(L)
+    n = L.n
+    lab = np.broadcast_to(np.arange(n), bonded.shape[:-2] + (n,)).copy()
+    while True:
+        new = lab
+        for d in range(4):                               # what vertex x sees across its direction d
+            new = np.minimum(new, np.where(bonded[..., site[:, d], which[:, d]], lab[..., L.nbr[:, d]], n))
+        new = np.take_along_axis(new, new, axis=-1)
+        if np.array_equal(new, lab):
+            return lab
+        lab = new
+
+
+def sequential_labels(L, bonded):
+    """the same labels by a sequential union-find over the bonded links (bonded [nE, 4]), smaller root wins"""
+    parent = list(range(L.n))
+
+    def find(x):
+        while parent[x] != x:
+            parent[x] = parent[parent[x]]
+            x = parent[x]
+        return x
+
+    for e, d in zip(*np.nonzero(bonded)):
+        x, y = find(int(e)), find(int(L.nbr[e, d]))
+        if x != y:
+            parent[max(x, y)] = min(x, y)
+    return np.array([find(x) for x in range(L.n)])
+
+
+def dev_update(L, phi, seed, chain, step):
+    """one update of one chain phi [2 n] on the level L (L.beta); returns (new state, info): `labels` the root of every vertex,
+    `flipped` the reflected vertices (ascending), `clusters` their number, `improved` the improved chi_m of the field before the
+    update, r, a, `bonded` [nE, 4] and `margin` = min |u - p| over ALL links whose test could go either way (a_x a_y > 0)"""
+    if not L.rotated:
+        return swm.dev_update(phi, L.Mt, L.Mx, L.beta, seed, chain, step)
+    n, nE = L.n, L.n // 2
+    ang = np.asarray(phi, dtype=np.float64).reshape(n, 2)
+    sig = sigma_of(ang)
+    r = normal(seed, chain, step)
+    a = _dots(sig, r)
+    U = link_uniforms(seed, chain, step, nE)
+    bonded, p, prod = _bonds(L, a, U)
+    lab = labels_of(L, bonded)
+    flip = coins(seed, chain, step, lab)
+    flipped = np.nonzero(flip)[0]
+    open_ = prod > 0.0
+    margin = float(np.min(np.abs(U - p)[open_])) if open_.any() else np.inf
+    out = ang.copy()
+    out[flipped] = angles_of(sig[flipped] - (2.0 * a[flipped])[:, None] * r[None, :])
+    info = {"labels": lab, "flipped": flipped, "clusters": int(np.count_nonzero(lab == np.arange(n))), "improved": improved_of(a, lab),
+            "margin": margin, "r": r, "a": a, "bonded": bonded}
+    return out.reshape(2 * n), info
+
+
+def dev_update_batch(L, phi, seed, chain0, step):
+    """dev_update of every chain of phi [B, 2 n] at once (long CPU chains on small levels); returns (new states, info) with
+    `flipped`, `clusters` [B] counts and `improved` [B]"""
+    if not L.rotated:
+        return swm.dev_update_batch(phi, L.Mt, L.Mx, L.beta, seed, chain0, step)
+    B, n, nE = phi.shape[0], L.n, L.n // 2
+    ang = phi.reshape(B, n, 2)
+    sig = sigma_of(ang)
+    chain = chain0 + np.arange(B, dtype=np.uint64)
+    u, v = uniforms(seed, chain, step, 0, P_SIGMA_SW_REFLECT, 0)
+    rz = 1.0 - 2.0 * u
+    rho = np.sqrt(np.maximum(0.0, 1.0 - rz * rz))
+    az = 2.0 * np.pi * v - np.pi
+    r = np.stack([rho * np.cos(az), rho * np.sin(az), rz], axis=1)                       # [B, 3]
+    a = (r[:, None, 0] * sig[..., 0] + r[:, None, 1] * sig[..., 1]) + r[:, None, 2] * sig[..., 2]
+    e = np.arange(nE, dtype=np.uint64)[None, :]
+    u0, v0 = uniforms(seed, chain[:, None], step, e, P_SIGMA_SW_BOND, 0)
+    u1, v1 = uniforms(seed, chain[:, None], step, e, P_SIGMA_SW_BOND, 1)
+    bonded, _, _ = _bonds(L, a, np.stack([u0, v0, u1, v1], axis=-1))                     # [B, nE, 4]
+    lab = labels_of(L, bonded)
+    uc, _ = uniforms(seed, chain[:, None], step, lab.astype(np.uint64), P_SIGMA_SW_FLIP)
+    flip = uc < 0.5
+    A = np.zeros((B, n), dtype=np.int64)
+    np.add.at(A, (np.arange(B)[:, None], lab), np.rint(a * FIX).astype(np.int64))
+    improved = 3.0 * ((A.astype(np.float64) / FIX) ** 2).sum(axis=1) / n
+    new = angles_of(sig - (2.0 * a)[..., None] * r[:, None, :])
+    info = {"flipped": flip.sum(axis=1), "clusters": (lab == np.arange(n)[None, :]).sum(axis=1), "improved": improved}
+    return np.where(flip[..., None], new, ang).reshape(B, 2 * n), info
+
+
+def dev_draw(L, phi, seed, chain0, update0, n_updates):
+    """mlmcpi_sigma_level_sw_draw on [B, 2 n]: returns (new states, flipped [B], clusters [B], improved [B], min margin)"""
+    if not L.rotated:
+        return swm.dev_draw(phi, L.Mt, L.Mx, L.beta, seed, chain0, update0, n_updates)
+    out = np.array(phi, dtype=np.float64, copy=True)
+    B = out.shape[0]
+    flipped, clusters, improved, margin = np.zeros(B, dtype=np.int64), np.zeros(B, dtype=np.int64), np.zeros(B), np.inf
+    for b in range(B):
+        for k in range(n_updates):
+            out[b], info = dev_update(L, out[b], seed, chain0 + b, update0 + k)
+            flipped[b] += len(info["flipped"])
+            clusters[b] += info["clusters"]
+            improved[b] += info["improved"]
+            margin = min(margin, info["margin"])
+    return out, flipped, clusters, improved, margin
+
+
+def tile_links(L, W, H):
+    """the kernels' partition of the 2 n links of a rotated level for tiles of W x H plane cells (w x h where the plane ends; cell
+    (a, b) = E(a, b) and O(a, b)).  Returns (interior, crossing): interior [nE, 4] = the tile (ty ntx + tx) whose union-find in LDS
+    takes link (e, d) -- its O end O(a - (d >> 1), b - (d & 1)) is a cell of the same tile without a periodic wrap: li >= d >> 1 and
+    lj >= d & 1 in tile coordinates -- or -1; crossing = the list of (e, d) the merge launch unites, in the order of its lanes:
+    the links d = 2, 3 of the first column of every tile column, then the links d = 1, 3 of the first row of every tile row, the
+    d = 3 link of a tile's corner cell (a lane of both sets) taken by the first set only"""
+    assert L.rotated
+    ht, hx = L.Mt // 2, L.Mx // 2
+    ntx, nty = -(-ht // W), -(-hx // H)
+    e = np.arange(ht * hx)
+    a, b = e % ht, e // ht
+    li, lj = a % W, b % H
+    tile = (b // H) * ntx + a // W
+    interior = np.stack([np.where((li >= (d >> 1)) & (lj >= (d & 1)), tile, -1) for d in range(4)], axis=1)
+    crossing = []
+    for x in range(2 * ntx * hx):
+        crossing.append(((x >> 1) // ntx * ht + ((x >> 1) % ntx) * W, 2 + (x & 1)))
+    for y in range(2 * nty * ht):
+        d, ca, cb = 1 + ((y & 1) << 1), (y >> 1) % ht, ((y >> 1) // ht) * H
+        if d == 3 and ca % W == 0:
+            continue
+        crossing.append((cb * ht + ca, d))
+    return interior, crossing
