@@ -526,7 +526,7 @@ private:
 
 /** The Wolff single-cluster sampler of the O(3) nonlinear sigma model on either kind of lattice (mlmcpi_sigma_level_cluster_draw
  *  with the action's level: the unrotated lattice delegates to mlmcpi_sigma_cluster_draw, the same bits; the rotated level of
- *  the CoarsenRotate hierarchy runs sigma_level_cluster.hip, so the sampler can be the coarse sampler of a two-level or
+ *  the CoarsenRotate hierarchy runs sigma_cluster.hip, so the sampler can be the coarse sampler of a two-level or
  *  hierarchical run; everything is sized by the level's n = sample_size / 2 vertices).  It is NOT
  *  the reference's ClusterSampler for this action: single_cluster_update (clustersampler.cc:52-89) bonds all eight entries of
  *  Lattice2D::neighbour_vertices while the action couples four, which samples another model; this is the same
@@ -620,7 +620,7 @@ private:
 
 /** The Swendsen-Wang multi-cluster sampler of the O(3) nonlinear sigma model on either kind of lattice
  *  (mlmcpi_sigma_level_sw_draw with the action's level: the unrotated lattice delegates to mlmcpi_sigma_sw_draw, the same bits;
- *  the rotated level of the CoarsenRotate hierarchy runs sigma_level_sw.hip, so the sampler can be the coarse sampler of a
+ *  the rotated level of the CoarsenRotate hierarchy runs sigma_sw.hip, so the sampler can be the coarse sampler of a
  *  two-level or hierarchical run; everything is sized by the level's n = sample_size / 2 vertices): the
  *  multi-cluster form of WolffClusterSampler's embedding, the project's own sampler like that one.  One draw = n_updates
  *  updates of every chain, then the copy out; it runs its own update counter, which advances by n_updates per draw; set_state

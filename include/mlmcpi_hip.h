@@ -562,7 +562,7 @@ int mlmcpi_sigma_level_copy_from_fine(const mlmcpi_sigma_level *fine, const doub
                                       void *stream);
 int mlmcpi_sigma_level_copy_from_coarse(const mlmcpi_sigma_level *fine, const double *d_coarse, double *d_fine, uint32_t B,
                                         void *stream);
-/* The Wolff single-cluster update on a level (sigma_level_cluster.hip): n_updates updates of every chain of
+/* The Wolff single-cluster update on a level (sigma_cluster.hip): n_updates updates of every chain of
  * d_state [B][2 n], in place.  Unrotated: mlmcpi_sigma_cluster_* on (Mt, Mx, beta), the same bits.  Rotated: the level is
  * bipartite, every link has one E end; its 2 n links are (e, d), e an E vertex (e < n / 2), d its direction in the order above;
  * from O(a, b), direction d' crosses link (neighbour, 3 - d').  Where a plane extent is 1 several neighbours of a vertex
@@ -578,7 +578,7 @@ int mlmcpi_sigma_level_cluster_workspace_bytes(const mlmcpi_sigma_level *level, 
 int mlmcpi_sigma_level_cluster_draw(const mlmcpi_sigma_level *level, double *d_state, uint32_t B, uint32_t n_updates,
                                     uint64_t seed, uint32_t chain0, uint32_t update0, uint32_t *d_cluster_sites,
                                     void *d_work, void *stream);
-/* The Swendsen-Wang multi-cluster update on a level (sigma_level_sw.hip): n_updates updates of every chain of
+/* The Swendsen-Wang multi-cluster update on a level (sigma_sw.hip): n_updates updates of every chain of
  * d_state [B][2 n], in place.  Unrotated: mlmcpi_sigma_sw_* on (Mt, Mx, beta), the same bits and the same workspace size.
  * Rotated: n = Mt Mx / 2 vertices, plane E then plane O of ht x hx = Mt/2 x Mx/2 each, index p ht hx + ht b + a; the links are
  * named as the level Wolff update names them: (e, d), e an E vertex (e < n / 2), d in 0..3, E(a, b) -> O(a, b), O(a, b-1),

@@ -231,12 +231,12 @@ enum Purpose : uint32_t {
   P_SIGMA_REFLECT = 19,    // sigma-model Wolff update (sigma_cluster.hip), site 0, step = update counter: sub 0 (u, v) -> normal r with
                            // r_z = 1 - 2 u, azimuth 2 pi v - pi; sub 1 u -> seed vertex min(floor(u N), N - 1) (N: the level's vertices)
   P_SIGMA_BOND = 20,       // sigma-model Wolff update, site = vertex l, step = update counter, sub 0: u decides link (l, 0) (to the +i
-                           // neighbour), v decides link (l, 1) (to the +j neighbour).  On a rotated level (sigma_level_cluster.hip):
+                           // neighbour), v decides link (l, 1) (to the +j neighbour).  On a rotated level (sigma_cluster.hip):
                            // site = the E vertex e of the link, sub d >> 1 (0 or 1): u decides link (e, d) for d even, v for d odd
   P_SIGMA_SW_REFLECT = 21, // sigma-model Swendsen-Wang update (sigma_sw.hip), site 0, step = update counter, sub 0: (u, v) -> normal r
                            // by the map of purpose 19 sub 0
   P_SIGMA_SW_BOND = 22,    // Swendsen-Wang update, site = vertex l, sub 0: u decides link (l, 0), v decides link (l, 1).  On a rotated
-                           // level (sigma_level_sw.hip): site = the E vertex e of the link, sub d >> 1: u decides link (e, d) for d even,
+                           // level (sigma_sw.hip): site = the E vertex e of the link, sub d >> 1: u decides link (e, d) for d even,
                            // v for d odd
   P_SIGMA_SW_FLIP = 23,    // Swendsen-Wang update, site = the root (smallest vertex; on a rotated level the smallest LEVEL index) of a
                            // cluster, sub 0: reflected iff u < 0.5

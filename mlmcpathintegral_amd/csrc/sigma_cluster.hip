@@ -1,4 +1,9 @@
-// sigma_cluster.hip -- the Wolff single-cluster update of the O(3) nonlinear sigma model (gfx950, wave64).
+// sigma_cluster.hip -- the Wolff single-cluster update of the O(3) nonlinear sigma model (gfx950, wave64), on the unrotated
+// lattice (mlmcpi_sigma_cluster_*) and on the levels of its CoarsenRotate hierarchy (mlmcpi_sigma_level_cluster_*; an unrotated
+// level IS the lattice and takes its entry point).  One kernel per geometry, on the helpers of sigma_cluster_device.hpp: the
+// two differ in the neighbour of a task and the name of its link.  One kernel instantiated on the geometry was built and
+// withdrawn: the rotated wave-team instance with its bitmap in LDS went from 127 to 129 VGPRs, four waves per SIMD to three
+// (EXPERIMENTS.md).  The plan, the attribute guard, the workspace and the launch exist once.
 //
 // NOT the reference's ClusterSampler for this action: ClusterSampler::single_cluster_update (sampler/clustersampler.cc:52-89)
 // walks the eight entries of Lattice2D::neighbour_vertices (lattice2d.cc:135-155), the action couples four of them
@@ -6,9 +11,10 @@
 // the same walk over the four links per vertex the action has, with the action's own new_reflection / S_ell / flip
 // (nonlinearsigmaaction.cc:166-208).
 //
-// The update, restated (tests/sigma_cluster_model.py).  Vertex l = Mt j + i; link (l, 0) joins l to its +i
-// neighbour, link (l, 1) to its +j neighbour (2 N links; on an extent of 2 the two links between a pair are two links).  With
-// r the reflection normal and a_l = r . sigma_l of the field BEFORE the update, link (x, y) is bonded iff its uniform
+// The update, restated (tests/sigma_cluster_model.py, tests/sigma_level_cluster_model.py).  A geometry has N
+// vertices and 2 N links, every vertex four of them (where an extent is too small for four distinct neighbours, several links
+// join one pair: distinct links with a uniform each, as the action counts each of those bonds).  With r the reflection normal
+// and a_l = r . sigma_l of the field BEFORE the update, link (x, y) is bonded iff (a_x a_y) > 0 and its uniform
 // < 1 - exp(min(0, -2 beta (a_x a_y)))  (the walk evaluates S_ell with one end already flipped: r . sigma' = -r . sigma).  The
 // cluster is the connected component of the seed vertex in the graph of bonded links; every vertex of it is reflected once,
 // sigma' = sigma - 2 a r, and stored in the canonical form (sigma2d.hip).  Every decision is a function of (link, chain,
@@ -16,30 +22,19 @@
 //
 // RNG contract, step = global update counter:
 //   P_SIGMA_REFLECT  site 0, sub 0: (u, v) -> r_z = 1 - 2 u, azimuth 2 pi v - pi;  sub 1: u -> seed vertex min(floor(u N), N - 1)
-//   P_SIGMA_BOND     site l, sub 0: u decides link (l, 0), v decides link (l, 1)
+//   P_SIGMA_BOND     unrotated: site l, sub 0: u decides link (l, 0), v decides link (l, 1)
+//                    rotated:   site e (the E end), sub d >> 1: u decides link (e, d) for d even, v for d odd
 #include <mutex>
 
 #include "internal.hpp"
 
-#include "sigma_device.hpp"  // fp contraction is off from here on
+#include "sigma_cluster_device.hpp"  // fp contraction is off from here on
 
 namespace mlmcpi {
 
-constexpr uint32_t kScWaveChains = 4;          // team = wave: chains per workgroup of 256 threads
+constexpr uint32_t kScWaveChains = kClusterThreads / kWave;  // team = wave: chains per workgroup of 256 threads
 constexpr uint32_t kScWaveLdsWords = 2048;     // team = wave: bitmap in LDS up to 8 KiB per chain (65 536 vertices)
 constexpr uint32_t kScBlockLdsWords = 32768;   // team = workgroup: bitmap in LDS up to 128 KiB (2^20 vertices)
-constexpr uint32_t kScBlockThreads = 1024;
-
-// What orders one phase of a team behind the one before it: the phase's stores (state, queue, bitmap) drained and, for a
-// team of several waves, the barrier.  A team of one wave runs in lockstep and needs the drain only.
-template <bool BLOCK>
-__device__ __forceinline__ void team_sync() {
-  __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");
-  if (BLOCK) __syncthreads();
-  else __builtin_amdgcn_wave_barrier();
-}
-
-__device__ __forceinline__ double reflect_dot(const V3 &r, const V3 &s) { return (r.x * s.x + r.y * s.y) + r.z * s.z; }
 
 // n_updates updates of every chain, in place.  A chain belongs to a team of lanes: one wave (BLOCK = false, kScWaveChains
 // chains per workgroup) or the whole workgroup (BLOCK = true).  Growth by frontier expansion: the vertices of the cluster
@@ -52,7 +47,7 @@ __device__ __forceinline__ double reflect_dot(const V3 &r, const V3 &s) { return
 // The frontier loop ends after at most N levels (a vertex joins once, a level without a new member is the last one); `level <
 // N` states that cap explicitly.  Queue positions are < N for the same reason; the store is guarded all the same.
 template <bool BLOCK, bool LDS_MAP>
-__global__ void __launch_bounds__(BLOCK ? kScBlockThreads : kScWaveChains * kWave)
+__global__ void __launch_bounds__(BLOCK ? kClusterBlockThreads : kClusterThreads)
     sigma_cluster_kernel(double2 *phi_all, uint32_t Mt, uint32_t Mx, double beta2, uint32_t B, uint32_t n_updates, RngKey key0,
                          uint32_t *queue_vertex, double *queue_a, uint32_t *map_all, uint32_t words, uint32_t *cluster_sites) {
   extern __shared__ uint32_t lds_map[];
@@ -86,7 +81,7 @@ __global__ void __launch_bounds__(BLOCK ? kScBlockThreads : kScWaveChains * kWav
     seed = seed < N ? seed : N - 1;
     if (lane == 0) {
       qv[0] = seed;
-      qa[0] = reflect_dot(r, sigma_of(phi[seed]));
+      qa[0] = dot3(r, sigma_of(phi[seed]));
       map[seed >> 5] = 1u << (seed & 31u);
       s_tail[slot] = 1;
     }
@@ -110,10 +105,10 @@ __global__ void __launch_bounds__(BLOCK ? kScBlockThreads : kScWaveChains * kWav
           const uint32_t bit = 1u << (y & 31u);
           // a relaxed atomic load: other lanes set bits meanwhile; a stale 0 costs a test, the atomic OR below decides
           if (!(__hip_atomic_load(&map[y >> 5], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP) & bit)) {
-            ay = reflect_dot(r, sigma_of(phi[y]));
+            ay = dot3(r, sigma_of(phi[y]));
             const double prod = ax * ay;
             if (prod > 0.0) {                            // else p = 0: never bonded, no random number
-              const double p = 1.0 - exp(fmin(0.0, -(beta2 * prod)));
+              const double p = bond_probability(prod, beta2);
               // +i: link (x, 0), -i: link (y, 0), +j: link (x, 1), -j: link (y, 1)
               const U4 w = philox4x32_10((d & 1u) ? y : x, key.chain, key.step, (uint32_t)P_SIGMA_BOND << 24, key.k0, key.k1);
               const double uni = (d & 2u) ? u01(w.z, w.w) : u01(w.x, w.y);
@@ -154,6 +149,128 @@ __global__ void __launch_bounds__(BLOCK ? kScBlockThreads : kScWaveChains * kWav
   if (cluster_sites && lane == 0) cluster_sites[b] += total;
 }
 
+// n_updates updates of every chain of a rotated level, in place: the algorithm of sigma_cluster_kernel (teams of one wave or
+// one workgroup; frontier expansion over a queue of (vertex, a) pairs; a lane takes one (frontier vertex, direction) task,
+// pre-checks the membership bitmap with a relaxed atomic load and claims the neighbour with an atomic OR; one ballot, one
+// prefix count and one atomic add on the tail counter per wave and round; reflections from the queue once growth has ended,
+// the same pass clearing the members' bitmap words) with the neighbour and the link of a task from the plane arithmetic of
+// the rotated level (RotatedGeometry, sigma_cluster_device.hpp, names the links).  The queue carries the linear index: one
+// division by ht per task (DESIGN.md 4.6a says why not (a, b, p) packed).
+// The frontier loop ends after at most n levels (a vertex joins once, a level without a new member is the last one); `level <
+// n` states that cap explicitly.  Queue positions are < n for the same reason; the store is guarded all the same.
+template <bool BLOCK, bool LDS_MAP>
+__global__ void __launch_bounds__(BLOCK ? kClusterBlockThreads : kClusterThreads)
+    sigma_rot_cluster_kernel(double2 *phi_all, SigmaLevel L, double beta2, uint32_t B, uint32_t n_updates, RngKey key0,
+                             uint32_t *queue_vertex, double *queue_a, uint32_t *map_all, uint32_t words, uint32_t *cluster_sites) {
+  extern __shared__ uint32_t lds_map[];
+  __shared__ uint32_t s_tail[kScWaveChains];
+  const uint32_t T = BLOCK ? blockDim.x : (uint32_t)kWave;
+  const uint32_t lane = BLOCK ? threadIdx.x : threadIdx.x & (kWave - 1);
+  const uint32_t wave_lane = threadIdx.x & (kWave - 1);
+  const uint32_t slot = BLOCK ? 0 : threadIdx.x >> 6;
+  const uint32_t b = BLOCK ? blockIdx.x : blockIdx.x * kScWaveChains + slot;
+  if (b >= B) return;                                    // team uniform (BLOCK: the grid has B workgroups)
+  const uint32_t n = L.nvert(), ht = L.ht, hx = L.hx, nq = L.q;
+  double2 *phi = phi_all + (size_t)b * n;
+  uint32_t *qv = queue_vertex + (size_t)b * n;
+  double *qa = queue_a + (size_t)b * n;
+  uint32_t *map = LDS_MAP ? lds_map + slot * words : map_all + (size_t)b * words;
+  for (uint32_t w = lane; w < words; w += T) map[w] = 0;
+  RngKey key = key0;
+  key.chain = key0.chain + b;
+  uint32_t total = 0;
+  team_sync<BLOCK>();
+
+  for (uint32_t k = 0; k < n_updates; ++k, ++key.step) {
+    double u, v, us, unused;
+    rng_uniforms(key, 0, P_SIGMA_REFLECT, 0, u, v);
+    rng_uniforms(key, 0, P_SIGMA_REFLECT, 1, us, unused);
+    const double rz = 1.0 - 2.0 * u, t = 1.0 - rz * rz, rho = t > 0.0 ? sqrt(t) : 0.0;
+    double sa, ca;
+    sincos(kTwoPi * v - kPi, &sa, &ca);
+    const V3 r{rho * ca, rho * sa, rz};
+    uint32_t seed = (uint32_t)(us * (double)n);
+    seed = seed < n ? seed : n - 1;
+    if (lane == 0) {
+      qv[0] = seed;
+      qa[0] = dot3(r, sigma_of(phi[seed]));
+      map[seed >> 5] = 1u << (seed & 31u);
+      s_tail[slot] = 1;
+    }
+    team_sync<BLOCK>();
+
+    uint32_t head = 0, tail = 1;
+    for (uint32_t level = 0; level < n && head < tail; ++level) {
+      for (uint32_t base = head; base < tail; base += T / 4) {  // team uniform trip count: the ballot below sees whole waves
+        const uint32_t q = base + (lane >> 2), d = lane & 3u;
+        bool add = false;
+        uint32_t y = 0;
+        double ay = 0.0;
+        if (q < tail) {
+          const uint32_t x = qv[q];
+          const double ax = qa[q];
+          const bool odd = x >= nq;                      // plane O
+          const uint32_t c = odd ? x - nq : x, cb = c / ht, ca_ = c - cb * ht;
+          // E: d -> O(a - (d >> 1), b - (d & 1)); O: d' -> E(a + 1 - (d' >> 1), b + 1 - (d' & 1))
+          uint32_t ya = ca_, yb = cb;
+          if (odd) {
+            if (!(d & 2u)) ya = ca_ + 1 == ht ? 0 : ca_ + 1;
+            if (!(d & 1u)) yb = cb + 1 == hx ? 0 : cb + 1;
+          } else {
+            if (d & 2u) ya = ca_ == 0 ? ht - 1 : ca_ - 1;
+            if (d & 1u) yb = cb == 0 ? hx - 1 : cb - 1;
+          }
+          const uint32_t yc = yb * ht + ya;              // < nq
+          y = odd ? yc : nq + yc;
+          const uint32_t bit = 1u << (y & 31u);
+          // a relaxed atomic load: other lanes set bits meanwhile; a stale 0 costs a test, the atomic OR below decides
+          if (!(__hip_atomic_load(&map[y >> 5], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP) & bit)) {
+            ay = dot3(r, sigma_of(phi[y]));
+            const double prod = ax * ay;
+            if (prod > 0.0) {                            // else p = 0: never bonded, no random number
+              const double p = bond_probability(prod, beta2);
+              // the link's name from its E end: (x, d) from E, (y, 3 - d') from O
+              const uint32_t e = odd ? yc : x, de = odd ? 3u - d : d;
+              const U4 w = philox4x32_10(e, key.chain, key.step, ((uint32_t)P_SIGMA_BOND << 24) | (de >> 1), key.k0, key.k1);
+              const double uni = (de & 1u) ? u01(w.z, w.w) : u01(w.x, w.y);
+              if (uni < p) add = !(atomicOr(&map[y >> 5], bit) & bit);
+            }
+          }
+        }
+        const unsigned long long joiners = __ballot(add);
+        if (joiners) {                                   // wave uniform
+          const uint32_t leader = (uint32_t)__builtin_ctzll(joiners);
+          uint32_t first = 0;
+          if (wave_lane == leader) first = atomicAdd(&s_tail[slot], (uint32_t)__builtin_popcountll(joiners));
+          first = __shfl(first, leader);
+          const uint32_t pos = first + (uint32_t)__builtin_popcountll(joiners & ((1ull << wave_lane) - 1ull));
+          if (add && pos < n) {
+            qv[pos] = y;
+            qa[pos] = ay;
+          }
+        }
+      }
+      team_sync<BLOCK>();
+      head = tail;
+      tail = s_tail[slot];
+      tail = tail < n ? tail : n;                        // the queue holds n entries (a vertex joins once)
+      if (BLOCK) __syncthreads();                        // nobody appends to the next level before everybody has read the tail
+    }
+
+    for (uint32_t q = lane; q < tail; q += T) {
+      const uint32_t x = qv[q];
+      const double c = 2.0 * qa[q];
+      const V3 s = sigma_of(phi[x]);
+      phi[x] = angles_of(V3{s.x - c * r.x, s.y - c * r.y, s.z - c * r.z});
+      map[x >> 5] = 0;                                   // every bit of the word that is set belongs to a member
+    }
+    total += tail;
+    // the next update reads what this one stored (other lanes, other waves of the team): drain the stores first
+    team_sync<BLOCK>();
+  }
+  if (cluster_sites && lane == 0) cluster_sites[b] += total;
+}
+
 namespace {
 
 struct ScPlan {
@@ -162,15 +279,16 @@ struct ScPlan {
   size_t lds_bytes;
 };
 
-// Launch plan.  A team is one wave when there are enough chains to give every SIMD of the device a wave
-// (B >= 4 x kComputeUnits), the workgroup otherwise; the bitmap sits in LDS where it fits.  Knobs (bit-identical results):
-// MLMCPI_SIGMA_CLUSTER_TEAM=wave|block, MLMCPI_SIGMA_CLUSTER_BITMAP=global|lds.
+// Launch plan, a function of the number of vertices and the batch on either geometry.  A team is one wave
+// when there are enough chains to give every SIMD of the device a wave (B >= 4 x kComputeUnits), the workgroup otherwise; the
+// bitmap sits in LDS where it fits.  Knobs (bit-identical results): MLMCPI_SIGMA_CLUSTER_TEAM=wave|block,
+// MLMCPI_SIGMA_CLUSTER_BITMAP=global|lds.
 ScPlan sc_plan(uint32_t N, uint32_t B, const Tuning &tune) {
   ScPlan p;
   p.words = (N + 31) / 32;
   p.block = tune.sigma_cluster_team ? tune.sigma_cluster_team == 2 : B < 4 * kComputeUnits;
   p.lds_map = !tune.sigma_cluster_map_global && p.words <= (p.block ? kScBlockLdsWords : kScWaveLdsWords);
-  p.threads = p.block ? (N >= 16384 ? kScBlockThreads : 256u) : kScWaveChains * kWave;
+  p.threads = p.block ? (N >= 16384 ? kClusterBlockThreads : 256u) : kScWaveChains * kWave;
   p.grid = p.block ? B : (B + kScWaveChains - 1) / kScWaveChains;
   p.lds_bytes = p.lds_map ? (size_t)p.words * sizeof(uint32_t) * (p.block ? 1 : kScWaveChains) : 0;
   return p;
@@ -179,14 +297,17 @@ ScPlan sc_plan(uint32_t N, uint32_t B, const Tuning &tune) {
 std::mutex g_sc_attr_mutex;
 bool g_sc_attr_set[64] = {false};
 
+// dynamic LDS above 64 KiB: the workgroup team's bitmap up to its bound, on either geometry
 int sc_init_attrs() {
   int dev = 0;
   MLMCPI_HIP_TRY(hipGetDevice(&dev));
   if (dev < 0 || dev >= 64) return fail(MLMCPI_ERR_INVALID, "device index %d out of range", dev);
   std::lock_guard<std::mutex> lock(g_sc_attr_mutex);
   if (g_sc_attr_set[dev]) return MLMCPI_OK;
-  MLMCPI_HIP_TRY(hipFuncSetAttribute((const void *)sigma_cluster_kernel<true, true>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                     kScBlockLdsWords * sizeof(uint32_t)));
+  MLMCPI_HIP_TRY(hipFuncSetAttribute((const void *)sigma_cluster_kernel<true, true>,
+                                     hipFuncAttributeMaxDynamicSharedMemorySize, kScBlockLdsWords * sizeof(uint32_t)));
+  MLMCPI_HIP_TRY(hipFuncSetAttribute((const void *)sigma_rot_cluster_kernel<true, true>,
+                                     hipFuncAttributeMaxDynamicSharedMemorySize, kScBlockLdsWords * sizeof(uint32_t)));
   g_sc_attr_set[dev] = true;
   return MLMCPI_OK;
 }
@@ -205,6 +326,41 @@ int sc_check(const mlmcpi_lattice_action *act, const char *what) {
 size_t sc_section_a(uint32_t N, uint32_t B) { return align256((size_t)B * N * sizeof(double)); }
 size_t sc_section_v(uint32_t N, uint32_t B) { return align256((size_t)B * N * sizeof(uint32_t)); }
 size_t sc_section_map(uint32_t N, uint32_t B) { return align256((size_t)B * ((N + 31) / 32) * sizeof(uint32_t)); }
+size_t sc_workspace(uint32_t N, uint32_t B) { return sc_section_a(N, B) + sc_section_v(N, B) + sc_section_map(N, B); }
+
+// the draw on either geometry, arguments checked; `rot` is the rotated level, NULL on the unrotated Mt x Mx lattice
+int sc_draw(uint32_t Mt, uint32_t Mx, const SigmaLevel *rot, double beta, double *d_phi, uint32_t B, uint32_t n_updates, uint64_t seed,
+            uint32_t chain0, uint32_t update0, uint32_t *d_cluster_sites, void *d_work, void *stream) {
+  if (int rc = sc_init_attrs()) return rc;
+  const uint32_t N = rot ? rot->nvert() : Mt * Mx;
+  const ScPlan p = sc_plan(N, B, tuning());
+  char *w = (char *)d_work;
+  double *qa = (double *)w;
+  uint32_t *qv = (uint32_t *)(w + sc_section_a(N, B));
+  uint32_t *map = (uint32_t *)(w + sc_section_a(N, B) + sc_section_v(N, B));
+  const RngKey key = make_key(seed, chain0, update0);
+  const hipStream_t st = as_stream(stream);
+#define MLMCPI_SC_LAUNCH(KERNEL, BLOCK, LDS, ...)                                                                              \
+  hipLaunchKernelGGL((KERNEL<BLOCK, LDS>), dim3(p.grid), dim3(p.threads), p.lds_bytes, st, (double2 *)d_phi, __VA_ARGS__, 2.0 * beta, B, \
+                     n_updates, key, qv, qa, map, p.words, d_cluster_sites)
+#define MLMCPI_SC_DISPATCH(KERNEL, ...)                                                                                        \
+  do {                                                                                                                         \
+    if (p.block && p.lds_map) MLMCPI_SC_LAUNCH(KERNEL, true, true, __VA_ARGS__);                                               \
+    else if (p.block) MLMCPI_SC_LAUNCH(KERNEL, true, false, __VA_ARGS__);                                                      \
+    else if (p.lds_map) MLMCPI_SC_LAUNCH(KERNEL, false, true, __VA_ARGS__);                                                    \
+    else MLMCPI_SC_LAUNCH(KERNEL, false, false, __VA_ARGS__);                                                                  \
+  } while (0)
+  if (rot) {
+    MLMCPI_SC_DISPATCH(sigma_rot_cluster_kernel, *rot);
+    MLMCPI_LAUNCH_CHECK("sigma_rot_cluster_kernel");
+  } else {
+    MLMCPI_SC_DISPATCH(sigma_cluster_kernel, Mt, Mx);
+    MLMCPI_LAUNCH_CHECK("sigma_cluster_kernel");
+  }
+#undef MLMCPI_SC_DISPATCH
+#undef MLMCPI_SC_LAUNCH
+  return MLMCPI_OK;
+}
 
 }  // namespace
 }  // namespace mlmcpi
@@ -216,8 +372,7 @@ extern "C" {
 int mlmcpi_sigma_cluster_workspace_bytes(const mlmcpi_lattice_action *act, uint32_t B, size_t *bytes) {
   if (int rc = sc_check(act, "mlmcpi_sigma_cluster_workspace_bytes")) return rc;
   MLMCPI_REQUIRE(bytes && B > 0, "bad arguments");
-  const uint32_t N = act->Mt * act->Mx;
-  *bytes = sc_section_a(N, B) + sc_section_v(N, B) + sc_section_map(N, B);
+  *bytes = sc_workspace(act->Mt * act->Mx, B);
   return MLMCPI_OK;
 }
 
@@ -226,25 +381,32 @@ int mlmcpi_sigma_cluster_draw(const mlmcpi_lattice_action *act, double *d_phi, u
   if (int rc = sc_check(act, "mlmcpi_sigma_cluster_draw")) return rc;
   MLMCPI_REQUIRE(d_phi && d_work && B > 0, "bad arguments");
   MLMCPI_REQUIRE((uint64_t)update0 + n_updates <= 0xFFFFFFFFull, "update counter overflows");
-  if (int rc = sc_init_attrs()) return rc;
-  const uint32_t N = act->Mt * act->Mx;
-  const ScPlan p = sc_plan(N, B, tuning());
-  char *w = (char *)d_work;
-  double *qa = (double *)w;
-  uint32_t *qv = (uint32_t *)(w + sc_section_a(N, B));
-  uint32_t *map = (uint32_t *)(w + sc_section_a(N, B) + sc_section_v(N, B));
-  const RngKey key = make_key(seed, chain0, update0);
-  const hipStream_t st = as_stream(stream);
-#define MLMCPI_SC_LAUNCH(BLOCK, LDS)                                                                                           \
-  hipLaunchKernelGGL((sigma_cluster_kernel<BLOCK, LDS>), dim3(p.grid), dim3(p.threads), p.lds_bytes, st, (double2 *)d_phi, act->Mt, \
-                     act->Mx, 2.0 * act->beta, B, n_updates, key, qv, qa, map, p.words, d_cluster_sites)
-  if (p.block && p.lds_map) MLMCPI_SC_LAUNCH(true, true);
-  else if (p.block) MLMCPI_SC_LAUNCH(true, false);
-  else if (p.lds_map) MLMCPI_SC_LAUNCH(false, true);
-  else MLMCPI_SC_LAUNCH(false, false);
-#undef MLMCPI_SC_LAUNCH
-  MLMCPI_LAUNCH_CHECK("sigma_cluster_kernel");
+  return sc_draw(act->Mt, act->Mx, nullptr, act->beta, d_phi, B, n_updates, seed, chain0, update0, d_cluster_sites, d_work, stream);
+}
+
+int mlmcpi_sigma_level_cluster_workspace_bytes(const mlmcpi_sigma_level *level, uint32_t B, size_t *bytes) {
+  if (int rc = check_cluster_level(level)) return rc;
+  MLMCPI_REQUIRE(bytes && B > 0, "bad arguments");
+  if (!level->rotated) {
+    const mlmcpi_lattice_action act = level_as_lattice(level);
+    return mlmcpi_sigma_cluster_workspace_bytes(&act, B, bytes);
+  }
+  *bytes = sc_workspace(make_level(*level).nvert(), B);
   return MLMCPI_OK;
+}
+
+int mlmcpi_sigma_level_cluster_draw(const mlmcpi_sigma_level *level, double *d_state, uint32_t B, uint32_t n_updates,
+                                    uint64_t seed, uint32_t chain0, uint32_t update0, uint32_t *d_cluster_sites, void *d_work,
+                                    void *stream) {
+  if (int rc = check_cluster_level(level)) return rc;
+  MLMCPI_REQUIRE(d_state && d_work && B > 0, "bad arguments");
+  MLMCPI_REQUIRE((uint64_t)update0 + n_updates <= 0xFFFFFFFFull, "update counter overflows");
+  if (!level->rotated) {
+    const mlmcpi_lattice_action act = level_as_lattice(level);
+    return mlmcpi_sigma_cluster_draw(&act, d_state, B, n_updates, seed, chain0, update0, d_cluster_sites, d_work, stream);
+  }
+  const SigmaLevel L = make_level(*level);
+  return sc_draw(0, 0, &L, level->beta, d_state, B, n_updates, seed, chain0, update0, d_cluster_sites, d_work, stream);
 }
 
 }  // extern "C"

@@ -1,0 +1,221 @@
+// sigma_cluster_device.hpp -- what the cluster samplers of the O(3) nonlinear sigma model share (sigma_cluster.hip: Wolff,
+// sigma_sw.hip: Swendsen-Wang; each on the unrotated lattice and on the rotated level of the CoarsenRotate hierarchy): the
+// embedding (normal, bond rule, reflection), the team's phase fence, the lock-free union-find and the fixed-order reduction of
+// the improved estimator, and the two geometries the kernels are instantiated on.  Includes sigma_device.hpp (through
+// sigma_level_device.hpp), so the including file is compiled without fp contraction.
+#pragma once
+#include "sigma_level_device.hpp"
+
+namespace mlmcpi {
+
+constexpr uint32_t kClusterThreads = 256;        // Wolff, team = wave: four chains per workgroup; SW tiled plan: every launch but the last
+constexpr uint32_t kClusterBlockThreads = 1024;  // Wolff, team = workgroup; the fixed configuration of sw_finish; the SW chain plan's workgroup
+// SW chain plan: a (8 B), the root's sum (8 B) and the parent (4 B) of every vertex in LDS beside the 12 KiB of sw_finish
+constexpr uint32_t kSwChainBytesPerVertex = 20;
+constexpr uint32_t kSwChainMaxN = (160 * 1024 - 12 * 1024 - 512) / kSwChainBytesPerVertex;  // 7552 vertices
+constexpr double kSwFix = 4294967296.0;          // 2^32
+constexpr int kUfPlain = -1;                     // uf_find: plain loads (nobody writes the parents any more)
+
+// ---- host: what both samplers ask of a level ---------------------------------------------------------------------------------
+inline int check_cluster_level(const mlmcpi_sigma_level *level) {
+  if (int rc = check_sigma_level(level)) return rc;
+  MLMCPI_REQUIRE(level->beta > 0.0, "beta must be positive");
+  return MLMCPI_OK;
+}
+
+// an unrotated level IS the lattice and takes the lattice's entry point
+inline mlmcpi_lattice_action level_as_lattice(const mlmcpi_sigma_level *l) {
+  return mlmcpi_lattice_action{MLMCPI_NONLINEAR_SIGMA, l->Mt, l->Mx, l->beta, 0.0};
+}
+
+// ---- the embedding ---------------------------------------------------------------------------------------------------------
+// the reflection normal of an update: (u, v) of (site 0, sub 0) -> r_z = 1 - 2 u, azimuth 2 pi v - pi.  Wolff draws it under
+// P_SIGMA_REFLECT, Swendsen-Wang under P_SIGMA_SW_REFLECT.
+__device__ __forceinline__ V3 reflection_normal(const RngKey &key, uint32_t purpose) {
+  double u, v;
+  rng_uniforms(key, 0, purpose, 0, u, v);
+  const double rz = 1.0 - 2.0 * u, t = 1.0 - rz * rz, rho = t > 0.0 ? sqrt(t) : 0.0;
+  double sa, ca;
+  sincos(kTwoPi * v - kPi, &sa, &ca);
+  return V3{rho * ca, rho * sa, rz};
+}
+
+// the bond probability of a link with prod = a_x a_y > 0 (prod <= 0: p = 0, never bonded, and no caller asks)
+__device__ __forceinline__ double bond_probability(double prod, double beta2) { return 1.0 - exp(fmin(0.0, -(beta2 * prod))); }
+
+// the product first: the same bits from either end of the link
+__device__ __forceinline__ bool bonded(double ax, double ay, double beta2, double uni) {
+  const double prod = ax * ay;
+  if (!(prod > 0.0)) return false;                       // p = 0: never bonded
+  return uni < bond_probability(prod, beta2);
+}
+
+// sigma' = sigma - 2 a r in the canonical form (sigma2d.hip)
+__device__ __forceinline__ double2 reflected(const V3 &s, double a, const V3 &r) {
+  const double c = 2.0 * a;
+  return angles_of(V3{s.x - c * r.x, s.y - c * r.y, s.z - c * r.z});
+}
+
+// What orders one phase of a team behind the one before it: the phase's stores (state, queue, bitmap) drained and, for a
+// team of several waves, the barrier.  A team of one wave runs in lockstep and needs the drain only.
+template <bool BLOCK>
+__device__ __forceinline__ void team_sync() {
+  __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");
+  if (BLOCK) __syncthreads();
+  else __builtin_amdgcn_wave_barrier();
+}
+
+// ---- the geometries ---------------------------------------------------------------------------------------------------------
+// A geometry answers what the Swendsen-Wang kernels and the host ask and nothing else: the number of vertices, which vertices
+// own links, how many each, their far ends and their bond bits.  The chain kernel of sigma_sw.hip is written once and
+// instantiated on LatticeGeometry and RotatedGeometry; its tile front ends (bond + label, merge) differ for real and stay one
+// per geometry, and so do the Wolff kernels of sigma_cluster.hip (the reason is given there), which walk the same links.
+
+// The unrotated lattice: vertex l = Mt j + i; link (l, 0) joins l to its +i neighbour, link (l, 1) to its +j neighbour (periodic,
+// 2 N links; on an extent of 2 the two links between a pair are two links with a uniform each).  One Philox call per vertex:
+// site l, sub 0, u decides link (l, 0), v decides link (l, 1).
+struct LatticeGeometry {
+  uint32_t Mt, Mx;
+  static constexpr uint32_t kOwnedLinks = 2;
+  __host__ __device__ uint32_t nvert() const { return Mt * Mx; }
+  __host__ __device__ uint32_t nowners() const { return Mt * Mx; }
+
+  __device__ __forceinline__ void far_ends(uint32_t l, uint32_t (&y)[2]) const {
+    const uint32_t i = l % Mt, j = l / Mt;
+    y[0] = i + 1 == Mt ? l - i : l + 1;
+    y[1] = j + 1 == Mx ? i : l + Mt;
+  }
+
+  // (bond of link (l, 0), bond of link (l, 1)) as bits 0 and 1
+  static __device__ __forceinline__ uint32_t bonds(const RngKey &key, uint32_t l, double a, double a_right, double a_up, double beta2) {
+    const U4 w = philox4x32_10(l, key.chain, key.step, (uint32_t)P_SIGMA_SW_BOND << 24, key.k0, key.k1);
+    return (bonded(a, a_right, beta2, u01(w.x, w.y)) ? 1u : 0u) | (bonded(a, a_up, beta2, u01(w.z, w.w)) ? 2u : 0u);
+  }
+  // the form the chain kernel calls on either geometry: ay[d] = a of the far end of link (l, d).  The bond + label kernel keeps
+  // the scalar form: built through this one it comes out with its LDS reads in another order.
+  static __device__ __forceinline__ uint32_t bonds(const RngKey &key, uint32_t l, double a, const double (&ay)[2], double beta2) {
+    return bonds(key, l, a, ay[0], ay[1], beta2);
+  }
+};
+
+// The rotated level (sigma_level_device.hpp): n = 2 q vertices, plane E then plane O of ht x hx each, index p q + ht b + a.  It is
+// bipartite: every link has exactly one E end, so the 2 n links are named (e, d) with e an E vertex (e < q) and d its direction
+// in the reference's order: E(a, b) -> O(a, b), O(a, b-1), O(a-1, b), O(a-1, b-1).  Seen from O(a, b), direction d' -> E(a+1, b+1),
+// E(a+1, b), E(a, b+1), E(a, b) crosses link (neighbour, 3 - d').  Where a plane extent is 1 several of the four neighbours of a
+// vertex are one vertex; those are distinct links with a uniform each.  Two Philox calls per E vertex: site e, sub d >> 1, u
+// decides link (e, d) for d even, v for d odd.
+struct RotatedGeometry {
+  uint32_t ht, hx, q;  // q = ht hx
+  static constexpr uint32_t kOwnedLinks = 4;
+  explicit RotatedGeometry(const SigmaLevel &L) : ht(L.ht), hx(L.hx), q(L.q) {}
+  __host__ __device__ uint32_t nvert() const { return 2 * q; }
+  __host__ __device__ uint32_t nowners() const { return q; }
+
+  __device__ __forceinline__ void far_ends(uint32_t e, uint32_t (&y)[4]) const {
+    const uint32_t cb = e / ht, ca = e - cb * ht;
+    const uint32_t am = ca == 0 ? ht - 1 : ca - 1, bm = cb == 0 ? hx - 1 : cb - 1;
+    y[0] = q + cb * ht + ca;
+    y[1] = q + bm * ht + ca;
+    y[2] = q + cb * ht + am;
+    y[3] = q + bm * ht + am;
+  }
+
+  // the bonds of the links (e, 0) .. (e, 3) as bits 0 .. 3; ao[d] = a of the O end of link (e, d)
+  static __device__ __forceinline__ uint32_t bonds(const RngKey &key, uint32_t e, double a, const double (&ao)[4], double beta2) {
+    const U4 w0 = philox4x32_10(e, key.chain, key.step, (uint32_t)P_SIGMA_SW_BOND << 24, key.k0, key.k1);
+    const U4 w1 = philox4x32_10(e, key.chain, key.step, ((uint32_t)P_SIGMA_SW_BOND << 24) | 1u, key.k0, key.k1);
+    return (bonded(a, ao[0], beta2, u01(w0.x, w0.y)) ? 1u : 0u) | (bonded(a, ao[1], beta2, u01(w0.z, w0.w)) ? 2u : 0u) |
+           (bonded(a, ao[2], beta2, u01(w1.x, w1.y)) ? 4u : 0u) | (bonded(a, ao[3], beta2, u01(w1.z, w1.w)) ? 8u : 0u);
+  }
+};
+
+// ---- the union-find of the Swendsen-Wang labelling -------------------------------------------------------------------------
+// The parent of a vertex is a vertex of its cluster with a smaller or equal index; a root is its own parent.  union(x, y): find
+// both roots, hang the larger under the smaller with an atomic min on the parent word of the larger; if the word held
+// something else meanwhile (another lane got there first), go on with (what it held, the smaller root): the edge the min may
+// have replaced is the one that pair restores.  max(x, y) decreases with every retry, a path visits decreasing indices: the
+// number of vertices bounds every loop, and the final root of a component is its smallest vertex whatever the order of
+// arrival.  Every loop carries that bound as `cap`; a cap that is hit all the same sets `capped`, which the kernels turn into
+// a status word the entry point returns as an error.  No loop waits on another lane's store.
+template <int SCOPE>
+__device__ __forceinline__ uint32_t uf_parent(const uint32_t *parent, uint32_t x) {
+  // other lanes (tiled plan: workgroups on other XCDs) lower parent words meanwhile: an atomic load of that scope, not a plain one
+  if constexpr (SCOPE == kUfPlain) return parent[x];
+  else return __hip_atomic_load(parent + x, __ATOMIC_RELAXED, SCOPE);
+}
+
+// the root above x; a path visits strictly decreasing indices, so `cap` >= the number of vertices bounds it
+template <int SCOPE>
+__device__ __forceinline__ uint32_t uf_find(const uint32_t *parent, uint32_t x, uint32_t cap, bool &capped) {
+  for (uint32_t it = 0; it < cap; ++it) {
+    const uint32_t p = uf_parent<SCOPE>(parent, x);
+    if (p == x) return x;
+    x = p;
+  }
+  capped = true;
+  return x;
+}
+
+template <int SCOPE>
+__device__ __forceinline__ void uf_union(uint32_t *parent, uint32_t x, uint32_t y, uint32_t cap, bool &capped) {
+  for (uint32_t it = 0; it < cap; ++it) {                // max(x, y) decreases with every retry
+    x = uf_find<SCOPE>(parent, x, cap, capped);
+    y = uf_find<SCOPE>(parent, y, cap, capped);
+    if (x == y || capped) return;                        // x == y: also union(x, x), a no-op
+    if (x < y) {
+      const uint32_t t = x;
+      x = y;
+      y = t;
+    }
+    const uint32_t old = __hip_atomic_fetch_min(parent + x, y, __ATOMIC_RELAXED, SCOPE);
+    if (old == x) return;                                // x was a root still: it hangs under y now
+    x = old;                                             // somebody else hung x under `old`: unite that with y
+  }
+  capped = true;
+}
+
+// ---- Swendsen-Wang: the coin, the fixed point and the reductions -----------------------------------------------------------
+__device__ __forceinline__ bool sw_coin(const RngKey &key, uint32_t root) {
+  double u, unused;
+  rng_uniforms(key, root, P_SIGMA_SW_FLIP, 0, u, unused);
+  return u < 0.5;
+}
+
+__device__ __forceinline__ long long sw_fixed(double a) { return llrint(a * kSwFix); }
+
+// sum over the roots of (A_C 2^-32)^2 and their number, in the fixed configuration (kClusterBlockThreads threads, every thread
+// of the workgroup calls it); thread 0 adds 3 / N x the sum to *improved and the number to *clusters (either may be NULL)
+__device__ __forceinline__ void sw_finish(const uint32_t *parent, const long long *sum, uint32_t N, double *red, uint32_t *redc,
+                                          double *improved, uint32_t *clusters) {
+  const uint32_t t = threadIdx.x;
+  double s = 0.0;
+  uint32_t c = 0;
+  for (uint32_t l = t; l < N; l += kClusterBlockThreads)
+    if (parent[l] == l) {
+      const double A = (double)sum[l] * (1.0 / kSwFix);
+      s += A * A;
+      ++c;
+    }
+  red[t] = s;
+  redc[t] = c;
+  __syncthreads();
+  for (uint32_t off = kClusterBlockThreads / 2; off > 0; off >>= 1) {
+    if (t < off) {
+      red[t] += red[t + off];
+      redc[t] += redc[t + off];
+    }
+    __syncthreads();
+  }
+  if (t == 0) {
+    if (improved) *improved += red[0] * (3.0 / (double)N);
+    if (clusters) *clusters += redc[0];
+  }
+}
+
+// one atomic per wave: the lanes of the wave that flipped a vertex (every lane of the wave calls it)
+__device__ __forceinline__ void sw_count_flips(bool flip, uint32_t *flipped_b) {
+  const unsigned long long m = __ballot(flip);
+  if (flipped_b && m && (threadIdx.x & (kWave - 1)) == (uint32_t)__builtin_ctzll(m)) atomicAdd(flipped_b, (uint32_t)__builtin_popcountll(m));
+}
+
+}  // namespace mlmcpi

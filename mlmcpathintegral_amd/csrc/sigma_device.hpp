@@ -19,6 +19,9 @@ __device__ __forceinline__ V3 sigma_of(double2 a) {
   return V3{st * cp, st * sp, ct};
 }
 
+// one association everywhere: (x x + y y) + z z
+__device__ __forceinline__ double dot3(const V3 &a, const V3 &b) { return (a.x * b.x + a.y * b.y) + a.z * b.z; }
+
 __device__ __forceinline__ double2 angles_of(const V3 &s) {
   return make_double2(atan2(sqrt(s.x * s.x + s.y * s.y), s.z), atan2(s.y, s.x));
 }

@@ -95,8 +95,6 @@ __device__ __forceinline__ void coarse_bond_site(const SigmaLevel &L, uint32_t x
   }
 }
 
-__device__ __forceinline__ double dot3(const V3 &a, const V3 &b) { return a.x * b.x + a.y * b.y + a.z * b.z; }
-
 // -log p(z; s) of the density p(z) = s exp(s z) / (2 sinh s) on [-1, 1] (distribution/compactexpdistribution.cc) for a spin sig
 // under the neighbour sum Dl, s = beta |Dl|, z = sig . Dl / |Dl|:  log p = s (z - 1) + log s - log(1 - exp(-2 s)), which
 // neither overflows at large s nor cancels at small s; Dl = 0 gives the uniform density 1/2.

@@ -1,4 +1,8 @@
-// sigma_sw.hip -- the Swendsen-Wang multi-cluster update of the O(3) nonlinear sigma model (gfx950, wave64).
+// sigma_sw.hip -- the Swendsen-Wang multi-cluster update of the O(3) nonlinear sigma model (gfx950, wave64), on the unrotated
+// lattice (mlmcpi_sigma_sw_*) and on the levels of its CoarsenRotate hierarchy (mlmcpi_sigma_level_sw_*; an unrotated level IS
+// the lattice and takes its entry point).  The geometry lives in sigma_cluster_device.hpp (LatticeGeometry, RotatedGeometry): the
+// chain kernel is instantiated on it, the resolve and finish kernels use none, the two tile front ends (bond + label, merge)
+// are written once per geometry.
 //
 // The multi-cluster form of the embedding sigma_cluster.hip grows one cluster of: one update tests ALL 2 N links once, labels
 // EVERY connected component of the graph of bonded links and reflects each component with probability 1/2.  The reference has
@@ -24,141 +28,34 @@
 // order, then a fixed tree.  That sum is the same bits under every plan, and it is ADDED to the caller's accumulator update by
 // update, so that 10 updates equal 5 + 5 to the bit.
 //
-// Labelling.  The parent of a vertex is a vertex of its cluster with a smaller or equal index; a root is its own parent.
-// union(x, y): find both roots, hang the larger under the smaller with an atomic min on the parent word of the larger; if
-// the word held something else meanwhile (another lane got there first), go on with (what it held, the smaller root): the
-// edge the min may have replaced is the one that pair restores.  max(x, y) decreases with every retry, a path visits
-// decreasing indices: N iterations bound every loop, and the final root of a component is its smallest vertex whatever the
-// order of arrival.  A cap that is hit all the same sets a status word the entry point returns as an error.
+// On a rotated level (tests/sigma_level_sw_model.py) the same update with the level's indices: n = Mt Mx / 2 vertices, plane E then
+// plane O, the 2 n links named (e, d) from their E end (sigma_cluster_device.hpp), the root of a cluster its smallest LEVEL
+// index (also when the cluster is a lone O vertex), P_SIGMA_SW_BOND at site e, sub d >> 1: u decides link (e, d) for d even, v
+// for d odd.  union(x, x) returns at once (level (2, 2): the four links of E(0, 0) all end at O(0, 0)).
+//
+// Labelling: the parent array and the union by atomic min of sigma_cluster_device.hpp (uf_*), where its termination argument
+// is written out.
 #include <mutex>
 
 #include "internal.hpp"
 
-#include "sigma_device.hpp"  // fp contraction is off from here on
+#include "sigma_cluster_device.hpp"  // fp contraction is off from here on
 
 namespace mlmcpi {
 
-constexpr uint32_t kSwThreads = 256;         // tiled plan: bond + label, merge, resolve
-constexpr uint32_t kSwFinishThreads = 1024;  // the fixed configuration of sw_finish; the chain plan's workgroup
-// chain plan: a (8 B), the root's sum (8 B) and the parent (4 B) of every vertex in LDS beside the 12 KiB of sw_finish
-constexpr uint32_t kSwChainBytesPerVertex = 20;
-constexpr uint32_t kSwChainMaxN = (160 * 1024 - 12 * 1024 - 512) / kSwChainBytesPerVertex;  // 7552 vertices
-constexpr double kSwFix = 4294967296.0;      // 2^32
-constexpr int kSwPlain = -1;                 // sw_find: plain loads (nobody writes the parents any more)
+constexpr uint32_t kSwMaxTile = 64;          // the largest tile extent MLMCPI_SIGMA_SW_TILE admits, in cells
 
-__device__ __forceinline__ double sw_dot(const V3 &r, const V3 &s) { return (r.x * s.x + r.y * s.y) + r.z * s.z; }
-
-__device__ __forceinline__ V3 sw_normal(const RngKey &key) {
-  double u, v;
-  rng_uniforms(key, 0, P_SIGMA_SW_REFLECT, 0, u, v);
-  const double rz = 1.0 - 2.0 * u, t = 1.0 - rz * rz, rho = t > 0.0 ? sqrt(t) : 0.0;
-  double sa, ca;
-  sincos(kTwoPi * v - kPi, &sa, &ca);
-  return V3{rho * ca, rho * sa, rz};
-}
-
-__device__ __forceinline__ bool sw_bonded(double ax, double ay, double beta2, double uni) {
-  const double prod = ax * ay;
-  if (!(prod > 0.0)) return false;                       // p = 0: never bonded
-  return uni < 1.0 - exp(fmin(0.0, -(beta2 * prod)));
-}
-
-// (bond of link (l, 0), bond of link (l, 1)) as bits 0 and 1
-__device__ __forceinline__ uint32_t sw_bonds(const RngKey &key, uint32_t l, double a, double a_right, double a_up, double beta2) {
-  const U4 w = philox4x32_10(l, key.chain, key.step, (uint32_t)P_SIGMA_SW_BOND << 24, key.k0, key.k1);
-  return (sw_bonded(a, a_right, beta2, u01(w.x, w.y)) ? 1u : 0u) | (sw_bonded(a, a_up, beta2, u01(w.z, w.w)) ? 2u : 0u);
-}
-
-__device__ __forceinline__ bool sw_coin(const RngKey &key, uint32_t root) {
-  double u, unused;
-  rng_uniforms(key, root, P_SIGMA_SW_FLIP, 0, u, unused);
-  return u < 0.5;
-}
-
-__device__ __forceinline__ double2 sw_reflected(const V3 &s, double a, const V3 &r) {
-  const double c = 2.0 * a;
-  return angles_of(V3{s.x - c * r.x, s.y - c * r.y, s.z - c * r.z});
-}
-
-__device__ __forceinline__ long long sw_fixed(double a) { return llrint(a * kSwFix); }
-
-template <int SCOPE>
-__device__ __forceinline__ uint32_t sw_parent(const uint32_t *parent, uint32_t x) {
-  // other lanes (tiled plan: workgroups on other XCDs) lower parent words meanwhile: an atomic load of that scope, not a plain one
-  if constexpr (SCOPE == kSwPlain) return parent[x];
-  else return __hip_atomic_load(parent + x, __ATOMIC_RELAXED, SCOPE);
-}
-
-// the root above x; a path visits strictly decreasing indices, so `cap` >= the number of vertices bounds it
-template <int SCOPE>
-__device__ __forceinline__ uint32_t sw_find(const uint32_t *parent, uint32_t x, uint32_t cap, bool &capped) {
-  for (uint32_t it = 0; it < cap; ++it) {
-    const uint32_t p = sw_parent<SCOPE>(parent, x);
-    if (p == x) return x;
-    x = p;
-  }
-  capped = true;
-  return x;
-}
-
-template <int SCOPE>
-__device__ __forceinline__ void sw_union(uint32_t *parent, uint32_t x, uint32_t y, uint32_t cap, bool &capped) {
-  for (uint32_t it = 0; it < cap; ++it) {                // max(x, y) decreases with every retry
-    x = sw_find<SCOPE>(parent, x, cap, capped);
-    y = sw_find<SCOPE>(parent, y, cap, capped);
-    if (x == y || capped) return;
-    if (x < y) {
-      const uint32_t t = x;
-      x = y;
-      y = t;
-    }
-    const uint32_t old = __hip_atomic_fetch_min(parent + x, y, __ATOMIC_RELAXED, SCOPE);
-    if (old == x) return;                                // x was a root still: it hangs under y now
-    x = old;                                             // somebody else hung x under `old`: unite that with y
-  }
-  capped = true;
-}
-
-// sum over the roots of (A_C 2^-32)^2 and their number, in the fixed configuration (kSwFinishThreads threads, every thread of
-// the workgroup calls it); thread 0 adds 3 / N x the sum to *improved and the number to *clusters (either may be NULL)
-__device__ __forceinline__ void sw_finish(const uint32_t *parent, const long long *sum, uint32_t N, double *red, uint32_t *redc,
-                                          double *improved, uint32_t *clusters) {
-  const uint32_t t = threadIdx.x;
-  double s = 0.0;
-  uint32_t c = 0;
-  for (uint32_t l = t; l < N; l += kSwFinishThreads)
-    if (parent[l] == l) {
-      const double A = (double)sum[l] * (1.0 / kSwFix);
-      s += A * A;
-      ++c;
-    }
-  red[t] = s;
-  redc[t] = c;
-  __syncthreads();
-  for (uint32_t off = kSwFinishThreads / 2; off > 0; off >>= 1) {
-    if (t < off) {
-      red[t] += red[t + off];
-      redc[t] += redc[t + off];
-    }
-    __syncthreads();
-  }
-  if (t == 0) {
-    if (improved) *improved += red[0] * (3.0 / (double)N);
-    if (clusters) *clusters += redc[0];
-  }
-}
-
-// one atomic per wave: the lanes of the wave that flipped a vertex
-__device__ __forceinline__ void sw_count_flips(bool flip, uint32_t *flipped_b) {
-  const unsigned long long m = __ballot(flip);
-  if (flipped_b && m && (threadIdx.x & (kWave - 1)) == (uint32_t)__builtin_ctzll(m)) atomicAdd(flipped_b, (uint32_t)__builtin_popcountll(m));
+// rotated level, launch 1: a of the tile's E cells [W H], a of its O cells and their -a / -b halo [(W + 1)(H + 1)], the parents
+// [2 W H] uint32, the bond bits [W H] uint8
+__host__ __device__ constexpr size_t sw_rot_tile_lds(uint32_t W, uint32_t H) {
+  return ((size_t)W * H + (size_t)(W + 1) * (H + 1)) * sizeof(double) + (size_t)2 * W * H * sizeof(uint32_t) + (size_t)W * H;
 }
 
 // ---- tiled plan, launch 1: bonds of the tile's vertices, union-find on the tile's interior links in LDS --------------------
 // A workgroup takes a tile of W x H vertices (w x h where the lattice ends: masked, not padded) of one chain.  LDS: a of the
 // tile and of its +i / +j halo [(H + 1)(W + 1)] double, the parents [H W] uint32 (local index W lj + li: the order of the
 // global index inside a tile), the bond bits [H W] uint8.
-__global__ void __launch_bounds__(kSwThreads)
+__global__ void __launch_bounds__(kClusterThreads)
     sigma_sw_bond_label_kernel(const double2 *phi_all, uint32_t Mt, uint32_t Mx, double beta2, RngKey key0, uint32_t W, uint32_t H,
                                uint32_t ntx, uint32_t nty, uint32_t *label_all, uint8_t *bits_all, long long *qa_all,
                                long long *sum_all, uint32_t *status) {
@@ -174,15 +71,15 @@ __global__ void __launch_bounds__(kSwThreads)
   const double2 *phi = phi_all + (size_t)b * N;
   RngKey key = key0;
   key.chain = key0.chain + b;
-  const V3 r = sw_normal(key);
+  const V3 r = reflection_normal(key, P_SIGMA_SW_REFLECT);
 
-  for (uint32_t p = threadIdx.x; p < (w + 1) * (h + 1) - 1; p += kSwThreads) {   // - 1: the corner of the halo has no link
+  for (uint32_t p = threadIdx.x; p < (w + 1) * (h + 1) - 1; p += kClusterThreads) {   // - 1: the corner of the halo has no link
     const uint32_t li = p % (w + 1), lj = p / (w + 1);
     uint32_t gi = i0 + li, gj = j0 + lj;
     gi = gi == Mt ? 0 : gi;
     gj = gj == Mx ? 0 : gj;
     const uint32_t l = gj * Mt + gi;
-    const double al = sw_dot(r, sigma_of(phi[l]));
+    const double al = dot3(r, sigma_of(phi[l]));
     a[lj * SA + li] = al;
     if (li < w && lj < h) {
       qa_all[(size_t)b * N + l] = sw_fixed(al);
@@ -190,24 +87,24 @@ __global__ void __launch_bounds__(kSwThreads)
     }
   }
   __syncthreads();
-  for (uint32_t p = threadIdx.x; p < w * h; p += kSwThreads) {
+  for (uint32_t p = threadIdx.x; p < w * h; p += kClusterThreads) {
     const uint32_t li = p % w, lj = p / w, loc = lj * W + li, l = (j0 + lj) * Mt + i0 + li;
-    const uint32_t bits = sw_bonds(key, l, a[lj * SA + li], a[lj * SA + li + 1], a[(lj + 1) * SA + li], beta2);
+    const uint32_t bits = LatticeGeometry::bonds(key, l, a[lj * SA + li], a[lj * SA + li + 1], a[(lj + 1) * SA + li], beta2);
     bits_all[(size_t)b * N + l] = (uint8_t)bits;
     lbits[loc] = (uint8_t)bits;
     parent[loc] = loc;
   }
   __syncthreads();
   bool capped = false;
-  for (uint32_t p = threadIdx.x; p < w * h; p += kSwThreads) {
+  for (uint32_t p = threadIdx.x; p < w * h; p += kClusterThreads) {
     const uint32_t li = p % w, lj = p / w, loc = lj * W + li, bits = lbits[loc];
-    if ((bits & 1u) && li + 1 < w) sw_union<__HIP_MEMORY_SCOPE_WORKGROUP>(parent, loc, loc + 1, W * H, capped);
-    if ((bits & 2u) && lj + 1 < h) sw_union<__HIP_MEMORY_SCOPE_WORKGROUP>(parent, loc, loc + W, W * H, capped);
+    if ((bits & 1u) && li + 1 < w) uf_union<__HIP_MEMORY_SCOPE_WORKGROUP>(parent, loc, loc + 1, W * H, capped);
+    if ((bits & 2u) && lj + 1 < h) uf_union<__HIP_MEMORY_SCOPE_WORKGROUP>(parent, loc, loc + W, W * H, capped);
   }
   __syncthreads();
-  for (uint32_t p = threadIdx.x; p < w * h; p += kSwThreads) {
+  for (uint32_t p = threadIdx.x; p < w * h; p += kClusterThreads) {
     const uint32_t li = p % w, lj = p / w;
-    const uint32_t root = sw_find<__HIP_MEMORY_SCOPE_WORKGROUP>(parent, lj * W + li, W * H, capped);
+    const uint32_t root = uf_find<__HIP_MEMORY_SCOPE_WORKGROUP>(parent, lj * W + li, W * H, capped);
     label_all[(size_t)b * N + (j0 + lj) * Mt + i0 + li] = (j0 + root / W) * Mt + i0 + root % W;
   }
   if (capped) atomicOr(status, 1u);
@@ -215,10 +112,10 @@ __global__ void __launch_bounds__(kSwThreads)
 
 // ---- launch 2: one lane per link that leaves its tile (the periodic wrap and both links of an extent-2 pair included) -------
 // per chain ntx Mx links of direction 0 (from the last column of every tile column) and nty Mt of direction 1
-__global__ void __launch_bounds__(kSwThreads)
+__global__ void __launch_bounds__(kClusterThreads)
     sigma_sw_merge_kernel(uint32_t Mt, uint32_t Mx, uint32_t W, uint32_t H, uint32_t ntx, uint32_t nty, uint32_t blocks,
                           uint32_t *label_all, const uint8_t *bits_all, uint32_t *status) {
-  const uint32_t b = blockIdx.x / blocks, e = (blockIdx.x % blocks) * kSwThreads + threadIdx.x;
+  const uint32_t b = blockIdx.x / blocks, e = (blockIdx.x % blocks) * kClusterThreads + threadIdx.x;
   const uint32_t N = Mt * Mx, E0 = ntx * Mx, E1 = nty * Mt;
   if (e >= E0 + E1) return;
   uint32_t l, y, bit;
@@ -237,29 +134,137 @@ __global__ void __launch_bounds__(kSwThreads)
   }
   if (!(bits_all[(size_t)b * N + l] & bit)) return;
   bool capped = false;
-  sw_union<__HIP_MEMORY_SCOPE_AGENT>(label_all + (size_t)b * N, l, y, N, capped);
+  uf_union<__HIP_MEMORY_SCOPE_AGENT>(label_all + (size_t)b * N, l, y, N, capped);
+  if (capped) atomicOr(status, 1u);
+}
+
+// ---- rotated level, launch 1: bonds of the tile's E vertices, union-find on the tile's interior links in LDS ----------------
+// A workgroup takes a tile of W x H plane CELLS of one chain: cell (a, b) is the pair E(a, b), O(a, b) (w x h cells where the
+// plane ends: masked, not padded).  The links (e, d) of E(a, b) end at O(a - (d >> 1), b - (d & 1)), so the tile needs a of its
+// own cells and of the O vertices one column to the -a side and one row to the -b side: the O image is (w + 1) x (h + 1) with
+// its row 0 and column 0 the halo.  A link is INTERIOR to the tile iff its O end is a cell of the tile without a periodic wrap:
+// li >= (d >> 1) and lj >= (d & 1) in tile coordinates; every other link is a crossing link of launch 2 (also the wrap of a
+// plane that one tile covers).
+// Local order of the union-find: E cell (li, lj) -> W lj + li, O cell (li, lj) -> W H + W lj + li.  Inside a plane the level
+// index is ht b + a, which orders the cells of a tile by (b, a) exactly as W lj + li orders them by (lj, li); and every E vertex
+// of the level (index < n / 2) precedes every O vertex, as every local E index (< W H) precedes every local O index.  So the
+// local order is the order of the level index restricted to the tile, and a local root -- the smallest local index of its
+// component -- is the smallest level index of it.
+__global__ void __launch_bounds__(kClusterThreads)
+    sigma_rot_sw_bond_label_kernel(const double2 *phi_all, SigmaLevel L, double beta2, RngKey key0, uint32_t W, uint32_t H,
+                                   uint32_t ntx, uint32_t nty, uint32_t *label_all, uint8_t *bits_all, long long *qa_all,
+                                   long long *sum_all, uint32_t *status) {
+  extern __shared__ double sw_lds[];
+  const uint32_t SA = W + 1, WH = W * H;
+  double *aE = sw_lds;
+  double *aO = aE + WH;
+  uint32_t *parent = (uint32_t *)(aO + (size_t)SA * (H + 1));
+  uint8_t *lbits = (uint8_t *)(parent + 2 * WH);
+  const uint32_t tiles = ntx * nty, b = blockIdx.x / tiles, tile = blockIdx.x % tiles;
+  const uint32_t a0 = (tile % ntx) * W, b0 = (tile / ntx) * H;
+  const uint32_t ht = L.ht, hx = L.hx, q = L.q, n = 2 * q;
+  const uint32_t w = ht - a0 < W ? ht - a0 : W, h = hx - b0 < H ? hx - b0 : H;
+  const double2 *phi = phi_all + (size_t)b * n;
+  RngKey key = key0;
+  key.chain = key0.chain + b;
+  const V3 r = reflection_normal(key, P_SIGMA_SW_REFLECT);
+
+  for (uint32_t p = threadIdx.x; p < (w + 1) * (h + 1); p += kClusterThreads) {
+    const uint32_t li = p % (w + 1), lj = p / (w + 1);   // O image: (0, .) and (., 0) are the halo, (li, lj) is cell (li - 1, lj - 1)
+    const uint32_t oa = a0 + li == 0 ? ht - 1 : a0 + li - 1, ob = b0 + lj == 0 ? hx - 1 : b0 + lj - 1;
+    const uint32_t lo = q + ob * ht + oa;
+    const double ao = dot3(r, sigma_of(phi[lo]));
+    aO[lj * SA + li] = ao;
+    if (li > 0 && lj > 0) {                              // a cell of the tile: its O vertex and its E vertex
+      const uint32_t le = lo - q;
+      const double ae = dot3(r, sigma_of(phi[le]));
+      aE[(lj - 1) * W + li - 1] = ae;
+      qa_all[(size_t)b * n + lo] = sw_fixed(ao);
+      qa_all[(size_t)b * n + le] = sw_fixed(ae);
+      if (sum_all) {
+        sum_all[(size_t)b * n + lo] = 0;
+        sum_all[(size_t)b * n + le] = 0;
+      }
+    }
+  }
+  __syncthreads();
+  for (uint32_t p = threadIdx.x; p < w * h; p += kClusterThreads) {
+    const uint32_t li = p % w, lj = p / w, loc = lj * W + li, e = (b0 + lj) * ht + a0 + li;
+    const double ao[4] = {aO[(lj + 1) * SA + li + 1], aO[lj * SA + li + 1], aO[(lj + 1) * SA + li], aO[lj * SA + li]};
+    const uint32_t bits = RotatedGeometry::bonds(key, e, aE[loc], ao, beta2);
+    bits_all[(size_t)b * q + e] = (uint8_t)bits;
+    lbits[loc] = (uint8_t)bits;
+    parent[loc] = loc;
+    parent[WH + loc] = WH + loc;
+  }
+  __syncthreads();
+  bool capped = false;
+  for (uint32_t p = threadIdx.x; p < w * h; p += kClusterThreads) {
+    const uint32_t li = p % w, lj = p / w, loc = lj * W + li, bits = lbits[loc];
+    if (bits & 1u) uf_union<__HIP_MEMORY_SCOPE_WORKGROUP>(parent, loc, WH + loc, 2 * WH, capped);
+    if ((bits & 2u) && lj > 0) uf_union<__HIP_MEMORY_SCOPE_WORKGROUP>(parent, loc, WH + loc - W, 2 * WH, capped);
+    if ((bits & 4u) && li > 0) uf_union<__HIP_MEMORY_SCOPE_WORKGROUP>(parent, loc, WH + loc - 1, 2 * WH, capped);
+    if ((bits & 8u) && li > 0 && lj > 0) uf_union<__HIP_MEMORY_SCOPE_WORKGROUP>(parent, loc, WH + loc - W - 1, 2 * WH, capped);
+  }
+  __syncthreads();
+  for (uint32_t p = threadIdx.x; p < 2 * w * h; p += kClusterThreads) {
+    const uint32_t plane = p >= w * h ? 1u : 0u, c = p - plane * w * h, li = c % w, lj = c / w;
+    const uint32_t root = uf_find<__HIP_MEMORY_SCOPE_WORKGROUP>(parent, plane * WH + lj * W + li, 2 * WH, capped);
+    const uint32_t rplane = root >= WH ? 1u : 0u, rc = root - rplane * WH;
+    label_all[(size_t)b * n + plane * q + (b0 + lj) * ht + a0 + li] = rplane * q + (b0 + rc / W) * ht + a0 + rc % W;
+  }
+  if (capped) atomicOr(status, 1u);
+}
+
+// ---- rotated level, launch 2: one lane per link that leaves its tile -------------------------------------------------------------------
+// Per chain: 2 ntx hx lanes for the links d = 2, 3 of the E vertices in the first column of every tile column (their O end is
+// one column to the -a side: another tile, or the wrap), then 2 nty ht lanes for the links d = 1, 3 of the E vertices in the
+// first row of every tile row.  The d = 3 link of a tile's corner cell is in both sets: the lane of the second set returns, so
+// it is crossed once.
+__global__ void __launch_bounds__(kClusterThreads)
+    sigma_rot_sw_merge_kernel(SigmaLevel L, uint32_t W, uint32_t H, uint32_t ntx, uint32_t nty, uint32_t blocks, uint32_t *label_all,
+                              const uint8_t *bits_all, uint32_t *status) {
+  const uint32_t b = blockIdx.x / blocks, x = (blockIdx.x % blocks) * kClusterThreads + threadIdx.x;
+  const uint32_t ht = L.ht, hx = L.hx, q = L.q, n = 2 * q, E0 = 2 * ntx * hx, E1 = 2 * nty * ht;
+  if (x >= E0 + E1) return;
+  uint32_t ca, cb, d;
+  if (x < E0) {
+    d = 2u + (x & 1u);
+    ca = ((x >> 1) % ntx) * W;
+    cb = (x >> 1) / ntx;
+  } else {
+    const uint32_t y = x - E0;
+    d = 1u + ((y & 1u) << 1);
+    ca = (y >> 1) % ht;
+    cb = ((y >> 1) / ht) * H;
+    if (d == 3u && ca % W == 0) return;                  // the corner cell's d = 3 link: the first set has it
+  }
+  const uint32_t e = cb * ht + ca;
+  if (!(bits_all[(size_t)b * q + e] & (1u << d))) return;
+  const uint32_t oa = (d & 2u) ? (ca == 0 ? ht - 1 : ca - 1) : ca, ob = (d & 1u) ? (cb == 0 ? hx - 1 : cb - 1) : cb;
+  bool capped = false;
+  uf_union<__HIP_MEMORY_SCOPE_AGENT>(label_all + (size_t)b * n, e, q + ob * ht + oa, n, capped);
   if (capped) atomicOr(status, 1u);
 }
 
 // ---- launch 3: every vertex follows its label to the final root, adds q(a) to the root's slot, evaluates the root's coin -----
 // and, when the coin says so, stores its reflection (non-temporal; nothing is stored otherwise)
-__global__ void __launch_bounds__(kSwThreads)
-    sigma_sw_resolve_kernel(double2 *phi_all, uint32_t Mt, uint32_t Mx, RngKey key0, uint32_t blocks, const uint32_t *label_all,
+__global__ void __launch_bounds__(kClusterThreads)
+    sigma_sw_resolve_kernel(double2 *phi_all, uint32_t N, RngKey key0, uint32_t blocks, const uint32_t *label_all,
                             const long long *qa_all, long long *sum_all, uint32_t *flipped, uint32_t *status) {
-  const uint32_t b = blockIdx.x / blocks, l = (blockIdx.x % blocks) * kSwThreads + threadIdx.x;
-  const uint32_t N = Mt * Mx;
+  const uint32_t b = blockIdx.x / blocks, l = (blockIdx.x % blocks) * kClusterThreads + threadIdx.x;
   RngKey key = key0;
   key.chain = key0.chain + b;
   bool flip = false, capped = false;
   if (l < N) {
-    const uint32_t root = sw_find<kSwPlain>(label_all + (size_t)b * N, l, N, capped);
+    const uint32_t root = uf_find<kUfPlain>(label_all + (size_t)b * N, l, N, capped);
     if (sum_all) atomicAdd((unsigned long long *)(sum_all + (size_t)b * N + root), (unsigned long long)qa_all[(size_t)b * N + l]);
     flip = !capped && sw_coin(key, root);
     if (flip) {
-      const V3 r = sw_normal(key);
+      const V3 r = reflection_normal(key, P_SIGMA_SW_REFLECT);
       double2 *p = phi_all + (size_t)b * N + l;
       const V3 s = sigma_of(*p);
-      const double2 out = sw_reflected(s, sw_dot(r, s), r);
+      const double2 out = reflected(s, dot3(r, s), r);
       __builtin_nontemporal_store(out.x, &p->x);
       __builtin_nontemporal_store(out.y, &p->y);
     }
@@ -269,24 +274,28 @@ __global__ void __launch_bounds__(kSwThreads)
 }
 
 // ---- launch 4 (only when outputs are asked for): one workgroup per chain --------------------------------------------------
-__global__ void __launch_bounds__(kSwFinishThreads)
+__global__ void __launch_bounds__(kClusterBlockThreads)
     sigma_sw_finish_kernel(const uint32_t *label_all, const long long *sum_all, uint32_t N, double *improved, uint32_t *clusters) {
-  __shared__ double red[kSwFinishThreads];
-  __shared__ uint32_t redc[kSwFinishThreads];
+  __shared__ double red[kClusterBlockThreads];
+  __shared__ uint32_t redc[kClusterBlockThreads];
   const uint32_t b = blockIdx.x;
   sw_finish(label_all + (size_t)b * N, sum_all + (size_t)b * N, N, red, redc, improved ? improved + b : nullptr,
             clusters ? clusters + b : nullptr);
 }
 
 // ---- chain plan: one workgroup per chain, all n_updates updates in one launch, labels, sums and a in LDS ------------------
-// Thread t owns the vertices t, t + 1024, ..: it alone reads and writes their angles, update after update.
-__global__ void __launch_bounds__(kSwFinishThreads)
-    sigma_sw_chain_kernel(double2 *phi_all, uint32_t Mt, uint32_t Mx, double beta2, uint32_t n_updates, RngKey key0, uint32_t *flipped,
+// Thread t owns the vertices t, t + 1024, ..: it alone reads and writes their angles, update after update.  Bonds are drawn and
+// united from the vertices that own links: every vertex its +i and +j link on the lattice; on a rotated level a lane with an E
+// vertex makes two Philox calls and handles its four links, a lane with an O vertex makes none.
+template <class Geometry>
+__global__ void __launch_bounds__(kClusterBlockThreads)
+    sigma_sw_chain_kernel(double2 *phi_all, Geometry g, double beta2, uint32_t n_updates, RngKey key0, uint32_t *flipped,
                           uint32_t *clusters, double *improved, uint32_t *status) {
   extern __shared__ double sw_lds[];
-  __shared__ double red[kSwFinishThreads];
-  __shared__ uint32_t redc[kSwFinishThreads];
-  const uint32_t N = Mt * Mx, b = blockIdx.x, t = threadIdx.x;
+  __shared__ double red[kClusterBlockThreads];
+  __shared__ uint32_t redc[kClusterBlockThreads];
+  constexpr uint32_t NL = Geometry::kOwnedLinks;
+  const uint32_t N = g.nvert(), owners = g.nowners(), b = blockIdx.x, t = threadIdx.x;
   double *a = sw_lds;
   long long *sum = (long long *)(a + N);
   uint32_t *parent = (uint32_t *)(sum + N);
@@ -297,26 +306,30 @@ __global__ void __launch_bounds__(kSwFinishThreads)
   uint32_t nflip = 0;
   bool capped = false;
   for (uint32_t n = 0; n < n_updates; ++n, ++key.step) {
-    const V3 r = sw_normal(key);
-    for (uint32_t l = t; l < N; l += kSwFinishThreads) {
-      a[l] = sw_dot(r, sigma_of(phi[l]));
+    const V3 r = reflection_normal(key, P_SIGMA_SW_REFLECT);
+    for (uint32_t l = t; l < N; l += kClusterBlockThreads) {
+      a[l] = dot3(r, sigma_of(phi[l]));
       sum[l] = 0;
       parent[l] = l;
     }
     __syncthreads();
-    for (uint32_t l = t; l < N; l += kSwFinishThreads) {
-      const uint32_t i = l % Mt, j = l / Mt;
-      const uint32_t right = i + 1 == Mt ? l - i : l + 1, up = j + 1 == Mx ? i : l + Mt;
-      const uint32_t bits = sw_bonds(key, l, a[l], a[right], a[up], beta2);
-      if (bits & 1u) sw_union<__HIP_MEMORY_SCOPE_WORKGROUP>(parent, l, right, N, capped);
-      if (bits & 2u) sw_union<__HIP_MEMORY_SCOPE_WORKGROUP>(parent, l, up, N, capped);
+    for (uint32_t l = t; l < owners; l += kClusterBlockThreads) {
+      uint32_t y[NL];
+      g.far_ends(l, y);
+      double ay[NL];
+#pragma unroll
+      for (uint32_t d = 0; d < NL; ++d) ay[d] = a[y[d]];
+      const uint32_t bits = Geometry::bonds(key, l, a[l], ay, beta2);
+#pragma unroll
+      for (uint32_t d = 0; d < NL; ++d)
+        if (bits & (1u << d)) uf_union<__HIP_MEMORY_SCOPE_WORKGROUP>(parent, l, y[d], N, capped);
     }
     __syncthreads();
-    for (uint32_t l = t; l < N; l += kSwFinishThreads) {
-      const uint32_t root = sw_find<kSwPlain>(parent, l, N, capped);
+    for (uint32_t l = t; l < N; l += kClusterBlockThreads) {
+      const uint32_t root = uf_find<kUfPlain>(parent, l, N, capped);
       if (improved) atomicAdd((unsigned long long *)(sum + root), (unsigned long long)sw_fixed(a[l]));
       if (!capped && sw_coin(key, root)) {
-        phi[l] = sw_reflected(sigma_of(phi[l]), a[l], r);
+        phi[l] = reflected(sigma_of(phi[l]), a[l], r);
         ++nflip;
       }
     }
@@ -335,42 +348,66 @@ namespace {
 
 struct SwPlan {
   bool ok, chain;
-  uint32_t W, H, ntx, nty;          // tiled: tile extents, tiles per direction
+  uint32_t W, H, ntx, nty;                // tiled: tile extents (vertices; on a rotated level cells), tiles per direction
   uint32_t merge_blocks, resolve_blocks;  // tiled: workgroups per chain of launches 2 and 3
-  size_t lds_bytes;                 // dynamic LDS of the chain kernel / of launch 1
+  size_t lds_bytes;                       // dynamic LDS of the chain kernel / of launch 1
 };
+
+// what the tiled plan asks of a geometry: the plane the tiles divide, the default tile, the crossing links of launch 2 and the
+// LDS of launch 1.
+// Unrotated: tiles of 64 x 32 vertices; a tile holds a of its vertices and of the +i / +j halo, the parents and the bond bits.
+inline void sw_tiling(const LatticeGeometry &g, uint32_t &pw, uint32_t &ph, uint32_t &W, uint32_t &H) { pw = g.Mt, ph = g.Mx, W = 64, H = 32; }
+inline uint32_t sw_crossing(const LatticeGeometry &g, const SwPlan &p) { return p.ntx * g.Mx + p.nty * g.Mt; }
+inline size_t sw_tile_lds(const LatticeGeometry &, uint32_t W, uint32_t H) {
+  return (size_t)(W + 1) * (H + 1) * sizeof(double) + (size_t)W * H * (sizeof(uint32_t) + sizeof(uint8_t));
+}
+// Rotated: default tile 32 x 32 cells, by LDS arithmetic and not by a timing sweep: a tile of W x H cells takes 25 W H + 8 (W + H
+// + 1) B (sw_rot_tile_lds), so 32 x 32 takes 26 120 B = 25.5 KiB and six workgroups of four waves share the 160 KiB of a CU (24 of
+// its 32 wave slots); it holds 2048 vertices, as the 64 x 32 vertex tile of the unrotated default does, the halo is 65 / 1024 =
+// 6 % of the cells read, and among the tiles of that area the square one has the fewest crossing links (2 W + 2 H - 1 = 127 of
+// 4096).  64 x 64 cells take 101 KiB: one workgroup per CU, and the attribute of sw_init_attrs.
+inline void sw_tiling(const RotatedGeometry &g, uint32_t &pw, uint32_t &ph, uint32_t &W, uint32_t &H) { pw = g.ht, ph = g.hx, W = 32, H = 32; }
+inline uint32_t sw_crossing(const RotatedGeometry &g, const SwPlan &p) { return 2 * p.ntx * g.hx + 2 * p.nty * g.ht; }
+inline size_t sw_tile_lds(const RotatedGeometry &, uint32_t W, uint32_t H) { return sw_rot_tile_lds(W, H); }
 
 // Launch plan; it chooses and calls nothing.  The chain plan where a chain fits its LDS bound and one
 // workgroup per chain fills the device (B >= kComputeUnits: a chain's workgroup is 16 waves and takes more than half a CU's
 // LDS, so one is resident per CU), the tiled plan otherwise.  Knobs (bit-identical results): MLMCPI_SIGMA_SW_PLAN=chain|tiled,
-// MLMCPI_SIGMA_SW_TILE=WxH.  ok = false: the chain plan was forced on a lattice beyond its bound.
-SwPlan sw_plan(uint32_t Mt, uint32_t Mx, uint32_t B, const Tuning &tune) {
+// MLMCPI_SIGMA_SW_TILE=WxH (vertices; on a rotated level cells).  ok = false: the chain plan was forced beyond its bound.
+template <class Geometry>
+SwPlan sw_plan(const Geometry &g, uint32_t B, const Tuning &tune) {
   SwPlan p{};
-  const uint32_t N = Mt * Mx;
+  const uint32_t N = g.nvert();
+  uint32_t pw, ph;
+  sw_tiling(g, pw, ph, p.W, p.H);
   p.chain = tune.sigma_sw_plan ? tune.sigma_sw_plan == 1 : (N <= kSwChainMaxN && B >= kComputeUnits);
   p.ok = !p.chain || N <= kSwChainMaxN;
-  p.W = tune.sigma_sw_tile_w ? tune.sigma_sw_tile_w : 64;
-  p.H = tune.sigma_sw_tile_h ? tune.sigma_sw_tile_h : 32;
-  p.ntx = (Mt + p.W - 1) / p.W;
-  p.nty = (Mx + p.H - 1) / p.H;
-  p.merge_blocks = (p.ntx * Mx + p.nty * Mt + kSwThreads - 1) / kSwThreads;
-  p.resolve_blocks = (N + kSwThreads - 1) / kSwThreads;
-  p.lds_bytes = p.chain ? (size_t)N * kSwChainBytesPerVertex
-                        : (size_t)(p.W + 1) * (p.H + 1) * sizeof(double) + (size_t)p.W * p.H * (sizeof(uint32_t) + sizeof(uint8_t));
+  if (tune.sigma_sw_tile_w) p.W = tune.sigma_sw_tile_w;
+  if (tune.sigma_sw_tile_h) p.H = tune.sigma_sw_tile_h;
+  p.ntx = (pw + p.W - 1) / p.W;
+  p.nty = (ph + p.H - 1) / p.H;
+  p.merge_blocks = (sw_crossing(g, p) + kClusterThreads - 1) / kClusterThreads;
+  p.resolve_blocks = (N + kClusterThreads - 1) / kClusterThreads;
+  p.lds_bytes = p.chain ? (size_t)N * kSwChainBytesPerVertex : sw_tile_lds(g, p.W, p.H);
   return p;
 }
 
 std::mutex g_sw_attr_mutex;
 bool g_sw_attr_set[64] = {false};
 
+// dynamic LDS above 64 KiB: the chain kernels up to their bound, the rotated launch 1 at the largest tile
 int sw_init_attrs() {
   int dev = 0;
   MLMCPI_HIP_TRY(hipGetDevice(&dev));
   if (dev < 0 || dev >= 64) return fail(MLMCPI_ERR_INVALID, "device index %d out of range", dev);
   std::lock_guard<std::mutex> lock(g_sw_attr_mutex);
   if (g_sw_attr_set[dev]) return MLMCPI_OK;
-  MLMCPI_HIP_TRY(hipFuncSetAttribute((const void *)sigma_sw_chain_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
+  MLMCPI_HIP_TRY(hipFuncSetAttribute((const void *)sigma_sw_chain_kernel<LatticeGeometry>, hipFuncAttributeMaxDynamicSharedMemorySize,
                                      kSwChainMaxN * kSwChainBytesPerVertex));
+  MLMCPI_HIP_TRY(hipFuncSetAttribute((const void *)sigma_sw_chain_kernel<RotatedGeometry>, hipFuncAttributeMaxDynamicSharedMemorySize,
+                                     kSwChainMaxN * kSwChainBytesPerVertex));
+  MLMCPI_HIP_TRY(hipFuncSetAttribute((const void *)sigma_rot_sw_bond_label_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
+                                     (int)sw_rot_tile_lds(kSwMaxTile, kSwMaxTile)));
   g_sw_attr_set[dev] = true;
   return MLMCPI_OK;
 }
@@ -385,37 +422,52 @@ int sw_check(const mlmcpi_lattice_action *act, const char *what) {
   return MLMCPI_OK;
 }
 
-// workspace sections: status word (256 B), label [B N] uint32, q(a) [B N] int64, cluster sums [B N] int64, bond bits [B N] uint8
+// workspace sections: status word (256 B), label [B N] uint32, q(a) [B N] int64, cluster sums [B N] int64, bond bits [B owners]
+// uint8 (two bits per vertex; on a rotated level four bits per E vertex)
 constexpr size_t kSwStatusBytes = 256;
 size_t sw_section_label(uint32_t N, uint32_t B) { return align256((size_t)B * N * sizeof(uint32_t)); }
 size_t sw_section_fixed(uint32_t N, uint32_t B) { return align256((size_t)B * N * sizeof(long long)); }
-size_t sw_section_bits(uint32_t N, uint32_t B) { return align256((size_t)B * N); }
+size_t sw_section_bits(uint32_t owners, uint32_t B) { return align256((size_t)B * owners); }
+template <class Geometry>
+size_t sw_workspace(const Geometry &g, uint32_t B) {
+  return kSwStatusBytes + sw_section_label(g.nvert(), B) + 2 * sw_section_fixed(g.nvert(), B) + sw_section_bits(g.nowners(), B);
+}
 
-}  // namespace
-}  // namespace mlmcpi
-
-using namespace mlmcpi;
-
-extern "C" {
-
-int mlmcpi_sigma_sw_workspace_bytes(const mlmcpi_lattice_action *act, uint32_t B, size_t *bytes) {
-  if (int rc = sw_check(act, "mlmcpi_sigma_sw_workspace_bytes")) return rc;
-  MLMCPI_REQUIRE(bytes && B > 0, "bad arguments");
-  const uint32_t N = act->Mt * act->Mx;
-  *bytes = kSwStatusBytes + sw_section_label(N, B) + 2 * sw_section_fixed(N, B) + sw_section_bits(N, B);
+// launches 1 and 2 of the tiled plan, one pair per geometry: the lattice's take its extents, the rotated level's the level
+int sw_front_end(const LatticeGeometry &g, const SwPlan &p, const double2 *phi, double beta2, const RngKey &key, uint32_t B, uint32_t *label,
+                 uint8_t *bits, long long *qa, long long *sum, uint32_t *status, hipStream_t st) {
+  hipLaunchKernelGGL(sigma_sw_bond_label_kernel, dim3(B * p.ntx * p.nty), dim3(kClusterThreads), p.lds_bytes, st, phi, g.Mt, g.Mx, beta2,
+                     key, p.W, p.H, p.ntx, p.nty, label, bits, qa, sum, status);
+  MLMCPI_LAUNCH_CHECK("sigma_sw_bond_label_kernel");
+  hipLaunchKernelGGL(sigma_sw_merge_kernel, dim3(B * p.merge_blocks), dim3(kClusterThreads), 0, st, g.Mt, g.Mx, p.W, p.H, p.ntx, p.nty,
+                     p.merge_blocks, label, bits, status);
+  MLMCPI_LAUNCH_CHECK("sigma_sw_merge_kernel");
   return MLMCPI_OK;
 }
 
-int mlmcpi_sigma_sw_draw(const mlmcpi_lattice_action *act, double *d_phi, uint32_t B, uint32_t n_updates, uint64_t seed, uint32_t chain0,
-                         uint32_t update0, uint32_t *d_flipped, uint32_t *d_clusters, double *d_improved, void *d_work, void *stream) {
-  if (int rc = sw_check(act, "mlmcpi_sigma_sw_draw")) return rc;
-  MLMCPI_REQUIRE(d_phi && d_work && B > 0, "bad arguments");
-  MLMCPI_REQUIRE((uint64_t)update0 + n_updates <= 0xFFFFFFFFull, "update counter overflows");
-  const uint32_t Mt = act->Mt, Mx = act->Mx, N = Mt * Mx;
-  const SwPlan p = sw_plan(Mt, Mx, B, tuning());
+int sw_front_end(const SigmaLevel &L, const SwPlan &p, const double2 *phi, double beta2, const RngKey &key, uint32_t B, uint32_t *label,
+                 uint8_t *bits, long long *qa, long long *sum, uint32_t *status, hipStream_t st) {
+  hipLaunchKernelGGL(sigma_rot_sw_bond_label_kernel, dim3(B * p.ntx * p.nty), dim3(kClusterThreads), p.lds_bytes, st, phi, L, beta2, key,
+                     p.W, p.H, p.ntx, p.nty, label, bits, qa, sum, status);
+  MLMCPI_LAUNCH_CHECK("sigma_rot_sw_bond_label_kernel");
+  hipLaunchKernelGGL(sigma_rot_sw_merge_kernel, dim3(B * p.merge_blocks), dim3(kClusterThreads), 0, st, L, p.W, p.H, p.ntx, p.nty,
+                     p.merge_blocks, label, bits, status);
+  MLMCPI_LAUNCH_CHECK("sigma_rot_sw_merge_kernel");
+  return MLMCPI_OK;
+}
+
+// the draw on either geometry, arguments checked: the workspace laid out, the launches issued, the status word read back.
+// `front` is what sw_front_end takes for this geometry, `what` the entry point, `where` the noun ("lattice", "level") of its
+// messages and `chain_kernel` the name of the chain kernel's instance in a launch error.
+template <class Geometry, class Front>
+int sw_draw(const Geometry &g, const Front &front, double beta, double *d_phi, uint32_t B, uint32_t n_updates, uint64_t seed, uint32_t chain0, uint32_t update0,
+            uint32_t *d_flipped, uint32_t *d_clusters, double *d_improved, void *d_work, void *stream, const char *what, const char *where,
+            const char *chain_kernel) {
+  const uint32_t N = g.nvert();
+  const SwPlan p = sw_plan(g, B, tuning());
   if (!p.ok)
-    return fail(MLMCPI_ERR_UNSUPPORTED, "mlmcpi_sigma_sw_draw: MLMCPI_SIGMA_SW_PLAN=chain holds a chain of at most %u vertices in LDS, "
-                "this lattice has %u", kSwChainMaxN, N);
+    return fail(MLMCPI_ERR_UNSUPPORTED, "%s: MLMCPI_SIGMA_SW_PLAN=chain holds a chain of at most %u vertices in LDS, this %s has %u", what,
+                kSwChainMaxN, where, N);
   const uint64_t widest = (uint64_t)B * (p.ntx * p.nty > p.resolve_blocks ? p.ntx * p.nty : p.resolve_blocks);
   MLMCPI_REQUIRE(p.chain || (widest < (1ull << 31) && (uint64_t)B * p.merge_blocks < (1ull << 31)), "too many workgroups for one launch: split the batch");
   if (n_updates == 0) return MLMCPI_OK;
@@ -427,37 +479,82 @@ int mlmcpi_sigma_sw_draw(const mlmcpi_lattice_action *act, double *d_phi, uint32
   long long *sum = (long long *)(w + kSwStatusBytes + sw_section_label(N, B) + sw_section_fixed(N, B));
   uint8_t *bits = (uint8_t *)(w + kSwStatusBytes + sw_section_label(N, B) + 2 * sw_section_fixed(N, B));
   const hipStream_t st = as_stream(stream);
-  const double beta2 = 2.0 * act->beta;
+  const double beta2 = 2.0 * beta;
   MLMCPI_HIP_TRY(hipMemsetAsync(status, 0, sizeof(uint32_t), st));
   if (p.chain) {
-    hipLaunchKernelGGL(sigma_sw_chain_kernel, dim3(B), dim3(kSwFinishThreads), p.lds_bytes, st, (double2 *)d_phi, Mt, Mx, beta2, n_updates,
-                       make_key(seed, chain0, update0), d_flipped, d_clusters, d_improved, status);
-    MLMCPI_LAUNCH_CHECK("sigma_sw_chain_kernel");
+    hipLaunchKernelGGL(sigma_sw_chain_kernel<Geometry>, dim3(B), dim3(kClusterBlockThreads), p.lds_bytes, st, (double2 *)d_phi, g, beta2,
+                       n_updates, make_key(seed, chain0, update0), d_flipped, d_clusters, d_improved, status);
+    MLMCPI_LAUNCH_CHECK(chain_kernel);
   } else {
     const bool outputs = d_clusters || d_improved;
     for (uint32_t k = 0; k < n_updates; ++k) {
       const RngKey key = make_key(seed, chain0, update0 + k);
-      hipLaunchKernelGGL(sigma_sw_bond_label_kernel, dim3(B * p.ntx * p.nty), dim3(kSwThreads), p.lds_bytes, st, (const double2 *)d_phi, Mt,
-                         Mx, beta2, key, p.W, p.H, p.ntx, p.nty, label, bits, qa, d_improved ? sum : nullptr, status);
-      MLMCPI_LAUNCH_CHECK("sigma_sw_bond_label_kernel");
-      hipLaunchKernelGGL(sigma_sw_merge_kernel, dim3(B * p.merge_blocks), dim3(kSwThreads), 0, st, Mt, Mx, p.W, p.H, p.ntx, p.nty,
-                         p.merge_blocks, label, bits, status);
-      MLMCPI_LAUNCH_CHECK("sigma_sw_merge_kernel");
-      hipLaunchKernelGGL(sigma_sw_resolve_kernel, dim3(B * p.resolve_blocks), dim3(kSwThreads), 0, st, (double2 *)d_phi, Mt, Mx, key,
+      if (int rc = sw_front_end(front, p, (const double2 *)d_phi, beta2, key, B, label, bits, qa, d_improved ? sum : nullptr, status, st)) return rc;
+      hipLaunchKernelGGL(sigma_sw_resolve_kernel, dim3(B * p.resolve_blocks), dim3(kClusterThreads), 0, st, (double2 *)d_phi, N, key,
                          p.resolve_blocks, label, qa, d_improved ? sum : nullptr, d_flipped, status);
       MLMCPI_LAUNCH_CHECK("sigma_sw_resolve_kernel");
       if (outputs) {
-        hipLaunchKernelGGL(sigma_sw_finish_kernel, dim3(B), dim3(kSwFinishThreads), 0, st, label, sum, N, d_improved, d_clusters);
+        hipLaunchKernelGGL(sigma_sw_finish_kernel, dim3(B), dim3(kClusterBlockThreads), 0, st, label, sum, N, d_improved, d_clusters);
         MLMCPI_LAUNCH_CHECK("sigma_sw_finish_kernel");
       }
     }
   }
-  // a find or union loop that ran into its cap (it cannot, by the argument above): an error, never a hang
+  // a find or union loop that ran into its cap (it cannot, by the argument of sigma_cluster_device.hpp): an error, never a hang
   uint32_t h_status = 0;
   MLMCPI_HIP_TRY(hipMemcpyAsync(&h_status, status, sizeof(uint32_t), hipMemcpyDeviceToHost, st));
   MLMCPI_HIP_TRY(hipStreamSynchronize(st));
-  if (h_status) return fail(MLMCPI_ERR_HIP, "mlmcpi_sigma_sw_draw: a labelling loop reached its iteration cap (status %u); the state is undefined", h_status);
+  if (h_status) return fail(MLMCPI_ERR_HIP, "%s: a labelling loop reached its iteration cap (status %u); the state is undefined", what, h_status);
   return MLMCPI_OK;
+}
+
+}  // namespace
+}  // namespace mlmcpi
+
+using namespace mlmcpi;
+
+extern "C" {
+
+int mlmcpi_sigma_sw_workspace_bytes(const mlmcpi_lattice_action *act, uint32_t B, size_t *bytes) {
+  if (int rc = sw_check(act, "mlmcpi_sigma_sw_workspace_bytes")) return rc;
+  MLMCPI_REQUIRE(bytes && B > 0, "bad arguments");
+  *bytes = sw_workspace(LatticeGeometry{act->Mt, act->Mx}, B);
+  return MLMCPI_OK;
+}
+
+int mlmcpi_sigma_sw_draw(const mlmcpi_lattice_action *act, double *d_phi, uint32_t B, uint32_t n_updates, uint64_t seed, uint32_t chain0,
+                         uint32_t update0, uint32_t *d_flipped, uint32_t *d_clusters, double *d_improved, void *d_work, void *stream) {
+  if (int rc = sw_check(act, "mlmcpi_sigma_sw_draw")) return rc;
+  MLMCPI_REQUIRE(d_phi && d_work && B > 0, "bad arguments");
+  MLMCPI_REQUIRE((uint64_t)update0 + n_updates <= 0xFFFFFFFFull, "update counter overflows");
+  const LatticeGeometry g{act->Mt, act->Mx};
+  return sw_draw(g, g, act->beta, d_phi, B, n_updates, seed, chain0, update0, d_flipped, d_clusters, d_improved, d_work, stream,
+                 "mlmcpi_sigma_sw_draw", "lattice", "sigma_sw_chain_kernel");
+}
+
+int mlmcpi_sigma_level_sw_workspace_bytes(const mlmcpi_sigma_level *level, uint32_t B, size_t *bytes) {
+  if (int rc = check_cluster_level(level)) return rc;
+  MLMCPI_REQUIRE(bytes && B > 0, "bad arguments");
+  if (!level->rotated) {
+    const mlmcpi_lattice_action act = level_as_lattice(level);
+    return mlmcpi_sigma_sw_workspace_bytes(&act, B, bytes);
+  }
+  *bytes = sw_workspace(RotatedGeometry(make_level(*level)), B);
+  return MLMCPI_OK;
+}
+
+int mlmcpi_sigma_level_sw_draw(const mlmcpi_sigma_level *level, double *d_state, uint32_t B, uint32_t n_updates, uint64_t seed,
+                               uint32_t chain0, uint32_t update0, uint32_t *d_flipped, uint32_t *d_clusters, double *d_improved,
+                               void *d_work, void *stream) {
+  if (int rc = check_cluster_level(level)) return rc;
+  MLMCPI_REQUIRE(d_state && d_work && B > 0, "bad arguments");
+  MLMCPI_REQUIRE((uint64_t)update0 + n_updates <= 0xFFFFFFFFull, "update counter overflows");
+  if (!level->rotated) {
+    const mlmcpi_lattice_action act = level_as_lattice(level);
+    return mlmcpi_sigma_sw_draw(&act, d_state, B, n_updates, seed, chain0, update0, d_flipped, d_clusters, d_improved, d_work, stream);
+  }
+  const SigmaLevel L = make_level(*level);
+  return sw_draw(RotatedGeometry(L), L, level->beta, d_state, B, n_updates, seed, chain0, update0, d_flipped, d_clusters, d_improved,
+                 d_work, stream, "mlmcpi_sigma_level_sw_draw", "level", "sigma_rot_sw_chain_kernel");
 }
 
 }  // extern "C"

@@ -1,5 +1,5 @@
 """numpy restatement of the Wolff single-cluster update of the O(3) sigma model on a level of its CoarsenRotate hierarchy
-(mlmcpathintegral_amd/csrc/sigma_level_cluster.hip): the contract's second statement.
+(mlmcpathintegral_amd/csrc/sigma_cluster.hip): the contract's second statement.
 
 An unrotated Level calls through to tests/sigma_cluster_model.py, so that the two stay one definition.  A rotated Level is
 table driven from sigma_level_model.Level (L.nbr, L.n): n = Mt Mx / 2 vertices, plane E (indices < n / 2) then plane O.  The

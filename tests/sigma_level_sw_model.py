@@ -1,5 +1,5 @@
 """numpy restatement of the Swendsen-Wang multi-cluster update of the O(3) sigma model on a level of its CoarsenRotate
-hierarchy (mlmcpathintegral_amd/csrc/sigma_level_sw.hip): the contract's second statement.
+hierarchy (mlmcpathintegral_amd/csrc/sigma_sw.hip): the contract's second statement.
 
 An unrotated Level calls through to tests/sigma_sw_model.py, so that the two stay one definition.  A rotated Level is table
 driven from sigma_level_model.Level (L.nbr, L.n), with the link naming of tests/sigma_level_cluster_model.py: n = Mt Mx / 2

@@ -1,5 +1,5 @@
 """GPU: the Wolff single-cluster update of the O(3) sigma model on the levels of its CoarsenRotate hierarchy
-(mlmcpi_sigma_level_cluster_draw, sigma_level_cluster.hip) against its numpy restatement (tests/sigma_level_cluster_model.py)
+(mlmcpi_sigma_level_cluster_draw, sigma_cluster.hip) against its numpy restatement (tests/sigma_level_cluster_model.py)
 update by update, its invariances bit for bit (call split, batch split, every knob of the launch plan), the delegation of an
 unrotated level, its law against the device's rotated heat bath and the CPU model, the hierarchical chain it is there for, and
 host/driver --coarsesampler levelwolff."""

@@ -1,5 +1,5 @@
 """GPU: the Swendsen-Wang multi-cluster update of the O(3) sigma model on the levels of its CoarsenRotate hierarchy
-(mlmcpi_sigma_level_sw_draw, sigma_level_sw.hip) against its numpy restatement (tests/sigma_level_sw_model.py) update by
+(mlmcpi_sigma_level_sw_draw, sigma_sw.hip) against its numpy restatement (tests/sigma_level_sw_model.py) update by
 update, its invariances bit for bit (call split, batch split, launch plan, tile, outputs asked for or not), the delegation of an
 unrotated level, its law and its improved estimator against the device's rotated heat bath and the CPU model, the hierarchical
 chain it is there for, and host/driver --coarsesampler levelsw."""

@@ -1,5 +1,5 @@
 """First measurements of the Wolff single-cluster update on ROTATED levels of the O(3) sigma model
-(mlmcpi_sigma_level_cluster_draw, sigma_level_cluster.hip), one process on one GPU, after the pattern of
+(mlmcpi_sigma_level_cluster_draw, sigma_cluster.hip), one process on one GPU, after the pattern of
 tools/exp_sigma_cluster.py.  Shapes: the rotated partner of 64^2 x 4096 chains (n = 2048 vertices) and of 1024^2 x 32 chains
 (n = 524 288), beta = 1.0 and 1.5, states thermalised with rotated heat-bath draws and then cluster draws.  Per setting: ms
 per draw of k = 10 updates (HIP events, median of 20 draws after 5 warm-up draws), flipped vertices per update, vertex flips

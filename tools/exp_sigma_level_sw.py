@@ -1,5 +1,5 @@
 """First measurements of the Swendsen-Wang update on ROTATED levels of the O(3) sigma model (mlmcpi_sigma_level_sw_draw,
-sigma_level_sw.hip), one process on one GPU, after the pattern of tools/exp_sigma_level_cluster.py.  Shapes: the rotated
+sigma_sw.hip), one process on one GPU, after the pattern of tools/exp_sigma_level_cluster.py.  Shapes: the rotated
 partner of 64^2 x 4096 chains (n = 2048 vertices, chain plan) and of 1024^2 x 32 chains (n = 524 288, tiled plan), beta = 1.0
 and 1.5, states thermalised with rotated heat-bath draws and then Swendsen-Wang updates.  Per setting, for a draw of ONE
 Swendsen-Wang update (outputs asked for), a draw of 10 level-Wolff updates and the rotated 10 + 1 sweep draw: ms per draw (HIP

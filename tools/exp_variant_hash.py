@@ -4,8 +4,11 @@ Schwinger closed-form launches of every depth, 64 x 64 and 64 x 32 tiles, GFF re
 tiles, with and without the heat bath and the QoI -- and, under MLMCPI_OR_KERNEL=block, the Schwinger sweep-by-sweep plan
 (lines starting "block": state hashes, and the QoI values themselves, which two builds may sum in different tile orders).
 Behind them the 1-D paths: HMC draws and whole-chain runs on every launch geometry, rotor sweeps with both heat-bath samplers,
-the two-level step of the three actions and the exact harmonic-oscillator draw.
+the two-level step of the three actions and the exact harmonic-oscillator draw.  First of all the sigma-model cluster samplers
+(lines starting "sigma"): Wolff and Swendsen-Wang, unrotated and rotated, under every forced plan, with and without their
+optional outputs; `--sigma-cluster` stops after that section.
    MLMCPI_LIB_VARIANT=r04 python tools/exp_variant_hash.py > a.txt; python tools/exp_variant_hash.py > b.txt
+   python tools/exp_variant_hash.py [--sigma-cluster]
    python tools/exp_variant_hash.py --compare a.txt b.txt   (other lines equal; block lines: states equal, QoI to 1e-13)"""
 import hashlib, sys
 import torch
@@ -38,6 +41,42 @@ SEED = 11
 
 def h(t):
     return hashlib.sha256(t.cpu().numpy().tobytes()).hexdigest()[:16]
+
+
+# ---- the O(3) sigma-model cluster samplers: 10 updates of each draw on the lattice and on its rotated level, every forced plan
+def sigma_cluster_section():
+    wolff_plans = [(("MLMCPI_SIGMA_CLUSTER_TEAM", t), ("MLMCPI_SIGMA_CLUSTER_BITMAP", m)) for t in ("wave", "block") for m in ("global", "lds")]
+    sw_plans = [(("MLMCPI_SIGMA_SW_PLAN", "chain"),), (("MLMCPI_SIGMA_SW_PLAN", "tiled"),),
+                (("MLMCPI_SIGMA_SW_PLAN", "tiled"), ("MLMCPI_SIGMA_SW_TILE", "16x8"))]
+    for Mt, Mx, B in ((16, 16, 3), (130, 70, 3), (512, 300, 2)):
+        for rotated in (0, 1):
+            lv = abi.sigma_level(Mt, Mx, rotated, 1.2)
+            x0 = ops.sigma_level_initialise(lv, B, SEED)
+            for name, plans, draw in (("wolff", wolff_plans, lambda x, out: ops.sigma_level_cluster_draw(lv, x, 10, SEED, 2, 7, count=out)),
+                                      ("sw", sw_plans, lambda x, out: ops.sigma_level_sw_draw(lv, x, 10, SEED, 2, 7, outputs=out))):
+                for plan in plans:
+                    for k, v in plan:
+                        abi.set_option(k, v)
+                    try:
+                        for out in (False, True):
+                            x = x0.clone()
+                            try:
+                                r = draw(x, out)
+                                r = () if r is None else r if isinstance(r, tuple) else (r,)
+                                res = " ".join([h(x)] + [h(t) for t in r])
+                            except RuntimeError as e:   # the chain plan forced beyond its bound, and nothing else
+                                if "MLMCPI_SIGMA_SW_PLAN=chain holds a chain of at most" not in str(e):
+                                    raise
+                                res = "refused"
+                            print(f"sigma {name} {Mt}x{Mx} rotated={rotated} {' '.join(v for _, v in plan)} outputs={out}: {res}", flush=True)
+                    finally:
+                        for k, _ in plan:
+                            abi.set_option(k, "")
+
+
+if "--sigma-cluster" in sys.argv[1:]:   # this section alone
+    sigma_cluster_section()
+    sys.exit(0)
 
 
 for Mt, Mx, B, beta in ((128, 128, 3, 1.0), (192, 128, 2, 1.0), (256, 192, 2, 0.7), (192, 96, 2, 1.0), (64, 64, 2, 1.0), (128, 128, 2, 3.0), (1024, 1024, 2, 1.0)):
@@ -127,3 +166,5 @@ for name in ("harmonic", "quartic", "rotor"):
             print(f"twolevel {name} M={M} step {d}: {h(step.theta)} {h(acc)} {h(step.terms)}", flush=True)
 
 print(f"ho_exact M=128 B=32: {h(ops.HOExactSampler(path_act('harmonic', 128), 32, seed=SEED, chain0=2).draw())}", flush=True)
+
+sigma_cluster_section()
