@@ -25,6 +25,10 @@
 //          --n_level 2 --n_updates 4
 //          (the Swendsen-Wang sampler on the coarsest level of a hierarchical or --method twolevel run, n_updates updates per coarse
 //           draw: the rotated level with --n_level 2, the unrotated M/2 level with --n_level 3)
+//   driver --action nonlinearsigma --Mt_lat 16 --beta 1.5 --sampler swendsenwang --n_updates 1 --batch 64 --n_samples 500 --correlator 1
+//          (--correlator 1, single-level heatbath / wolff / swendsenwang runs: all `batch` chains are sampled, Q is their mean per
+//           sample, and after the statistics come the time-slice correlators C_t, C_x per lag, chi and F from them, and the
+//           second-moment correlation length xi_2 with its jackknife error over the chains)
 //   driver --action rotor --M_lat 256 --T_final 25.6 --m0 0.25 --sampler cluster --n_updates 10 --n_samples 20000
 //          (cluster samplers: rotor and schwinger; also --coarsesampler cluster for twolevel / hierarchical rotor runs)
 //   driver --method throughput --action schwinger --Mt_lat 1024 --sampler heatbath --batch 32 --n_samples 20
@@ -50,7 +54,7 @@ int main(int argc, char **argv) {
       {"sampler", "hmc"}, {"nt", "100"}, {"dt", "0.1"}, {"n_burnin", "100"}, {"n_samples", "20000"}, {"n_sweep_overrelax", "10"},
       {"n_sweep_heatbath", "1"}, {"autotune", "1"}, {"window", "20"}, {"method", "singlelevel"}, {"n_level", "3"},
       {"epsilon", "0.01"}, {"coarsening", "both"}, {"coarsesampler", "hmc"}, {"renormalisation", "none"}, {"n_meas", "200"},
-      {"batch", "1"}, {"seed", "2481317"}, {"warmup", "5"}, {"random_order", "0"}, {"n_updates", "10"}};
+      {"batch", "1"}, {"seed", "2481317"}, {"warmup", "5"}, {"random_order", "0"}, {"n_updates", "10"}, {"correlator", "0"}};
   for (int i = 1; i + 1 < argc; i += 2) {
     if (std::strncmp(argv[i], "--", 2) || !o.count(argv[i] + 2)) fatal(std::string("unknown option ") + argv[i]);
     o[argv[i] + 2] = argv[i + 1];
@@ -75,6 +79,7 @@ int main(int argc, char **argv) {
   }
   std::shared_ptr<Action> action;
   std::shared_ptr<QoI> qoi;
+  std::shared_ptr<SigmaCorrelator> correlator;
   std::shared_ptr<QoIFactory> qoi_factory;
   std::shared_ptr<ConditionedFineActionFactory> cfa_factory;
   double analytic = NAN;
@@ -85,6 +90,17 @@ int main(int argc, char **argv) {
   const std::map<std::string, CoarseningType> coarsenings = {{"both", CoarsenBoth}, {"temporal", CoarsenTemporal},
       {"spatial", CoarsenSpatial}, {"alternate", CoarsenAlternate}, {"rotate", CoarsenRotate}};
   if (!coarsenings.count(o["coarsening"])) fatal("unknown coarsening " + o["coarsening"]);
+  // --correlator 1: the time-slice correlators of the sigma model and xi_2 beside the QoI (qoi.hh SigmaCorrelator)
+  if (o["correlator"] != "0" && o["correlator"] != "1") fatal("--correlator takes 0 or 1, not " + o["correlator"]);
+  const bool wants_correlator = o["correlator"] == "1";
+  if (wants_correlator && a != "nonlinearsigma")
+    fatal(" --correlator 1 is not supported for chosen action: the time-slice correlator is built for nonlinearsigma only, not " + a);
+  if (wants_correlator && o["method"] != "singlelevel")
+    fatal("nonlinearsigma: --correlator 1 runs --method singlelevel only, not " + o["method"] + " (the two-level estimator has no "
+          "difference estimator for C(tau); the throughput loop measures the QoI alone)");
+  if (wants_correlator && o["sampler"] != "heatbath" && o["sampler"] != "wolff" && o["sampler"] != "swendsenwang")
+    fatal("nonlinearsigma: --correlator 1 takes --sampler heatbath, wolff or swendsenwang, not " + o["sampler"]);
+  if (wants_correlator && world > 1) fatal("nonlinearsigma: --correlator 1 runs on one rank (its sums are not exchanged)");
   // driver_qm.cc:62-70, driver_qft.cc:69-80: the cluster sampler exists for the rotor and the quenched Schwinger action
   const bool wants_cluster = o["sampler"] == "cluster" ||
                              (o["coarsesampler"] == "cluster" && (o["sampler"] == "hierarchical" || o["method"] == "twolevel"));
@@ -190,6 +206,7 @@ int main(int argc, char **argv) {
       fatal("nonlinearsigma: non-perturbative renormalisation not implemented for non-linear sigma model.");
     action = std::make_shared<NonlinearSigmaAction>(lat, nullptr, renorm, num("beta"));
     qoi = std::make_shared<QoI2DMagneticSusceptibility>(lat);
+    if (wants_correlator) correlator = std::make_shared<SigmaCorrelator>(lat);
     qoi_factory = std::make_shared<QoI2DMagneticSusceptibilityFactory>();
     cfa_factory = std::make_shared<NonlinearSigmaConditionedFineActionFactory>();
   } else if (a == "schwinger" || a == "gff") {
@@ -347,11 +364,51 @@ int main(int argc, char **argv) {
   if (o["method"] != "singlelevel") fatal("unknown method " + o["method"]);
   SingleLevelMCParameters mp;
   mp.n_burnin = (unsigned)num("n_burnin"); mp.n_samples = (unsigned)num("n_samples"); mp.n_autocorr_window = (unsigned)num("window");
-  MonteCarloSingleLevel mc(action, qoi, factory, mp, exchange);
+  // with --correlator 1 the loop runs on all `batch` chains (Q = their mean per sample) and measures C(tau) on the same states
+  MonteCarloSingleLevel mc(action, qoi, factory, mp, exchange, correlator ? batch : 1u, correlator);
   mc.evaluate();
   std::cout << std::endl << "=== Single level MC ===" << std::endl;
   mc.show_statistics();
   mc.get_sampler()->show_stats();
+  if (correlator) {
+    const SigmaCorrelator::Estimate e = correlator->means_and_errors();
+    const unsigned Mt = correlator->Mt(), Mx = correlator->Mx(), nt = Mt / 2 + 1, nx = Mx / 2 + 1, B = correlator->batch();
+    const std::vector<double> Ct = correlator->direction(e.mean, 0), Cx = correlator->direction(e.mean, 1);
+    const std::vector<double> Et = correlator->direction(e.error, 0), Ex = correlator->direction(e.error, 1);
+    std::vector<double> avg_err(nt, 0.0);  // of (C_t + C_x) / 2 where Mt = Mx: chain spread again, else the mean of the two naive errors
+    if (Mt == Mx) {
+      const std::vector<std::vector<double>> m = correlator->chain_means();
+      for (unsigned tau = 0; tau < nt; ++tau) {
+        if (B < 2) { avg_err[tau] = 0.5 * (Et[tau] + Ex[tau]); continue; }
+        double s2 = 0.0;
+        for (unsigned b = 0; b < B; ++b) {
+          const double d = 0.5 * (m[b][tau] + m[b][nt + tau]) - 0.5 * (Ct[tau] + Cx[tau]);
+          s2 += d * d;
+        }
+        avg_err[tau] = std::sqrt(s2 / ((double)B * (B - 1.0)));
+      }
+    }
+    std::cout << std::endl << "=== Time-slice correlator ===" << std::endl
+              << " samples = " << correlator->samples() << ", chains = " << B << ", errors: "
+              << (e.chain_spread ? "spread of the per-chain means" : "naive (one chain: autocorrelation ignored)") << std::endl
+              << std::setprecision(6) << std::fixed;
+    for (unsigned tau = 0; tau < std::max(nt, nx); ++tau) {
+      std::cout << " C(tau = " << tau << "):";
+      if (tau < nt) std::cout << " C_t = " << Ct[tau] << " +/- " << Et[tau];
+      if (tau < nx) std::cout << " C_x = " << Cx[tau] << " +/- " << Ex[tau];
+      if (Mt == Mx) std::cout << " avg = " << 0.5 * (Ct[tau] + Cx[tau]) << " +/- " << avg_err[tau];
+      std::cout << std::endl;
+    }
+    std::cout << " chi from C_t = " << correlator_susceptibility(Ct, Mt) << ", from C_x = " << correlator_susceptibility(Cx, Mx) << std::endl
+              << " F_t = " << structure_factor(Ct, Mt) << ", F_x = " << structure_factor(Cx, Mx) << std::endl;
+    for (int d = 0; d < 2; ++d) {
+      const SigmaCorrelator::Xi xi = correlator->xi(d);
+      std::cout << " xi_2 (" << (d ? "x" : "t") << ") = " << xi.value;
+      if (xi.has_error) std::cout << " +/- " << xi.error << " (jackknife over chains)";
+      else std::cout << " (one chain: no jackknife error)";
+      std::cout << ", xi_2 / M = " << xi.value / (d ? Mx : Mt) << std::endl;
+    }
+  }
   if (!std::isnan(analytic)) {  // driver_qm.cc:411-425
     auto st = mc.get_statistics();
     std::cout << std::setprecision(6) << " analytic result = " << analytic << std::endl

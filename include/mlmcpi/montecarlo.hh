@@ -23,18 +23,20 @@ public:
    *  (the sampler's Philox chain index should be the rank, SamplerFactory's business) and the ranks meet in ONE
    *  all-reduce per pass of the do-while below. */
   MonteCarloSingleLevel(std::shared_ptr<Action> action_, std::shared_ptr<QoI> qoi_, std::shared_ptr<SamplerFactory> f,
-                        const SingleLevelMCParameters p, std::shared_ptr<Exchange> exchange_ = nullptr)
+                        const SingleLevelMCParameters p, std::shared_ptr<Exchange> exchange_ = nullptr, unsigned int batch_ = 1,
+                        std::shared_ptr<SigmaCorrelator> correlator_ = nullptr)
       : action(action_), sampler(f->get(action_)), qoi(qoi_), param(p), exchange(exchange_),
-        stats_Q(std::make_shared<Statistics>("Q", p.n_autocorr_window, exchange_)) {}
+        stats_Q(std::make_shared<Statistics>("Q", p.n_autocorr_window, exchange_)), batch(batch_), correlator(correlator_) {}
 
-  /** montecarlosinglelevel.cc:23-94 */
+  /** montecarlosinglelevel.cc:23-94.  batch > 1 (the sampler's batch): the state holds that many chains and a sample's Q is
+   *  the mean of the QoI over them; `correlator`: every sample after burn-in is measured by it as well, on the same state. */
   void evaluate() {
-    std::shared_ptr<SampleState> phi_state = std::make_shared<SampleState>(action->sample_size());
+    std::shared_ptr<SampleState> phi_state = std::make_shared<SampleState>(action->sample_size(), batch);
     const int rank = exchange ? exchange->rank() : 0, size = exchange ? exchange->size() : 1;
     stats_Q->hard_reset();
     for (unsigned int i = 0; i < param.n_burnin; ++i) {
       sampler->draw(phi_state);
-      stats_Q->record_sample(qoi->evaluate(phi_state));
+      stats_Q->record_sample(measure(phi_state));
     }
     const double two_epsilon_inv2 = 2. / (param.epsilon * param.epsilon);
     stats_Q->reset();
@@ -45,7 +47,8 @@ public:
     do {
       for (unsigned int k = stats_Q->local_samples(); k < n_local_target; ++k) {
         sampler->draw(phi_state);
-        stats_Q->record_sample(qoi->evaluate(phi_state));
+        stats_Q->record_sample(measure(phi_state));
+        if (correlator) correlator->accumulate(phi_state);
       }
       // The reference reads tau_int() and variance() (five scalar all-reduces, one vector all-reduce) and then
       // all-reduces the logical AND of "this rank has its share" (:78-86).  One reduction serves all of it: the packed
@@ -67,6 +70,12 @@ public:
   unsigned int passes() const { return n_passes; }  // collectives issued by the last evaluate()
 
 private:
+  double measure(const std::shared_ptr<SampleState> phi_state) {
+    if (batch == 1) return qoi->evaluate(phi_state);
+    double s = 0.0;
+    for (double q : qoi->evaluate_batch(phi_state)) s += q;
+    return s / batch;
+  }
   std::shared_ptr<Action> action;
   std::shared_ptr<Sampler> sampler;
   std::shared_ptr<QoI> qoi;
@@ -74,6 +83,8 @@ private:
   std::shared_ptr<Exchange> exchange;
   std::shared_ptr<Statistics> stats_Q;
   unsigned int n_passes = 0;
+  const unsigned int batch;
+  std::shared_ptr<SigmaCorrelator> correlator;
 };
 
 }  // namespace mlmcpi

@@ -4,7 +4,11 @@
 // loops that accumulate statistics on the device with mlmcpi_stats_accumulate).
 #ifndef MLMCPI_QOI_HH
 #define MLMCPI_QOI_HH
+#include <algorithm>
+#include <cmath>
+
 #include "action.hh"
+#include "correlator.hh"
 
 namespace mlmcpi {
 
@@ -119,6 +123,127 @@ public:
 private:
   const unsigned int Mt_lat, Mx_lat, n_vertices;
   const bool rotated;
+};
+
+/** The time-slice correlators C_t(tau), C_x(tau) of the O(3) sigma model on a lattice, rotated or not
+ *  (mlmcpi_sigma_level_correlator; definitions in mlmcpi_hip.h).  Not a QoI: its value is a vector of n_out() =
+ *  (Mt/2 + 1) + (Mx/2 + 1) numbers per chain, C_t first.  accumulate() adds the sample's C and C^2 to per-chain sums on the
+ *  device; the means, their errors and xi_2 (correlator.hh) are host arithmetic on those sums. */
+class SigmaCorrelator {
+public:
+  struct Estimate {
+    std::vector<double> mean, error;
+    bool chain_spread;  // true: error = spread of the per-chain means (batch >= 2); false: the naive error of one chain
+  };
+  struct Xi {
+    double value, error;
+    bool has_error;  // the jackknife over chains needs batch >= 2
+  };
+  explicit SigmaCorrelator(const std::shared_ptr<Lattice2D> lattice)
+      : level{lattice->getMt_lat(), lattice->getMx_lat(), lattice->is_rotated() ? 1 : 0, 0.0}, n_vertices(lattice->getNvertices()) {
+    uint32_t n = 0;
+    check(mlmcpi_sigma_level_correlator_size(&level, &n), "sigma_level_correlator_size");
+    n_out_ = n;
+  }
+  unsigned int n_out() const { return n_out_; }
+  unsigned int Mt() const { return level.Mt; }
+  unsigned int Mx() const { return level.Mx; }
+  /** d_out[b][n_out()] = the correlators of chain b, enqueued on the default stream */
+  void evaluate_device(const std::shared_ptr<SampleState> phi, double *d_out) { launch(phi, d_out, nullptr); }
+  /** one more sample: its correlators are added to the per-chain sums (the batch is fixed by the first call) */
+  void accumulate(const std::shared_ptr<SampleState> phi) {
+    if (!acc || B != phi->batch()) {
+      if (n_calls) fatal("SigmaCorrelator::accumulate: the batch changed between samples.");
+      B = phi->batch();
+      acc = std::make_unique<DeviceVector>(2 * (size_t)B * n_out_);
+      out = std::make_unique<DeviceVector>((size_t)B * n_out_);
+    }
+    launch(phi, (double *)out->ptr(), (double *)acc->ptr());
+    ++n_calls;
+  }
+  unsigned int samples() const { return n_calls; }
+  unsigned int batch() const { return B; }
+  /** per-chain means of C over the accumulated samples, [batch][n_out()] */
+  std::vector<std::vector<double>> chain_means() const {
+    if (!n_calls) fatal("SigmaCorrelator: no samples accumulated.");
+    const std::vector<double> a = acc->download<double>();
+    std::vector<std::vector<double>> m(B, std::vector<double>(n_out_));
+    for (unsigned int b = 0; b < B; ++b)
+      for (unsigned int k = 0; k < n_out_; ++k) m[b][k] = a[2 * ((size_t)b * n_out_ + k)] / n_calls;
+    return m;
+  }
+  /** mean and error per entry.  batch >= 2: the error is the spread of the per-chain means over sqrt(batch), so
+   *  autocorrelation inside a chain cannot understate it; batch 1: the naive error of the samples (it ignores autocorrelation) */
+  Estimate means_and_errors() const {
+    if (!n_calls) fatal("SigmaCorrelator: no samples accumulated.");
+    const std::vector<double> a = acc->download<double>();
+    Estimate e{std::vector<double>(n_out_, 0.0), std::vector<double>(n_out_, 0.0), B >= 2};
+    const double n = n_calls;
+    for (unsigned int k = 0; k < n_out_; ++k) {
+      if (B >= 2) {
+        double s = 0.0, s2 = 0.0;
+        for (unsigned int b = 0; b < B; ++b) s += a[2 * ((size_t)b * n_out_ + k)] / n;
+        const double m = s / B;
+        for (unsigned int b = 0; b < B; ++b) {
+          const double d = a[2 * ((size_t)b * n_out_ + k)] / n - m;
+          s2 += d * d;
+        }
+        e.mean[k] = m;
+        e.error[k] = std::sqrt(s2 / ((double)B * (B - 1.0)));
+      } else {
+        const double m = a[2 * k] / n, var = n_calls > 1 ? std::max(0.0, (a[2 * k + 1] / n - m * m) * n / (n - 1.0)) : 0.0;
+        e.mean[k] = m;
+        e.error[k] = std::sqrt(var / n);
+      }
+    }
+    return e;
+  }
+  /** the part of a vector of n_out() entries that belongs to direction d (0: t, 1: x) */
+  std::vector<double> direction(const std::vector<double> &v, int d) const {
+    const unsigned int nt = level.Mt / 2 + 1;
+    return d == 0 ? std::vector<double>(v.begin(), v.begin() + nt) : std::vector<double>(v.begin() + nt, v.end());
+  }
+  /** xi_2 of direction d from the mean correlator; batch >= 2: with the jackknife error over the chains */
+  Xi xi(int d) const {
+    const unsigned int M = d == 0 ? level.Mt : level.Mx;
+    const std::vector<std::vector<double>> m = chain_means();
+    std::vector<double> all(n_out_, 0.0);
+    for (unsigned int b = 0; b < B; ++b)
+      for (unsigned int k = 0; k < n_out_; ++k) all[k] += m[b][k];
+    std::vector<double> mean(all);
+    for (double &v : mean) v /= B;
+    Xi r{xi_second_moment(direction(mean, d), M), 0.0, B >= 2};
+    if (B >= 2) {
+      std::vector<double> x(B), leave(n_out_);
+      double xm = 0.0, s2 = 0.0;
+      for (unsigned int b = 0; b < B; ++b) {
+        for (unsigned int k = 0; k < n_out_; ++k) leave[k] = (all[k] - m[b][k]) / (B - 1.0);
+        x[b] = xi_second_moment(direction(leave, d), M);
+        xm += x[b] / B;
+      }
+      for (unsigned int b = 0; b < B; ++b) s2 += (x[b] - xm) * (x[b] - xm);
+      r.error = std::sqrt((B - 1.0) / B * s2);
+    }
+    return r;
+  }
+
+private:
+  void launch(const std::shared_ptr<SampleState> phi, double *d_out, double *d_acc) {
+    if (phi->size() != 2 * n_vertices) fatal("Evaluating SigmaCorrelator on state of wrong size.");
+    if (!work || work_B != phi->batch()) {
+      check(mlmcpi_sigma_level_correlator_workspace_bytes(&level, phi->batch(), &work_bytes), "sigma_level_correlator_workspace_bytes");
+      work = std::make_unique<DeviceBuffer>(work_bytes);
+      work_B = phi->batch();
+    }
+    check(mlmcpi_sigma_level_correlator(&level, phi->device(), phi->batch(), d_out, d_acc, work->p, work_bytes, nullptr),
+          "sigma_level_correlator");
+  }
+  const mlmcpi_sigma_level level;
+  const unsigned int n_vertices;
+  unsigned int n_out_ = 0, B = 0, work_B = 0, n_calls = 0;
+  size_t work_bytes = 0;
+  std::unique_ptr<DeviceBuffer> work;
+  std::unique_ptr<DeviceVector> acc, out;
 };
 
 }  // namespace mlmcpi

@@ -562,6 +562,26 @@ int mlmcpi_sigma_level_copy_from_fine(const mlmcpi_sigma_level *fine, const doub
                                       void *stream);
 int mlmcpi_sigma_level_copy_from_coarse(const mlmcpi_sigma_level *fine, const double *d_coarse, double *d_fine, uint32_t B,
                                         void *stream);
+/* The zero-momentum (time-slice) two-point function on a level (sigma_correlator.hip); rotated = 0 is the plain
+ * lattice.  Vertices (i, j), 0 <= i < Mt, 0 <= j < Mx (a rotated level holds those with i + j even), N = the level's n.
+ *   slice sums   S^t_i = sum_j sigma(i, j) over the level's vertices with first coordinate i;  S^x_j = sum_i sigma(i, j).  On a
+ *                rotated level a slice holds Mx/2 (Mt/2) vertices and all Mt (Mx) slices exist.
+ *   correlators  C_t(tau) = (1/N) sum_i S^t_i . S^t_{(i + tau) mod Mt}, tau = 0 .. Mt/2;
+ *                C_x(tau) = (1/N) sum_j S^x_j . S^x_{(j + tau) mod Mx}, tau = 0 .. Mx/2.
+ * d_out [B][n_out], n_out = (Mt/2 + 1) + (Mx/2 + 1) (_correlator_size), C_t first.  With w(0) = w(M/2) = 1 and w = 2 otherwise (an
+ * extent of 2: tau = 0, 1, both weight 1), sum_tau w C_d = chi_m = |sum sigma|^2 / N in both directions, and F_d = sum_tau w C_d
+ * cos(2 pi tau / M_d) = |sum_i S_i exp(2 pi i i / M_d)|^2 / N is the structure factor at the lowest momentum; the second-moment
+ * correlation length xi_2,d = sqrt(chi_m / F_d - 1) / (2 sin(pi / M_d)) is host arithmetic on means (include/mlmcpi/qoi.hh).
+ * d_acc (may be NULL) [B][n_out][2]: C is ADDED to [.][.][0] and C^2 to [.][.][1] in the launch that writes d_out; the caller
+ * counts the calls.  d_work: _correlator_workspace_bytes(level, B) bytes, 256-byte aligned; content at entry ignored.  The state
+ * is read once (one sincos pair per vertex); every sum is taken in an order fixed by the level alone, without atomics, so a
+ * chain's output is the same bits whatever B and however the chains are split over calls.  The launch geometry takes B <= 65535
+ * chains per call.  MLMCPI_ERR_INVALID, with nothing launched: NULL level, odd or zero extents, Mt Mx > 2^30, NULL d_state, d_out
+ * or d_work, B = 0 or B > 65535, work_bytes below _correlator_workspace_bytes. */
+int mlmcpi_sigma_level_correlator_size(const mlmcpi_sigma_level *level, uint32_t *n_out);
+int mlmcpi_sigma_level_correlator_workspace_bytes(const mlmcpi_sigma_level *level, uint32_t B, size_t *bytes);
+int mlmcpi_sigma_level_correlator(const mlmcpi_sigma_level *level, const double *d_state, uint32_t B, double *d_out,
+                                  double *d_acc /* may be NULL */, void *d_work, size_t work_bytes, void *stream);
 /* The Wolff single-cluster update on a level (sigma_cluster.hip): n_updates updates of every chain of
  * d_state [B][2 n], in place.  Unrotated: mlmcpi_sigma_cluster_* on (Mt, Mx, beta), the same bits.  Rotated: the level is
  * bipartite, every link has one E end; its 2 n links are (e, d), e an E vertex (e < n / 2), d its direction in the order above;

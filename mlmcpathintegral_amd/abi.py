@@ -166,6 +166,9 @@ SIGNATURES = {
     "mlmcpi_sigma_level_sweep_draw": (_i, [_SL, _vp, _vp, _u32, _u32, _u32, _u64, _u32, _u32, _vp]),
     "mlmcpi_sigma_level_copy_from_fine": (_i, [_SL, _vp, _vp, _u32, _vp]),
     "mlmcpi_sigma_level_copy_from_coarse": (_i, [_SL, _vp, _vp, _u32, _vp]),
+    "mlmcpi_sigma_level_correlator_size": (_i, [_SL, C.POINTER(_u32)]),
+    "mlmcpi_sigma_level_correlator_workspace_bytes": (_i, [_SL, _u32, C.POINTER(_sz)]),
+    "mlmcpi_sigma_level_correlator": (_i, [_SL, _vp, _u32, _vp, _vp, _vp, _sz, _vp]),
     "mlmcpi_sigma_level_cluster_workspace_bytes": (_i, [_SL, _u32, C.POINTER(_sz)]),
     "mlmcpi_sigma_level_cluster_draw": (_i, [_SL, _vp, _u32, _u32, _u64, _u32, _u32, _vp, _vp, _vp]),
     "mlmcpi_sigma_level_sw_workspace_bytes": (_i, [_SL, _u32, C.POINTER(_sz)]),

@@ -445,6 +445,34 @@ def sigma_level_magnetic_susceptibility(level, x):
     return out
 
 
+def sigma_level_correlator_size(level):
+    """n_out = (Mt/2 + 1) + (Mx/2 + 1): the lags of C_t, then those of C_x"""
+    n = C.c_uint32(0)
+    abi.call("mlmcpi_sigma_level_correlator_size", C.byref(level), C.byref(n))
+    return n.value
+
+
+def sigma_level_correlator_workspace(level, B, device="cuda"):
+    """workspace of sigma_level_correlator for B chains (uint8 tensor)"""
+    nbytes = C.c_size_t(0)
+    abi.call("mlmcpi_sigma_level_correlator_workspace_bytes", C.byref(level), B, C.byref(nbytes))
+    return torch.empty(nbytes.value, dtype=torch.uint8, device=device)
+
+
+def sigma_level_correlator(level, x, acc=None, work=None):
+    """time-slice correlators of every chain of x [B, 2 n] on a level, rotated or not (mlmcpi_sigma_level_correlator): returns
+    [B, n_out], C_t(0 .. Mt/2) then C_x(0 .. Mx/2); acc [B, n_out, 2] (optional) is added to: C and C^2"""
+    _check_state(x, sigma_level_size(level))
+    B, n_out = x.shape[0], sigma_level_correlator_size(level)
+    if work is None:
+        work = sigma_level_correlator_workspace(level, B, x.device)
+    if acc is not None:
+        assert acc.dtype == torch.float64 and tuple(acc.shape) == (B, n_out, 2), acc.shape
+    out = _f64(B, n_out, x)
+    abi.call("mlmcpi_sigma_level_correlator", C.byref(level), _p(x), B, _p(out), _p(acc), _p(work), work.numel(), _stream())
+    return out
+
+
 def sigma_level_sweep_draw(level, x, scratch, n_overrelax, n_heatbath, seed, chain0, sweep0):
     """OverrelaxedHeatBathSampler::draw on a level, in place"""
     _check_state(x, sigma_level_size(level))
