@@ -704,6 +704,41 @@ int mlmcpi_test_vs_draw(uint64_t seed, uint32_t chain, uint32_t step, double sca
  * value per concentration class, lw[8][8] = log2 of the acceptance factor of a bin */
 int mlmcpi_vs_table(double scale, uint8_t *sel, float *lw);
 
+/* The fp64 device primitives the samplers share (device_common.hpp, vonmises.hpp, fillin.hpp, sigma_device.hpp), one call per
+ * element: (d_out0[k], d_out1[k]) = fn(d_a[k], d_b[k]).  One thread per element, 256 per block; the kernel calls the
+ * primitive in its header, nothing is restated.  d_b is read by the functions of two operands only (it may be NULL for the
+ * others); d_out1[k] is 0 where a function has one result.  Unknown fn, n == 0 or a NULL pointer: MLMCPI_ERR_INVALID, nothing
+ * is launched.  Operands that are not doubles travel as bit patterns: "words" = the 64 bits of d_a[k], lo = bits 0..31,
+ * hi = bits 32..63. */
+enum mlmcpi_math_fn {
+  MLMCPI_MATH_FAST_RCP = 0,          /* fast_rcp(a) */
+  MLMCPI_MATH_FAST_DIV = 1,          /* fast_div(a, b) */
+  MLMCPI_MATH_FAST_SQRT = 2,         /* fast_sqrt(a) */
+  MLMCPI_MATH_FAST_ACOS = 3,         /* fast_acos(a) */
+  MLMCPI_MATH_SIN_REDUCED = 4,       /* sin_reduced(a) */
+  MLMCPI_MATH_COSPI_UNIT = 5,        /* cospi_unit(a) */
+  MLMCPI_MATH_COS_REDUCED = 6,       /* cos_reduced(a) */
+  MLMCPI_MATH_COS_HALF = 7,          /* cos_half(a) */
+  MLMCPI_MATH_LOG_UNIT = 8,          /* log_unit(a) */
+  MLMCPI_MATH_SINCOS_2PI_UNIT = 9,   /* sincos_2pi_unit(a) -> (sn, cs) */
+  MLMCPI_MATH_BOX_MULLER = 10,       /* box_muller(u = a, v = b) -> (n0, n1) */
+  MLMCPI_MATH_MOD_2PI = 11,          /* mod_2pi(a) */
+  MLMCPI_MATH_MOD_2PI_FAST = 12,     /* mod_2pi_fast(a) */
+  MLMCPI_MATH_U01 = 13,              /* u01(lo, hi) of the words of a */
+  MLMCPI_MATH_U01_52 = 14,           /* u01_52(lo, hi) of the words of a */
+  MLMCPI_MATH_VM_ENVELOPE = 15,      /* vm_envelope(kappa = a) */
+  MLMCPI_MATH_BESSEL_I0_SCALED = 16, /* bessel_i0_scaled(a) */
+  MLMCPI_MATH_TWO_PI_I0_SCALED = 17, /* two_pi_i0_scaled(a) */
+  MLMCPI_MATH_BESSEL_I0 = 18,        /* fillin.hpp bessel_i0(a) */
+  MLMCPI_MATH_COMPACT_EXP_INVERSE = 19, /* compact_exp_inverse(s = a, u = b) */
+  MLMCPI_MATH_VM_TRY = 20,           /* vm_try(lo, hi of the words of a, kappa = b, R = vm_envelope(b)) -> (c, decision 1 | 0 | -1) */
+  MLMCPI_MATH_VM_SCREEN = 21,        /* vm_screen(c = a), the fp32 screen vm_try applies to its c -> (af, band), each fp32 value as a double */
+  MLMCPI_MATH_VM_EXACT = 22,         /* vm_exact(lo, tail, c = a) with b = m + tail, m = 0..2047 the acceptance bits (lo = m << 1),
+                                        tail in [0, 1) a multiple of 2^-41 (so that b holds both exactly) -> decision 1 | 0 */
+  MLMCPI_MATH_COUNT = 23
+};
+int mlmcpi_test_math(uint32_t fn, const double *d_a, const double *d_b, uint32_t n, double *d_out0, double *d_out1, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -17,6 +17,12 @@ LIB_PATH = os.path.join(_HERE, f"libmlmcpi_hip_{_VARIANT}.so" if _VARIANT else "
 HARMONIC, QUARTIC, ROTOR, GFF, SCHWINGER = range(5)
 NONLINEAR_SIGMA = 5  # O(3) nonlinear sigma model (2-D lattice action, uses beta)
 
+# enum mlmcpi_math_fn (mlmcpi_test_math), in the header's order; tests/test_device_math_reference.py compares with the header
+MATH_FN = {name: k for k, name in enumerate((
+    "fast_rcp", "fast_div", "fast_sqrt", "fast_acos", "sin_reduced", "cospi_unit", "cos_reduced", "cos_half", "log_unit",
+    "sincos_2pi_unit", "box_muller", "mod_2pi", "mod_2pi_fast", "u01", "u01_52", "vm_envelope", "bessel_i0_scaled",
+    "two_pi_i0_scaled", "bessel_i0", "compact_exp_inverse", "vm_try", "vm_screen", "vm_exact"))}
+
 
 class MlmcpiError(RuntimeError):
     pass
@@ -147,6 +153,7 @@ SIGNATURES = {
     "mlmcpi_schwinger_beta_coarse_nonperturbative": (_i, [_d, _u32, C.c_int32, _vp]),
     "mlmcpi_test_vs_draw": (_i, [_u64, _u32, _u32, _d, _vp, _vp, _u32, _vp, _vp]),
     "mlmcpi_vs_table": (_i, [_d, _vp, _vp]),
+    "mlmcpi_test_math": (_i, [_u32, _vp, _vp, _u32, _vp, _vp, _vp]),
     "mlmcpi_path_cluster_draw": (_i, [_PA, _vp, _u32, _u32, _u64, _u32, _u32, _vp, _vp]),
     "mlmcpi_schwinger_cluster_workspace_bytes": (_i, [_LA, _u32, C.POINTER(_sz)]),
     "mlmcpi_schwinger_cluster_init": (_i, [_LA, _vp, _u32, _u64, _u32, _vp]),

@@ -30,7 +30,8 @@ __device__ __forceinline__ double mod_2pi(double x) { return x - 2. * kPi * floo
 // of ~16 (an fp64 division is a v_rcp_f64 plus two Newton steps plus scale / fixup).  The two forms
 // can differ only when (x + pi)/(2 pi) lies within an ulp of an integer, and then by exactly 2 pi,
 // i.e. they return the same angle.  Used inside the sweeps, where link angles only ever enter
-// 2 pi-periodic functions or another mod_2pi.
+// 2 pi-periodic functions or another mod_2pi.  Either form returns [-pi, pi] up to the rounding of 2 pi k at magnitude
+// |x| + pi: mod_2pi(11 pi rounded up) is pi + 3.6e-15 (tests/test_device_math_gpu.py).
 __device__ __forceinline__ double mod_2pi_fast(double x) {
   return fma(-kTwoPi, floor(fma(x, 1.0 / kTwoPi, 0.5)), x);  // 3 instructions: v_fma, v_floor, v_fma
 }

@@ -29,6 +29,8 @@ __device__ __forceinline__ double2 angles_of(const V3 &s) {
 // x ~ p(x) ∝ exp(s x) on [-1, 1] (distribution/compactexpdistribution.{hh,cc}) by inversion:
 //   x = log1p(u expm1(2 s)) / s - 1 = 1 + log1p((1 - u) expm1(-2 s)) / s,
 // the second form because it cannot overflow at large s; x = 2 u - 1 at s = 0 (the reference's form is NaN there).
+// Absolute error <= 2^-50 + 1.5 2^-52 |y| / ((1 + y) s), y = (1 - u) expm1(-2 s): log1p is ill-conditioned at y -> -1 (small u at
+// s >~ 1; measured 3.8e-15 at s = 4, u = 0.003).  That term is the image of a change of u by less than its own spacing.
 __device__ __forceinline__ double compact_exp_inverse(double s, double u) {
   if (!(s > 0.0)) return 2.0 * u - 1.0;
   double x = 1.0 + log1p((1.0 - u) * expm1(-2.0 * s)) / s;

@@ -32,7 +32,10 @@ namespace mlmcpi {
 // b alone decides the test unless c exp(1 - c) falls into [b, b + 1) / 2048 (about one attempt in 10^3); only then is
 // the tail u2' (53 bits) taken from a second call (word 3 | kVmRefine), and the decision is the exact fp64 one
 // (c (2 - c) > u2 or log(c / u2) + 1 - c >= 0).  The screening test runs in fp32 (hardware exp) with a guard band that
-// covers the fp32 rounding, so whichever tier decides, the decision is the one the exact test would take.
+// covers the fp32 rounding, so whichever tier decides, the decision is the one the exact test would take for the c of the
+// proposal f that is returned (c is one fma away from f; against the c of the ideal f(u1) it carries kappa times the
+// rounding of f, 3e4 ulp at kappa = 1e4).  One exception: beyond c = 88 exp(1 - c) leaves the fp32 range, the screen sees
+// a = 0 with a band of 0 and rejects; the exact test would accept at u2 = 0 alone, once in 2^64 attempts.
 
 // cos(d / 2) for any |d| < 2^30: d / (4 pi) reduced to t in [-1/2, 1/2], cos(2 pi t) = cos(pi * 2|t|)
 __device__ __forceinline__ double cos_half(double d) {
@@ -60,15 +63,22 @@ __device__ __forceinline__ double u01_52(uint32_t lo, uint32_t hi) {
   return __hiloint2double((int)((hi >> 12) | 0x3FF00000u), (int)__builtin_amdgcn_alignbit(hi, lo, 12)) - 1.0;
 }
 
+// The fp32 screen of an attempt: the acceptance probability a = c exp(1 - c) and the guard band around it.  (A function of
+// its own so that tests/test_device_math_gpu.py can read the two numbers vm_try compares with.)
+__device__ __forceinline__ void vm_screen(double c, float &af, float &band) {
+  const float cf = (float)c;
+  af = cf * __expf(1.0f - cf);              // acceptance probability c exp(1 - c), fp32
+  band = af * (1e-5f * (1.0f + cf));        // >> its fp32 error (~4e-7 (1 + c) relative)
+}
+
 // One attempt from the word pair (lo, hi): proposal f = cos(theta), c, and the screening decision:
 // 1 accepted, 0 rejected, -1 open (the 11 leading bits of u2 do not decide).
 __device__ __forceinline__ int vm_try(uint32_t lo, uint32_t hi, double kappa, double R, double &f, double &c) {
   const double z = cospi_unit(u01_52(lo, hi));
   f = fast_div(fma(R, z, kappa), fma(kappa, z, R));
   c = fma(-kappa, f, R);
-  const float cf = (float)c;
-  const float af = cf * __expf(1.0f - cf);              // acceptance probability c exp(1 - c), fp32
-  const float band = af * (1e-5f * (1.0f + cf));        // >> its fp32 error (~4e-7 (1 + c) relative)
+  float af, band;
+  vm_screen(c, af, band);
   const float lo_s = (float)((lo >> 1) & 0x7FFu) * (1.0f / 2048.0f), hi_s = lo_s + (1.0f / 2048.0f);  // u2 in [lo_s, hi_s)
   return hi_s <= af - band ? 1 : (lo_s >= af + band ? 0 : -1);
 }
@@ -144,8 +154,9 @@ __device__ __forceinline__ double expsin2_draw(const RngKey &k, uint32_t site, d
 }
 
 // exp(-z) I0(z), z >= 0 (the normalisation of the rotor's conditioned fine action): power series in
-// z^2/4 for z < 30 (all terms positive: no cancellation), Hankel asymptotic series beyond.  Relative
-// accuracy ~1e-15.  The reference calls gsl_sf_bessel_I0_scaled (expsin2distribution.cc:7-17).
+// z^2/4 for z < 30 (all terms positive: no cancellation), Hankel asymptotic series beyond.  Relative accuracy: 1e-15 for
+// z >= 30; below, (z + 123) 2^-53 <= 1.7e-14 by counting the roundings of the series (measured 1.7e-15 at z = 26.4,
+// tests/test_device_math_gpu.py).  The reference calls gsl_sf_bessel_I0_scaled (expsin2distribution.cc:7-17).
 __device__ __forceinline__ double bessel_i0_scaled(double z) {
   if (z < 30.0) {
     const double q = 0.25 * z * z;

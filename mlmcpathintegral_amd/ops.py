@@ -736,6 +736,16 @@ def test_vs_draw(seed, chain, step, scale, xp, xm):
     return out
 
 
+def test_math(fn, a, b=None):
+    """(out0, out1) = fn(a, b) element by element: one of the fp64 device primitives (abi.MATH_FN: name or number; enum
+    mlmcpi_math_fn in include/mlmcpi_hip.h says what each reads and returns).  a, b: float64 device tensors of one size."""
+    fn = abi.MATH_FN[fn] if isinstance(fn, str) else int(fn)
+    assert a.dtype == torch.float64 and (b is None or (b.dtype == torch.float64 and b.numel() == a.numel()))
+    out0, out1 = torch.empty_like(a), torch.empty_like(a)
+    abi.call("mlmcpi_test_math", fn, _p(a), _p(b), a.numel(), _p(out0), _p(out1), _stream())
+    return out0, out1
+
+
 def test_expsin2(seed, chain, step, sigma):
     out = torch.empty_like(sigma)
     abi.call("mlmcpi_test_expsin2", seed, chain, step, _p(sigma), sigma.numel(), _p(out), _stream())
