@@ -248,6 +248,7 @@ int main(int argc, char **argv) {
     if (name == "swendsenwang" || name == "levelsw") {  // levelsw: on whatever level the hierarchy hands it (checked above)
       ClusterParameters cp;
       cp.n_burnin = (unsigned)num("n_burnin"); cp.n_updates = (unsigned)num("n_updates"); cp.batch = batch;
+      cp.structure = name == "swendsenwang" && wants_correlator;  // xi_2 from cluster sums beside the plain one
       return std::make_shared<SwendsenWangSamplerFactory>(cp);
     }
     if (name != "heatbath") fatal("unknown sampler " + name);
@@ -407,6 +408,19 @@ int main(int argc, char **argv) {
       if (xi.has_error) std::cout << " +/- " << xi.error << " (jackknife over chains)";
       else std::cout << " (one chain: no jackknife error)";
       std::cout << ", xi_2 / M = " << xi.value / (d ? Mx : Mt) << std::endl;
+    }
+    // --sampler swendsenwang: the same two numbers from the cluster sums of the updates (the field BEFORE each update)
+    const auto sw = std::dynamic_pointer_cast<SwendsenWangSampler>(mc.get_sampler());
+    if (sw && sw->has_structure()) {
+      for (int d = 0; d < 2; ++d) {
+        const SwendsenWangSampler::Estimate F = sw->improved_structure_factor(d);
+        std::cout << " improved F (" << (d ? "x" : "t") << ") = " << F.value << " +/- " << F.error << std::endl;
+      }
+      for (int d = 0; d < 2; ++d) {
+        const SwendsenWangSampler::Estimate xi = sw->improved_xi(d);
+        std::cout << " improved xi_2 (" << (d ? "x" : "t") << ") = " << xi.value << " +/- " << xi.error
+                  << ", xi_2 / M = " << xi.value / (d ? Mx : Mt) << std::endl;
+      }
     }
   }
   if (!std::isnan(analytic)) {  // driver_qm.cc:411-425

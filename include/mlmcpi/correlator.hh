@@ -25,11 +25,17 @@ inline double structure_factor(const std::vector<double> &C, unsigned int M) {
   return s;
 }
 
+/** xi_2 from the susceptibility and the structure factor, however they were estimated (the cluster-improved pair of
+ *  mlmcpi_sigma_level_sw_structure_draw included): sqrt(chi / F - 1) / (2 sin(pi / M)), NaN where chi / F < 1 */
+inline double xi_from_chi_and_F(double chi, double F, unsigned int M) {
+  const double r = chi / F - 1.0;
+  return std::sqrt(r) / (2.0 * std::sin(std::acos(-1.0) / M));
+}
+
 /** second-moment correlation length xi_2 = sqrt(chi / F - 1) / (2 sin(pi / M)); for a single-cosh correlator of mass m it is
  *  exactly 1 / (2 sinh(m / 2)).  NaN where chi / F < 1 (noise) */
 inline double xi_second_moment(const std::vector<double> &C, unsigned int M) {
-  const double r = correlator_susceptibility(C, M) / structure_factor(C, M) - 1.0;
-  return std::sqrt(r) / (2.0 * std::sin(std::acos(-1.0) / M));
+  return xi_from_chi_and_F(correlator_susceptibility(C, M), structure_factor(C, M), M);
 }
 
 }  // namespace mlmcpi

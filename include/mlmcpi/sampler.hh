@@ -14,6 +14,7 @@
 #include <vector>
 
 #include "action.hh"
+#include "correlator.hh"
 
 namespace mlmcpi {
 
@@ -399,6 +400,7 @@ struct ClusterParameters {
   unsigned int n_updates = 10;
   unsigned int batch = 1;
   unsigned int n_meas = 20;  // draws timed for cost_per_sample (10 000 in the reference's constructor)
+  bool structure = false;    // SwendsenWangSampler: also the cluster-improved structure factor and xi_2 (off: the plain entry point)
 };
 
 /** ClusterSampler on a 1-D lattice (sampler/clustersampler.{hh,cc}; single_cluster_update1d): the rotor.  One draw =
@@ -626,21 +628,30 @@ private:
  *  updates of every chain, then the copy out; it runs its own update counter, which advances by n_updates per draw; set_state
  *  is a no-op.  Every draw also returns the clusters and the improved estimator of chi_m (3 sum_C A_C^2 / N of the field
  *  before each update): the sampler keeps, since the last reset_improved(), the mean over draws of the per-draw value (the
- *  mean over the draw's updates and over the chains) and its standard error over the draws. */
+ *  mean over the draw's updates and over the chains) and its standard error over the draws.
+ *  With ClusterParameters::structure it calls mlmcpi_sigma_level_sw_structure_draw (the same state and the same three outputs)
+ *  and keeps PER CHAIN the sums of the improved chi_m, F_t and F_x since reset_improved(): improved_structure_factor(d) is the
+ *  mean over the chains with their spread as the error, improved_xi(d) is xi_2 from the chain-averaged improved (chi, F) with a
+ *  jackknife over the chains, the arithmetic of SigmaCorrelator::xi (NaN where chi / F < 1). */
 class SwendsenWangSampler : public Sampler {
 public:
+  struct Estimate {
+    double value, error;
+    bool has_error;  // the spread and the jackknife over chains need batch >= 2
+  };
   SwendsenWangSampler(const std::shared_ptr<Action> action_, const ClusterParameters p)
       : Sampler(), action(std::dynamic_pointer_cast<NonlinearSigmaAction>(action_)), n_updates(p.n_updates), B(p.batch),
-        clusters(p.batch, sizeof(uint32_t)), improved(p.batch) {
+        with_structure(p.structure), clusters(p.batch, sizeof(uint32_t)), improved(p.batch), structure(2 * (size_t)p.batch),
+        chain_chi(p.batch, 0.0), chain_F{std::vector<double>(p.batch, 0.0), std::vector<double>(p.batch, 0.0)} {
     if (!action) fatal(" swendsenwang sampler not supported for chosen action: it is built for the nonlinear sigma model only.");
     if (n_updates == 0) fatal("SwendsenWangSampler: n_updates must be positive.");
     // the device adds the clusters of one call to a uint32 per chain: n_updates updates of at most N clusters each
     if ((uint64_t)n_updates * (action->sample_size() / 2) > 0xFFFFFFFFull)
       fatal("SwendsenWangSampler: n_updates x vertices must stay below 2^32 (the per-chain counter of one draw).");
-    size_t bytes = 0;
     const mlmcpi_sigma_level lv = action->level();
-    check(mlmcpi_sigma_level_sw_workspace_bytes(&lv, B, &bytes), "sigma_level_sw_workspace_bytes");
-    work = std::make_shared<DeviceBuffer>(bytes);
+    if (with_structure) check(mlmcpi_sigma_level_sw_structure_workspace_bytes(&lv, B, &work_bytes), "sigma_level_sw_structure_workspace_bytes");
+    else check(mlmcpi_sigma_level_sw_workspace_bytes(&lv, B, &work_bytes), "sigma_level_sw_workspace_bytes");
+    work = std::make_shared<DeviceBuffer>(work_bytes);
     phi_state_cur = std::make_shared<SampleState>(action->sample_size(), B);
     action->initialise_state(phi_state_cur);
     std::shared_ptr<SampleState> tmp = std::make_shared<SampleState>(action->sample_size(), B);
@@ -658,14 +669,31 @@ public:
     check(mlmcpi_memset(clusters.ptr(), 0, B * sizeof(uint32_t), nullptr), "mlmcpi_memset");
     check(mlmcpi_memset(improved.ptr(), 0, B * sizeof(double), nullptr), "mlmcpi_memset");
     const mlmcpi_sigma_level lv = action->level();
-    check(mlmcpi_sigma_level_sw_draw(&lv, phi_state_cur->device_mutable(), B, n_updates, action->get_seed(),
-                                     action->get_chain0(), update_counter, nullptr, (uint32_t *)clusters.ptr(),
-                                     (double *)improved.ptr(), work->p, nullptr),
-          "sigma_level_sw_draw");
+    if (with_structure) {
+      check(mlmcpi_memset(structure.ptr(), 0, 2 * (size_t)B * sizeof(double), nullptr), "mlmcpi_memset");
+      check(mlmcpi_sigma_level_sw_structure_draw(&lv, phi_state_cur->device_mutable(), B, n_updates, action->get_seed(),
+                                               action->get_chain0(), update_counter, nullptr, (uint32_t *)clusters.ptr(),
+                                               (double *)improved.ptr(), (double *)structure.ptr(), work->p, work_bytes, nullptr),
+            "sigma_level_sw_structure_draw");
+    } else {
+      check(mlmcpi_sigma_level_sw_draw(&lv, phi_state_cur->device_mutable(), B, n_updates, action->get_seed(),
+                                       action->get_chain0(), update_counter, nullptr, (uint32_t *)clusters.ptr(),
+                                       (double *)improved.ptr(), work->p, nullptr),
+            "sigma_level_sw_draw");
+    }
     update_counter += n_updates;
     double c = 0.0, v = 0.0;
     for (uint32_t x : clusters.download<uint32_t>()) c += x;
-    for (double x : improved.download<double>()) v += x;
+    const std::vector<double> imp = improved.download<double>();
+    for (double x : imp) v += x;
+    if (with_structure) {
+      const std::vector<double> F = structure.download<double>();
+      for (unsigned int b = 0; b < B; ++b) {
+        chain_chi[b] += imp[b];
+        chain_F[0][b] += F[2 * b];
+        chain_F[1][b] += F[2 * b + 1];
+      }
+    }
     v /= (double)B * n_updates;                          // this draw's value: the mean over its updates and the chains
     clusters_total += c / B;
     improved_sum += v;
@@ -679,7 +707,47 @@ public:
   void set_state(std::shared_ptr<SampleState>) override {}
   double cost_per_sample() override { return cost_per_sample_; }
   /** forget the clusters and improved values recorded so far (the constructor does, after burn-in and timing draws) */
-  void reset_improved() { clusters_total = improved_sum = improved_sum2 = 0.0; draws_counted = 0; }
+  void reset_improved() {
+    clusters_total = improved_sum = improved_sum2 = 0.0;
+    draws_counted = 0;
+    std::fill(chain_chi.begin(), chain_chi.end(), 0.0);
+    for (std::vector<double> &f : chain_F) std::fill(f.begin(), f.end(), 0.0);
+  }
+  bool has_structure() const { return with_structure; }
+  /** improved structure factor of direction d (0: t, 1: x) at the lowest momentum: the mean over the chains of their means
+   *  since the last reset; batch >= 2: with the spread of the per-chain means over sqrt(batch) */
+  Estimate improved_structure_factor(int d) const {
+    need_structure("improved_structure_factor");
+    const double n = (double)draws_counted * n_updates;
+    double m = 0.0, s2 = 0.0;
+    for (unsigned int b = 0; b < B; ++b) m += chain_F[d][b] / n / B;
+    for (unsigned int b = 0; b < B; ++b) s2 += (chain_F[d][b] / n - m) * (chain_F[d][b] / n - m);
+    return Estimate{m, B >= 2 ? std::sqrt(s2 / ((double)B * (B - 1.0))) : 0.0, B >= 2};
+  }
+  /** xi_2 of direction d from the chain-averaged improved chi_m and F_d (xi_from_chi_and_F: NaN where chi / F < 1); batch >= 2:
+   *  with the jackknife error over the chains, as SigmaCorrelator::xi forms it */
+  Estimate improved_xi(int d) const {
+    need_structure("improved_xi");
+    const mlmcpi_sigma_level lv = action->level();
+    const unsigned int M = d == 0 ? lv.Mt : lv.Mx;
+    double chi = 0.0, F = 0.0;
+    for (unsigned int b = 0; b < B; ++b) {
+      chi += chain_chi[b];
+      F += chain_F[d][b];
+    }
+    Estimate r{xi_from_chi_and_F(chi / B, F / B, M), 0.0, B >= 2};
+    if (B >= 2) {
+      std::vector<double> x(B);
+      double xm = 0.0, s2 = 0.0;
+      for (unsigned int b = 0; b < B; ++b) {
+        x[b] = xi_from_chi_and_F((chi - chain_chi[b]) / (B - 1.0), (F - chain_F[d][b]) / (B - 1.0), M);
+        xm += x[b] / B;
+      }
+      for (unsigned int b = 0; b < B; ++b) s2 += (x[b] - xm) * (x[b] - xm);
+      r.error = std::sqrt((B - 1.0) / B * s2);
+    }
+    return r;
+  }
   /** clusters per update, averaged over the chains and the updates since the last reset */
   double mean_clusters_per_update() const { return draws_counted ? clusters_total / ((double)draws_counted * n_updates) : 0.0; }
   /** improved estimator of chi_m, averaged over the chains and the updates since the last reset */
@@ -697,12 +765,20 @@ public:
   }
 
 private:
+  void need_structure(const char *what) const {
+    if (!with_structure) fatal(std::string("SwendsenWangSampler::") + what + ": constructed without ClusterParameters::structure.");
+    if (!draws_counted) fatal(std::string("SwendsenWangSampler::") + what + ": no draws since reset_improved().");
+  }
   const std::shared_ptr<NonlinearSigmaAction> action;
   const unsigned int n_updates, B;
+  const bool with_structure;
   std::shared_ptr<SampleState> phi_state_cur;
   std::shared_ptr<DeviceBuffer> work;
-  DeviceVector clusters;  // uint32 per chain: the clusters of the draw at hand
-  DeviceVector improved;  // double per chain: the improved values of the draw at hand, summed over its updates
+  size_t work_bytes = 0;
+  DeviceVector clusters;   // uint32 per chain: the clusters of the draw at hand
+  DeviceVector improved;   // double per chain: the improved values of the draw at hand, summed over its updates
+  DeviceVector structure;  // double [batch][2]: the improved (F_t, F_x) of the draw at hand, summed over its updates
+  std::vector<double> chain_chi, chain_F[2];  // per chain, since reset_improved(): sums over the updates of improved chi_m, F_t, F_x
   double clusters_total = 0.0, improved_sum = 0.0, improved_sum2 = 0.0;
   uint64_t draws_counted = 0;
   uint32_t update_counter = 0;

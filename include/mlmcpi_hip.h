@@ -623,6 +623,27 @@ int mlmcpi_sigma_level_sw_workspace_bytes(const mlmcpi_sigma_level *level, uint3
 int mlmcpi_sigma_level_sw_draw(const mlmcpi_sigma_level *level, double *d_state, uint32_t B, uint32_t n_updates, uint64_t seed,
                                uint32_t chain0, uint32_t update0, uint32_t *d_flipped, uint32_t *d_clusters, double *d_improved,
                                void *d_work, void *stream);
+/* The same update with the cluster-improved structure factor at the lowest momentum: the state, d_flipped,
+ * d_clusters and d_improved are the bits of mlmcpi_sigma_level_sw_draw; rotated = 0 serves the plain lattice.
+ * Positions.  Unrotated: l = Mt j + i sits at (i, j).  Rotated: plane p, cell (a, b), index p ht hx + ht b + a, sits at (i, j) =
+ * (2 a + p, 2 b + p), the slice assignment of mlmcpi_sigma_level_correlator.  Direction d = 0 is t (x_0 = i, M_0 = Mt), d = 1 is x
+ * (x_1 = j, M_1 = Mx).  Weights: (w^s_d, w^c_d)(l) = sincospi(2.0 * x_d / M_d) in double, the quotient formed from the integers
+ * by the one device function every kernel calls, so an extent of 2 gives exactly 0 and +-1.
+ * Per cluster C and direction d two 64-bit fixed-point sums, Ac_d = sum_{l in C} llrint((a_l w^c_d(l)) 2^32) and As_d with w^s_d,
+ * the product formed first, no fp contraction, added by integer atomics as A_C is (|a w| <= 1 and n <= 2^30: inside 63 bits).
+ * Per update F_d^imp = R(Ac_d) 3 / n + R(As_d) 3 / n, R(S) = the sum over the roots of (S 2^-32)^2 in the fixed configuration of
+ * the improved chi_m (1024 threads, thread t takes t, t + 1024, .., then the fixed tree), one such sum per S, each scaled and ADDED
+ * to d_structure[b][d] in turn (cos, then sin), exactly as chi_m's is added to d_improved.  d_structure (double [B][2]: F_t^imp,
+ * F_x^imp) is so ADDED to update by update and is the same bits under every launch plan, tile, batch split, chain0 and call
+ * split (10 = 5 + 5).  It is the mean of 3 |sum_l +-a_l e^{2 pi i x_d / M_d}|^2 / n over the coins: an unbiased estimator of the structure factor F_d = |sum_l sigma_l e^{2 pi i x_d / M_d}|^2 / n.
+ * Workspace: that of mlmcpi_sigma_level_sw_draw + 32 B per vertex and chain (four more root slots); work_bytes is what d_work
+ * holds.  MLMCPI_SIGMA_SW_PLAN and MLMCPI_SIGMA_SW_TILE govern it; the chain plan keeps its 20 B per vertex and its bound.
+ * Errors as for mlmcpi_sigma_level_sw_draw, and MLMCPI_ERR_INVALID, nothing launched, for NULL d_structure or work_bytes below
+ * _structure_workspace_bytes. */
+int mlmcpi_sigma_level_sw_structure_workspace_bytes(const mlmcpi_sigma_level *level, uint32_t B, size_t *bytes);
+int mlmcpi_sigma_level_sw_structure_draw(const mlmcpi_sigma_level *level, double *d_state, uint32_t B, uint32_t n_updates,
+                                         uint64_t seed, uint32_t chain0, uint32_t update0, uint32_t *d_flipped, uint32_t *d_clusters,
+                                         double *d_improved, double *d_structure, void *d_work, size_t work_bytes, void *stream);
 /* NonlinearSigmaConditionedFineAction (nonlinearsigmaconditionedfineaction.cc:7-44) on a level.  Every fine-only vertex (the
  * (i + j) odd ones of an unrotated level, the O plane of a rotated one) has coarse neighbours only, so the fill is a product of
  * independent heat-bath laws and _evaluate is minus the log of its density.

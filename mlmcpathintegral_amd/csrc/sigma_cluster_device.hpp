@@ -77,8 +77,12 @@ __device__ __forceinline__ void team_sync() {
 struct LatticeGeometry {
   uint32_t Mt, Mx;
   static constexpr uint32_t kOwnedLinks = 2;
+  static constexpr bool kStructure = false;
   __host__ __device__ uint32_t nvert() const { return Mt * Mx; }
   __host__ __device__ uint32_t nowners() const { return Mt * Mx; }
+  // the structure sums: the periodic extent of direction d (0: t, 1: x) and the position of vertex l along it, l at (i, j)
+  __host__ __device__ uint32_t extent(uint32_t d) const { return d ? Mx : Mt; }
+  __device__ __forceinline__ uint32_t position(uint32_t l, uint32_t d) const { return d ? l / Mt : l % Mt; }
 
   __device__ __forceinline__ void far_ends(uint32_t l, uint32_t (&y)[2]) const {
     const uint32_t i = l % Mt, j = l / Mt;
@@ -107,9 +111,17 @@ struct LatticeGeometry {
 struct RotatedGeometry {
   uint32_t ht, hx, q;  // q = ht hx
   static constexpr uint32_t kOwnedLinks = 4;
+  static constexpr bool kStructure = false;
   explicit RotatedGeometry(const SigmaLevel &L) : ht(L.ht), hx(L.hx), q(L.q) {}
   __host__ __device__ uint32_t nvert() const { return 2 * q; }
   __host__ __device__ uint32_t nowners() const { return q; }
+  // the structure sums: the level's extents Mt = 2 ht, Mx = 2 hx; plane p, cell (a, b) sits at (i, j) = (2 a + p, 2 b + p), the
+  // slice assignment of mlmcpi_sigma_level_correlator
+  __host__ __device__ uint32_t extent(uint32_t d) const { return 2 * (d ? hx : ht); }
+  __device__ __forceinline__ uint32_t position(uint32_t l, uint32_t d) const {
+    const uint32_t p = l >= q ? 1u : 0u, c = l - p * q;
+    return 2 * (d ? c / ht : c % ht) + p;
+  }
 
   __device__ __forceinline__ void far_ends(uint32_t e, uint32_t (&y)[4]) const {
     const uint32_t cb = e / ht, ca = e - cb * ht;
@@ -127,6 +139,16 @@ struct RotatedGeometry {
     return (bonded(a, ao[0], beta2, u01(w0.x, w0.y)) ? 1u : 0u) | (bonded(a, ao[1], beta2, u01(w0.z, w0.w)) ? 2u : 0u) |
            (bonded(a, ao[2], beta2, u01(w1.x, w1.y)) ? 4u : 0u) | (bonded(a, ao[3], beta2, u01(w1.z, w1.w)) ? 8u : 0u);
   }
+};
+
+// A geometry whose kernels also form the structure sums (the improved structure factor, below): the compile-time option of the
+// chain kernel.  It carries the caller's accumulator [B][2] and the chain kernel's table of weights [B][2 (M_0 + M_1)], so that
+// the instances on the plain geometries keep their arguments.
+template <class G>
+struct WithStructure : G {
+  double *structure, *weights;
+  static constexpr bool kStructure = true;
+  WithStructure(const G &g, double *s, double *w) : G(g), structure(s), weights(w) {}
 };
 
 // ---- the union-find of the Swendsen-Wang labelling -------------------------------------------------------------------------
@@ -210,6 +232,42 @@ __device__ __forceinline__ void sw_finish(const uint32_t *parent, const long lon
     if (improved) *improved += red[0] * (3.0 / (double)N);
     if (clusters) *clusters += redc[0];
   }
+}
+
+// ---- Swendsen-Wang: the structure sums (improved structure factor at the lowest momentum) ----------------------
+// the weights of a vertex at position x of a periodic direction of extent M: s = sin(2 pi x / M), c = cos(2 pi x / M).  The one
+// place that forms them, from the integers: both plans and both geometries get the same bits, and M = 2 gives exactly 0 and +-1.
+__device__ __forceinline__ void sw_phase(uint32_t x, uint32_t M, double &s, double &c) { sincospi(2.0 * (double)x / (double)M, &s, &c); }
+
+constexpr uint32_t kSwCombineRounds = 4;   // roots a wave combines for before its left-over lanes add one by one
+constexpr uint32_t kSwCombineMin = 4;      // lanes that must share a root for the wave reduction to be the cheaper way
+
+// v[0 .. NV) of every active lane added onto slot[root + k stride], k < NV.  Integer adds commute, so the lanes of a wave that share
+// a root may add up first and send one atomic per value; the slots hold the same bits either way.  The percolating cluster
+// otherwise serialises every lane of every wave on one address.  Every lane of the wave calls it: the loop's trip count comes
+// from ballots and is uniform, the shuffles run with all lanes, and no lane waits on another lane's store.
+template <int SCOPE, uint32_t NV>
+__device__ __forceinline__ void sw_add_combined(long long *slot, size_t stride, uint32_t root, bool active, const long long (&v)[NV]) {
+  const uint32_t lane = threadIdx.x & (kWave - 1);
+  unsigned long long todo = __ballot(active);
+  for (uint32_t round = 0; round < kSwCombineRounds && todo; ++round) {
+    const uint32_t lead = (uint32_t)__builtin_ctzll(todo);
+    const bool same = ((todo >> lane) & 1ull) && root == (uint32_t)__shfl((int)root, (int)lead);
+    const unsigned long long m = __ballot(same);
+    todo &= ~m;
+    if ((uint32_t)__builtin_popcountll(m) < kSwCombineMin) {
+      if (same)
+        for (uint32_t k = 0; k < NV; ++k) __hip_atomic_fetch_add(slot + root + k * stride, v[k], __ATOMIC_RELAXED, SCOPE);
+      continue;
+    }
+    for (uint32_t k = 0; k < NV; ++k) {
+      long long s = same ? v[k] : 0;
+      for (int off = kWave / 2; off > 0; off >>= 1) s += __shfl_xor(s, off);
+      if (lane == lead) __hip_atomic_fetch_add(slot + root + k * stride, s, __ATOMIC_RELAXED, SCOPE);
+    }
+  }
+  if ((todo >> lane) & 1ull)
+    for (uint32_t k = 0; k < NV; ++k) __hip_atomic_fetch_add(slot + root + k * stride, v[k], __ATOMIC_RELAXED, SCOPE);
 }
 
 // one atomic per wave: the lanes of the wave that flipped a vertex (every lane of the wave calls it)

@@ -33,6 +33,11 @@
 // index (also when the cluster is a lone O vertex), P_SIGMA_SW_BOND at site e, sub d >> 1: u decides link (e, d) for d even, v
 // for d odd.  union(x, x) returns at once (level (2, 2): the four links of E(0, 0) all end at O(0, 0)).
 //
+// Improved structure factor (mlmcpi_sigma_level_sw_structure_draw): per cluster and direction d the two sums
+// of q(a_l w), w = cos, sin of 2 pi x_d(l) / M_d from sw_phase, on four further root slots; each is finished as A_C is and added
+// to structure[b][d], cos then sin.  The structure instances: sigma_sw_resolve_structure_kernel<Geometry>,
+// sigma_sw_finish_structure_kernel, sigma_sw_chain_kernel<WithStructure<Geometry>>; the instances of the plain draw are untouched.
+//
 // Labelling: the parent array and the union by atomic min of sigma_cluster_device.hpp (uf_*), where its termination argument
 // is written out.
 #include <mutex>
@@ -273,6 +278,49 @@ __global__ void __launch_bounds__(kClusterThreads)
   if (capped) atomicOr(status, 1u);
 }
 
+// launch 3 with the structure sums: the same update, and q(a) and the four weighted values q(a w) go onto the root's five slots
+// (`section` apart), the lanes of a wave that share a root combined first.  a is formed again from the field before the update
+// (the same dot3 on the same bits as launch 1; nobody else stores this vertex).  Every lane stays to the end: the combining
+// shuffles run with the whole wave.
+template <class Geometry>
+__global__ void __launch_bounds__(kClusterThreads)
+    sigma_sw_resolve_structure_kernel(double2 *phi_all, Geometry g, RngKey key0, uint32_t blocks, const uint32_t *label_all,
+                                      const long long *qa_all, long long *sum_all, size_t section, uint32_t *flipped, uint32_t *status) {
+  const uint32_t N = g.nvert(), b = blockIdx.x / blocks, l = (blockIdx.x % blocks) * kClusterThreads + threadIdx.x;
+  const bool active = l < N;
+  RngKey key = key0;
+  key.chain = key0.chain + b;
+  const V3 r = reflection_normal(key, P_SIGMA_SW_REFLECT);
+  bool flip = false, capped = false;
+  uint32_t root = 0;
+  long long v[5] = {0, 0, 0, 0, 0};
+  V3 s{0.0, 0.0, 0.0};
+  double a = 0.0;
+  if (active) {
+    root = uf_find<kUfPlain>(label_all + (size_t)b * N, l, N, capped);
+    s = sigma_of(phi_all[(size_t)b * N + l]);
+    a = dot3(r, s);
+    v[0] = qa_all[(size_t)b * N + l];
+#pragma unroll
+    for (uint32_t d = 0; d < 2; ++d) {
+      double ws, wc;
+      sw_phase(g.position(l, d), g.extent(d), ws, wc);
+      v[1 + 2 * d] = sw_fixed(a * wc);
+      v[2 + 2 * d] = sw_fixed(a * ws);
+    }
+    flip = !capped && sw_coin(key, root);
+  }
+  sw_add_combined<__HIP_MEMORY_SCOPE_AGENT>(sum_all + (size_t)b * N, section, root, active, v);
+  if (flip) {
+    double2 *p = phi_all + (size_t)b * N + l;
+    const double2 out = reflected(s, a, r);
+    __builtin_nontemporal_store(out.x, &p->x);
+    __builtin_nontemporal_store(out.y, &p->y);
+  }
+  sw_count_flips(flip, flipped ? flipped + b : nullptr);
+  if (capped) atomicOr(status, 1u);
+}
+
 // ---- launch 4 (only when outputs are asked for): one workgroup per chain --------------------------------------------------
 __global__ void __launch_bounds__(kClusterBlockThreads)
     sigma_sw_finish_kernel(const uint32_t *label_all, const long long *sum_all, uint32_t N, double *improved, uint32_t *clusters) {
@@ -281,6 +329,53 @@ __global__ void __launch_bounds__(kClusterBlockThreads)
   const uint32_t b = blockIdx.x;
   sw_finish(label_all + (size_t)b * N, sum_all + (size_t)b * N, N, red, redc, improved ? improved + b : nullptr,
             clusters ? clusters + b : nullptr);
+}
+
+// launch 4 with the structure sums: what the plain one does and the same fixed-configuration finish of the four structure
+// slots, cos then sin of direction d ADDED to structure[b][d] one after the other; the four slots of every root go back to
+// zero as they are read (the resolve kernel adds to roots only)
+__global__ void __launch_bounds__(kClusterBlockThreads)
+    sigma_sw_finish_structure_kernel(const uint32_t *label_all, long long *sum_all, size_t section, uint32_t N, double *improved,
+                                     uint32_t *clusters, double *structure) {
+  __shared__ double red[kClusterBlockThreads];
+  __shared__ uint32_t redc[kClusterBlockThreads];
+  const uint32_t b = blockIdx.x;
+  const uint32_t *label = label_all + (size_t)b * N;
+  long long *sum = sum_all + (size_t)b * N;
+  // one walk over the labels for the five slots: per slot the terms meet in the order of sw_finish (thread t takes t, t + 1024,
+  // .., then the fixed tree), so every sum is the bits of a sw_finish of its own
+  const uint32_t t = threadIdx.x;
+  double s[5] = {0.0, 0.0, 0.0, 0.0, 0.0};
+  uint32_t c = 0;
+  for (uint32_t l = t; l < N; l += kClusterBlockThreads)
+    if (label[l] == l) {
+#pragma unroll
+      for (uint32_t k = 0; k < 5; ++k) {
+        const double S = (double)sum[k * section + l] * (1.0 / kSwFix);
+        s[k] += S * S;
+        if (k) sum[k * section + l] = 0;
+      }
+      ++c;
+    }
+#pragma unroll
+  for (uint32_t k = 0; k < 5; ++k) {
+    red[t] = s[k];
+    if (k == 0) redc[t] = c;
+    __syncthreads();
+    for (uint32_t off = kClusterBlockThreads / 2; off > 0; off >>= 1) {
+      if (t < off) {
+        red[t] += red[t + off];
+        if (k == 0) redc[t] += redc[t + off];
+      }
+      __syncthreads();
+    }
+    if (t == 0) {
+      const double v = red[0] * (3.0 / (double)N);
+      if (k) structure[2 * b + ((k - 1) >> 1)] += v;
+      else if (improved) improved[b] += v;
+      if (k == 0 && clusters) clusters[b] += redc[0];
+    }
+  }
 }
 
 // ---- chain plan: one workgroup per chain, all n_updates updates in one launch, labels, sums and a in LDS ------------------
@@ -305,6 +400,20 @@ __global__ void __launch_bounds__(kClusterBlockThreads)
   key.chain = key0.chain + b;
   uint32_t nflip = 0;
   bool capped = false;
+  if constexpr (Geometry::kStructure) {
+    // the weights of every position of both directions, once per launch, into this chain's table in the workspace: (cos, sin)
+    // of position x of direction d at 2 (d M_0 + x).  Formed by sw_phase as everywhere; inside the update loop sincospi would
+    // take the kernel beyond its 128 registers.  The barrier of the first update orders the table before its readers.
+    const uint32_t M0 = g.extent(0), M1 = g.extent(1);
+    double *table = g.weights + (size_t)b * 2 * (M0 + M1);
+    for (uint32_t x = t; x < M0 + M1; x += kClusterBlockThreads) {
+      const uint32_t d = x >= M0 ? 1u : 0u;
+      double ws, wc;
+      sw_phase(x - d * M0, d ? M1 : M0, ws, wc);
+      table[2 * x] = wc;
+      table[2 * x + 1] = ws;
+    }
+  }
   for (uint32_t n = 0; n < n_updates; ++n, ++key.step) {
     const V3 r = reflection_normal(key, P_SIGMA_SW_REFLECT);
     for (uint32_t l = t; l < N; l += kClusterBlockThreads) {
@@ -326,7 +435,12 @@ __global__ void __launch_bounds__(kClusterBlockThreads)
     }
     __syncthreads();
     for (uint32_t l = t; l < N; l += kClusterBlockThreads) {
-      const uint32_t root = uf_find<kUfPlain>(parent, l, N, capped);
+      // structure instance: the root is stored over the parent (a lane that reads the word meanwhile gets the old parent or the
+      // root, both above it), so that the four passes below read it in one load.  A root stores itself over itself and no other
+      // vertex can come to hold its own index, so parent[l] == l holds for the same l as before: sw_finish sees the same roots
+      // and the same sums as the plain instance, and d_improved and d_clusters are its bits.
+      const uint32_t root = uf_find<Geometry::kStructure ? __HIP_MEMORY_SCOPE_WORKGROUP : kUfPlain>(parent, l, N, capped);
+      if constexpr (Geometry::kStructure) __hip_atomic_store(parent + l, root, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
       if (improved) atomicAdd((unsigned long long *)(sum + root), (unsigned long long)sw_fixed(a[l]));
       if (!capped && sw_coin(key, root)) {
         phi[l] = reflected(sigma_of(phi[l]), a[l], r);
@@ -334,8 +448,35 @@ __global__ void __launch_bounds__(kClusterBlockThreads)
       }
     }
     __syncthreads();
-    if (outputs) sw_finish(parent, sum, N, red, redc, improved ? improved + b : nullptr, clusters ? clusters + b : nullptr);
-    __syncthreads();
+    if constexpr (!Geometry::kStructure) {
+      if (outputs) sw_finish(parent, sum, N, red, redc, improved ? improved + b : nullptr, clusters ? clusters + b : nullptr);
+      __syncthreads();
+    } else {
+      // Pass 0 finishes the cluster sums as above.  Pass k = 1 + 2 d + (0: cos, 1: sin) takes the one slot per vertex again: zero,
+      // add q(a w) onto the root's slot, finish into structure[b][d].  a is still the field's before the update, w comes from the
+      // table; the trip counts are uniform (sw_add_combined shuffles).  One copy of the code serves the five passes.
+      const double *table = g.weights + (size_t)b * 2 * (g.extent(0) + g.extent(1));
+#pragma unroll 1
+      for (uint32_t k = 0; k < 5; ++k) {
+        const uint32_t d = k ? (k - 1) >> 1 : 0;
+        if (k > 0) {
+          for (uint32_t l = t; l < N; l += kClusterBlockThreads) sum[l] = 0;
+          __syncthreads();
+#pragma unroll 1
+          for (uint32_t base = 0; base < N; base += kClusterBlockThreads) {
+            const uint32_t l = base + t;
+            const bool active = l < N;
+            const long long v[1] = {active ? sw_fixed(a[l] * table[2 * (d * g.extent(0) + g.position(l, d)) + ((k - 1) & 1u)]) : 0};
+            sw_add_combined<__HIP_MEMORY_SCOPE_WORKGROUP>(sum, 0, active ? parent[l] : 0u, active, v);
+          }
+          __syncthreads();
+        }
+        if (k > 0 || outputs)
+          sw_finish(parent, sum, N, red, redc, k ? g.structure + 2 * b + d : (improved ? improved + b : nullptr),
+                    k || !clusters ? nullptr : clusters + b);
+        __syncthreads();
+      }
+    }
   }
   if (flipped) {
     for (int off = kWave / 2; off > 0; off >>= 1) nflip += __shfl_down(nflip, off);
@@ -406,6 +547,10 @@ int sw_init_attrs() {
                                      kSwChainMaxN * kSwChainBytesPerVertex));
   MLMCPI_HIP_TRY(hipFuncSetAttribute((const void *)sigma_sw_chain_kernel<RotatedGeometry>, hipFuncAttributeMaxDynamicSharedMemorySize,
                                      kSwChainMaxN * kSwChainBytesPerVertex));
+  MLMCPI_HIP_TRY(hipFuncSetAttribute((const void *)sigma_sw_chain_kernel<WithStructure<LatticeGeometry>>,
+                                     hipFuncAttributeMaxDynamicSharedMemorySize, kSwChainMaxN * kSwChainBytesPerVertex));
+  MLMCPI_HIP_TRY(hipFuncSetAttribute((const void *)sigma_sw_chain_kernel<WithStructure<RotatedGeometry>>,
+                                     hipFuncAttributeMaxDynamicSharedMemorySize, kSwChainMaxN * kSwChainBytesPerVertex));
   MLMCPI_HIP_TRY(hipFuncSetAttribute((const void *)sigma_rot_sw_bond_label_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
                                      (int)sw_rot_tile_lds(kSwMaxTile, kSwMaxTile)));
   g_sw_attr_set[dev] = true;
@@ -423,14 +568,20 @@ int sw_check(const mlmcpi_lattice_action *act, const char *what) {
 }
 
 // workspace sections: status word (256 B), label [B N] uint32, q(a) [B N] int64, cluster sums [B N] int64, bond bits [B owners]
-// uint8 (two bits per vertex; on a rotated level four bits per E vertex)
+// uint8 (two bits per vertex; on a rotated level four bits per E vertex).  With structure sums four more [B N] int64 sections
+// follow the cluster sums (slot k of a root is k sections behind its cluster sum), before the bond bits.  The chain plan uses
+// the status word only; with structure sums it also keeps its table of weights, 16 (M_0 + M_1) B per chain, from the start of the
+// q(a) section on (sw_chain_table: the six int64 sections are contiguous, 48 B per vertex and chain, and 3 N >= M_0 + M_1).
+constexpr uint32_t kSwStructureSlots = 4;
 constexpr size_t kSwStatusBytes = 256;
 size_t sw_section_label(uint32_t N, uint32_t B) { return align256((size_t)B * N * sizeof(uint32_t)); }
 size_t sw_section_fixed(uint32_t N, uint32_t B) { return align256((size_t)B * N * sizeof(long long)); }
 size_t sw_section_bits(uint32_t owners, uint32_t B) { return align256((size_t)B * owners); }
+inline double *sw_chain_table(void *d_work, uint32_t N, uint32_t B) { return (double *)((char *)d_work + kSwStatusBytes + sw_section_label(N, B)); }
 template <class Geometry>
-size_t sw_workspace(const Geometry &g, uint32_t B) {
-  return kSwStatusBytes + sw_section_label(g.nvert(), B) + 2 * sw_section_fixed(g.nvert(), B) + sw_section_bits(g.nowners(), B);
+size_t sw_workspace(const Geometry &g, uint32_t B, bool structure = false) {
+  return kSwStatusBytes + sw_section_label(g.nvert(), B) + (2 + (structure ? kSwStructureSlots : 0)) * sw_section_fixed(g.nvert(), B) +
+         sw_section_bits(g.nowners(), B);
 }
 
 // launches 1 and 2 of the tiled plan, one pair per geometry: the lattice's take its extents, the rotated level's the level
@@ -458,11 +609,12 @@ int sw_front_end(const SigmaLevel &L, const SwPlan &p, const double2 *phi, doubl
 
 // the draw on either geometry, arguments checked: the workspace laid out, the launches issued, the status word read back.
 // `front` is what sw_front_end takes for this geometry, `what` the entry point, `where` the noun ("lattice", "level") of its
-// messages and `chain_kernel` the name of the chain kernel's instance in a launch error.
+// messages and `chain_kernel` the name of the chain kernel's instance in a launch error.  d_structure != NULL: the structure
+// instances of the kernels and the larger workspace (the caller has checked its size).
 template <class Geometry, class Front>
 int sw_draw(const Geometry &g, const Front &front, double beta, double *d_phi, uint32_t B, uint32_t n_updates, uint64_t seed, uint32_t chain0, uint32_t update0,
-            uint32_t *d_flipped, uint32_t *d_clusters, double *d_improved, void *d_work, void *stream, const char *what, const char *where,
-            const char *chain_kernel) {
+            uint32_t *d_flipped, uint32_t *d_clusters, double *d_improved, double *d_structure, void *d_work, void *stream, const char *what,
+            const char *where, const char *chain_kernel) {
   const uint32_t N = g.nvert();
   const SwPlan p = sw_plan(g, B, tuning());
   if (!p.ok)
@@ -477,19 +629,40 @@ int sw_draw(const Geometry &g, const Front &front, double beta, double *d_phi, u
   uint32_t *label = (uint32_t *)(w + kSwStatusBytes);
   long long *qa = (long long *)(w + kSwStatusBytes + sw_section_label(N, B));
   long long *sum = (long long *)(w + kSwStatusBytes + sw_section_label(N, B) + sw_section_fixed(N, B));
-  uint8_t *bits = (uint8_t *)(w + kSwStatusBytes + sw_section_label(N, B) + 2 * sw_section_fixed(N, B));
+  uint8_t *bits = (uint8_t *)(w + kSwStatusBytes + sw_section_label(N, B) + (2 + (d_structure ? kSwStructureSlots : 0)) * sw_section_fixed(N, B));
+  const size_t section = d_structure ? sw_section_fixed(N, B) / sizeof(long long) : 0;
+  // the room of sw_chain_table (it holds on every level: both extents are even and >= 2)
+  MLMCPI_REQUIRE(!d_structure || (uint64_t)3 * N >= (uint64_t)g.extent(0) + g.extent(1), "the table of weights does not fit the workspace");
   const hipStream_t st = as_stream(stream);
   const double beta2 = 2.0 * beta;
   MLMCPI_HIP_TRY(hipMemsetAsync(status, 0, sizeof(uint32_t), st));
-  if (p.chain) {
+  if (p.chain && d_structure) {
+    hipLaunchKernelGGL(sigma_sw_chain_kernel<WithStructure<Geometry>>, dim3(B), dim3(kClusterBlockThreads), p.lds_bytes, st, (double2 *)d_phi,
+                       WithStructure<Geometry>(g, d_structure, sw_chain_table(d_work, N, B)), beta2, n_updates, make_key(seed, chain0, update0), d_flipped, d_clusters,
+                       d_improved, status);
+    MLMCPI_LAUNCH_CHECK(chain_kernel);
+  } else if (p.chain) {
     hipLaunchKernelGGL(sigma_sw_chain_kernel<Geometry>, dim3(B), dim3(kClusterBlockThreads), p.lds_bytes, st, (double2 *)d_phi, g, beta2,
                        n_updates, make_key(seed, chain0, update0), d_flipped, d_clusters, d_improved, status);
     MLMCPI_LAUNCH_CHECK(chain_kernel);
   } else {
     const bool outputs = d_clusters || d_improved;
+    // the bond + label kernels zero the cluster sum of every vertex and are the ones of the plain draw; the four structure slots
+    // are zeroed here once, and after every update by the finish kernel at the roots it has read (nothing else was added to)
+    if (d_structure) MLMCPI_HIP_TRY(hipMemsetAsync(sum + section, 0, kSwStructureSlots * sw_section_fixed(N, B), st));
     for (uint32_t k = 0; k < n_updates; ++k) {
       const RngKey key = make_key(seed, chain0, update0 + k);
-      if (int rc = sw_front_end(front, p, (const double2 *)d_phi, beta2, key, B, label, bits, qa, d_improved ? sum : nullptr, status, st)) return rc;
+      if (int rc = sw_front_end(front, p, (const double2 *)d_phi, beta2, key, B, label, bits, qa, d_improved || d_structure ? sum : nullptr, status, st))
+        return rc;
+      if (d_structure) {
+        hipLaunchKernelGGL(sigma_sw_resolve_structure_kernel<Geometry>, dim3(B * p.resolve_blocks), dim3(kClusterThreads), 0, st,
+                           (double2 *)d_phi, g, key, p.resolve_blocks, label, qa, sum, section, d_flipped, status);
+        MLMCPI_LAUNCH_CHECK("sigma_sw_resolve_structure_kernel");
+        hipLaunchKernelGGL(sigma_sw_finish_structure_kernel, dim3(B), dim3(kClusterBlockThreads), 0, st, label, sum, section, N, d_improved,
+                           d_clusters, d_structure);
+        MLMCPI_LAUNCH_CHECK("sigma_sw_finish_structure_kernel");
+        continue;
+      }
       hipLaunchKernelGGL(sigma_sw_resolve_kernel, dim3(B * p.resolve_blocks), dim3(kClusterThreads), 0, st, (double2 *)d_phi, N, key,
                          p.resolve_blocks, label, qa, d_improved ? sum : nullptr, d_flipped, status);
       MLMCPI_LAUNCH_CHECK("sigma_sw_resolve_kernel");
@@ -527,7 +700,7 @@ int mlmcpi_sigma_sw_draw(const mlmcpi_lattice_action *act, double *d_phi, uint32
   MLMCPI_REQUIRE(d_phi && d_work && B > 0, "bad arguments");
   MLMCPI_REQUIRE((uint64_t)update0 + n_updates <= 0xFFFFFFFFull, "update counter overflows");
   const LatticeGeometry g{act->Mt, act->Mx};
-  return sw_draw(g, g, act->beta, d_phi, B, n_updates, seed, chain0, update0, d_flipped, d_clusters, d_improved, d_work, stream,
+  return sw_draw(g, g, act->beta, d_phi, B, n_updates, seed, chain0, update0, d_flipped, d_clusters, d_improved, nullptr, d_work, stream,
                  "mlmcpi_sigma_sw_draw", "lattice", "sigma_sw_chain_kernel");
 }
 
@@ -554,7 +727,40 @@ int mlmcpi_sigma_level_sw_draw(const mlmcpi_sigma_level *level, double *d_state,
   }
   const SigmaLevel L = make_level(*level);
   return sw_draw(RotatedGeometry(L), L, level->beta, d_state, B, n_updates, seed, chain0, update0, d_flipped, d_clusters, d_improved,
-                 d_work, stream, "mlmcpi_sigma_level_sw_draw", "level", "sigma_rot_sw_chain_kernel");
+                 nullptr, d_work, stream, "mlmcpi_sigma_level_sw_draw", "level", "sigma_rot_sw_chain_kernel");
+}
+
+int mlmcpi_sigma_level_sw_structure_workspace_bytes(const mlmcpi_sigma_level *level, uint32_t B, size_t *bytes) {
+  if (int rc = check_cluster_level(level)) return rc;
+  MLMCPI_REQUIRE(bytes && B > 0, "bad arguments");
+  if (!level->rotated) {
+    const mlmcpi_lattice_action act = level_as_lattice(level);
+    if (int rc = sw_check(&act, "mlmcpi_sigma_level_sw_structure_workspace_bytes")) return rc;
+    *bytes = sw_workspace(LatticeGeometry{act.Mt, act.Mx}, B, true);
+  } else {
+    *bytes = sw_workspace(RotatedGeometry(make_level(*level)), B, true);
+  }
+  return MLMCPI_OK;
+}
+
+int mlmcpi_sigma_level_sw_structure_draw(const mlmcpi_sigma_level *level, double *d_state, uint32_t B, uint32_t n_updates, uint64_t seed,
+                                         uint32_t chain0, uint32_t update0, uint32_t *d_flipped, uint32_t *d_clusters, double *d_improved,
+                                         double *d_structure, void *d_work, size_t work_bytes, void *stream) {
+  size_t need = 0;
+  if (int rc = mlmcpi_sigma_level_sw_structure_workspace_bytes(level, B ? B : 1, &need)) return rc;
+  MLMCPI_REQUIRE(d_state && d_work && B > 0, "bad arguments");
+  MLMCPI_REQUIRE(d_structure, "d_structure is NULL: mlmcpi_sigma_level_sw_draw is the entry point without structure sums");
+  MLMCPI_REQUIRE(work_bytes >= need, "the workspace is smaller than mlmcpi_sigma_level_sw_structure_workspace_bytes asks for");
+  MLMCPI_REQUIRE((uint64_t)update0 + n_updates <= 0xFFFFFFFFull, "update counter overflows");
+  const char *what = "mlmcpi_sigma_level_sw_structure_draw";
+  if (!level->rotated) {
+    const LatticeGeometry g{level->Mt, level->Mx};
+    return sw_draw(g, g, level->beta, d_state, B, n_updates, seed, chain0, update0, d_flipped, d_clusters, d_improved, d_structure, d_work,
+                   stream, what, "level", "sigma_sw_chain_kernel (structure)");
+  }
+  const SigmaLevel L = make_level(*level);
+  return sw_draw(RotatedGeometry(L), L, level->beta, d_state, B, n_updates, seed, chain0, update0, d_flipped, d_clusters, d_improved,
+                 d_structure, d_work, stream, what, "level", "sigma_rot_sw_chain_kernel (structure)");
 }
 
 }  // extern "C"

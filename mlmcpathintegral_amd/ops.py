@@ -523,19 +523,35 @@ def sigma_level_sw_workspace(level, B, device="cuda"):
     return torch.empty(nbytes.value, dtype=torch.uint8, device=device)
 
 
-def sigma_level_sw_draw(level, x, n_updates, seed, chain0, update0, outputs=True, work=None):
+def sigma_level_sw_structure_workspace(level, B, device="cuda"):
+    """workspace of sigma_level_sw_draw(..., structure=True) for B chains (uint8 tensor): 32 B per vertex and chain more"""
+    nbytes = C.c_size_t(0)
+    abi.call("mlmcpi_sigma_level_sw_structure_workspace_bytes", C.byref(level), B, C.byref(nbytes))
+    return torch.empty(nbytes.value, dtype=torch.uint8, device=device)
+
+
+def sigma_level_sw_draw(level, x, n_updates, seed, chain0, update0, outputs=True, work=None, structure=False):
     """Swendsen-Wang multi-cluster updates on a level, rotated or not (mlmcpi_sigma_level_sw_draw): n_updates updates of every
     chain of x [B, 2 n], in place, update counters update0 + k; returns, per chain and summed over this call's updates, (flipped
-    vertices int32 [B], clusters int32 [B], improved chi_m float64 [B]), or None with outputs=False"""
+    vertices int32 [B], clusters int32 [B], improved chi_m float64 [B]), or None with outputs=False.  structure=True
+    (mlmcpi_sigma_level_sw_structure_draw; `work` from sigma_level_sw_structure_workspace): the same state and outputs and a fourth
+    tensor, float64 [B, 2], the improved structure factors (F_t, F_x) at the lowest momentum summed over this call's updates"""
     _check_state(x, sigma_level_size(level))
     B = x.shape[0]
     if work is None:
-        work = sigma_level_sw_workspace(level, B, x.device)
+        work = (sigma_level_sw_structure_workspace if structure else sigma_level_sw_workspace)(level, B, x.device)
     flipped = clusters = improved = None
     if outputs:
         flipped = torch.zeros(B, dtype=torch.int32, device=x.device)
         clusters = torch.zeros(B, dtype=torch.int32, device=x.device)
         improved = torch.zeros(B, dtype=torch.float64, device=x.device)
+    if structure:
+        if not outputs:
+            raise ValueError("structure=True returns outputs")
+        factors = torch.zeros(B, 2, dtype=torch.float64, device=x.device)
+        abi.call("mlmcpi_sigma_level_sw_structure_draw", C.byref(level), _p(x), B, n_updates, seed, chain0, update0, _p(flipped),
+                 _p(clusters), _p(improved), _p(factors), _p(work), work.numel(), _stream())
+        return flipped, clusters, improved, factors
     abi.call("mlmcpi_sigma_level_sw_draw", C.byref(level), _p(x), B, n_updates, seed, chain0, update0, _p(flipped), _p(clusters),
              _p(improved), _p(work), _stream())
     return (flipped, clusters, improved) if outputs else None
