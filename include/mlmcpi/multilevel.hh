@@ -262,6 +262,8 @@ public:
   }
   void set_state(std::shared_ptr<SampleState> phi_state) override { theta_fine->data = phi_state->data; }
   double cost_per_sample() override { return cost_per_sample_; }
+  /** the Philox step of the next draw (the constructor's timing draws have used the first n_meas) */
+  uint32_t steps_used() const { return step; }
 
 private:
   /** every level of a hierarchy gets its own Philox key: the fill-in streams of two levels share
@@ -343,6 +345,8 @@ public:
     for (unsigned int ell = 0; ell < n_level; ++ell)
       std::cout << "  level " << ell << " : p = " << (ell == n_level - 1 ? coarse_sampler->p_accept() : twolevel_step[ell]->p_accept()) << std::endl;
   }
+  /** acceptance probability of level ell's own step (what show_stats prints) */
+  double level_p_accept(unsigned int ell) { return ell == n_level - 1 ? coarse_sampler->p_accept() : twolevel_step[ell]->p_accept(); }
 
 private:
   const unsigned int n_level;
@@ -428,6 +432,8 @@ public:
     for (unsigned int ell = 0; ell < n_level; ++ell)
       std::cout << " level " << ell << " : average spacing between samples " << t_indep[ell] << std::endl << *stats_sampler[ell];
   }
+  /** average spacing between the samples level ell handed on (what show_stats prints) */
+  double independent_spacing(unsigned int ell) const { return t_indep[ell]; }
 
 private:
   const unsigned int n_level;
@@ -684,6 +690,8 @@ public:
     std::cout << " Q = " << std::setprecision(6) << numerical_result() << " +/- " << statistical_error() << std::endl;
   }
   std::shared_ptr<Statistics> level_statistics(unsigned int ell) { return stats_qoi[ell]; }
+  /** the sample target of level ell as the last update() left it */
+  unsigned int target_samples(unsigned int ell) const { return n_target[ell]; }
   bool verbose = false;
 
 private:

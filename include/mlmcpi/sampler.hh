@@ -103,6 +103,8 @@ public:
   }
   void set_state(std::shared_ptr<SampleState> phi_state) override { phi_state_cur->data = phi_state->data; }
   double get_dt() const { return dt_hmc; }
+  /** the Philox trajectory counter: the `traj0` of the next launch (burn-in and tuning have advanced it) */
+  uint32_t trajectories_used() const { return traj; }
   std::shared_ptr<SampleState> current_state() { return phi_state_cur; }
 
   /** hmcsampler.cc:77-113: bisection on [dt/2, 2dt], fixed iteration count, result kept only if some
@@ -449,6 +451,9 @@ public:
     std::cout << std::setprecision(3) << std::fixed << "  cluster updates per draw = " << n_updates << std::endl
               << "  mean cluster size        = " << mean_cluster_size() << " sites" << std::endl;
   }
+  /** the host total of flipped sites (folds so far) and the device counters not yet folded into it; read only */
+  double flipped_sites_folded() const { return flipped_total; }
+  std::vector<uint32_t> flipped_sites_unfolded() const { return sites.download<uint32_t>(); }
 
 private:
   /** the device counters are 32 bits per chain: add them to the host total and zero them before they can wrap */
@@ -590,6 +595,9 @@ public:
     std::cout << std::setprecision(3) << std::fixed << "  cluster updates per draw = " << n_updates << std::endl
               << "  mean cluster size        = " << mean_cluster_size() << " sites" << std::endl;
   }
+  /** the host total of flipped sites (folds so far) and the device counters not yet folded into it; read only */
+  double flipped_sites_folded() const { return flipped_total; }
+  std::vector<uint32_t> flipped_sites_unfolded() const { return sites.download<uint32_t>(); }
 
 private:
   void fold_sites() {

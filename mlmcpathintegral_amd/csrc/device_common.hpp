@@ -435,4 +435,17 @@ __device__ __forceinline__ void store_streaming(double2 *p, double x, double y) 
   __builtin_nontemporal_store(v, reinterpret_cast<d2_t *>(p));
 }
 
+// stats->record_sample of one value into a chain's packed sums a[5] = [n, sum v, sum v^2, sum v^3, sum v^4]: the one recurrence of
+// mlmcpi_stats_accumulate and of every kernel that records a QoI it has just finished.  The roundings are spelled out (one fused
+// multiply-add per sum, on products rounded on their own), so that a unit compiled without fp contraction records the same bits as
+// one compiled with it: a fused record equals mlmcpi_stats_accumulate on the same value whatever kernel wrote it.
+__device__ __forceinline__ void record_moments(double *a, double v) {
+  const double v2 = __dmul_rn(v, v), v3 = __dmul_rn(v, v2);
+  a[0] += 1.0;
+  a[1] += v;
+  a[2] = __fma_rn(v, v, a[2]);
+  a[3] = __fma_rn(v, v2, a[3]);
+  a[4] = __fma_rn(v, v3, a[4]);
+}
+
 }  // namespace mlmcpi

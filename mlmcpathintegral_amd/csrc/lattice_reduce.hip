@@ -118,14 +118,7 @@ __global__ void __launch_bounds__(256) lattice_finish_kernel(const double *__res
   if (lane == 0) {
     const double v = (op == L_CHARGE) ? (1. / (4. * kPi * kPi)) * s * s : scale * s;  // qoi2dsusceptibility.cc:26
     out[b] = v;
-    if (acc) {
-      double *a = acc + 5 * (size_t)b;
-      a[0] += 1.0;
-      a[1] += v;
-      a[2] += v * v;
-      a[3] += v * v * v;
-      a[4] += v * v * v * v;
-    }
+    if (acc) record_moments(acc + 5 * (size_t)b, v);
   }
 }
 
@@ -176,13 +169,7 @@ __global__ void stats_window_record_kernel(double *__restrict__ state, const dou
 __global__ void stats_accumulate_kernel(double *__restrict__ acc, const double *__restrict__ q, uint32_t B) {
   const uint32_t b = blockIdx.x * blockDim.x + threadIdx.x;
   if (b >= B) return;
-  const double v = q[b];
-  double *a = acc + 5 * (size_t)b;
-  a[0] += 1.0;
-  a[1] += v;
-  a[2] += v * v;
-  a[3] += v * v * v;
-  a[4] += v * v * v * v;
+  record_moments(acc + 5 * (size_t)b, q[b]);
 }
 
 // ---- host dispatch ----------------------------------------------------------------------------------------

@@ -45,14 +45,7 @@ __global__ void path_finish_kernel(const double *__restrict__ partial, uint32_t 
   // R_WINDING: chi = Q^2 / (4 pi^2 T)  (qoisusceptibility.cc:20-22); others: scale * sum
   const double v = (op == R_WINDING) ? (1. / (4. * kPi * kPi)) * (s * s) * scale : scale * s;
   out[b] = v;
-  if (acc) {  // stats->record_sample of the value as well (the recurrence of stats_accumulate_kernel)
-    double *a = acc + 5 * (size_t)b;
-    a[0] += 1.0;
-    a[1] += v;
-    a[2] += v * v;
-    a[3] += v * v * v;
-    a[4] += v * v * v * v;
-  }
+  if (acc) record_moments(acc + 5 * (size_t)b, v);  // stats->record_sample of the value as well (the recurrence of stats_accumulate_kernel)
 }
 
 template <int KIND>

@@ -168,14 +168,7 @@ __global__ void __launch_bounds__(256) sigma_finish_kernel(const double *__restr
   if constexpr (OP == 0) q = scale * v[0];
   else q = (v[0] * v[0] + v[1] * v[1] + v[2] * v[2]) * scale;
   out[b] = q;
-  if (acc) {
-    double *a = acc + 5 * (size_t)b;
-    a[0] += 1.0;
-    a[1] += q;
-    a[2] += q * q;
-    a[3] += q * q * q;
-    a[4] += q * q * q * q;
-  }
+  if (acc) record_moments(acc + 5 * (size_t)b, q);
 }
 
 // NonlinearSigmaAction::force (nonlinearsigmaaction.cc:94-112): dS/dtheta, dS/dphi per vertex
