@@ -162,6 +162,17 @@ int mlmcpi_path_hmc_run(const mlmcpi_path_action *act, double *d_x, uint32_t B, 
                         double *d_qoi, int32_t *d_accept_count, void *stream);
 /* 1 if d_qoi of mlmcpi_path_hmc_run is chain-major [B][n_draws] for this action / nt, 0 if draw-major */
 int mlmcpi_path_hmc_run_layout(const mlmcpi_path_action *act, uint32_t B, uint32_t nt, int32_t *chain_major);
+/* The launch geometry the three calls above choose from (kind, M, B, nt); host only, no device is touched.  NT threads hold
+ * R consecutive sites each.  halo == 0: one workgroup holds the whole periodic path in registers (NT * R == M, nseg == 1,
+ * owned_len == M) and mlmcpi_path_hmc_run is one launch (chain_major == 1, what mlmcpi_path_hmc_run_layout reports).
+ * Otherwise segment s of nseg owns the sites [s * owned_len, min(M, (s + 1) * owned_len)) in the middle of a buffer of NT * R
+ * sites whose first and last halo = nt + 1 sites are recomputed copies of the neighbouring segments.  An nt too long for the
+ * buffer (2 halo + 64 > NT * R) is MLMCPI_ERR_INVALID here as in the calls above. */
+typedef struct mlmcpi_path_hmc_plan_info {
+  uint32_t R, NT, nseg, owned_len, halo;
+  int32_t chain_major;
+} mlmcpi_path_hmc_plan_info;
+int mlmcpi_path_hmc_plan(const mlmcpi_path_action *act, uint32_t B, uint32_t nt, mlmcpi_path_hmc_plan_info *out);
 
 /* OverrelaxedHeatBathSampler::draw (sampler/overrelaxedheatbathsampler.cc:8-31) for the rotor:
  * n_overrelax sweeps of RotorAction::overrelaxation_update (rotoraction.cc:40-56) then n_heatbath

@@ -461,4 +461,19 @@ int mlmcpi_path_hmc_run_layout(const mlmcpi_path_action *act, uint32_t B, uint32
   return MLMCPI_OK;
 }
 
+// host only: the plan the three entry points above run, and plan_hmc's own status for an nt that is too long
+int mlmcpi_path_hmc_plan(const mlmcpi_path_action *act, uint32_t B, uint32_t nt, mlmcpi_path_hmc_plan_info *out) {
+  if (int rc = check_action(act)) return rc;
+  MLMCPI_REQUIRE(out && B > 0, "bad arguments");
+  HmcPlan pl;
+  if (int rc = plan_hmc(act->kind, act->M, B, nt, &pl)) return rc;
+  out->R = pl.R;
+  out->NT = pl.NT;
+  out->nseg = pl.nseg;
+  out->owned_len = pl.owned_len;
+  out->halo = pl.halo;
+  out->chain_major = pl.halo == 0 ? 1 : 0;
+  return MLMCPI_OK;
+}
+
 }  // extern "C"

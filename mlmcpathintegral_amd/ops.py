@@ -110,11 +110,17 @@ def path_hmc_run(hmc, x, n_draws, qoi_kind):
     abi.call("mlmcpi_path_hmc_run", C.byref(hmc.act), _p(x), hmc.B, hmc.nt, float(hmc.dt), hmc.n_rep, n_draws, qoi_kind,
              hmc.seed, hmc.chain0, hmc.traj, _p(hmc.work), _p(q), _p(cnt), _stream())
     hmc.traj += n_draws * hmc.n_rep
-    layout = C.c_int32(0)
-    abi.call("mlmcpi_path_hmc_run_layout", C.byref(hmc.act), hmc.B, hmc.nt, C.byref(layout))
-    if not layout.value:
+    if not path_hmc_plan(hmc.act, hmc.B, hmc.nt)["chain_major"]:
         q = q.reshape(n_draws, hmc.B).t().contiguous()
     return q, cnt
+
+
+def path_hmc_plan(act, B, nt):
+    """The launch geometry of PathHMC / path_hmc_run for these arguments (mlmcpi_path_hmc_plan; no device needed): a dict of
+    R, NT, nseg, owned_len, halo, chain_major"""
+    info = abi.PathHmcPlan()
+    abi.call("mlmcpi_path_hmc_plan", C.byref(act), B, nt, C.byref(info))
+    return {n: getattr(info, n) for n, _ in abi.PathHmcPlan._fields_}
 
 
 class PathTwoLevelStep:
