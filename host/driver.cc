@@ -29,6 +29,7 @@
 //          (--correlator 1, single-level heatbath / wolff / swendsenwang runs: all `batch` chains are sampled, Q is their mean per
 //           sample, and after the statistics come the time-slice correlators C_t, C_x per lag, chi and F from them, and the
 //           second-moment correlation length xi_2 with its jackknife error over the chains)
+//          (with --sampler swendsenwang the cluster-improved F, xi_2 and, per lag, C_t and C_x follow: DESIGN.md 4.6b)
 //   driver --action rotor --M_lat 256 --T_final 25.6 --m0 0.25 --sampler cluster --n_updates 10 --n_samples 20000
 //          (cluster samplers: rotor and schwinger; also --coarsesampler cluster for twolevel / hierarchical rotor runs)
 //   driver --method throughput --action schwinger --Mt_lat 1024 --sampler heatbath --batch 32 --n_samples 20
@@ -249,6 +250,7 @@ int main(int argc, char **argv) {
       ClusterParameters cp;
       cp.n_burnin = (unsigned)num("n_burnin"); cp.n_updates = (unsigned)num("n_updates"); cp.batch = batch;
       cp.structure = name == "swendsenwang" && wants_correlator;  // xi_2 from cluster sums beside the plain one
+      cp.correlator = cp.structure;                                // and the improved C(tau) they come from: one call per draw
       return std::make_shared<SwendsenWangSamplerFactory>(cp);
     }
     if (name != "heatbath") fatal("unknown sampler " + name);
@@ -420,6 +422,18 @@ int main(int argc, char **argv) {
         const SwendsenWangSampler::Estimate xi = sw->improved_xi(d);
         std::cout << " improved xi_2 (" << (d ? "x" : "t") << ") = " << xi.value << " +/- " << xi.error
                   << ", xi_2 / M = " << xi.value / (d ? Mx : Mt) << std::endl;
+      }
+    }
+    // and the cluster-improved correlators themselves, per lag, in the format of the plain block
+    if (sw && sw->has_correlator()) {
+      const SwendsenWangSampler::CorrelatorEstimate ie = sw->improved_correlator();
+      const std::vector<double> It = correlator->direction(ie.mean, 0), Ix = correlator->direction(ie.mean, 1);
+      const std::vector<double> IEt = correlator->direction(ie.error, 0), IEx = correlator->direction(ie.error, 1);
+      for (unsigned tau = 0; tau < std::max(nt, nx); ++tau) {
+        std::cout << " improved C(tau = " << tau << "):";
+        if (tau < nt) std::cout << " improved C_t = " << It[tau] << " +/- " << IEt[tau];
+        if (tau < nx) std::cout << " improved C_x = " << Ix[tau] << " +/- " << IEx[tau];
+        std::cout << std::endl;
       }
     }
   }

@@ -403,6 +403,7 @@ struct ClusterParameters {
   unsigned int batch = 1;
   unsigned int n_meas = 20;  // draws timed for cost_per_sample (10 000 in the reference's constructor)
   bool structure = false;    // SwendsenWangSampler: also the cluster-improved structure factor and xi_2 (off: the plain entry point)
+  bool correlator = false;   // SwendsenWangSampler: also the cluster-improved time-slice correlator C(tau) (off: the plain entry point)
 };
 
 /** ClusterSampler on a 1-D lattice (sampler/clustersampler.{hh,cc}; single_cluster_update1d): the rotor.  One draw =
@@ -640,24 +641,40 @@ private:
  *  With ClusterParameters::structure it calls mlmcpi_sigma_level_sw_structure_draw (the same state and the same three outputs)
  *  and keeps PER CHAIN the sums of the improved chi_m, F_t and F_x since reset_improved(): improved_structure_factor(d) is the
  *  mean over the chains with their spread as the error, improved_xi(d) is xi_2 from the chain-averaged improved (chi, F) with a
- *  jackknife over the chains, the arithmetic of SigmaCorrelator::xi (NaN where chi / F < 1). */
+ *  jackknife over the chains, the arithmetic of SigmaCorrelator::xi (NaN where chi / F < 1).
+ *  With ClusterParameters::correlator it calls mlmcpi_sigma_level_sw_correlator_draw (again the same state and three outputs)
+ *  and keeps PER CHAIN the sums of the improved C_t and C_x, every lag, since reset_improved(): improved_correlator() gives
+ *  their means and errors as SigmaCorrelator::means_and_errors does.  With both options set it still makes that one call per
+ *  draw: F_d of a draw is then structure_factor() of the draw's improved C_d (correlator.hh), chain by chain. */
 class SwendsenWangSampler : public Sampler {
 public:
   struct Estimate {
     double value, error;
     bool has_error;  // the spread and the jackknife over chains need batch >= 2
   };
+  struct CorrelatorEstimate {
+    std::vector<double> mean, error;  // [n_out], C_t first: the layout of SigmaCorrelator::Estimate
+    bool chain_spread;                // true: error = spread of the per-chain means (batch >= 2); false: no error (one chain)
+  };
   SwendsenWangSampler(const std::shared_ptr<Action> action_, const ClusterParameters p)
       : Sampler(), action(std::dynamic_pointer_cast<NonlinearSigmaAction>(action_)), n_updates(p.n_updates), B(p.batch),
-        with_structure(p.structure), clusters(p.batch, sizeof(uint32_t)), improved(p.batch), structure(2 * (size_t)p.batch),
-        chain_chi(p.batch, 0.0), chain_F{std::vector<double>(p.batch, 0.0), std::vector<double>(p.batch, 0.0)} {
+        with_structure(p.structure), with_correlator(p.correlator), clusters(p.batch, sizeof(uint32_t)), improved(p.batch),
+        structure(2 * (size_t)p.batch), chain_chi(p.batch, 0.0),
+        chain_F{std::vector<double>(p.batch, 0.0), std::vector<double>(p.batch, 0.0)} {
     if (!action) fatal(" swendsenwang sampler not supported for chosen action: it is built for the nonlinear sigma model only.");
     if (n_updates == 0) fatal("SwendsenWangSampler: n_updates must be positive.");
     // the device adds the clusters of one call to a uint32 per chain: n_updates updates of at most N clusters each
     if ((uint64_t)n_updates * (action->sample_size() / 2) > 0xFFFFFFFFull)
       fatal("SwendsenWangSampler: n_updates x vertices must stay below 2^32 (the per-chain counter of one draw).");
     const mlmcpi_sigma_level lv = action->level();
-    if (with_structure) check(mlmcpi_sigma_level_sw_structure_workspace_bytes(&lv, B, &work_bytes), "sigma_level_sw_structure_workspace_bytes");
+    if (with_correlator) {
+      uint32_t n = 0;
+      check(mlmcpi_sigma_level_correlator_size(&lv, &n), "sigma_level_correlator_size");
+      n_out = n;
+      corr = std::make_unique<DeviceVector>((size_t)B * n_out);
+      chain_C.assign((size_t)B * n_out, 0.0);
+      check(mlmcpi_sigma_level_sw_correlator_workspace_bytes(&lv, B, &work_bytes), "sigma_level_sw_correlator_workspace_bytes");
+    } else if (with_structure) check(mlmcpi_sigma_level_sw_structure_workspace_bytes(&lv, B, &work_bytes), "sigma_level_sw_structure_workspace_bytes");
     else check(mlmcpi_sigma_level_sw_workspace_bytes(&lv, B, &work_bytes), "sigma_level_sw_workspace_bytes");
     work = std::make_shared<DeviceBuffer>(work_bytes);
     phi_state_cur = std::make_shared<SampleState>(action->sample_size(), B);
@@ -677,7 +694,13 @@ public:
     check(mlmcpi_memset(clusters.ptr(), 0, B * sizeof(uint32_t), nullptr), "mlmcpi_memset");
     check(mlmcpi_memset(improved.ptr(), 0, B * sizeof(double), nullptr), "mlmcpi_memset");
     const mlmcpi_sigma_level lv = action->level();
-    if (with_structure) {
+    if (with_correlator) {
+      check(mlmcpi_memset(corr->ptr(), 0, (size_t)B * n_out * sizeof(double), nullptr), "mlmcpi_memset");
+      check(mlmcpi_sigma_level_sw_correlator_draw(&lv, phi_state_cur->device_mutable(), B, n_updates, action->get_seed(),
+                                                action->get_chain0(), update_counter, nullptr, (uint32_t *)clusters.ptr(),
+                                                (double *)improved.ptr(), (double *)corr->ptr(), work->p, work_bytes, nullptr),
+            "sigma_level_sw_correlator_draw");
+    } else if (with_structure) {
       check(mlmcpi_memset(structure.ptr(), 0, 2 * (size_t)B * sizeof(double), nullptr), "mlmcpi_memset");
       check(mlmcpi_sigma_level_sw_structure_draw(&lv, phi_state_cur->device_mutable(), B, n_updates, action->get_seed(),
                                                action->get_chain0(), update_counter, nullptr, (uint32_t *)clusters.ptr(),
@@ -694,7 +717,19 @@ public:
     for (uint32_t x : clusters.download<uint32_t>()) c += x;
     const std::vector<double> imp = improved.download<double>();
     for (double x : imp) v += x;
-    if (with_structure) {
+    if (with_correlator) {
+      const std::vector<double> C = corr->download<double>();
+      for (size_t k = 0; k < C.size(); ++k) chain_C[k] += C[k];
+      if (with_structure) {                              // F_d of the draw from its improved C_d, chain by chain
+        const unsigned int nt = lv.Mt / 2 + 1;
+        for (unsigned int b = 0; b < B; ++b) {
+          const std::vector<double>::const_iterator c = C.begin() + (size_t)b * n_out;
+          chain_chi[b] += imp[b];
+          chain_F[0][b] += structure_factor(std::vector<double>(c, c + nt), lv.Mt);
+          chain_F[1][b] += structure_factor(std::vector<double>(c + nt, c + n_out), lv.Mx);
+        }
+      }
+    } else if (with_structure) {
       const std::vector<double> F = structure.download<double>();
       for (unsigned int b = 0; b < B; ++b) {
         chain_chi[b] += imp[b];
@@ -720,8 +755,26 @@ public:
     draws_counted = 0;
     std::fill(chain_chi.begin(), chain_chi.end(), 0.0);
     for (std::vector<double> &f : chain_F) std::fill(f.begin(), f.end(), 0.0);
+    std::fill(chain_C.begin(), chain_C.end(), 0.0);
   }
   bool has_structure() const { return with_structure; }
+  bool has_correlator() const { return with_correlator; }
+  /** the improved C_t (first Mt / 2 + 1 entries) and C_x: per lag the mean over the chains of their means over the updates since
+   *  the last reset; batch >= 2: with the spread of the per-chain means over sqrt(batch), as SigmaCorrelator::means_and_errors */
+  CorrelatorEstimate improved_correlator() const {
+    if (!with_correlator) fatal("SwendsenWangSampler::improved_correlator: constructed without ClusterParameters::correlator.");
+    if (!draws_counted) fatal("SwendsenWangSampler::improved_correlator: no draws since reset_improved().");
+    CorrelatorEstimate e{std::vector<double>(n_out, 0.0), std::vector<double>(n_out, 0.0), B >= 2};
+    const double n = (double)draws_counted * n_updates;
+    for (unsigned int k = 0; k < n_out; ++k) {
+      double m = 0.0, s2 = 0.0;
+      for (unsigned int b = 0; b < B; ++b) m += chain_C[(size_t)b * n_out + k] / n / B;
+      for (unsigned int b = 0; b < B; ++b) s2 += (chain_C[(size_t)b * n_out + k] / n - m) * (chain_C[(size_t)b * n_out + k] / n - m);
+      e.mean[k] = m;
+      e.error[k] = B >= 2 ? std::sqrt(s2 / ((double)B * (B - 1.0))) : 0.0;
+    }
+    return e;
+  }
   /** improved structure factor of direction d (0: t, 1: x) at the lowest momentum: the mean over the chains of their means
    *  since the last reset; batch >= 2: with the spread of the per-chain means over sqrt(batch) */
   Estimate improved_structure_factor(int d) const {
@@ -779,7 +832,10 @@ private:
   }
   const std::shared_ptr<NonlinearSigmaAction> action;
   const unsigned int n_updates, B;
-  const bool with_structure;
+  const bool with_structure, with_correlator;
+  unsigned int n_out = 0;
+  std::unique_ptr<DeviceVector> corr;  // double [batch][n_out]: the improved C of the draw at hand, summed over its updates
+  std::vector<double> chain_C;         // per chain and lag, since reset_improved(): sums over the updates of the improved C
   std::shared_ptr<SampleState> phi_state_cur;
   std::shared_ptr<DeviceBuffer> work;
   size_t work_bytes = 0;

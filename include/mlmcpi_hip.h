@@ -655,6 +655,36 @@ int mlmcpi_sigma_level_sw_structure_workspace_bytes(const mlmcpi_sigma_level *le
 int mlmcpi_sigma_level_sw_structure_draw(const mlmcpi_sigma_level *level, double *d_state, uint32_t B, uint32_t n_updates,
                                          uint64_t seed, uint32_t chain0, uint32_t update0, uint32_t *d_flipped, uint32_t *d_clusters,
                                          double *d_improved, double *d_structure, void *d_work, size_t work_bytes, void *stream);
+/* The same update with the cluster-improved time-slice correlator: the state, d_flipped, d_clusters and
+ * d_improved are the bits of mlmcpi_sigma_level_sw_draw and no further random number is drawn; rotated = 0 serves the plain
+ * lattice.  Positions x_d(l) and directions are those of mlmcpi_sigma_level_sw_structure_draw and mlmcpi_sigma_level_correlator.
+ * With a_l = r . sigma_l of the field BEFORE the update and C the update's clusters,
+ *   P_C,d(i)     = sum_{l in C, x_d(l) = i} a_l
+ *   C_d^imp(tau) = (3 / n) sum_C sum_{i < M_d} P_C,d(i) P_C,d((i + tau) mod M_d),   tau = 0 .. M_d / 2,
+ * the mean over the coins of 3 (r . S'_i)(r . S'_{i + tau}) / n summed over i (cross terms of two clusters vanish) and over r the
+ * mean of C_d(tau): an unbiased estimator of the plain correlator whose noise falls with the signal.  Per update, with the
+ * weights w of mlmcpi_sigma_level_correlator, sum_tau w C_d^imp = the improved chi_m and sum_tau w C_d^imp cos(2 pi tau / M_d) =
+ * the improved F_d, up to the roundings below.
+ * d_corr (double [B][n_out], n_out = (Mt/2 + 1) + (Mx/2 + 1), C_t first: the layout of mlmcpi_sigma_level_correlator) is ADDED to
+ * update by update.  Arithmetic: P is summed as q(a) = llrint(a 2^32) by integer atomics into a table keyed by (root, slice); a
+ * pair of occupied slices contributes llrint(((double)P (double)P') 2^(s - 64)) to a 64-bit accumulator per (chain, d, tau); at
+ * the end of the update d_corr += ((double)acc 2^-s) (3.0 / n).  s = min(32, 62 - ceil(log2(n n_slice))), n_slice = n / min(Mt, Mx)
+ * the vertices of the larger slice: sum_i sum_C |P(i)| |P(i + tau)| <= n n_slice, so the accumulator stays inside 63 bits.  A
+ * cluster that occupies w slices of a direction is paired at tau <= min(M_d / 2, w - 1) only: a link changes the slice index by at
+ * most 1, so larger lags hold nothing.  Every sum is an integer sum, so d_corr is the same bits under every launch plan, tile,
+ * batch split, chain0 and call split (4 = 1 + 3).  MLMCPI_SIGMA_SW_PLAN and MLMCPI_SIGMA_SW_TILE govern it; the chain plan runs
+ * one update per launch and keeps its bound.
+ * Workspace: that of mlmcpi_sigma_level_sw_draw, then per chain and direction a table of 2^lg slots of 16 B, 2^lg the smallest
+ * power of two >= 2 n (32 .. 64 B per vertex, chain and direction), 4 B per vertex, chain and direction of occupied-slice counts
+ * and 8 B per chain and lag: 72 .. 136 B per vertex and chain more; work_bytes is what d_work holds.
+ * Errors as for mlmcpi_sigma_level_sw_structure_draw (a probe loop of the table that hit its cap, the capacity, sets the same
+ * status word: MLMCPI_ERR_HIP), and MLMCPI_ERR_INVALID, nothing launched, for NULL d_corr, work_bytes below
+ * _correlator_workspace_bytes, or odd extents. */
+int mlmcpi_sigma_level_sw_correlator_workspace_bytes(const mlmcpi_sigma_level *level, uint32_t B, size_t *bytes);
+int mlmcpi_sigma_level_sw_correlator_draw(const mlmcpi_sigma_level *level, double *d_state, uint32_t B, uint32_t n_updates,
+                                          uint64_t seed, uint32_t chain0, uint32_t update0, uint32_t *d_flipped, uint32_t *d_clusters,
+                                          double *d_improved, double *d_corr /* [B][n_out], ADDED to, update by update */,
+                                          void *d_work, size_t work_bytes, void *stream);
 /* NonlinearSigmaConditionedFineAction (nonlinearsigmaconditionedfineaction.cc:7-44) on a level.  Every fine-only vertex (the
  * (i + j) odd ones of an unrotated level, the O plane of a rotated one) has coarse neighbours only, so the fill is a product of
  * independent heat-bath laws and _evaluate is minus the log of its density.

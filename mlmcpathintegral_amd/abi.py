@@ -188,6 +188,8 @@ SIGNATURES = {
     "mlmcpi_sigma_level_sw_draw": (_i, [_SL, _vp, _u32, _u32, _u64, _u32, _u32, _vp, _vp, _vp, _vp, _vp]),
     "mlmcpi_sigma_level_sw_structure_workspace_bytes": (_i, [_SL, _u32, C.POINTER(_sz)]),
     "mlmcpi_sigma_level_sw_structure_draw": (_i, [_SL, _vp, _u32, _u32, _u64, _u32, _u32, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "mlmcpi_sigma_level_sw_correlator_workspace_bytes": (_i, [_SL, _u32, C.POINTER(_sz)]),
+    "mlmcpi_sigma_level_sw_correlator_draw": (_i, [_SL, _vp, _u32, _u32, _u64, _u32, _u32, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
     "mlmcpi_sigma_cfa_fill": (_i, [_SL, _vp, _u32, _u64, _u32, _u32, _vp]),
     "mlmcpi_sigma_cfa_evaluate": (_i, [_SL, _vp, _u32, _vp, _vp]),
     "mlmcpi_sigma_twolevel_workspace_bytes": (_i, [_SL, _u32, C.POINTER(_sz)]),

@@ -78,6 +78,7 @@ struct LatticeGeometry {
   uint32_t Mt, Mx;
   static constexpr uint32_t kOwnedLinks = 2;
   static constexpr bool kStructure = false;
+  static constexpr bool kRoots = false;
   __host__ __device__ uint32_t nvert() const { return Mt * Mx; }
   __host__ __device__ uint32_t nowners() const { return Mt * Mx; }
   // the structure sums: the periodic extent of direction d (0: t, 1: x) and the position of vertex l along it, l at (i, j)
@@ -112,6 +113,7 @@ struct RotatedGeometry {
   uint32_t ht, hx, q;  // q = ht hx
   static constexpr uint32_t kOwnedLinks = 4;
   static constexpr bool kStructure = false;
+  static constexpr bool kRoots = false;
   explicit RotatedGeometry(const SigmaLevel &L) : ht(L.ht), hx(L.hx), q(L.q) {}
   __host__ __device__ uint32_t nvert() const { return 2 * q; }
   __host__ __device__ uint32_t nowners() const { return q; }
@@ -149,6 +151,17 @@ struct WithStructure : G {
   double *structure, *weights;
   static constexpr bool kStructure = true;
   WithStructure(const G &g, double *s, double *w) : G(g), structure(s), weights(w) {}
+};
+
+// A geometry whose chain kernel also leaves every vertex's final root and q(a) of the field before the update in the workspace,
+// [B][N] each, where the tiled plan has them after its resolve launch (the improved correlator, below, reads them from there
+// under either plan).  The caller launches it with one update per launch.
+template <class G>
+struct WithRoots : G {
+  uint32_t *roots;
+  long long *qa;
+  static constexpr bool kRoots = true;
+  WithRoots(const G &g, uint32_t *r, long long *q) : G(g), roots(r), qa(q) {}
 };
 
 // ---- the union-find of the Swendsen-Wang labelling -------------------------------------------------------------------------
@@ -268,6 +281,86 @@ __device__ __forceinline__ void sw_add_combined(long long *slot, size_t stride, 
   }
   if ((todo >> lane) & 1ull)
     for (uint32_t k = 0; k < NV; ++k) __hip_atomic_fetch_add(slot + root + k * stride, v[k], __ATOMIC_RELAXED, SCOPE);
+}
+
+// ---- Swendsen-Wang: the slice table of the improved correlator ---------------------------------------------------
+// Per chain and direction an open-addressing table of 2^lg >= 2 N slots of 16 B: the key word ((root << 32) | (slice + 1); 0 =
+// empty) and the value word, P_C,d(slice) = the sum of q(a) over the vertices of cluster `root` in that slice.  Linear probing
+// from a multiplicative hash.  At most N keys of a direction exist, so the load stays <= 1/2 and an empty slot ends every probe;
+// all the same every probe loop carries the capacity as its cap and reports a cap that is hit.  Nothing is ever removed from a
+// table between its clear and its last reader, so a key, once stored, stays where it is.
+__device__ __forceinline__ unsigned long long sw_slice_key(uint32_t root, uint32_t slice) {
+  return ((unsigned long long)root << 32) | (unsigned long long)(slice + 1u);
+}
+
+__device__ __forceinline__ uint32_t sw_slice_hash(unsigned long long key, uint32_t lg) {
+  return (uint32_t)((key * 0x9E3779B97F4A7C15ull) >> (64u - lg));
+}
+
+// v added onto the value of `key`, which is inserted first where it is missing: a 64-bit compare-and-swap on the key word
+// claims an empty slot, the lane whose swap wins adds 1 to the occupied-slice count of its root.  A lane that loses a swap
+// looks at what the winner stored and goes on; it never waits for a store.
+__device__ __forceinline__ void sw_slice_add(unsigned long long *table, uint32_t lg, uint32_t *count, uint32_t root, uint32_t slice,
+                                             long long v, bool &capped) {
+  const unsigned long long key = sw_slice_key(root, slice);
+  const uint32_t cap = 1u << lg;
+  uint32_t slot = sw_slice_hash(key, lg);
+  for (uint32_t it = 0; it < cap; ++it) {
+    unsigned long long *kw = table + 2 * (size_t)slot;
+    unsigned long long seen = __hip_atomic_load(kw, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    bool created = false;
+    if (seen == 0ull) {
+      created = __hip_atomic_compare_exchange_strong(kw, &seen, key, __ATOMIC_RELAXED, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      if (created) seen = key;                             // else `seen` holds what the winner stored
+    }
+    if (seen == key) {
+      __hip_atomic_fetch_add((long long *)(kw + 1), v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      if (created) __hip_atomic_fetch_add(count + root, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      return;
+    }
+    slot = (slot + 1u) & (cap - 1u);
+  }
+  capped = true;
+}
+
+// the value of (root, slice) in a table nobody writes any more; 0 where the key is absent
+__device__ __forceinline__ long long sw_slice_lookup(const unsigned long long *table, uint32_t lg, uint32_t root, uint32_t slice,
+                                                     bool &capped) {
+  const unsigned long long key = sw_slice_key(root, slice);
+  const uint32_t cap = 1u << lg;
+  uint32_t slot = sw_slice_hash(key, lg);
+  for (uint32_t it = 0; it < cap; ++it) {
+    const unsigned long long seen = table[2 * (size_t)slot];
+    if (seen == key) return (long long)table[2 * (size_t)slot + 1];
+    if (seen == 0ull) return 0;
+    slot = (slot + 1u) & (cap - 1u);
+  }
+  capped = true;
+  return 0;
+}
+
+// v of every active lane added onto (root, slice), the lanes of a wave that share the key combined first as sw_add_combined
+// combines them (in direction x whole runs of lanes share one).  Every lane of the wave calls it: the combining rounds take
+// their trip count from ballots, the shuffles run with all lanes; the probe loop that follows has no ballot in it.
+__device__ __forceinline__ void sw_slice_add_combined(unsigned long long *table, uint32_t lg, uint32_t *count, uint32_t root, uint32_t slice,
+                                                      bool active, long long v, bool &capped) {
+  const uint32_t lane = threadIdx.x & (kWave - 1);
+  unsigned long long todo = __ballot(active);
+  bool mine = active;
+  for (uint32_t round = 0; round < kSwCombineRounds && todo; ++round) {
+    const int lead = __builtin_ctzll(todo);
+    const bool same = ((todo >> lane) & 1ull) && root == (uint32_t)__shfl((int)root, lead) && slice == (uint32_t)__shfl((int)slice, lead);
+    const unsigned long long m = __ballot(same);
+    todo &= ~m;
+    if ((uint32_t)__builtin_popcountll(m) < kSwCombineMin) continue;   // too few: each of them adds its own
+    long long s = same ? v : 0;
+    for (int off = kWave / 2; off > 0; off >>= 1) s += __shfl_xor(s, off);
+    if (same) {
+      mine = lane == (uint32_t)lead;
+      v = s;
+    }
+  }
+  if (mine) sw_slice_add(table, lg, count, root, slice, v, capped);
 }
 
 // one atomic per wave: the lanes of the wave that flipped a vertex (every lane of the wave calls it)

@@ -38,6 +38,12 @@
 // to structure[b][d], cos then sin.  The structure instances: sigma_sw_resolve_structure_kernel<Geometry>,
 // sigma_sw_finish_structure_kernel, sigma_sw_chain_kernel<WithStructure<Geometry>>; the instances of the plain draw are untouched.
 //
+// Improved correlator (mlmcpi_sigma_level_sw_correlator_draw): per cluster, direction and slice the sum of q(a)
+// in a hash table keyed by (root, slice), per cluster and lag the products of those sums in a 64-bit fixed-point accumulator,
+// added to corr[b][n_out] update by update.  The instances: sigma_sw_chain_kernel<WithRoots<Geometry>> (it leaves roots and q(a)
+// where the tiled plan has them), sigma_sw_slice_sum_kernel<Geometry>, sigma_sw_slice_pair_kernel, sigma_sw_slice_finish_kernel;
+// the instances of the plain and the structure draw are untouched.
+//
 // Labelling: the parent array and the union by atomic min of sigma_cluster_device.hpp (uf_*), where its termination argument
 // is written out.
 #include <mutex>
@@ -441,6 +447,10 @@ __global__ void __launch_bounds__(kClusterBlockThreads)
       // and the same sums as the plain instance, and d_improved and d_clusters are its bits.
       const uint32_t root = uf_find<Geometry::kStructure ? __HIP_MEMORY_SCOPE_WORKGROUP : kUfPlain>(parent, l, N, capped);
       if constexpr (Geometry::kStructure) __hip_atomic_store(parent + l, root, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+      if constexpr (Geometry::kRoots) {                    // the improved correlator reads both from the workspace
+        g.roots[(size_t)b * N + l] = root;
+        g.qa[(size_t)b * N + l] = sw_fixed(a[l]);
+      }
       if (improved) atomicAdd((unsigned long long *)(sum + root), (unsigned long long)sw_fixed(a[l]));
       if (!capped && sw_coin(key, root)) {
         phi[l] = reflected(sigma_of(phi[l]), a[l], r);
@@ -483,6 +493,105 @@ __global__ void __launch_bounds__(kClusterBlockThreads)
     if ((t & (kWave - 1)) == 0 && nflip) atomicAdd(flipped + b, nflip);
   }
   if (capped) atomicOr(status, 1u);
+}
+
+// ---- the improved correlator (mlmcpi_sigma_level_sw_correlator_draw) ------------------------------------------
+// After an update of either plan the workspace holds a label array whose walk ends at every vertex's final root (tiled: the
+// parents of launch 3; chain: the roots themselves) and q(a) of the field before the update.  Three launches follow, the same
+// for both plans and both geometries, and every sum in them is an integer sum: no order matters.
+//
+// (1) one lane per vertex: q(a) onto P_C,d(x_d(l)) of the chain's table of either direction.  Every lane stays to the end.
+template <class Geometry>
+__global__ void __launch_bounds__(kClusterThreads)
+    sigma_sw_slice_sum_kernel(Geometry g, uint32_t blocks, const uint32_t *label_all, const long long *qa_all, unsigned long long *table_all,
+                              uint32_t lg, uint32_t *count_all, uint32_t *status) {
+  const uint32_t N = g.nvert(), b = blockIdx.x / blocks, l = (blockIdx.x % blocks) * kClusterThreads + threadIdx.x;
+  const bool active = l < N;
+  bool capped = false;
+  uint32_t root = 0;
+  long long v = 0;
+  if (active) {
+    root = uf_find<kUfPlain>(label_all + (size_t)b * N, l, N, capped);
+    v = qa_all[(size_t)b * N + l];
+  }
+#pragma unroll
+  for (uint32_t d = 0; d < 2; ++d)
+    sw_slice_add_combined(table_all + ((size_t)(2 * b + d) << (lg + 1)), lg, count_all + (size_t)(2 * b + d) * N, root,
+                          active ? g.position(l, d) : 0u, active, v, capped);
+  if (capped) atomicOr(status, 1u);
+}
+
+// (2) one lane per slot of the table of (chain, direction), kSwPairBatches slots in turn: an occupied slot (C, i, P) meets
+// (C, (i + tau) mod M) for tau = 0 .. min(M / 2, w - 1), w the number of slices C occupies in that direction.  A larger lag finds
+// nothing: a link changes the slice index by at most 1 on either geometry, so the slices of a cluster are an arc of the ring,
+// and one that holds i and i + tau, tau <= M / 2, holds tau + 1 slices at least.  The term llrint(P P' 2^(s - 64)) (the product of
+// the two integers in double, then the exact scale) goes onto acc[chain][direction][tau]: the lanes of a wave are added up
+// first, the waves and batches of a workgroup meet in LDS for the lags below kSwPairLdsLags (where nearly every term falls:
+// without that stage every wave of a chain sends its atomics to the same few words), and the workgroup sends one atomic per
+// lag it holds; a lag beyond goes to the accumulator directly.  The loop over the lags runs to the wave's largest, so that its
+// ballots and shuffles see all lanes.  Integer sums throughout: no order matters.
+constexpr uint32_t kSwPairBatches = 16;    // slots a lane takes in turn
+constexpr uint32_t kSwPairLdsLags = 128;   // lags a workgroup sums in LDS before it adds to the accumulator
+
+__global__ void __launch_bounds__(kClusterThreads)
+    sigma_sw_slice_pair_kernel(const unsigned long long *table_all, uint32_t lg, const uint32_t *count_all, uint32_t N, uint32_t M0, uint32_t M1,
+                               uint32_t blocks, double scale, long long *acc_all, uint32_t *status) {
+  __shared__ long long part[kSwPairLdsLags];
+  const uint32_t bd = blockIdx.x / blocks, d = bd & 1u, slot0 = (blockIdx.x % blocks) * (kClusterThreads * kSwPairBatches) + threadIdx.x;
+  const uint32_t lane = threadIdx.x & (kWave - 1), M = d ? M1 : M0;
+  const unsigned long long *table = table_all + ((size_t)bd << (lg + 1));
+  long long *acc = acc_all + (size_t)(bd >> 1) * (M0 / 2 + M1 / 2 + 2) + (d ? M0 / 2 + 1 : 0);
+  bool capped = false;
+  if (threadIdx.x < kSwPairLdsLags) part[threadIdx.x] = 0;
+  __syncthreads();
+  for (uint32_t batch = 0; batch < kSwPairBatches; ++batch) {
+    const uint32_t slot = slot0 + batch * kClusterThreads;
+    const unsigned long long key = slot < (1u << lg) ? table[2 * (size_t)slot] : 0ull;
+    const uint32_t root = (uint32_t)(key >> 32), i = (uint32_t)key - 1u;
+    uint32_t ntau = 0;
+    long long Pq = 0;
+    if (key) {
+      const uint32_t w = count_all[(size_t)bd * N + root];
+      ntau = (w - 1u < M / 2 ? w - 1u : M / 2) + 1u;
+      Pq = (long long)table[2 * (size_t)slot + 1];
+    }
+    const double P = (double)Pq;
+    uint32_t tmax = ntau;
+    for (int off = kWave / 2; off > 0; off >>= 1) {
+      const uint32_t o = (uint32_t)__shfl_xor((int)tmax, off);
+      tmax = o > tmax ? o : tmax;
+    }
+    for (uint32_t tau = 0; tau < tmax; ++tau) {
+      long long term = 0;
+      if (tau < ntau) {
+        uint32_t k = i + tau;
+        if (k >= M) k -= M;
+        const long long Q = tau ? sw_slice_lookup(table, lg, root, k, capped) : Pq;
+        term = llrint((P * (double)Q) * scale);
+      }
+      const unsigned long long m = __ballot(term != 0);
+      if (!m) continue;
+      if (__builtin_popcountll(m) > 1) {
+        for (int off = kWave / 2; off > 0; off >>= 1) term += __shfl_xor(term, off);
+        if (lane != (uint32_t)__builtin_ctzll(m)) term = 0;
+      }
+      if (term) {
+        if (tau < kSwPairLdsLags) __hip_atomic_fetch_add(part + tau, term, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+        else __hip_atomic_fetch_add(acc + tau, term, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      }
+    }
+  }
+  __syncthreads();
+  if (threadIdx.x < kSwPairLdsLags && threadIdx.x <= M / 2 && part[threadIdx.x])
+    __hip_atomic_fetch_add(acc + threadIdx.x, part[threadIdx.x], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  if (capped) atomicOr(status, 1u);
+}
+
+// (3) one lane per (chain, lag): corr[b][k] += (acc 2^-s) 3 / N
+__global__ void __launch_bounds__(kClusterThreads)
+    sigma_sw_slice_finish_kernel(const long long *acc_all, uint32_t total, double inv_scale, double three_over_n, double *corr) {
+  const uint32_t k = blockIdx.x * kClusterThreads + threadIdx.x;
+  if (k < total) corr[k] += ((double)acc_all[k] * inv_scale) * three_over_n;
 }
 
 namespace {
@@ -551,6 +660,10 @@ int sw_init_attrs() {
                                      hipFuncAttributeMaxDynamicSharedMemorySize, kSwChainMaxN * kSwChainBytesPerVertex));
   MLMCPI_HIP_TRY(hipFuncSetAttribute((const void *)sigma_sw_chain_kernel<WithStructure<RotatedGeometry>>,
                                      hipFuncAttributeMaxDynamicSharedMemorySize, kSwChainMaxN * kSwChainBytesPerVertex));
+  MLMCPI_HIP_TRY(hipFuncSetAttribute((const void *)sigma_sw_chain_kernel<WithRoots<LatticeGeometry>>, hipFuncAttributeMaxDynamicSharedMemorySize,
+                                     kSwChainMaxN * kSwChainBytesPerVertex));
+  MLMCPI_HIP_TRY(hipFuncSetAttribute((const void *)sigma_sw_chain_kernel<WithRoots<RotatedGeometry>>, hipFuncAttributeMaxDynamicSharedMemorySize,
+                                     kSwChainMaxN * kSwChainBytesPerVertex));
   MLMCPI_HIP_TRY(hipFuncSetAttribute((const void *)sigma_rot_sw_bond_label_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
                                      (int)sw_rot_tile_lds(kSwMaxTile, kSwMaxTile)));
   g_sw_attr_set[dev] = true;
@@ -584,6 +697,59 @@ size_t sw_workspace(const Geometry &g, uint32_t B, bool structure = false) {
          sw_section_bits(g.nowners(), B);
 }
 
+// The improved correlator's part of the workspace, behind that of the plain draw: the tables [B][2][2^lg] of 16 B slots, the
+// occupied-slice counts [B][2][N] uint32 and the accumulators [B][n_out] int64, contiguous, cleared by one memset per update.
+// lg: the smallest with 2^lg >= 2 N.  s: the fixed-point scale of the accumulators, min(32, 62 - ceil(log2(N N_slice))) with
+// N_slice = N / min(M_0, M_1) the vertices of the larger slice: sum_i sum_C |P(i)| |P(i + tau)| <= sum_i N_slice sum_C n_C(i)
+// = N N_slice (|a| <= 1, n_C(i) the vertices of C in slice i), so |acc| <= 2^62 + N / 2 with the roundings of the terms.
+struct SwCorr {
+  double *corr;
+  uint32_t lg, n_out, s;
+  size_t table_bytes, count_bytes, acc_bytes;
+  size_t bytes() const { return table_bytes + count_bytes + acc_bytes; }
+};
+
+template <class Geometry>
+SwCorr sw_corr(const Geometry &g, uint32_t B, double *d_corr) {
+  SwCorr c{};
+  const uint32_t N = g.nvert(), M0 = g.extent(0), M1 = g.extent(1);
+  c.corr = d_corr;
+  c.lg = 1;
+  while ((1ull << c.lg) < 2ull * N) ++c.lg;
+  c.n_out = M0 / 2 + M1 / 2 + 2;
+  const uint64_t bound = (uint64_t)N * (N / (M0 < M1 ? M0 : M1));
+  uint32_t lb = 0;
+  while ((1ull << lb) < bound) ++lb;
+  c.s = 62 - lb < 32 ? 62 - lb : 32;
+  c.table_bytes = align256(((size_t)2 * B << c.lg) * 16);
+  c.count_bytes = align256((size_t)2 * B * N * sizeof(uint32_t));
+  c.acc_bytes = align256((size_t)B * c.n_out * sizeof(long long));
+  return c;
+}
+
+// the three launches of the improved correlator for the update whose roots and q(a) the workspace holds
+template <class Geometry>
+int sw_corr_update(const Geometry &g, const SwPlan &p, const SwCorr &c, uint32_t B, const uint32_t *label, const long long *qa, char *extra,
+                   uint32_t *status, hipStream_t st) {
+  const uint32_t N = g.nvert();
+  unsigned long long *table = (unsigned long long *)extra;
+  uint32_t *count = (uint32_t *)(extra + c.table_bytes);
+  long long *acc = (long long *)(extra + c.table_bytes + c.count_bytes);
+  MLMCPI_HIP_TRY(hipMemsetAsync(extra, 0, c.bytes(), st));
+  hipLaunchKernelGGL(sigma_sw_slice_sum_kernel<Geometry>, dim3(B * p.resolve_blocks), dim3(kClusterThreads), 0, st, g, p.resolve_blocks, label,
+                     qa, table, c.lg, count, status);
+  MLMCPI_LAUNCH_CHECK("sigma_sw_slice_sum_kernel");
+  const uint32_t pair_blocks = ((1u << c.lg) + kClusterThreads * kSwPairBatches - 1) / (kClusterThreads * kSwPairBatches);
+  hipLaunchKernelGGL(sigma_sw_slice_pair_kernel, dim3(2 * B * pair_blocks), dim3(kClusterThreads), 0, st, (const unsigned long long *)table,
+                     c.lg, (const uint32_t *)count, N, g.extent(0), g.extent(1), pair_blocks, ldexp(1.0, (int)c.s - 64), acc, status);
+  MLMCPI_LAUNCH_CHECK("sigma_sw_slice_pair_kernel");
+  const uint32_t total = B * c.n_out;
+  hipLaunchKernelGGL(sigma_sw_slice_finish_kernel, dim3((total + kClusterThreads - 1) / kClusterThreads), dim3(kClusterThreads), 0, st,
+                     (const long long *)acc, total, ldexp(1.0, -(int)c.s), 3.0 / (double)N, c.corr);
+  MLMCPI_LAUNCH_CHECK("sigma_sw_slice_finish_kernel");
+  return MLMCPI_OK;
+}
+
 // launches 1 and 2 of the tiled plan, one pair per geometry: the lattice's take its extents, the rotated level's the level
 int sw_front_end(const LatticeGeometry &g, const SwPlan &p, const double2 *phi, double beta2, const RngKey &key, uint32_t B, uint32_t *label,
                  uint8_t *bits, long long *qa, long long *sum, uint32_t *status, hipStream_t st) {
@@ -614,7 +780,7 @@ int sw_front_end(const SigmaLevel &L, const SwPlan &p, const double2 *phi, doubl
 template <class Geometry, class Front>
 int sw_draw(const Geometry &g, const Front &front, double beta, double *d_phi, uint32_t B, uint32_t n_updates, uint64_t seed, uint32_t chain0, uint32_t update0,
             uint32_t *d_flipped, uint32_t *d_clusters, double *d_improved, double *d_structure, void *d_work, void *stream, const char *what,
-            const char *where, const char *chain_kernel) {
+            const char *where, const char *chain_kernel, double *d_corr = nullptr) {
   const uint32_t N = g.nvert();
   const SwPlan p = sw_plan(g, B, tuning());
   if (!p.ok)
@@ -622,6 +788,11 @@ int sw_draw(const Geometry &g, const Front &front, double beta, double *d_phi, u
                 kSwChainMaxN, where, N);
   const uint64_t widest = (uint64_t)B * (p.ntx * p.nty > p.resolve_blocks ? p.ntx * p.nty : p.resolve_blocks);
   MLMCPI_REQUIRE(p.chain || (widest < (1ull << 31) && (uint64_t)B * p.merge_blocks < (1ull << 31)), "too many workgroups for one launch: split the batch");
+  // d_corr != NULL (never with d_structure): the improved correlator's launches after every update, its workspace behind the plain draw's
+  const SwCorr corr = sw_corr(g, B, d_corr);
+  MLMCPI_REQUIRE(!d_corr || ((uint64_t)B * p.resolve_blocks < (1ull << 31) && ((uint64_t)2 * B << corr.lg) / kClusterThreads < (1ull << 31) &&
+                             (uint64_t)B * corr.n_out < (1ull << 31)),
+                 "too many workgroups for one launch: split the batch");
   if (n_updates == 0) return MLMCPI_OK;
   if (int rc = sw_init_attrs()) return rc;
   char *w = (char *)d_work;
@@ -635,8 +806,18 @@ int sw_draw(const Geometry &g, const Front &front, double beta, double *d_phi, u
   MLMCPI_REQUIRE(!d_structure || (uint64_t)3 * N >= (uint64_t)g.extent(0) + g.extent(1), "the table of weights does not fit the workspace");
   const hipStream_t st = as_stream(stream);
   const double beta2 = 2.0 * beta;
+  char *extra = w + sw_workspace(g, B);
   MLMCPI_HIP_TRY(hipMemsetAsync(status, 0, sizeof(uint32_t), st));
-  if (p.chain && d_structure) {
+  if (p.chain && d_corr) {
+    // one update per launch (the same bits as one launch of all: the call-split property), its roots and q(a) left in the workspace
+    for (uint32_t k = 0; k < n_updates; ++k) {
+      hipLaunchKernelGGL(sigma_sw_chain_kernel<WithRoots<Geometry>>, dim3(B), dim3(kClusterBlockThreads), p.lds_bytes, st, (double2 *)d_phi,
+                         WithRoots<Geometry>(g, label, qa), beta2, 1u, make_key(seed, chain0, update0 + k), d_flipped, d_clusters, d_improved,
+                         status);
+      MLMCPI_LAUNCH_CHECK(chain_kernel);
+      if (int rc = sw_corr_update(g, p, corr, B, label, qa, extra, status, st)) return rc;
+    }
+  } else if (p.chain && d_structure) {
     hipLaunchKernelGGL(sigma_sw_chain_kernel<WithStructure<Geometry>>, dim3(B), dim3(kClusterBlockThreads), p.lds_bytes, st, (double2 *)d_phi,
                        WithStructure<Geometry>(g, d_structure, sw_chain_table(d_work, N, B)), beta2, n_updates, make_key(seed, chain0, update0), d_flipped, d_clusters,
                        d_improved, status);
@@ -670,6 +851,8 @@ int sw_draw(const Geometry &g, const Front &front, double beta, double *d_phi, u
         hipLaunchKernelGGL(sigma_sw_finish_kernel, dim3(B), dim3(kClusterBlockThreads), 0, st, label, sum, N, d_improved, d_clusters);
         MLMCPI_LAUNCH_CHECK("sigma_sw_finish_kernel");
       }
+      if (d_corr)
+        if (int rc = sw_corr_update(g, p, corr, B, label, qa, extra, status, st)) return rc;
     }
   }
   // a find or union loop that ran into its cap (it cannot, by the argument of sigma_cluster_device.hpp): an error, never a hang
@@ -761,6 +944,41 @@ int mlmcpi_sigma_level_sw_structure_draw(const mlmcpi_sigma_level *level, double
   const SigmaLevel L = make_level(*level);
   return sw_draw(RotatedGeometry(L), L, level->beta, d_state, B, n_updates, seed, chain0, update0, d_flipped, d_clusters, d_improved,
                  d_structure, d_work, stream, what, "level", "sigma_rot_sw_chain_kernel (structure)");
+}
+
+int mlmcpi_sigma_level_sw_correlator_workspace_bytes(const mlmcpi_sigma_level *level, uint32_t B, size_t *bytes) {
+  if (int rc = check_cluster_level(level)) return rc;
+  MLMCPI_REQUIRE(bytes && B > 0, "bad arguments");
+  if (!level->rotated) {
+    const mlmcpi_lattice_action act = level_as_lattice(level);
+    if (int rc = sw_check(&act, "mlmcpi_sigma_level_sw_correlator_workspace_bytes")) return rc;
+    const LatticeGeometry g{act.Mt, act.Mx};
+    *bytes = sw_workspace(g, B) + sw_corr(g, B, nullptr).bytes();
+  } else {
+    const RotatedGeometry g(make_level(*level));
+    *bytes = sw_workspace(g, B) + sw_corr(g, B, nullptr).bytes();
+  }
+  return MLMCPI_OK;
+}
+
+int mlmcpi_sigma_level_sw_correlator_draw(const mlmcpi_sigma_level *level, double *d_state, uint32_t B, uint32_t n_updates, uint64_t seed,
+                                          uint32_t chain0, uint32_t update0, uint32_t *d_flipped, uint32_t *d_clusters, double *d_improved,
+                                          double *d_corr, void *d_work, size_t work_bytes, void *stream) {
+  size_t need = 0;
+  if (int rc = mlmcpi_sigma_level_sw_correlator_workspace_bytes(level, B ? B : 1, &need)) return rc;
+  MLMCPI_REQUIRE(d_state && d_work && B > 0, "bad arguments");
+  MLMCPI_REQUIRE(d_corr, "d_corr is NULL: mlmcpi_sigma_level_sw_draw is the entry point without the improved correlator");
+  MLMCPI_REQUIRE(work_bytes >= need, "the workspace is smaller than mlmcpi_sigma_level_sw_correlator_workspace_bytes asks for");
+  MLMCPI_REQUIRE((uint64_t)update0 + n_updates <= 0xFFFFFFFFull, "update counter overflows");
+  const char *what = "mlmcpi_sigma_level_sw_correlator_draw";
+  if (!level->rotated) {
+    const LatticeGeometry g{level->Mt, level->Mx};
+    return sw_draw(g, g, level->beta, d_state, B, n_updates, seed, chain0, update0, d_flipped, d_clusters, d_improved, nullptr, d_work,
+                   stream, what, "level", "sigma_sw_chain_kernel (roots)", d_corr);
+  }
+  const SigmaLevel L = make_level(*level);
+  return sw_draw(RotatedGeometry(L), L, level->beta, d_state, B, n_updates, seed, chain0, update0, d_flipped, d_clusters, d_improved,
+                 nullptr, d_work, stream, what, "level", "sigma_rot_sw_chain_kernel (roots)", d_corr);
 }
 
 }  // extern "C"

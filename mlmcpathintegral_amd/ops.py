@@ -536,16 +536,29 @@ def sigma_level_sw_structure_workspace(level, B, device="cuda"):
     return torch.empty(nbytes.value, dtype=torch.uint8, device=device)
 
 
-def sigma_level_sw_draw(level, x, n_updates, seed, chain0, update0, outputs=True, work=None, structure=False):
+def sigma_level_sw_correlator_workspace(level, B, device="cuda"):
+    """workspace of sigma_level_sw_draw(..., correlator=True) for B chains (uint8 tensor): the plain draw's plus the slice tables"""
+    nbytes = C.c_size_t(0)
+    abi.call("mlmcpi_sigma_level_sw_correlator_workspace_bytes", C.byref(level), B, C.byref(nbytes))
+    return torch.empty(nbytes.value, dtype=torch.uint8, device=device)
+
+
+def sigma_level_sw_draw(level, x, n_updates, seed, chain0, update0, outputs=True, work=None, structure=False, correlator=False):
     """Swendsen-Wang multi-cluster updates on a level, rotated or not (mlmcpi_sigma_level_sw_draw): n_updates updates of every
     chain of x [B, 2 n], in place, update counters update0 + k; returns, per chain and summed over this call's updates, (flipped
     vertices int32 [B], clusters int32 [B], improved chi_m float64 [B]), or None with outputs=False.  structure=True
     (mlmcpi_sigma_level_sw_structure_draw; `work` from sigma_level_sw_structure_workspace): the same state and outputs and a fourth
-    tensor, float64 [B, 2], the improved structure factors (F_t, F_x) at the lowest momentum summed over this call's updates"""
+    tensor, float64 [B, 2], the improved structure factors (F_t, F_x) at the lowest momentum summed over this call's updates.
+    correlator=True (mlmcpi_sigma_level_sw_correlator_draw; `work` from sigma_level_sw_correlator_workspace; exclusive with
+    structure=True): the same state and outputs and a fourth tensor, float64 [B, n_out] in the layout of sigma_level_correlator,
+    the cluster-improved time-slice correlators C_t then C_x summed over this call's updates"""
     _check_state(x, sigma_level_size(level))
     B = x.shape[0]
+    if structure and correlator:
+        raise ValueError("structure=True and correlator=True are exclusive: F and xi_2 follow from the improved correlator")
     if work is None:
-        work = (sigma_level_sw_structure_workspace if structure else sigma_level_sw_workspace)(level, B, x.device)
+        work = (sigma_level_sw_correlator_workspace if correlator else
+                sigma_level_sw_structure_workspace if structure else sigma_level_sw_workspace)(level, B, x.device)
     flipped = clusters = improved = None
     if outputs:
         flipped = torch.zeros(B, dtype=torch.int32, device=x.device)
@@ -558,6 +571,13 @@ def sigma_level_sw_draw(level, x, n_updates, seed, chain0, update0, outputs=True
         abi.call("mlmcpi_sigma_level_sw_structure_draw", C.byref(level), _p(x), B, n_updates, seed, chain0, update0, _p(flipped),
                  _p(clusters), _p(improved), _p(factors), _p(work), work.numel(), _stream())
         return flipped, clusters, improved, factors
+    if correlator:
+        if not outputs:
+            raise ValueError("correlator=True returns outputs")
+        corr = torch.zeros(B, sigma_level_correlator_size(level), dtype=torch.float64, device=x.device)
+        abi.call("mlmcpi_sigma_level_sw_correlator_draw", C.byref(level), _p(x), B, n_updates, seed, chain0, update0, _p(flipped),
+                 _p(clusters), _p(improved), _p(corr), _p(work), work.numel(), _stream())
+        return flipped, clusters, improved, corr
     abi.call("mlmcpi_sigma_level_sw_draw", C.byref(level), _p(x), B, n_updates, seed, chain0, update0, _p(flipped), _p(clusters),
              _p(improved), _p(work), _stream())
     return (flipped, clusters, improved) if outputs else None
