@@ -244,6 +244,7 @@ int main(int argc, char **argv) {
     if (name == "wolff" || name == "levelwolff") {  // levelwolff: on whatever level the hierarchy hands it (checked above)
       ClusterParameters cp;
       cp.n_burnin = (unsigned)num("n_burnin"); cp.n_updates = (unsigned)num("n_updates"); cp.batch = batch;
+      cp.improved = cp.structure = cp.correlator = name == "wolff" && wants_correlator;  // the single cluster's estimators
       return std::make_shared<WolffClusterSamplerFactory>(cp);
     }
     if (name == "swendsenwang" || name == "levelsw") {  // levelsw: on whatever level the hierarchy hands it (checked above)
@@ -411,22 +412,26 @@ int main(int argc, char **argv) {
       else std::cout << " (one chain: no jackknife error)";
       std::cout << ", xi_2 / M = " << xi.value / (d ? Mx : Mt) << std::endl;
     }
-    // --sampler swendsenwang: the same two numbers from the cluster sums of the updates (the field BEFORE each update)
+    // --sampler swendsenwang or wolff: the same two numbers from the cluster sums of the updates (the field BEFORE each update);
+    // the Wolff sampler's improved chi_m first (the Swendsen-Wang sampler prints its own with its statistics)
     const auto sw = std::dynamic_pointer_cast<SwendsenWangSampler>(mc.get_sampler());
-    if (sw && sw->has_structure()) {
+    const auto wolff = std::dynamic_pointer_cast<WolffClusterSampler>(mc.get_sampler());
+    if (wolff && wolff->has_improved())
+      std::cout << " improved chi_m = " << wolff->improved_mean() << " +/- " << wolff->improved_error() << std::endl;
+    if ((sw && sw->has_structure()) || (wolff && wolff->has_structure())) {
       for (int d = 0; d < 2; ++d) {
-        const SwendsenWangSampler::Estimate F = sw->improved_structure_factor(d);
+        const ClusterImprovedSums::Estimate F = sw ? sw->improved_structure_factor(d) : wolff->improved_structure_factor(d);
         std::cout << " improved F (" << (d ? "x" : "t") << ") = " << F.value << " +/- " << F.error << std::endl;
       }
       for (int d = 0; d < 2; ++d) {
-        const SwendsenWangSampler::Estimate xi = sw->improved_xi(d);
+        const ClusterImprovedSums::Estimate xi = sw ? sw->improved_xi(d) : wolff->improved_xi(d);
         std::cout << " improved xi_2 (" << (d ? "x" : "t") << ") = " << xi.value << " +/- " << xi.error
                   << ", xi_2 / M = " << xi.value / (d ? Mx : Mt) << std::endl;
       }
     }
     // and the cluster-improved correlators themselves, per lag, in the format of the plain block
-    if (sw && sw->has_correlator()) {
-      const SwendsenWangSampler::CorrelatorEstimate ie = sw->improved_correlator();
+    if ((sw && sw->has_correlator()) || (wolff && wolff->has_correlator())) {
+      const ClusterImprovedSums::CorrelatorEstimate ie = sw ? sw->improved_correlator() : wolff->improved_correlator();
       const std::vector<double> It = correlator->direction(ie.mean, 0), Ix = correlator->direction(ie.mean, 1);
       const std::vector<double> IEt = correlator->direction(ie.error, 0), IEx = correlator->direction(ie.error, 1);
       for (unsigned tau = 0; tau < std::max(nt, nx); ++tau) {

@@ -609,6 +609,40 @@ int mlmcpi_sigma_level_cluster_workspace_bytes(const mlmcpi_sigma_level *level, 
 int mlmcpi_sigma_level_cluster_draw(const mlmcpi_sigma_level *level, double *d_state, uint32_t B, uint32_t n_updates,
                                     uint64_t seed, uint32_t chain0, uint32_t update0, uint32_t *d_cluster_sites,
                                     void *d_work, void *stream);
+/* The same update with the improved estimators of the single cluster: the state and d_cluster_sites are the
+ * bits of mlmcpi_sigma_level_cluster_draw and no further random number is drawn; rotated = 0 serves the plain lattice.
+ * Positions x_d(l), directions (d = 0 is t, d = 1 is x), n_out and its layout are those of mlmcpi_sigma_level_correlator.  With C
+ * the cluster of one update, |C| its size and a_l = r . sigma_l of the field BEFORE the update,
+ *   P_d(i)       = sum_{l in C, x_d(l) = i} a_l,   A = sum_{l in C} a_l
+ *   chi^W        = 3 A^2 / |C|
+ *   F_d^W        = 3 (Ac_d^2 + As_d^2) / |C|,   Ac_d, As_d = sum_i P_d(i) (cos, sin)(2 pi i / M_d)
+ *   C_d^W(tau)   = (3 / |C|) sum_{i < M_d} P_d(i) P_d((i + tau) mod M_d),   tau = 0 .. M_d / 2.
+ * The seed vertex is uniform and independent of the bonds, so the mean over seeds of f(C) / |C| is (1 / n) sum_C f(C): in
+ * expectation these are the Swendsen-Wang improved estimators of the same bonds, unbiased for chi_m, F_d and C_d(tau).  Per
+ * update, with the weights w of mlmcpi_sigma_level_correlator, sum_tau w C_d^W = chi^W and sum_tau w C_d^W cos(2 pi tau / M_d) =
+ * F_d^W up to the roundings below.
+ * Arithmetic.  Every member adds q(a) = llrint(a 2^32) to the slice table of its chain (M_t + M_x 64-bit integers in the
+ * workspace) by integer atomics.  Then A = sum_i P_0(i), an exact integer, and d_improved[b] += (x x) (3.0 / |C|), x = (double)A
+ * 2^-32.  Ac_d = sum_i llrint((double)P_d(i) w^c_d(i)), As_d with w^s_d, (w^s, w^c)(i) = sincospi(2.0 * i / M_d) from the device
+ * function the correlator kernels call (an extent of 2 gives exactly 0 and +-1); d_structure[b][d] += (xc xc) (3.0 / |C|), then
+ * += (xs xs) (3.0 / |C|).  A pair of occupied slices contributes llrint(((double)P (double)P') 2^(s - 64)) to a 64-bit accumulator
+ * per (d, tau), s = min(32, 62 - ceil(log2(n n_slice))), n_slice = n / min(Mt, Mx) (one cluster's sum of |P| |P'| is at most n
+ * n_slice); d_corr[b][tau] += ((double)acc 2^-s) (3.0 / |C|).  With w_d slices that hold a member the lags tau <= min(M_d / 2,
+ * w_d - 1) are formed: a link moves the slice index by at most 1, so larger lags pair nothing.  No fp contraction; every sum is an integer
+ * sum, so all outputs are the same bits under every launch plan (MLMCPI_SIGMA_CLUSTER_TEAM / _BITMAP govern this draw too),
+ * batch split, chain0 and call split (10 = 5 + 5).
+ * d_improved (double [B]), d_structure (double [B][2]: F_t, F_x; may be NULL) and d_corr (double [B][n_out]; may be NULL) are
+ * ADDED to, update by update; d_cluster_sites as above.  Workspace: that of mlmcpi_sigma_level_cluster_draw, then per chain 28 B
+ * per slice (table 8, occupied-slice list 4, weights 16) and 8 B per lag and sum; its content at entry is ignored; work_bytes is what d_work
+ * holds.  MLMCPI_ERR_INVALID, nothing launched: NULL d_improved, work_bytes below _improved_workspace_bytes, and whatever
+ * mlmcpi_sigma_level_cluster_draw refuses. */
+int mlmcpi_sigma_level_cluster_improved_workspace_bytes(const mlmcpi_sigma_level *level, uint32_t B, size_t *bytes);
+int mlmcpi_sigma_level_cluster_improved_draw(const mlmcpi_sigma_level *level, double *d_state, uint32_t B, uint32_t n_updates,
+                                             uint64_t seed, uint32_t chain0, uint32_t update0,
+                                             uint32_t *d_cluster_sites /* may be NULL */, double *d_improved /* [B] */,
+                                             double *d_structure /* [B][2], may be NULL */,
+                                             double *d_corr /* [B][n_out], may be NULL */, void *d_work, size_t work_bytes,
+                                             void *stream);
 /* The Swendsen-Wang multi-cluster update on a level (sigma_sw.hip): n_updates updates of every chain of
  * d_state [B][2 n], in place.  Unrotated: mlmcpi_sigma_sw_* on (Mt, Mx, beta), the same bits and the same workspace size.
  * Rotated: n = Mt Mx / 2 vertices, plane E then plane O of ht x hx = Mt/2 x Mx/2 each, index p ht hx + ht b + a; the links are

@@ -184,6 +184,8 @@ SIGNATURES = {
     "mlmcpi_sigma_level_correlator": (_i, [_SL, _vp, _u32, _vp, _vp, _vp, _sz, _vp]),
     "mlmcpi_sigma_level_cluster_workspace_bytes": (_i, [_SL, _u32, C.POINTER(_sz)]),
     "mlmcpi_sigma_level_cluster_draw": (_i, [_SL, _vp, _u32, _u32, _u64, _u32, _u32, _vp, _vp, _vp]),
+    "mlmcpi_sigma_level_cluster_improved_workspace_bytes": (_i, [_SL, _u32, C.POINTER(_sz)]),
+    "mlmcpi_sigma_level_cluster_improved_draw": (_i, [_SL, _vp, _u32, _u32, _u64, _u32, _u32, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
     "mlmcpi_sigma_level_sw_workspace_bytes": (_i, [_SL, _u32, C.POINTER(_sz)]),
     "mlmcpi_sigma_level_sw_draw": (_i, [_SL, _vp, _u32, _u32, _u64, _u32, _u32, _vp, _vp, _vp, _vp, _vp]),
     "mlmcpi_sigma_level_sw_structure_workspace_bytes": (_i, [_SL, _u32, C.POINTER(_sz)]),

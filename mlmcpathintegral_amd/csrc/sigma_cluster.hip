@@ -271,6 +271,158 @@ __global__ void __launch_bounds__(BLOCK ? kClusterBlockThreads : kClusterThreads
   if (cluster_sites && lane == 0) cluster_sites[b] += total;
 }
 
+// ---- the improved draw (mlmcpi_sigma_level_cluster_improved_draw) ------------------------------------------
+// What the improved kernel asks of a geometry: the neighbour across direction d of vertex x, the name of that link for its
+// uniform (Philox site and sub-counter, and which of the call's two uniforms), and the slices of a vertex.  The two kernels
+// above spell the same arithmetic out; they are not rebuilt on these, so that their instructions stay what they were.
+struct WolffLatticeTasks {
+  LatticeGeometry g;
+  __device__ __forceinline__ uint32_t nvert() const { return g.nvert(); }
+  __device__ __forceinline__ uint32_t position(uint32_t x, uint32_t d) const { return g.position(x, d); }
+  __device__ __forceinline__ uint32_t neighbour(uint32_t x, uint32_t d, uint32_t &site, uint32_t &sub, bool &second) const {
+    const uint32_t Mt = g.Mt, Mx = g.Mx, i = x % Mt, j = x / Mt;
+    uint32_t y;
+    if (d == 0) y = i + 1 == Mt ? x - i : x + 1;
+    else if (d == 1) y = i == 0 ? x + (Mt - 1) : x - 1;
+    else if (d == 2) y = j + 1 == Mx ? i : x + Mt;
+    else y = j == 0 ? x + (Mx - 1) * Mt : x - Mt;
+    site = (d & 1u) ? y : x;                             // +i: link (x, 0), -i: link (y, 0), +j: link (x, 1), -j: link (y, 1)
+    sub = 0;
+    second = d & 2u;
+    return y;
+  }
+};
+
+struct WolffRotatedTasks {
+  RotatedGeometry g;
+  __device__ __forceinline__ uint32_t nvert() const { return g.nvert(); }
+  __device__ __forceinline__ uint32_t position(uint32_t x, uint32_t d) const { return g.position(x, d); }
+  __device__ __forceinline__ uint32_t neighbour(uint32_t x, uint32_t d, uint32_t &site, uint32_t &sub, bool &second) const {
+    const uint32_t ht = g.ht, hx = g.hx, nq = g.q;
+    const bool odd = x >= nq;                            // plane O
+    const uint32_t c = odd ? x - nq : x, cb = c / ht, ca = c - cb * ht;
+    // E: d -> O(a - (d >> 1), b - (d & 1)); O: d' -> E(a + 1 - (d' >> 1), b + 1 - (d' & 1))
+    uint32_t ya = ca, yb = cb;
+    if (odd) {
+      if (!(d & 2u)) ya = ca + 1 == ht ? 0 : ca + 1;
+      if (!(d & 1u)) yb = cb + 1 == hx ? 0 : cb + 1;
+    } else {
+      if (d & 2u) ya = ca == 0 ? ht - 1 : ca - 1;
+      if (d & 1u) yb = cb == 0 ? hx - 1 : cb - 1;
+    }
+    const uint32_t yc = yb * ht + ya;                    // < nq
+    const uint32_t de = odd ? 3u - d : d;                // the link's name from its E end: (x, d) from E, (y, 3 - d') from O
+    site = odd ? yc : x;
+    sub = de >> 1;
+    second = de & 1u;
+    return odd ? yc : nq + yc;
+  }
+};
+
+// The update of the two kernels above, decision by decision (the same state and cluster_sites bits), on either geometry, with
+// the improved estimators of wolff_improved_finish (sigma_cluster_device.hpp): the reflection pass adds q(a) of every member to
+// the chain's slice table, the epilogue of the update turns the table into chi^W, F_d^W and C_d^W(tau) and leaves it zero.
+template <class Tasks, bool BLOCK, bool LDS_MAP>
+__global__ void __launch_bounds__(BLOCK ? kClusterBlockThreads : kClusterThreads)
+    sigma_cluster_improved_kernel(double2 *phi_all, Tasks g, double beta2, uint32_t B, uint32_t n_updates, RngKey key0, uint32_t *queue_vertex,
+                                  double *queue_a, uint32_t *map_all, uint32_t words, uint32_t *cluster_sites, WolffImproved imp) {
+  extern __shared__ uint32_t lds_map[];
+  __shared__ uint32_t s_tail[kScWaveChains];
+  __shared__ uint32_t s_occupied[2 * kScWaveChains];
+  const uint32_t T = BLOCK ? blockDim.x : (uint32_t)kWave;
+  const uint32_t lane = BLOCK ? threadIdx.x : threadIdx.x & (kWave - 1);
+  const uint32_t wave_lane = threadIdx.x & (kWave - 1);
+  // the wave's number through readfirstlane: the chain and everything addressed through it are then scalars
+  const uint32_t slot = BLOCK ? 0 : (uint32_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+  const uint32_t b = BLOCK ? blockIdx.x : blockIdx.x * kScWaveChains + slot;
+  if (b >= B) return;                                    // team uniform (BLOCK: the grid has B workgroups)
+  const uint32_t N = g.nvert();
+  double2 *phi = phi_all + (size_t)b * N;
+  uint32_t *qv = queue_vertex + (size_t)b * N;
+  double *qa = queue_a + (size_t)b * N;
+  uint32_t *map = LDS_MAP ? lds_map + slot * words : map_all + (size_t)b * words;
+  for (uint32_t w = lane; w < words; w += T) map[w] = 0;
+  wolff_improved_clear(imp, b, lane, T);
+  RngKey key = key0;
+  key.chain = key0.chain + b;
+  uint32_t total = 0;
+  team_sync<BLOCK>();
+
+  for (uint32_t n = 0; n < n_updates; ++n, ++key.step) {
+    const V3 r = reflection_normal(key, P_SIGMA_REFLECT);
+    double us, unused;
+    rng_uniforms(key, 0, P_SIGMA_REFLECT, 1, us, unused);
+    uint32_t seed = (uint32_t)(us * (double)N);
+    seed = seed < N ? seed : N - 1;
+    if (lane == 0) {
+      qv[0] = seed;
+      qa[0] = dot3(r, sigma_of(phi[seed]));
+      map[seed >> 5] = 1u << (seed & 31u);
+      s_tail[slot] = 1;
+    }
+    team_sync<BLOCK>();
+
+    uint32_t head = 0, tail = 1;
+    for (uint32_t level = 0; level < N && head < tail; ++level) {
+      for (uint32_t base = head; base < tail; base += T / 4) {  // team uniform trip count: the ballot below sees whole waves
+        const uint32_t q = base + (lane >> 2), d = lane & 3u;
+        bool add = false;
+        uint32_t y = 0;
+        double ay = 0.0;
+        if (q < tail) {
+          const uint32_t x = qv[q];
+          const double ax = qa[q];
+          uint32_t site, sub;
+          bool second;
+          y = g.neighbour(x, d, site, sub, second);
+          const uint32_t bit = 1u << (y & 31u);
+          // a relaxed atomic load: other lanes set bits meanwhile; a stale 0 costs a test, the atomic OR below decides
+          if (y < N && !(__hip_atomic_load(&map[y >> 5], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP) & bit)) {
+            ay = dot3(r, sigma_of(phi[y]));
+            const double prod = ax * ay;
+            if (prod > 0.0) {                            // else p = 0: never bonded, no random number
+              const double p = bond_probability(prod, beta2);
+              const U4 w = philox4x32_10(site, key.chain, key.step, ((uint32_t)P_SIGMA_BOND << 24) | sub, key.k0, key.k1);
+              const double uni = second ? u01(w.z, w.w) : u01(w.x, w.y);
+              if (uni < p) add = !(atomicOr(&map[y >> 5], bit) & bit);
+            }
+          }
+        }
+        const unsigned long long joiners = __ballot(add);
+        if (joiners) {                                   // wave uniform
+          const uint32_t leader = (uint32_t)__builtin_ctzll(joiners);
+          uint32_t first = 0;
+          if (wave_lane == leader) first = atomicAdd(&s_tail[slot], (uint32_t)__builtin_popcountll(joiners));
+          first = __shfl(first, leader);
+          const uint32_t pos = first + (uint32_t)__builtin_popcountll(joiners & ((1ull << wave_lane) - 1ull));
+          if (add && pos < N) {
+            qv[pos] = y;
+            qa[pos] = ay;
+          }
+        }
+      }
+      team_sync<BLOCK>();
+      head = tail;
+      tail = s_tail[slot];
+      tail = tail < N ? tail : N;                        // the queue holds N entries (a vertex joins once)
+      if (BLOCK) __syncthreads();                        // nobody appends to the next level before everybody has read the tail
+    }
+
+    for (uint32_t q = lane; q < tail; q += T) {
+      const uint32_t x = qv[q];
+      const double a = qa[q];
+      phi[x] = reflected(sigma_of(phi[x]), a, r);
+      map[x >> 5] = 0;                                   // every bit of the word that is set belongs to a member
+      wolff_slice_add(imp, b, g.position(x, 0), g.position(x, 1), a);
+    }
+    wolff_improved_finish<BLOCK>(imp, b, lane, T, tail, s_occupied + 2 * slot);
+    total += tail;
+    // the next update reads what this one stored (other lanes, other waves of the team): drain the stores first
+    team_sync<BLOCK>();
+  }
+  if (cluster_sites && lane == 0) cluster_sites[b] += total;
+}
+
 namespace {
 
 struct ScPlan {
@@ -308,6 +460,10 @@ int sc_init_attrs() {
                                      hipFuncAttributeMaxDynamicSharedMemorySize, kScBlockLdsWords * sizeof(uint32_t)));
   MLMCPI_HIP_TRY(hipFuncSetAttribute((const void *)sigma_rot_cluster_kernel<true, true>,
                                      hipFuncAttributeMaxDynamicSharedMemorySize, kScBlockLdsWords * sizeof(uint32_t)));
+  MLMCPI_HIP_TRY(hipFuncSetAttribute((const void *)sigma_cluster_improved_kernel<WolffLatticeTasks, true, true>,
+                                     hipFuncAttributeMaxDynamicSharedMemorySize, kScBlockLdsWords * sizeof(uint32_t)));
+  MLMCPI_HIP_TRY(hipFuncSetAttribute((const void *)sigma_cluster_improved_kernel<WolffRotatedTasks, true, true>,
+                                     hipFuncAttributeMaxDynamicSharedMemorySize, kScBlockLdsWords * sizeof(uint32_t)));
   g_sc_attr_set[dev] = true;
   return MLMCPI_OK;
 }
@@ -328,9 +484,39 @@ size_t sc_section_v(uint32_t N, uint32_t B) { return align256((size_t)B * N * si
 size_t sc_section_map(uint32_t N, uint32_t B) { return align256((size_t)B * ((N + 31) / 32) * sizeof(uint32_t)); }
 size_t sc_workspace(uint32_t N, uint32_t B) { return sc_section_a(N, B) + sc_section_v(N, B) + sc_section_map(N, B); }
 
-// the draw on either geometry, arguments checked; `rot` is the rotated level, NULL on the unrotated Mt x Mx lattice
+// The improved draw's part of the workspace, behind that of the plain draw, and its fixed-point scale.  Per chain the slice
+// table [M0 + M1] int64, the accumulators [kWolffSums + n_out] int64, the occupied slices [M0 + M1] uint32 and the weights
+// [M0 + M1][2] double.  In the workspace
+// and not in LDS: at 1024 x 1024 the table is 16 KiB a chain beside the workgroup team's 128 KiB bitmap, and a
+// wave-team workgroup would hold four of them beside its four bitmaps.  s as in sigma_sw.hip (sw_corr): one cluster's
+// sum_i |P(i)| |P(i + tau)| is at most N N_slice as well.
+struct ScImprovedLayout {
+  uint32_t M0, M1, n_out, s;
+  size_t table_bytes, acc_bytes, occupied_bytes, weights_bytes;
+  size_t bytes() const { return table_bytes + acc_bytes + occupied_bytes + weights_bytes; }
+};
+
+ScImprovedLayout sc_improved_layout(uint32_t N, uint32_t M0, uint32_t M1, uint32_t B) {
+  ScImprovedLayout c{};
+  c.M0 = M0;
+  c.M1 = M1;
+  c.n_out = M0 / 2 + M1 / 2 + 2;
+  const uint64_t bound = (uint64_t)N * (N / (M0 < M1 ? M0 : M1));
+  uint32_t lb = 0;
+  while ((1ull << lb) < bound) ++lb;
+  c.s = 62 - lb < 32 ? 62 - lb : 32;
+  c.table_bytes = align256((size_t)B * (M0 + M1) * sizeof(long long));
+  c.acc_bytes = align256((size_t)B * (kWolffSums + c.n_out) * sizeof(long long));
+  c.occupied_bytes = align256((size_t)B * (M0 + M1) * sizeof(uint32_t));
+  c.weights_bytes = align256((size_t)B * (M0 + M1) * 2 * sizeof(double));
+  return c;
+}
+
+// the draw on either geometry, arguments checked; `rot` is the rotated level, NULL on the unrotated Mt x Mx lattice; with
+// d_improved the improved instances, whose part of the workspace follows the plain draw's
 int sc_draw(uint32_t Mt, uint32_t Mx, const SigmaLevel *rot, double beta, double *d_phi, uint32_t B, uint32_t n_updates, uint64_t seed,
-            uint32_t chain0, uint32_t update0, uint32_t *d_cluster_sites, void *d_work, void *stream) {
+            uint32_t chain0, uint32_t update0, uint32_t *d_cluster_sites, void *d_work, void *stream, double *d_improved = nullptr,
+            double *d_structure = nullptr, double *d_corr = nullptr) {
   if (int rc = sc_init_attrs()) return rc;
   const uint32_t N = rot ? rot->nvert() : Mt * Mx;
   const ScPlan p = sc_plan(N, B, tuning());
@@ -350,7 +536,27 @@ int sc_draw(uint32_t Mt, uint32_t Mx, const SigmaLevel *rot, double beta, double
     else if (p.lds_map) MLMCPI_SC_LAUNCH(KERNEL, false, true, __VA_ARGS__);                                                    \
     else MLMCPI_SC_LAUNCH(KERNEL, false, false, __VA_ARGS__);                                                                  \
   } while (0)
-  if (rot) {
+  if (d_improved) {
+    const ScImprovedLayout c = rot ? sc_improved_layout(N, 2 * rot->ht, 2 * rot->hx, B) : sc_improved_layout(N, Mt, Mx, B);
+    char *extra = w + sc_workspace(N, B);
+    const WolffImproved imp{(long long *)extra, (long long *)(extra + c.table_bytes), (uint32_t *)(extra + c.table_bytes + c.acc_bytes),
+                            (double *)(extra + c.table_bytes + c.acc_bytes + c.occupied_bytes), d_improved, d_structure, d_corr, c.M0, c.M1, ldexp(1.0, (int)c.s - 64), ldexp(1.0, -(int)c.s)};
+#define MLMCPI_SC_LAUNCH_IMPROVED(TASKS, BLOCK, LDS, G)                                                                        \
+  hipLaunchKernelGGL((sigma_cluster_improved_kernel<TASKS, BLOCK, LDS>), dim3(p.grid), dim3(p.threads), p.lds_bytes, st, (double2 *)d_phi, G, \
+                     2.0 * beta, B, n_updates, key, qv, qa, map, p.words, d_cluster_sites, imp)
+#define MLMCPI_SC_DISPATCH_IMPROVED(TASKS, G)                                                                                  \
+  do {                                                                                                                         \
+    if (p.block && p.lds_map) MLMCPI_SC_LAUNCH_IMPROVED(TASKS, true, true, G);                                                 \
+    else if (p.block) MLMCPI_SC_LAUNCH_IMPROVED(TASKS, true, false, G);                                                        \
+    else if (p.lds_map) MLMCPI_SC_LAUNCH_IMPROVED(TASKS, false, true, G);                                                      \
+    else MLMCPI_SC_LAUNCH_IMPROVED(TASKS, false, false, G);                                                                    \
+  } while (0)
+    if (rot) MLMCPI_SC_DISPATCH_IMPROVED(WolffRotatedTasks, WolffRotatedTasks{RotatedGeometry(*rot)});
+    else MLMCPI_SC_DISPATCH_IMPROVED(WolffLatticeTasks, (WolffLatticeTasks{LatticeGeometry{Mt, Mx}}));
+    MLMCPI_LAUNCH_CHECK("sigma_cluster_improved_kernel");
+#undef MLMCPI_SC_DISPATCH_IMPROVED
+#undef MLMCPI_SC_LAUNCH_IMPROVED
+  } else if (rot) {
     MLMCPI_SC_DISPATCH(sigma_rot_cluster_kernel, *rot);
     MLMCPI_LAUNCH_CHECK("sigma_rot_cluster_kernel");
   } else {
@@ -407,6 +613,36 @@ int mlmcpi_sigma_level_cluster_draw(const mlmcpi_sigma_level *level, double *d_s
   }
   const SigmaLevel L = make_level(*level);
   return sc_draw(0, 0, &L, level->beta, d_state, B, n_updates, seed, chain0, update0, d_cluster_sites, d_work, stream);
+}
+
+int mlmcpi_sigma_level_cluster_improved_workspace_bytes(const mlmcpi_sigma_level *level, uint32_t B, size_t *bytes) {
+  size_t plain = 0;
+  if (int rc = mlmcpi_sigma_level_cluster_workspace_bytes(level, B, &plain)) return rc;
+  MLMCPI_REQUIRE(bytes, "bad arguments");
+  const uint32_t N = level->rotated ? make_level(*level).nvert() : level->Mt * level->Mx;
+  *bytes = plain + sc_improved_layout(N, level->Mt, level->Mx, B).bytes();
+  return MLMCPI_OK;
+}
+
+int mlmcpi_sigma_level_cluster_improved_draw(const mlmcpi_sigma_level *level, double *d_state, uint32_t B, uint32_t n_updates,
+                                             uint64_t seed, uint32_t chain0, uint32_t update0, uint32_t *d_cluster_sites,
+                                             double *d_improved, double *d_structure, double *d_corr, void *d_work, size_t work_bytes,
+                                             void *stream) {
+  size_t need = 0;
+  if (int rc = mlmcpi_sigma_level_cluster_improved_workspace_bytes(level, B ? B : 1, &need)) return rc;
+  MLMCPI_REQUIRE(d_state && d_work && B > 0, "bad arguments");
+  MLMCPI_REQUIRE(d_improved, "d_improved is NULL: mlmcpi_sigma_level_cluster_draw is the entry point without the improved estimators");
+  MLMCPI_REQUIRE(work_bytes >= need, "the workspace is smaller than mlmcpi_sigma_level_cluster_improved_workspace_bytes asks for");
+  MLMCPI_REQUIRE((uint64_t)update0 + n_updates <= 0xFFFFFFFFull, "update counter overflows");
+  if (!level->rotated) {
+    const mlmcpi_lattice_action act = level_as_lattice(level);
+    if (int rc = sc_check(&act, "mlmcpi_sigma_level_cluster_improved_draw")) return rc;
+    return sc_draw(act.Mt, act.Mx, nullptr, act.beta, d_state, B, n_updates, seed, chain0, update0, d_cluster_sites, d_work, stream,
+                   d_improved, d_structure, d_corr);
+  }
+  const SigmaLevel L = make_level(*level);
+  return sc_draw(0, 0, &L, level->beta, d_state, B, n_updates, seed, chain0, update0, d_cluster_sites, d_work, stream, d_improved,
+                 d_structure, d_corr);
 }
 
 }  // extern "C"

@@ -522,6 +522,31 @@ def sigma_level_cluster_draw(level, x, n_updates, seed, chain0, update0, count=T
     return sites
 
 
+def sigma_level_cluster_improved_workspace(level, B, device="cuda"):
+    """workspace of sigma_level_cluster_improved_draw for B chains (uint8 tensor): the plain draw's plus the slice table"""
+    nbytes = C.c_size_t(0)
+    abi.call("mlmcpi_sigma_level_cluster_improved_workspace_bytes", C.byref(level), B, C.byref(nbytes))
+    return torch.empty(nbytes.value, dtype=torch.uint8, device=device)
+
+
+def sigma_level_cluster_improved_draw(level, x, n_updates, seed, chain0, update0, work=None, structure=False, correlator=False):
+    """sigma_level_cluster_draw with the improved estimators of the single cluster (mlmcpi_sigma_level_cluster_improved_draw): the
+    same state; returns, per chain and summed over this call's updates, (flipped vertices int32 [B], improved chi_m float64 [B]),
+    then with structure=True the improved structure factors (F_t, F_x) float64 [B, 2], then with correlator=True the improved
+    time-slice correlators float64 [B, n_out] in the layout of sigma_level_correlator"""
+    _check_state(x, sigma_level_size(level))
+    B = x.shape[0]
+    if work is None:
+        work = sigma_level_cluster_improved_workspace(level, B, x.device)
+    sites = torch.zeros(B, dtype=torch.int32, device=x.device)
+    improved = torch.zeros(B, dtype=torch.float64, device=x.device)
+    factors = torch.zeros(B, 2, dtype=torch.float64, device=x.device) if structure else None
+    corr = torch.zeros(B, sigma_level_correlator_size(level), dtype=torch.float64, device=x.device) if correlator else None
+    abi.call("mlmcpi_sigma_level_cluster_improved_draw", C.byref(level), _p(x), B, n_updates, seed, chain0, update0, _p(sites),
+             _p(improved), _p(factors), _p(corr), _p(work), work.numel(), _stream())
+    return (sites, improved) + ((factors,) if structure else ()) + ((corr,) if correlator else ())
+
+
 def sigma_level_sw_workspace(level, B, device="cuda"):
     """workspace of sigma_level_sw_draw for B chains (uint8 tensor)"""
     nbytes = C.c_size_t(0)
