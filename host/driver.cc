@@ -30,6 +30,10 @@
 //           sample, and after the statistics come the time-slice correlators C_t, C_x per lag, chi and F from them, and the
 //           second-moment correlation length xi_2 with its jackknife error over the chains)
 //          (with --sampler swendsenwang the cluster-improved F, xi_2 and, per lag, C_t and C_x follow: DESIGN.md 4.6b)
+//   driver --action harmonicoscillator --M_lat 16 --T_final 4 --sampler exact --batch 256 --n_samples 200 --path_correlator 9
+//          (--path_correlator N, single-level runs of the three 1-D actions: all `batch` chains are sampled and after the statistics
+//           come C(tau) = <x(0) x(tau)> (rotor: <cos(x(0) - x(tau))>) for tau < N, the effective mass per interior lag with its
+//           jackknife error and the gap m_eff / a; for the harmonic oscillator the exact lattice values beside them)
 //   driver --action rotor --M_lat 256 --T_final 25.6 --m0 0.25 --sampler cluster --n_updates 10 --n_samples 20000
 //          (cluster samplers: rotor and schwinger; also --coarsesampler cluster for twolevel / hierarchical rotor runs)
 //   driver --method throughput --action schwinger --Mt_lat 1024 --sampler heatbath --batch 32 --n_samples 20
@@ -55,7 +59,8 @@ int main(int argc, char **argv) {
       {"sampler", "hmc"}, {"nt", "100"}, {"dt", "0.1"}, {"n_burnin", "100"}, {"n_samples", "20000"}, {"n_sweep_overrelax", "10"},
       {"n_sweep_heatbath", "1"}, {"autotune", "1"}, {"window", "20"}, {"method", "singlelevel"}, {"n_level", "3"},
       {"epsilon", "0.01"}, {"coarsening", "both"}, {"coarsesampler", "hmc"}, {"renormalisation", "none"}, {"n_meas", "200"},
-      {"batch", "1"}, {"seed", "2481317"}, {"warmup", "5"}, {"random_order", "0"}, {"n_updates", "10"}, {"correlator", "0"}};
+      {"batch", "1"}, {"seed", "2481317"}, {"warmup", "5"}, {"random_order", "0"}, {"n_updates", "10"}, {"correlator", "0"},
+      {"path_correlator", "0"}};
   for (int i = 1; i + 1 < argc; i += 2) {
     if (std::strncmp(argv[i], "--", 2) || !o.count(argv[i] + 2)) fatal(std::string("unknown option ") + argv[i]);
     o[argv[i] + 2] = argv[i + 1];
@@ -65,6 +70,28 @@ int main(int argc, char **argv) {
   auto env_int = [](const char *k, int d) { const char *v = std::getenv(k); return v ? std::atoi(v) : d; };
   const int rank = env_int("RANK", 0), world = env_int("WORLD_SIZE", 1), local_rank = env_int("LOCAL_RANK", rank);
   const unsigned batch = (unsigned)num("batch");
+  // --path_correlator N: the time correlator C(tau), tau = 0 .. N - 1, of a 1-D path action beside the QoI, and the energy gap from
+  // its decay (qoi.hh PathCorrelator); 0: off.  Refused here, before any device call.
+  {
+    const std::string &v = o["path_correlator"];
+    if (v.empty() || v.size() > 9 || v.find_first_not_of("0123456789") != std::string::npos)
+      fatal("--path_correlator takes a non-negative integer (the number of lags, 0: off), not " + v);
+  }
+  const unsigned path_lags = (unsigned)std::stoul(o["path_correlator"]);
+  if (path_lags > 0) {
+    const std::string &pa = o["action"];
+    if (pa != "harmonicoscillator" && pa != "quarticoscillator" && pa != "rotor")
+      fatal("--path_correlator " + o["path_correlator"] + " is not supported for chosen action: the path correlator is built for "
+            "harmonicoscillator, quarticoscillator and rotor only, not " + pa + " (the sigma model has --correlator 1)");
+    if (o["method"] != "singlelevel")
+      fatal("--path_correlator runs --method singlelevel only, not " + o["method"] + " (the two-level and multilevel estimators have "
+            "no difference estimator for C(tau); the throughput loop measures the QoI alone)");
+    if (world > 1) fatal("--path_correlator runs on one rank (its sums are not exchanged)");
+    const unsigned M_lat = (unsigned)num("M_lat");
+    if (path_lags > M_lat / 2 + 1)
+      fatal("--path_correlator " + o["path_correlator"] + " is more than M_lat / 2 + 1 = " + std::to_string(M_lat / 2 + 1) +
+            " lags (C(M_lat - tau) = C(tau))");
+  }
   std::shared_ptr<Exchange> exchange;
   if (world > 1) {
     check(mlmcpi_set_device(local_rank), "mlmcpi_set_device");
@@ -81,6 +108,7 @@ int main(int argc, char **argv) {
   std::shared_ptr<Action> action;
   std::shared_ptr<QoI> qoi;
   std::shared_ptr<SigmaCorrelator> correlator;
+  std::shared_ptr<PathCorrelator> path_correlator;
   std::shared_ptr<QoIFactory> qoi_factory;
   std::shared_ptr<ConditionedFineActionFactory> cfa_factory;
   double analytic = NAN;
@@ -184,6 +212,8 @@ int main(int argc, char **argv) {
       qoi_factory = std::make_shared<QoISusceptibilityFactory>();
       cfa_factory = std::make_shared<RotorConditionedFineActionFactory>();
     }
+    if (path_lags > 0)
+      path_correlator = std::make_shared<PathCorrelator>(lat, a == "harmonicoscillator" ? MLMCPI_HARMONIC : a == "quarticoscillator" ? MLMCPI_QUARTIC : MLMCPI_ROTOR, path_lags);
   } else if (a == "nonlinearsigma") {  // driver_qft.cc:159-166, 241-246
     auto lat = std::make_shared<Lattice2D>((unsigned)num("Mt_lat"), (unsigned)num("Mt_lat"), coarsenings.at(o["coarsening"]));
     if (o["sampler"] != "heatbath" && o["sampler"] != "wolff" && o["sampler"] != "swendsenwang" && o["sampler"] != "hierarchical")
@@ -235,7 +265,7 @@ int main(int argc, char **argv) {
       hp.batch = batch;
       return std::make_shared<HMCSamplerFactory>(hp);
     }
-    if (name == "exact") return std::make_shared<ExactSamplerFactory>();  // driver_qm.cc: sampler = 'exact' (harmonic oscillator, GFF)
+    if (name == "exact") return std::make_shared<ExactSamplerFactory>(path_lags > 0 ? batch : 1u);  // driver_qm.cc: sampler = 'exact' (harmonic oscillator, GFF)
     if (name == "cluster") {  // driver_qm.cc:62-70, driver_qft.cc:69-80
       ClusterParameters cp;
       cp.n_burnin = (unsigned)num("n_burnin"); cp.n_updates = (unsigned)num("n_updates"); cp.batch = batch;
@@ -369,7 +399,10 @@ int main(int argc, char **argv) {
   SingleLevelMCParameters mp;
   mp.n_burnin = (unsigned)num("n_burnin"); mp.n_samples = (unsigned)num("n_samples"); mp.n_autocorr_window = (unsigned)num("window");
   // with --correlator 1 the loop runs on all `batch` chains (Q = their mean per sample) and measures C(tau) on the same states
-  MonteCarloSingleLevel mc(action, qoi, factory, mp, exchange, correlator ? batch : 1u, correlator);
+  // (--path_correlator N likewise)
+  std::shared_ptr<CorrelatorMeasurement> measured = correlator;
+  if (path_correlator) measured = path_correlator;
+  MonteCarloSingleLevel mc(action, qoi, factory, mp, exchange, measured ? batch : 1u, measured);
   mc.evaluate();
   std::cout << std::endl << "=== Single level MC ===" << std::endl;
   mc.show_statistics();
@@ -446,6 +479,32 @@ int main(int argc, char **argv) {
     auto st = mc.get_statistics();
     std::cout << std::setprecision(6) << " analytic result = " << analytic << std::endl
               << " |analytic - numerical| / error = " << std::fabs(analytic - st->average()) / st->error() << std::endl;
+  }
+  if (path_correlator) {
+    const PathCorrelator::Estimate e = path_correlator->means_and_errors();
+    const unsigned M_lat = path_correlator->M(), B = path_correlator->batch();
+    const double T_final = num("T_final"), a_lat = T_final / M_lat;
+    const bool ho = a == "harmonicoscillator";
+    std::cout << std::endl << "=== Path correlator ===" << std::endl
+              << " samples = " << path_correlator->samples() << ", chains = " << B << ", errors: "
+              << (e.chain_spread ? "spread of the per-chain means" : "naive (one chain: autocorrelation ignored)") << std::endl
+              << std::setprecision(8) << std::fixed;
+    for (unsigned tau = 0; tau < path_lags; ++tau) {
+      std::cout << " C(tau = " << tau << ") = " << e.mean[tau] << " +/- " << e.error[tau];
+      if (ho) std::cout << " exact = " << path_correlator_ho_exact(M_lat, T_final, num("m0"), num("mu2"), tau);
+      std::cout << std::endl;
+    }
+    for (unsigned tau = 1; tau + 1 < path_lags; ++tau) {
+      const PathCorrelator::Mass m = path_correlator->effective_mass(tau);
+      std::cout << " m_eff(tau = " << tau << ") = " << m.value;
+      if (m.has_error) std::cout << " +/- " << m.error << " (jackknife over chains)";
+      else std::cout << " (one chain: no jackknife error)";
+      std::cout << ", Delta E = m_eff / a = " << m.value / a_lat << std::endl;
+    }
+    if (ho) {
+      const double w = path_ho_lattice_omega(M_lat, T_final, num("mu2"));
+      std::cout << " exact lattice gap: omega~ = " << w << ", omega~ / a = " << w / a_lat << std::endl;
+    }
   }
   return 0;
 }

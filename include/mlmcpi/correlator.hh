@@ -1,5 +1,6 @@
 // correlator.hh -- host arithmetic on a mean time-slice correlator C(tau), tau = 0 .. M/2, of a periodic direction of even
-// extent M (mlmcpi_sigma_level_correlator; the class that measures it is SigmaCorrelator, qoi.hh).  No device code.
+// extent M (mlmcpi_sigma_level_correlator; the class that measures it is SigmaCorrelator, qoi.hh), and on the time correlator of
+// a 1-D path (below).  No device code.
 #ifndef MLMCPI_CORRELATOR_HH
 #define MLMCPI_CORRELATOR_HH
 #include <cmath>
@@ -36,6 +37,30 @@ inline double xi_from_chi_and_F(double chi, double F, unsigned int M) {
  *  exactly 1 / (2 sinh(m / 2)).  NaN where chi / F < 1 (noise) */
 inline double xi_second_moment(const std::vector<double> &C, unsigned int M) {
   return xi_from_chi_and_F(correlator_susceptibility(C, M), structure_factor(C, M), M);
+}
+
+// ---- the time correlator C(tau) = <x(0) x(tau)> of a 1-D path (mlmcpi_path_correlator; the class that measures it is
+// PathCorrelator, qoi.hh) ----
+
+/** effective mass at lag tau, 1 <= tau <= C.size() - 2: acosh((C(tau - 1) + C(tau + 1)) / (2 C(tau))), which is m exactly for
+ *  C = A cosh(m (M/2 - tau)), wrap-around included; times 1/a it is the gap E_1 - E_0 where one state dominates.  NaN where the
+ *  argument is < 1 (a triple that is not convex: noise) */
+inline double effective_mass(const std::vector<double> &C, unsigned int tau) {
+  const double r = (C[tau - 1] + C[tau + 1]) / (2.0 * C[tau]);
+  return r >= 1.0 ? std::acosh(r) : std::nan("");
+}
+
+/** omega~ of the lattice harmonic oscillator, cosh(omega~) = 1 + a^2 mu2 / 2, a = T_final / M: the gap in lattice units */
+inline double path_ho_lattice_omega(unsigned int M, double T_final, double mu2) {
+  const double a = T_final / M;
+  return std::acosh(1.0 + 0.5 * a * a * mu2);
+}
+
+/** <x_0 x_tau> of the harmonic oscillator S = (a m0 / 2) sum_j ((x_j - x_{j-1})^2 / a^2 + mu2 x_j^2) on the periodic lattice of
+ *  M sites: (a / m0) cosh(omega~ (M/2 - tau)) / (2 sinh(omega~) sinh(omega~ M / 2)); at tau = 0 the action's analytic <x^2> */
+inline double path_correlator_ho_exact(unsigned int M, double T_final, double m0, double mu2, unsigned int tau) {
+  const double a = T_final / M, w = path_ho_lattice_omega(M, T_final, mu2);
+  return (a / m0) * std::cosh(w * (0.5 * M - (double)tau)) / (2.0 * std::sinh(w) * std::sinh(0.5 * w * M));
 }
 
 }  // namespace mlmcpi

@@ -24,7 +24,7 @@ public:
    *  all-reduce per pass of the do-while below. */
   MonteCarloSingleLevel(std::shared_ptr<Action> action_, std::shared_ptr<QoI> qoi_, std::shared_ptr<SamplerFactory> f,
                         const SingleLevelMCParameters p, std::shared_ptr<Exchange> exchange_ = nullptr, unsigned int batch_ = 1,
-                        std::shared_ptr<SigmaCorrelator> correlator_ = nullptr)
+                        std::shared_ptr<CorrelatorMeasurement> correlator_ = nullptr)
       : action(action_), sampler(f->get(action_)), qoi(qoi_), param(p), exchange(exchange_),
         stats_Q(std::make_shared<Statistics>("Q", p.n_autocorr_window, exchange_)), batch(batch_), correlator(correlator_) {}
 
@@ -84,7 +84,7 @@ private:
   std::shared_ptr<Statistics> stats_Q;
   unsigned int n_passes = 0;
   const unsigned int batch;
-  std::shared_ptr<SigmaCorrelator> correlator;
+  std::shared_ptr<CorrelatorMeasurement> correlator;  // SigmaCorrelator or PathCorrelator
 };
 
 }  // namespace mlmcpi

@@ -125,11 +125,20 @@ private:
   const bool rotated;
 };
 
+/** What MonteCarloSingleLevel asks of a correlator it measures beside the QoI: one more sample of the state at hand, and how
+ *  many it has taken (SigmaCorrelator, PathCorrelator). */
+class CorrelatorMeasurement {
+public:
+  virtual ~CorrelatorMeasurement() {}
+  virtual void accumulate(const std::shared_ptr<SampleState> phi) = 0;
+  virtual unsigned int samples() const = 0;
+};
+
 /** The time-slice correlators C_t(tau), C_x(tau) of the O(3) sigma model on a lattice, rotated or not
  *  (mlmcpi_sigma_level_correlator; definitions in mlmcpi_hip.h).  Not a QoI: its value is a vector of n_out() =
  *  (Mt/2 + 1) + (Mx/2 + 1) numbers per chain, C_t first.  accumulate() adds the sample's C and C^2 to per-chain sums on the
  *  device; the means, their errors and xi_2 (correlator.hh) are host arithmetic on those sums. */
-class SigmaCorrelator {
+class SigmaCorrelator : public CorrelatorMeasurement {
 public:
   struct Estimate {
     std::vector<double> mean, error;
@@ -151,7 +160,7 @@ public:
   /** d_out[b][n_out()] = the correlators of chain b, enqueued on the default stream */
   void evaluate_device(const std::shared_ptr<SampleState> phi, double *d_out) { launch(phi, d_out, nullptr); }
   /** one more sample: its correlators are added to the per-chain sums (the batch is fixed by the first call) */
-  void accumulate(const std::shared_ptr<SampleState> phi) {
+  void accumulate(const std::shared_ptr<SampleState> phi) override {
     if (!acc || B != phi->batch()) {
       if (n_calls) fatal("SigmaCorrelator::accumulate: the batch changed between samples.");
       B = phi->batch();
@@ -161,7 +170,7 @@ public:
     launch(phi, (double *)out->ptr(), (double *)acc->ptr());
     ++n_calls;
   }
-  unsigned int samples() const { return n_calls; }
+  unsigned int samples() const override { return n_calls; }
   unsigned int batch() const { return B; }
   /** per-chain means of C over the accumulated samples, [batch][n_out()] */
   std::vector<std::vector<double>> chain_means() const {
@@ -241,6 +250,116 @@ private:
   const mlmcpi_sigma_level level;
   const unsigned int n_vertices;
   unsigned int n_out_ = 0, B = 0, work_B = 0, n_calls = 0;
+  size_t work_bytes = 0;
+  std::unique_ptr<DeviceBuffer> work;
+  std::unique_ptr<DeviceVector> acc, out;
+};
+
+/** The time correlator C(tau), tau = 0 .. n_lag - 1, of a 1-D path action (mlmcpi_path_correlator; definitions in
+ *  mlmcpi_hip.h): x_j x_{j+tau} averaged over the path for the oscillators, cos(x_j - x_{j+tau}) for the rotor.  Not a QoI: n_lag
+ *  numbers per chain.  accumulate() adds the sample's C and C^2 to per-chain sums on the device; the means, their errors and the
+ *  effective mass (correlator.hh) are host arithmetic on those sums. */
+class PathCorrelator : public CorrelatorMeasurement {
+public:
+  struct Estimate {
+    std::vector<double> mean, error;
+    bool chain_spread;  // true: error = spread of the per-chain means (batch >= 2); false: the naive error of one chain
+  };
+  struct Mass {
+    double value, error;
+    bool has_error;  // the jackknife over chains needs batch >= 2
+  };
+  PathCorrelator(const std::shared_ptr<Lattice1D> lattice, int kind, unsigned int n_lag_)
+      : act{kind, lattice->getM_lat(), lattice->getT_final(), 1.0, 1.0, 0.0, 0.0}, n_lag_(n_lag_) {}
+  unsigned int n_lag() const { return n_lag_; }
+  unsigned int M() const { return act.M; }
+  /** d_out[b][n_lag()] = the correlator of chain b, enqueued on the default stream */
+  void evaluate_device(const std::shared_ptr<SampleState> x, double *d_out) { launch(x, d_out, nullptr); }
+  /** one more sample: its correlator is added to the per-chain sums (the batch is fixed by the first call) */
+  void accumulate(const std::shared_ptr<SampleState> x) override {
+    if (!acc || B != x->batch()) {
+      if (n_calls) fatal("PathCorrelator::accumulate: the batch changed between samples.");
+      B = x->batch();
+      acc = std::make_unique<DeviceVector>(2 * (size_t)B * n_lag_);
+      out = std::make_unique<DeviceVector>((size_t)B * n_lag_);
+    }
+    launch(x, (double *)out->ptr(), (double *)acc->ptr());
+    ++n_calls;
+  }
+  unsigned int samples() const override { return n_calls; }
+  unsigned int batch() const { return B; }
+  /** per-chain means of C over the accumulated samples, [batch][n_lag()] */
+  std::vector<std::vector<double>> chain_means() const {
+    if (!n_calls) fatal("PathCorrelator: no samples accumulated.");
+    const std::vector<double> a = acc->download<double>();
+    std::vector<std::vector<double>> m(B, std::vector<double>(n_lag_));
+    for (unsigned int b = 0; b < B; ++b)
+      for (unsigned int k = 0; k < n_lag_; ++k) m[b][k] = a[2 * ((size_t)b * n_lag_ + k)] / n_calls;
+    return m;
+  }
+  /** mean and error per lag.  batch >= 2: the error is the spread of the per-chain means over sqrt(batch), so autocorrelation
+   *  inside a chain cannot understate it; batch 1: the naive error of the samples (it ignores autocorrelation) */
+  Estimate means_and_errors() const {
+    if (!n_calls) fatal("PathCorrelator: no samples accumulated.");
+    const std::vector<double> a = acc->download<double>();
+    Estimate e{std::vector<double>(n_lag_, 0.0), std::vector<double>(n_lag_, 0.0), B >= 2};
+    const double n = n_calls;
+    for (unsigned int k = 0; k < n_lag_; ++k) {
+      if (B >= 2) {
+        double s = 0.0, s2 = 0.0;
+        for (unsigned int b = 0; b < B; ++b) s += a[2 * ((size_t)b * n_lag_ + k)] / n;
+        const double m = s / B;
+        for (unsigned int b = 0; b < B; ++b) {
+          const double d = a[2 * ((size_t)b * n_lag_ + k)] / n - m;
+          s2 += d * d;
+        }
+        e.mean[k] = m;
+        e.error[k] = std::sqrt(s2 / ((double)B * (B - 1.0)));
+      } else {
+        const double m = a[2 * k] / n, var = n_calls > 1 ? std::max(0.0, (a[2 * k + 1] / n - m * m) * n / (n - 1.0)) : 0.0;
+        e.mean[k] = m;
+        e.error[k] = std::sqrt(var / n);
+      }
+    }
+    return e;
+  }
+  /** m_eff(tau), 1 <= tau <= n_lag() - 2, from the mean correlator; batch >= 2: with the jackknife error over the chains */
+  Mass effective_mass(unsigned int tau) const {
+    if (tau < 1 || tau + 1 >= n_lag_) fatal("PathCorrelator::effective_mass: lag outside 1 .. n_lag - 2.");
+    const std::vector<std::vector<double>> m = chain_means();
+    std::vector<double> all(n_lag_, 0.0);
+    for (unsigned int b = 0; b < B; ++b)
+      for (unsigned int k = 0; k < n_lag_; ++k) all[k] += m[b][k];
+    std::vector<double> mean(all);
+    for (double &v : mean) v /= B;
+    Mass r{mlmcpi::effective_mass(mean, tau), 0.0, B >= 2};
+    if (B >= 2) {
+      std::vector<double> x(B), leave(n_lag_);
+      double xm = 0.0, s2 = 0.0;
+      for (unsigned int b = 0; b < B; ++b) {
+        for (unsigned int k = 0; k < n_lag_; ++k) leave[k] = (all[k] - m[b][k]) / (B - 1.0);
+        x[b] = mlmcpi::effective_mass(leave, tau);
+        xm += x[b] / B;
+      }
+      for (unsigned int b = 0; b < B; ++b) s2 += (x[b] - xm) * (x[b] - xm);
+      r.error = std::sqrt((B - 1.0) / B * s2);
+    }
+    return r;
+  }
+
+private:
+  void launch(const std::shared_ptr<SampleState> x, double *d_out, double *d_acc) {
+    if (x->size() != act.M) fatal("Evaluating PathCorrelator on path of wrong size.");
+    if (!work || work_B != x->batch()) {
+      check(mlmcpi_path_correlator_workspace_bytes(&act, n_lag_, x->batch(), &work_bytes), "path_correlator_workspace_bytes");
+      work = std::make_unique<DeviceBuffer>(work_bytes);
+      work_B = x->batch();
+    }
+    check(mlmcpi_path_correlator(&act, x->device(), x->batch(), n_lag_, d_out, d_acc, work->p, work_bytes, nullptr), "path_correlator");
+  }
+  const mlmcpi_path_action act;  // kind and M are all the correlator reads
+  const unsigned int n_lag_;
+  unsigned int B = 0, work_B = 0, n_calls = 0;
   size_t work_bytes = 0;
   std::unique_ptr<DeviceBuffer> work;
   std::unique_ptr<DeviceVector> acc, out;

@@ -174,6 +174,52 @@ typedef struct mlmcpi_path_hmc_plan_info {
 } mlmcpi_path_hmc_plan_info;
 int mlmcpi_path_hmc_plan(const mlmcpi_path_action *act, uint32_t B, uint32_t nt, mlmcpi_path_hmc_plan_info *out);
 
+/* The time correlator of a path (path_correlator.hip): per chain b of d_x [B][M], for tau = 0 .. n_lag - 1,
+ *   kinds 0, 1 (oscillators)  C(tau) = (1/M) sum_j x_j x_{(j + tau) mod M}
+ *   kind 2 (rotor)            C(tau) = (1/M) sum_j cos(x_j - x_{(j + tau) mod M}), formed as c_j c_{j+tau} + s_j s_{j+tau} from one
+ *                             sincos per staged site
+ * into d_out [B][n_lag].  Only act->kind and act->M are read.  n_lag <= M/2 + 1: C(M - tau) = C(tau).
+ * Identities: C(0) = QoIXsquared (oscillators), C(0) = 1 (rotor); with w(0) = 1, w(M/2) = 1 for even M and w = 2 otherwise (M = 2:
+ * both lags weight 1; odd M: every lag but 0 weight 2), sum_{tau <= M/2} w C(tau) = (sum_j x_j)^2 / M for the oscillators and
+ * ((sum_j c_j)^2 + (sum_j s_j)^2) / M for the rotor.  The decay of <C(tau)> gives the gap: m_eff(tau) = acosh((C(tau - 1) + C(tau + 1)) /
+ * (2 C(tau))) = a (E_1 - E_0) where one state dominates (include/mlmcpi/correlator.hh has the lattice closed forms).
+ * Summation order: sites and lags go in tiles of J = 8 sites and T = 8 lags.  A path is cut into nseg segments of `owned` sites
+ * (a multiple of 8 but for the last; nseg = 1 while the path's tiles and the lag tiles fit one LDS image of 64 KiB).  For a
+ * segment and a lag, a group of G lanes (G = min(64, owned tiles rounded up to a power of two)) adds: lane g the site tiles g, g +
+ * G, .. ascending, sites ascending in a tile, one FMA per product (rotor: the c product, then the s product, of each site); the lanes
+ * by the shuffle tree, offsets G/2, .., 1.  Segments are added in ascending order; the sum is divided by M last.  The geometry is a
+ * function of (kind, M, n_lag) alone, there are no atomics and no tuning knob: a chain's output is the same bits for every B, every
+ * split of the chains over calls and every stream.
+ * n_lag cap: the LDS image of a segment holds tiles of 8 sites, 80 bytes each per component, the lag tiles beside at least one site
+ * tile: ceil(n_lag / 8) + 1 <= 65536 / (80 components), i.e. n_lag <= 6544 for the oscillators and <= 3264 for the rotor; beyond:
+ * MLMCPI_ERR_UNSUPPORTED.
+ * d_acc (may be NULL) [B][n_lag][2]: C is ADDED to [.][.][0] and C^2 to [.][.][1] in the launch that writes d_out; the caller
+ * counts the calls.  d_work: _workspace_bytes(act, n_lag, B) bytes (never 0), 256-byte aligned; content at entry ignored.
+ * Chains and segments share one index of workgroups, ceil(B / chains_per_workgroup) nseg of them, laid over grid x (2^31 / 256) and,
+ * beyond that, y: there is no 65535-chain limit (the bound, 2^23 x 65535 workgroups, is beyond any memory).
+ * MLMCPI_ERR_INVALID, with nothing launched and no output byte touched: NULL act, d_x, d_out or d_work; kind outside 0 .. 2; M = 0,
+ * B = 0 or n_lag = 0; n_lag > M/2 + 1; more workgroups than above; work_bytes below _workspace_bytes.
+ * _plan (host only, touches no device) reports the geometry and returns the status the call would. */
+typedef struct mlmcpi_path_correlator_plan_info {
+  uint64_t work_bytes;            /* what _workspace_bytes reports */
+  uint64_t grid;                  /* workgroups of the correlator launch; with work_bytes the only entries that depend on B */
+  uint32_t workgroup;             /* threads of a workgroup */
+  uint32_t chains_per_workgroup;  /* 4 (short paths: one wave per chain) or 1 */
+  uint32_t waves_per_chain;       /* 1 or 4 */
+  uint32_t group;                 /* G: lanes that share a lag tile */
+  uint32_t owned;                 /* sites a segment owns: segment s owns [s owned, min(M, (s + 1) owned)) */
+  uint32_t nseg;
+  uint32_t J, T;                  /* sites x lags of a lane's register tile */
+  uint32_t lag_tiles;             /* ceil(n_lag / T): lag tile q holds the lags [q T, min(n_lag, (q + 1) T)) */
+  uint32_t image_tiles;           /* tiles of J sites in a segment's LDS image: owned tiles + lag_tiles */
+  uint32_t components;            /* 1, rotor 2 */
+  uint32_t lds_bytes, lds_limit;  /* dynamic LDS of a workgroup, and the limit the kernel is written for */
+} mlmcpi_path_correlator_plan_info;
+int mlmcpi_path_correlator_workspace_bytes(const mlmcpi_path_action *act, uint32_t n_lag, uint32_t B, size_t *bytes);
+int mlmcpi_path_correlator(const mlmcpi_path_action *act, const double *d_x, uint32_t B, uint32_t n_lag, double *d_out /* [B][n_lag] */,
+                           double *d_acc /* [B][n_lag][2], may be NULL */, void *d_work, size_t work_bytes, void *stream);
+int mlmcpi_path_correlator_plan(const mlmcpi_path_action *act, uint32_t n_lag, uint32_t B, mlmcpi_path_correlator_plan_info *out);
+
 /* OverrelaxedHeatBathSampler::draw (sampler/overrelaxedheatbathsampler.cc:8-31) for the rotor:
  * n_overrelax sweeps of RotorAction::overrelaxation_update (rotoraction.cc:40-56) then n_heatbath
  * sweeps of heatbath_update (:20-37), even sites then odd sites within each sweep.  Sweep s of

@@ -65,6 +65,13 @@ class PathHmcPlan(C.Structure):
     _fields_ = [(n, C.c_uint32) for n in ("R", "NT", "nseg", "owned_len", "halo")] + [("chain_major", C.c_int32)]
 
 
+class PathCorrelatorPlan(C.Structure):
+    """mlmcpi_path_correlator_plan_info"""
+    _fields_ = [("work_bytes", C.c_uint64), ("grid", C.c_uint64)] + [(n, C.c_uint32) for n in (
+        "workgroup", "chains_per_workgroup", "waves_per_chain", "group", "owned", "nseg", "J", "T", "lag_tiles", "image_tiles",
+        "components", "lds_bytes", "lds_limit")]
+
+
 _vp, _u32, _u64, _i, _d, _sz = C.c_void_p, C.c_uint32, C.c_uint64, C.c_int, C.c_double, C.c_size_t
 _PA, _LA = C.POINTER(PathAction), C.POINTER(LatticeAction)
 _SL = C.POINTER(SigmaLevel)
@@ -100,6 +107,9 @@ SIGNATURES = {
     "mlmcpi_path_hmc_run": (_i, [_PA, _vp, _u32, _u32, _d, _u32, _u32, _i, _u64, _u32, _u32, _vp, _vp, _vp, _vp]),
     "mlmcpi_path_hmc_run_layout": (_i, [_PA, _u32, _u32, C.POINTER(C.c_int32)]),
     "mlmcpi_path_hmc_plan": (_i, [_PA, _u32, _u32, C.POINTER(PathHmcPlan)]),
+    "mlmcpi_path_correlator_workspace_bytes": (_i, [_PA, _u32, _u32, C.POINTER(_sz)]),
+    "mlmcpi_path_correlator": (_i, [_PA, _vp, _u32, _u32, _vp, _vp, _vp, _sz, _vp]),
+    "mlmcpi_path_correlator_plan": (_i, [_PA, _u32, _u32, C.POINTER(PathCorrelatorPlan)]),
     "mlmcpi_path_sweep_draw": (_i, [_PA, _vp, _vp, _u32, _u32, _u32, _u64, _u32, _u32, _vp]),
     "mlmcpi_path_sweep_draw_from": (_i, [_PA, _vp, _vp, _vp, _u32, _u32, _u32, _u64, _u32, _u32, _vp, _vp]),
     "mlmcpi_path_sweep_draw_qoi": (_i, [_PA, _vp, _vp, _vp, _u32, _u32, _u32, _u64, _u32, _u32, _vp, _vp, _vp, _vp]),

@@ -123,6 +123,35 @@ def path_hmc_plan(act, B, nt):
     return {n: getattr(info, n) for n, _ in abi.PathHmcPlan._fields_}
 
 
+def path_correlator_plan(act, n_lag, B):
+    """The launch geometry of path_correlator for these arguments (mlmcpi_path_correlator_plan; no device needed): a dict of
+    the fields of mlmcpi_path_correlator_plan_info"""
+    info = abi.PathCorrelatorPlan()
+    abi.call("mlmcpi_path_correlator_plan", C.byref(act), n_lag, B, C.byref(info))
+    return {n: getattr(info, n) for n, _ in abi.PathCorrelatorPlan._fields_}
+
+
+def path_correlator_workspace(act, n_lag, B, device="cuda"):
+    """workspace of path_correlator for B chains and n_lag lags (uint8 tensor)"""
+    nbytes = C.c_size_t(0)
+    abi.call("mlmcpi_path_correlator_workspace_bytes", C.byref(act), n_lag, B, C.byref(nbytes))
+    return torch.empty(nbytes.value, dtype=torch.uint8, device=device)
+
+
+def path_correlator(act, x, n_lag, acc=None, work=None):
+    """C(tau), tau = 0 .. n_lag - 1, of every chain of x [B, M] (mlmcpi_path_correlator): returns [B, n_lag]; acc [B, n_lag, 2]
+    (optional) is added to: C and C^2"""
+    _check_state(x, act.M)
+    B = x.shape[0]
+    if work is None:
+        work = path_correlator_workspace(act, n_lag, B, x.device)
+    if acc is not None:
+        assert acc.dtype == torch.float64 and tuple(acc.shape) == (B, n_lag, 2), acc.shape
+    out = _f64(B, n_lag, x)
+    abi.call("mlmcpi_path_correlator", C.byref(act), _p(x), B, n_lag, _p(out), _p(acc), _p(work), work.numel(), _stream())
+    return out
+
+
 class PathTwoLevelStep:
     """TwoLevelMetropolisStep (montecarlo/twolevelmetropolisstep.cc) on B device chains: Gaussian fill-in."""
 
