@@ -28,7 +28,7 @@
 
 #include "internal.hpp"
 
-#include "sigma_cluster_device.hpp"  // fp contraction is off from here on
+#include "sigma_cluster_device.hpp"  // the embedding and the geometries; fp contraction is off from here on
 
 namespace mlmcpi {
 
@@ -319,8 +319,166 @@ struct WolffRotatedTasks {
   }
 };
 
+// ---- the improved estimators of the single-cluster update ---------------------------------------------------
+// What the improved instances of the Wolff kernels carry beside the plain draw's arguments.  Per chain, in the workspace: the
+// slice table P_d(i) = the sum of q(a) over the members in slice i of direction d, [M_0 + M_1] int64, t slices first; the list
+// of the occupied slices of either direction, [M_0 + M_1] uint32; the accumulators, [kWolffSums + n_out] int64: A, Ac_0, As_0,
+// Ac_1, As_1, then one per (d, tau) in the layout of mlmcpi_sigma_level_correlator; the weights (w^s, w^c) of every slice,
+// [M_0 + M_1][2] double.  The kernel zeroes table and accumulators and forms the weights when it starts (sw_phase inside the
+// update loop costs the registers of its expansion across the whole loop, as in sigma_sw_chain.hip), and every update leaves
+// table and accumulators zero.  structure and corr may be NULL.
+constexpr uint32_t kWolffSums = 5;
+
+struct WolffImproved {
+  long long *table, *acc;
+  uint32_t *occupied;
+  double *weights;
+  double *improved, *structure, *corr;
+  uint32_t M0, M1;
+  double scale, inv_scale;   // 2^(s - 64) and 2^-s, s the fixed-point scale of the lag accumulators (sw_lag_scale)
+  __device__ __forceinline__ uint32_t slots() const { return kWolffSums + M0 / 2 + M1 / 2 + 2; }
+};
+
+// the sum of v over the lanes of the wave (every lane of the wave calls it)
+__device__ __forceinline__ long long wolff_wave_sum(long long v) {
+  for (int off = kWave / 2; off > 0; off >>= 1) v += __shfl_xor(v, off);
+  return v;
+}
+
+// the wave's sum of v onto *slot, one atomic per wave (every lane of the wave calls it)
+__device__ __forceinline__ void wolff_wave_add(long long *slot, long long v) {
+  v = wolff_wave_sum(v);
+  if ((threadIdx.x & (kWave - 1)) == 0 && v) __hip_atomic_fetch_add(slot, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+}
+
+__device__ __forceinline__ void wolff_improved_clear(const WolffImproved &w, uint32_t b, uint32_t lane, uint32_t T) {
+  const uint32_t M = w.M0 + w.M1, S = w.slots();
+  for (uint32_t i = lane; i < M; i += T) w.table[(size_t)b * M + i] = 0;
+  for (uint32_t k = lane; k < S; k += T) w.acc[(size_t)b * S + k] = 0;
+  if (w.structure)
+    for (uint32_t i = lane; i < M; i += T) {
+      double ws, wc;
+      sw_phase(i < w.M0 ? i : i - w.M0, i < w.M0 ? w.M0 : w.M1, ws, wc);
+      w.weights[2 * ((size_t)b * M + i)] = ws;
+      w.weights[2 * ((size_t)b * M + i) + 1] = wc;
+    }
+}
+
+// a member at (x0, x1) with a = r . sigma before the update: q(a) onto its two slices
+__device__ __forceinline__ void wolff_slice_add(const WolffImproved &w, uint32_t b, uint32_t x0, uint32_t x1, double a) {
+  long long *tab = w.table + (size_t)b * (w.M0 + w.M1);
+  const long long q = sw_fixed(a);
+  if (x0 < w.M0) __hip_atomic_fetch_add(tab + x0, q, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+  if (x1 < w.M1) __hip_atomic_fetch_add(tab + w.M0 + x1, q, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+}
+
+// The epilogue of an update whose `size` members have been added to the table; every lane of the team calls it and `count`
+// [2] is the team's in LDS.  Three phases with the team's fence between them; every sum is an integer sum and every output one
+// fixed expression of such sums, so the outputs do not depend on the team, on the order of the queue or on who adds first.
+// (1) Every slice of either direction: an occupied one (P != 0: the members of a cluster share the sign of a, so a slice with
+//     members sums to 0 only where every q(a) is 0, and then it contributes 0 everywhere; it is then also missing from w_d of
+//     (2), which can drop the largest lag of the slices either side of it: every member of such a slice has |a| < 2^-33, and a
+//     vertex other than the seed joins across a bond of probability <= 2 beta |a| < beta 2^-32) joins the list of its direction and
+//     adds P to A (direction t only) and llrint((double)P w) to Ac_d, As_d, (w^s, w^c) from sw_phase.
+// (2) Every lag tau <= min(M_d / 2, w_d - 1), w_d the occupied slices (a link moves the slice index by at most 1, so the
+//     occupied slices are an arc of the ring and larger lags pair nothing): the occupied slices i meet slice (i + tau) mod M_d
+//     of the table, llrint(((double)P (double)P') 2^(s - 64)) summed per wave and added to the accumulator of (d, tau).
+// (3) The outputs, each from its accumulator, which is zeroed again, and the occupied slices of the table back to 0.
+template <bool BLOCK>
+__device__ __forceinline__ void wolff_improved_finish(const WolffImproved &w, uint32_t b, uint32_t lane, uint32_t T, uint32_t size,
+                                                      uint32_t *count) {
+  const uint32_t M0 = w.M0, M1 = w.M1, M = M0 + M1, n_out = M0 / 2 + M1 / 2 + 2;
+  long long *tab = w.table + (size_t)b * M;
+  long long *acc = w.acc + (size_t)b * (kWolffSums + n_out);
+  uint32_t *occ = w.occupied + (size_t)b * M;
+  if (lane < 2) count[lane] = 0;
+  team_sync<BLOCK>();                                    // and the adds of the reflection pass have landed
+
+  long long sA = 0, c0 = 0, s0 = 0, c1 = 0, s1 = 0;
+  for (uint32_t i = lane; i < M; i += T) {
+    const long long P = __hip_atomic_load(tab + i, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+    if (P == 0) continue;
+    const bool d = i >= M0;
+    const uint32_t x = d ? i - M0 : i, Md = d ? M1 : M0;
+    if (w.structure) {
+      const double ws = w.weights[2 * ((size_t)b * M + i)], wc = w.weights[2 * ((size_t)b * M + i) + 1];
+      const long long c = llrint((double)P * wc), s = llrint((double)P * ws);
+      if (d) c1 += c, s1 += s;
+      else c0 += c, s0 += s;
+    }
+    if (!d) sA += P;
+    const uint32_t k = atomicAdd(count + (d ? 1 : 0), 1u);
+    if (k < Md) occ[(d ? M0 : 0) + k] = x;
+  }
+  wolff_wave_add(acc + 0, sA);
+  if (w.structure) {
+    wolff_wave_add(acc + 1, c0);
+    wolff_wave_add(acc + 2, s0);
+    wolff_wave_add(acc + 3, c1);
+    wolff_wave_add(acc + 4, s1);
+  }
+  team_sync<BLOCK>();
+
+  const uint32_t w0 = count[0] < M0 ? count[0] : M0, w1 = count[1] < M1 ? count[1] : M1;
+  if (w.corr) {
+#pragma unroll 1
+    for (uint32_t d = 0; d < 2; ++d) {
+      const uint32_t Md = d ? M1 : M0, wd = d ? w1 : w0, base = d ? M0 : 0;
+      long long *lag = acc + kWolffSums + (d ? M0 / 2 + 1 : 0);
+      const uint32_t ntau = wd == 0 ? 0 : (wd - 1 < Md / 2 ? wd - 1 : Md / 2) + 1;   // team uniform: the wave sums see whole waves
+      for (uint32_t tau = 0; tau < ntau; ++tau) {
+        long long part = 0;
+        for (uint32_t k = lane; k < wd; k += T) {
+          const uint32_t i = occ[base + k];
+          uint32_t j = i + tau;
+          if (j >= Md) j -= Md;
+          if (i < Md && j < Md) {
+            const long long P = __hip_atomic_load(tab + base + i, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+            const long long Q = tau ? __hip_atomic_load(tab + base + j, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP) : P;
+            part += llrint(((double)P * (double)Q) * w.scale);
+          }
+        }
+        wolff_wave_add(lag + tau, part);
+      }
+    }
+    team_sync<BLOCK>();
+  }
+
+  const double f = 3.0 / (double)size;
+  if (w.corr)
+    for (uint32_t k = lane; k < n_out; k += T) {
+      const long long v = __hip_atomic_load(acc + kWolffSums + k, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+      if (v) {
+        w.corr[(size_t)b * n_out + k] += ((double)v * w.inv_scale) * f;
+        acc[kWolffSums + k] = 0;
+      }
+    }
+  for (uint32_t k = lane; k < w0; k += T) {
+    const uint32_t i = occ[k];
+    if (i < M0) tab[i] = 0;
+  }
+  for (uint32_t k = lane; k < w1; k += T) {
+    const uint32_t i = occ[M0 + k];
+    if (i < M1) tab[M0 + i] = 0;
+  }
+  if (lane == 0) {
+    const double x = (double)__hip_atomic_load(acc + 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP) * (1.0 / kSwFix);
+    w.improved[b] += (x * x) * f;
+    acc[0] = 0;
+    if (w.structure)
+      for (uint32_t d = 0; d < 2; ++d) {
+        const double xc = (double)__hip_atomic_load(acc + 1 + 2 * d, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP) * (1.0 / kSwFix);
+        const double xs = (double)__hip_atomic_load(acc + 2 + 2 * d, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP) * (1.0 / kSwFix);
+        w.structure[(size_t)b * 2 + d] += (xc * xc) * f;
+        w.structure[(size_t)b * 2 + d] += (xs * xs) * f;
+        acc[1 + 2 * d] = 0;
+        acc[2 + 2 * d] = 0;
+      }
+  }
+}
+
 // The update of the two kernels above, decision by decision (the same state and cluster_sites bits), on either geometry, with
-// the improved estimators of wolff_improved_finish (sigma_cluster_device.hpp): the reflection pass adds q(a) of every member to
+// the improved estimators of wolff_improved_finish (above): the reflection pass adds q(a) of every member to
 // the chain's slice table, the epilogue of the update turns the table into chi^W, F_d^W and C_d^W(tau) and leaves it zero.
 template <class Tasks, bool BLOCK, bool LDS_MAP>
 __global__ void __launch_bounds__(BLOCK ? kClusterBlockThreads : kClusterThreads)
@@ -488,8 +646,7 @@ size_t sc_workspace(uint32_t N, uint32_t B) { return sc_section_a(N, B) + sc_sec
 // table [M0 + M1] int64, the accumulators [kWolffSums + n_out] int64, the occupied slices [M0 + M1] uint32 and the weights
 // [M0 + M1][2] double.  In the workspace
 // and not in LDS: at 1024 x 1024 the table is 16 KiB a chain beside the workgroup team's 128 KiB bitmap, and a
-// wave-team workgroup would hold four of them beside its four bitmaps.  s as in sigma_sw.hip (sw_corr): one cluster's
-// sum_i |P(i)| |P(i + tau)| is at most N N_slice as well.
+// wave-team workgroup would hold four of them beside its four bitmaps.  n_out and s from sw_lag_scale, where the bound is.
 struct ScImprovedLayout {
   uint32_t M0, M1, n_out, s;
   size_t table_bytes, acc_bytes, occupied_bytes, weights_bytes;
@@ -500,11 +657,9 @@ ScImprovedLayout sc_improved_layout(uint32_t N, uint32_t M0, uint32_t M1, uint32
   ScImprovedLayout c{};
   c.M0 = M0;
   c.M1 = M1;
-  c.n_out = M0 / 2 + M1 / 2 + 2;
-  const uint64_t bound = (uint64_t)N * (N / (M0 < M1 ? M0 : M1));
-  uint32_t lb = 0;
-  while ((1ull << lb) < bound) ++lb;
-  c.s = 62 - lb < 32 ? 62 - lb : 32;
+  const SwLagScale lags = sw_lag_scale(N, M0, M1);
+  c.n_out = lags.n_out;
+  c.s = lags.s;
   c.table_bytes = align256((size_t)B * (M0 + M1) * sizeof(long long));
   c.acc_bytes = align256((size_t)B * (kWolffSums + c.n_out) * sizeof(long long));
   c.occupied_bytes = align256((size_t)B * (M0 + M1) * sizeof(uint32_t));

@@ -31,6 +31,13 @@ def _check_state(x, n):
     assert x.dtype == torch.float64 and x.dim() == 2 and x.shape[1] == n, (x.shape, n)
 
 
+def _workspace(query, *args, device="cuda"):
+    """uint8 tensor of the size the ABI's `query`(*args, &bytes) asks for"""
+    nbytes = C.c_size_t(0)
+    abi.call(query, *args, C.byref(nbytes))
+    return torch.empty(nbytes.value, dtype=torch.uint8, device=device)
+
+
 # ---- 1-D paths -----------------------------------------------------------------------------------
 def path_evaluate(act, x):
     _check_state(x, act.M)
@@ -69,9 +76,7 @@ class PathHMC:
 
     def __init__(self, act, B, nt, dt, n_rep=1, seed=1, chain0=0, device="cuda"):
         self.act, self.B, self.nt, self.dt, self.n_rep, self.seed, self.chain0 = act, B, nt, dt, n_rep, seed, chain0
-        nbytes = C.c_size_t(0)
-        abi.call("mlmcpi_path_hmc_workspace_bytes", C.byref(act), B, nt, C.byref(nbytes))
-        self.work = torch.empty(nbytes.value, dtype=torch.uint8, device=device)
+        self.work = _workspace("mlmcpi_path_hmc_workspace_bytes", C.byref(act), B, nt, device=device)
         self.accept = torch.zeros(B, dtype=torch.int32, device=device)
         self.energies = torch.zeros((B, 4), dtype=torch.float64, device=device)
         self.traj = 0
@@ -133,9 +138,7 @@ def path_correlator_plan(act, n_lag, B):
 
 def path_correlator_workspace(act, n_lag, B, device="cuda"):
     """workspace of path_correlator for B chains and n_lag lags (uint8 tensor)"""
-    nbytes = C.c_size_t(0)
-    abi.call("mlmcpi_path_correlator_workspace_bytes", C.byref(act), n_lag, B, C.byref(nbytes))
-    return torch.empty(nbytes.value, dtype=torch.uint8, device=device)
+    return _workspace("mlmcpi_path_correlator_workspace_bytes", C.byref(act), n_lag, B, device=device)
 
 
 def path_correlator(act, x, n_lag, acc=None, work=None):
@@ -157,9 +160,7 @@ class PathTwoLevelStep:
 
     def __init__(self, fine, coarse, B, seed=1, chain0=0, device="cuda"):
         self.fine, self.coarse, self.B, self.seed, self.chain0 = fine, coarse, B, seed, chain0
-        nbytes = C.c_size_t(0)
-        abi.call("mlmcpi_path_twolevel_workspace_bytes", C.byref(fine), B, C.byref(nbytes))
-        self.work = torch.empty(nbytes.value, dtype=torch.uint8, device=device)
+        self.work = _workspace("mlmcpi_path_twolevel_workspace_bytes", C.byref(fine), B, device=device)
         self.accept = torch.zeros(B, dtype=torch.int32, device=device)
         self.terms = torch.zeros((B, 3), dtype=torch.float64, device=device)
         self.theta = torch.zeros((B, fine.M), dtype=torch.float64, device=device)  # current fine state
@@ -207,9 +208,7 @@ class GFFExactSampler:
 
     def __init__(self, act, B, seed=1, chain0=0, device="cuda"):
         self.act, self.B, self.seed, self.chain0 = act, B, seed, chain0
-        nbytes = C.c_size_t(0)
-        abi.call("mlmcpi_lattice_exact_workspace_bytes", C.byref(act), B, C.byref(nbytes))
-        self.work = torch.empty(nbytes.value, dtype=torch.uint8, device=device)
+        self.work = _workspace("mlmcpi_lattice_exact_workspace_bytes", C.byref(act), B, device=device)
         self.step = 0
 
     def draw(self, phi=None):
@@ -229,9 +228,7 @@ class LatticeTwoLevelStep:
         """cfa_kind 0: the conditioned fine action the reference's factory picks for the lattice; 1: the Gaussian variant
         (QuenchedSchwingerGaussianConditionedFineAction; lattices coarsened in both directions)"""
         self.fine, self.coarse, self.B, self.seed, self.chain0, self.cfa_kind = fine, coarse, B, seed, chain0, cfa_kind
-        nbytes = C.c_size_t(0)
-        abi.call("mlmcpi_lattice_twolevel_workspace_bytes", C.byref(fine), C.byref(coarse), B, C.byref(nbytes))
-        self.work = torch.empty(nbytes.value, dtype=torch.uint8, device=device)
+        self.work = _workspace("mlmcpi_lattice_twolevel_workspace_bytes", C.byref(fine), C.byref(coarse), B, device=device)
         self.accept = torch.zeros(B, dtype=torch.int32, device=device)
         self.terms = torch.zeros((B, 3), dtype=torch.float64, device=device)
         self.theta = torch.zeros((B, 2 * fine.Mt * fine.Mx), dtype=torch.float64, device=device)  # current fine state
@@ -393,9 +390,7 @@ def lattice_sweep_plan(act, B, n_overrelax, n_heatbath, fuse=0):
 
 def lattice_random_sweep_workspace(act, B, device="cuda"):
     """workspace of lattice_random_sweep_draw for B chains (uint8 tensor)"""
-    nbytes = C.c_size_t(0)
-    abi.call("mlmcpi_lattice_random_sweep_workspace_bytes", C.byref(act), B, C.byref(nbytes))
-    return torch.empty(nbytes.value, dtype=torch.uint8, device=device)
+    return _workspace("mlmcpi_lattice_random_sweep_workspace_bytes", C.byref(act), B, device=device)
 
 
 def lattice_random_sweep_draw(act, phi, n_overrelax, n_heatbath, seed, chain0, sweep0, work=None):
@@ -410,9 +405,7 @@ def lattice_random_sweep_draw(act, phi, n_overrelax, n_heatbath, seed, chain0, s
 
 def sigma_cluster_workspace(act, B, device="cuda"):
     """workspace of sigma_cluster_draw for B chains (uint8 tensor)"""
-    nbytes = C.c_size_t(0)
-    abi.call("mlmcpi_sigma_cluster_workspace_bytes", C.byref(act), B, C.byref(nbytes))
-    return torch.empty(nbytes.value, dtype=torch.uint8, device=device)
+    return _workspace("mlmcpi_sigma_cluster_workspace_bytes", C.byref(act), B, device=device)
 
 
 def sigma_cluster_draw(act, x, n_updates, seed, chain0, update0, count=True, work=None):
@@ -430,9 +423,7 @@ def sigma_cluster_draw(act, x, n_updates, seed, chain0, update0, count=True, wor
 
 def sigma_sw_workspace(act, B, device="cuda"):
     """workspace of sigma_sw_draw for B chains (uint8 tensor)"""
-    nbytes = C.c_size_t(0)
-    abi.call("mlmcpi_sigma_sw_workspace_bytes", C.byref(act), B, C.byref(nbytes))
-    return torch.empty(nbytes.value, dtype=torch.uint8, device=device)
+    return _workspace("mlmcpi_sigma_sw_workspace_bytes", C.byref(act), B, device=device)
 
 
 def sigma_sw_draw(act, x, n_updates, seed, chain0, update0, outputs=True, work=None):
@@ -489,9 +480,7 @@ def sigma_level_correlator_size(level):
 
 def sigma_level_correlator_workspace(level, B, device="cuda"):
     """workspace of sigma_level_correlator for B chains (uint8 tensor)"""
-    nbytes = C.c_size_t(0)
-    abi.call("mlmcpi_sigma_level_correlator_workspace_bytes", C.byref(level), B, C.byref(nbytes))
-    return torch.empty(nbytes.value, dtype=torch.uint8, device=device)
+    return _workspace("mlmcpi_sigma_level_correlator_workspace_bytes", C.byref(level), B, device=device)
 
 
 def sigma_level_correlator(level, x, acc=None, work=None):
@@ -533,9 +522,7 @@ def sigma_level_copy_from_coarse(fine_level, coarse, fine):
 
 def sigma_level_cluster_workspace(level, B, device="cuda"):
     """workspace of sigma_level_cluster_draw for B chains (uint8 tensor)"""
-    nbytes = C.c_size_t(0)
-    abi.call("mlmcpi_sigma_level_cluster_workspace_bytes", C.byref(level), B, C.byref(nbytes))
-    return torch.empty(nbytes.value, dtype=torch.uint8, device=device)
+    return _workspace("mlmcpi_sigma_level_cluster_workspace_bytes", C.byref(level), B, device=device)
 
 
 def sigma_level_cluster_draw(level, x, n_updates, seed, chain0, update0, count=True, work=None):
@@ -553,9 +540,7 @@ def sigma_level_cluster_draw(level, x, n_updates, seed, chain0, update0, count=T
 
 def sigma_level_cluster_improved_workspace(level, B, device="cuda"):
     """workspace of sigma_level_cluster_improved_draw for B chains (uint8 tensor): the plain draw's plus the slice table"""
-    nbytes = C.c_size_t(0)
-    abi.call("mlmcpi_sigma_level_cluster_improved_workspace_bytes", C.byref(level), B, C.byref(nbytes))
-    return torch.empty(nbytes.value, dtype=torch.uint8, device=device)
+    return _workspace("mlmcpi_sigma_level_cluster_improved_workspace_bytes", C.byref(level), B, device=device)
 
 
 def sigma_level_cluster_improved_draw(level, x, n_updates, seed, chain0, update0, work=None, structure=False, correlator=False):
@@ -578,23 +563,17 @@ def sigma_level_cluster_improved_draw(level, x, n_updates, seed, chain0, update0
 
 def sigma_level_sw_workspace(level, B, device="cuda"):
     """workspace of sigma_level_sw_draw for B chains (uint8 tensor)"""
-    nbytes = C.c_size_t(0)
-    abi.call("mlmcpi_sigma_level_sw_workspace_bytes", C.byref(level), B, C.byref(nbytes))
-    return torch.empty(nbytes.value, dtype=torch.uint8, device=device)
+    return _workspace("mlmcpi_sigma_level_sw_workspace_bytes", C.byref(level), B, device=device)
 
 
 def sigma_level_sw_structure_workspace(level, B, device="cuda"):
     """workspace of sigma_level_sw_draw(..., structure=True) for B chains (uint8 tensor): 32 B per vertex and chain more"""
-    nbytes = C.c_size_t(0)
-    abi.call("mlmcpi_sigma_level_sw_structure_workspace_bytes", C.byref(level), B, C.byref(nbytes))
-    return torch.empty(nbytes.value, dtype=torch.uint8, device=device)
+    return _workspace("mlmcpi_sigma_level_sw_structure_workspace_bytes", C.byref(level), B, device=device)
 
 
 def sigma_level_sw_correlator_workspace(level, B, device="cuda"):
     """workspace of sigma_level_sw_draw(..., correlator=True) for B chains (uint8 tensor): the plain draw's plus the slice tables"""
-    nbytes = C.c_size_t(0)
-    abi.call("mlmcpi_sigma_level_sw_correlator_workspace_bytes", C.byref(level), B, C.byref(nbytes))
-    return torch.empty(nbytes.value, dtype=torch.uint8, device=device)
+    return _workspace("mlmcpi_sigma_level_sw_correlator_workspace_bytes", C.byref(level), B, device=device)
 
 
 def sigma_level_sw_draw(level, x, n_updates, seed, chain0, update0, outputs=True, work=None, structure=False, correlator=False):
@@ -656,9 +635,7 @@ class SigmaTwoLevelStep:
 
     def __init__(self, fine, coarse, B, seed=1, chain0=0, device="cuda"):
         self.fine, self.coarse, self.B, self.seed, self.chain0 = fine, coarse, B, seed, chain0
-        nbytes = C.c_size_t(0)
-        abi.call("mlmcpi_sigma_twolevel_workspace_bytes", C.byref(fine), B, C.byref(nbytes))
-        self.work = torch.empty(nbytes.value, dtype=torch.uint8, device=device)
+        self.work = _workspace("mlmcpi_sigma_twolevel_workspace_bytes", C.byref(fine), B, device=device)
         self.accept = torch.zeros(B, dtype=torch.int32, device=device)
         self.terms = torch.zeros((B, 3), dtype=torch.float64, device=device)
         self.theta = torch.zeros((B, sigma_level_size(fine)), dtype=torch.float64, device=device)  # current fine state
@@ -767,9 +744,7 @@ class LatticeHMC:
 
     def __init__(self, act, B, nt, dt, n_rep=1, seed=1, chain0=0, device="cuda"):
         self.act, self.B, self.nt, self.dt, self.n_rep, self.seed, self.chain0 = act, B, nt, dt, n_rep, seed, chain0
-        nbytes = C.c_size_t(0)
-        abi.call("mlmcpi_lattice_hmc_workspace_bytes", C.byref(act), B, C.byref(nbytes))
-        self.work = torch.empty(nbytes.value, dtype=torch.uint8, device=device)
+        self.work = _workspace("mlmcpi_lattice_hmc_workspace_bytes", C.byref(act), B, device=device)
         self.accept = torch.zeros(B, dtype=torch.int32, device=device)
         self.energies = torch.zeros((B, 4), dtype=torch.float64, device=device)
         self.traj = 0

@@ -12,7 +12,9 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "mlmcpathintegral_amd", "csrc")
 SAMPLER_HEADERS = {"vonmises.hpp", "step_envelope.hpp", "site_update.hpp", "fillin.hpp"}
 UNITS_WITHOUT_SAMPLER = ("path1d", "path_hmc", "ho_exact", "lattice_reduce", "lattice_hmc", "gff_exact", "gff_levels", "cluster",
-                         "sigma_cluster", "sigma_sw", "sigma_levels", "sigma_twolevel", "schwinger_or_block")
+                         "sigma_cluster", "sigma_sw", "sigma_sw_tiled", "sigma_sw_chain", "sigma_sw_correlator", "sigma_levels",
+                         "sigma_twolevel", "schwinger_or_block")
+SW_UNITS = ("sigma_sw", "sigma_sw_tiled", "sigma_sw_chain", "sigma_sw_correlator")
 
 
 def _hipcc():
@@ -30,12 +32,36 @@ def test_every_header_compiles_on_its_own():
     assert r.returncode == 0, r.stdout + r.stderr
 
 
+def _deps(build, unit):
+    with open(os.path.join(build, unit + ".d")) as f:
+        deps = {os.path.basename(w.rstrip(":")) for w in re.split(r"[\s\\]+", f.read()) if w}
+    assert unit + ".hip" in deps and "device_common.hpp" in deps, (unit, sorted(deps))   # the file is what it should be
+    return deps
+
+
 def test_units_without_a_sampler_include_no_sampler_header():
     build = os.path.join(CSRC, "build")
     if not os.path.isdir(build):
         pytest.skip("no built tree")
     for unit in UNITS_WITHOUT_SAMPLER:
-        with open(os.path.join(build, unit + ".d")) as f:
-            deps = {os.path.basename(w.rstrip(":")) for w in re.split(r"[\s\\]+", f.read()) if w}
-        assert unit + ".hip" in deps and "device_common.hpp" in deps, (unit, sorted(deps))   # the file is what it should be
+        deps = _deps(build, unit)
         assert not deps & SAMPLER_HEADERS, (unit, sorted(deps & SAMPLER_HEADERS))
+
+
+def test_the_cluster_samplers_share_the_embedding_and_nothing_of_each_other():
+    """Wolff (sigma_cluster) and Swendsen-Wang (sigma_sw*) meet in sigma_cluster_device.hpp only: the Wolff unit does not see
+    the Swendsen-Wang device library or its host header, and the Wolff-only device code is in sigma_cluster.hip itself, which no
+    unit includes."""
+    build = os.path.join(CSRC, "build")
+    if not os.path.isdir(build):
+        pytest.skip("no built tree")
+    wolff = _deps(build, "sigma_cluster")
+    assert "sigma_cluster_device.hpp" in wolff
+    assert not wolff & {"sigma_sw_device.hpp", "sigma_sw_host.hpp"}, sorted(wolff)
+    with open(os.path.join(CSRC, "sigma_cluster_device.hpp")) as f:
+        shared = f.read()
+    assert "wolff_" not in shared and "WolffImproved" not in shared and "uf_union" not in shared
+    for unit in SW_UNITS:
+        deps = _deps(build, unit)
+        assert {"sigma_cluster_device.hpp", "sigma_sw_host.hpp"} <= deps, (unit, sorted(deps))
+        assert "sigma_cluster.hip" not in deps, (unit, sorted(deps))

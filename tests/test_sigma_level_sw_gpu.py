@@ -176,6 +176,28 @@ def test_the_chain_plan_beyond_its_capacity_is_refused(gpu_ops):
     assert torch.equal(x, x0)
 
 
+# ---- guard bands ------------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("plan,tile", [("chain", ""), ("tiled", "8x8")])
+@pytest.mark.parametrize("rot", [1, 0])
+def test_nothing_outside_the_workspace_is_written_and_its_content_at_entry_is_ignored(gpu_ops, rot, plan, tile):
+    """(12, 10), three chains, three updates; tiles of 8 x 8: 2 x 2 masked tiles on the lattice, one tile of 6 x 5 cells whose wrap
+    links all cross on the level.  The workspace sits in a buffer of 0xA5 with 256 B either side: both bands stay, and the state
+    and outputs are the bits of a run on a zeroed workspace of exactly the queried size."""
+    ops, B, n = gpu_ops, 3, 3
+    lv = _level(12, 10, rot, 1.5)
+    x0 = _thermalised(ops, lv, B, 9)
+    need = ops.sigma_level_sw_workspace(lv, B).numel()
+    with _plan(plan, tile):
+        ref, want = x0.clone(), _zeros(B)
+        _draw_into(ops, lv, ref, n, 10, 1, 3, want, work=torch.zeros(need, dtype=torch.uint8, device="cuda"))
+        wbuf = torch.full((256 + need + 256,), 0xA5, dtype=torch.uint8, device="cuda")
+        x, out = x0.clone(), _zeros(B)
+        _draw_into(ops, lv, x, n, 10, 1, 3, out, work=wbuf[256:256 + need])
+    assert (wbuf[:256] == 0xA5).all() and (wbuf[256 + need:] == 0xA5).all()
+    assert torch.equal(x, ref) and _same(out, want)
+    assert not torch.equal(ref, x0) and (want[1] > 0).all()
+
+
 # ---- an unrotated level is mlmcpi_sigma_sw_draw -----------------------------------------------------------------------------
 @pytest.mark.parametrize("Mt,Mx", [(16, 16), (130, 70)])
 def test_unrotated_level_gives_the_bits_and_the_workspace_of_the_lattice_entry_point(gpu_ops, Mt, Mx):
