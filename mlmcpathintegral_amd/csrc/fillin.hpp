@@ -1,6 +1,6 @@
 // fillin.hpp -- the densities and fill-in distributions of the Schwinger two-level step: -log of the ExpCos density, the
 // Bessel-product draw (exact and approximate) and the Gaussian fill-in of a 2 x 2 block.  Included by lattice_twolevel.hip,
-// and by runtime.hip for the test hook of bessel_i0 (mlmcpi_test_math).
+// and by test_math.hip for the test hook of bessel_i0 (mlmcpi_test_math).
 #pragma once
 #include "device_common.hpp"
 #include "vonmises.hpp"

@@ -6,6 +6,7 @@
 
 #include "../../include/mlmcpi_hip.h"
 #include "device_common.hpp"
+#include "device_once.hpp"
 
 namespace mlmcpi {
 
@@ -33,6 +34,15 @@ int fail_hip(hipError_t e, const char *what);
 
 inline hipStream_t as_stream(void *s) { return (hipStream_t)s; }
 
+// init() once for the current device (device_once.hpp): what a unit's kernels need before their first launch there
+template <class Init>
+int once_per_device(DeviceOnce &once, Init init) {
+  int dev = 0;
+  MLMCPI_HIP_TRY(hipGetDevice(&dev));
+  const int rc = device_once(once, dev, init);
+  return rc == kDeviceOutOfRange ? fail(MLMCPI_ERR_INVALID, "device index %d out of range", dev) : rc;
+}
+
 // Library-owned scratch for reduction partials: one buffer per (host thread, device, stream), grown on demand (the
 // first call of a given size allocates; steady state does not).  `stream` = the stream the caller launches on.
 int scratch(size_t bytes, void **d_ptr, hipStream_t stream);
@@ -42,7 +52,8 @@ inline RngKey make_key(uint64_t seed, uint32_t chain0, uint32_t step) {
 }
 
 // Tuning knobs (they never change results): read from the environment ONCE, at the first sweep call of the process, and
-// settable afterwards through mlmcpi_set_option (tests flip them between calls).
+// settable afterwards through mlmcpi_set_option (tests flip them between calls).  A new knob is a field here and an entry in the
+// table of options.hip.
 struct Tuning {
   uint32_t tile_w = 0, tile_h = 0, tile_nt = 0;  // MLMCPI_SWEEP_TILE=TWxTHxNT (0: default geometry)
   bool or_block = false;                         // MLMCPI_OR_KERNEL=block: 4 x 4 register blocks sweep by sweep instead of the closed form (Schwinger)
@@ -60,7 +71,7 @@ struct Tuning {
 Tuning tuning();  // a copy taken under the lock: callers snapshot it once per call
 
 // Table of the step-envelope heat-bath sampler for an action of the given scale (2 beta, 2 m0 / a), in the memory of the
-// current device: built and uploaded on first use (step_envelope.hpp, runtime.hip).
+// current device: built and uploaded on first use (step_envelope.hpp, step_envelope_tables.hip).
 int vs_table_device(double scale, const uint32_t **d_table);
 
 // the O(3) nonlinear sigma model (sigma2d.hip); arguments checked by the lattice entry points that dispatch here

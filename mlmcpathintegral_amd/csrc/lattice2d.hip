@@ -16,7 +16,6 @@
 // Reductions, force and HMC, level transfers and the two-level step, and the exact GFF sampler are in lattice_reduce.hip,
 // lattice_hmc.hip, lattice_twolevel.hip and gff_exact.hip.
 #include <algorithm>
-#include <mutex>
 
 #include <stdio.h>
 #include <string.h>
@@ -28,18 +27,13 @@
 namespace mlmcpi {
 
 // hipFuncSetAttribute applies to the current device: once per device, under a lock (one process may drive several GPUs)
-static std::mutex g_lds_attr_mutex;
-static bool g_lds_attr_set[64] = {false};
+static DeviceOnce g_lds_attr_once;
 static int init_sweep_kernels() {
-  int dev = 0;
-  MLMCPI_HIP_TRY(hipGetDevice(&dev));
-  if (dev < 0 || dev >= 64) return fail(MLMCPI_ERR_INVALID, "device index %d out of range", dev);
-  std::lock_guard<std::mutex> lock(g_lds_attr_mutex);
-  if (g_lds_attr_set[dev]) return MLMCPI_OK;
-  if (int rc = schwinger_allow_lds()) return rc;
-  if (int rc = gff_allow_lds()) return rc;
-  g_lds_attr_set[dev] = true;
-  return MLMCPI_OK;
+  return once_per_device(g_lds_attr_once, []() -> int {
+    if (int rc = schwinger_allow_lds()) return rc;
+    if (int rc = gff_allow_lds()) return rc;
+    return MLMCPI_OK;
+  });
 }
 
 // ---- launch plan: the per-draw constants; next_launch is the only place that chooses kernels.  No HIP call in here. ----

@@ -23,8 +23,6 @@
 // workspace, and every barrier comes with a workgroup-scope fence.
 #include <hipcub/hipcub.hpp>
 
-#include <mutex>
-
 #include "internal.hpp"
 #include "site_update.hpp"
 #include "step_envelope.hpp"
@@ -205,23 +203,18 @@ __global__ void __launch_bounds__(256) rs_order_kernel(const uint64_t *__restric
   if (t < total) order[t] = (uint32_t)sorted[t];
 }
 
-std::mutex g_rs_attr_mutex;
-bool g_rs_attr_set[64] = {false};
+DeviceOnce g_rs_attr_once;
 
 int rs_init_attrs() {
-  int dev = 0;
-  MLMCPI_HIP_TRY(hipGetDevice(&dev));
-  if (dev < 0 || dev >= 64) return fail(MLMCPI_ERR_INVALID, "device index %d out of range", dev);
-  std::lock_guard<std::mutex> lock(g_rs_attr_mutex);
-  if (g_rs_attr_set[dev]) return MLMCPI_OK;
+  return once_per_device(g_rs_attr_once, []() -> int {
 #define RS_ATTR(ACT, NT) \
   MLMCPI_HIP_TRY(hipFuncSetAttribute((const void *)random_sweep_kernel<ACT, true, NT>, hipFuncAttributeMaxDynamicSharedMemorySize, kRsLdsMax))
-  RS_ATTR(RS_GFF, 256); RS_ATTR(RS_GFF, 1024);
-  RS_ATTR(RS_SCHW, 256); RS_ATTR(RS_SCHW, 1024);
-  RS_ATTR(RS_SIGMA, 256);  // the sigma model's update needs ~170 VGPRs: 256 threads (1024 would spill to scratch)
+    RS_ATTR(RS_GFF, 256); RS_ATTR(RS_GFF, 1024);
+    RS_ATTR(RS_SCHW, 256); RS_ATTR(RS_SCHW, 1024);
+    RS_ATTR(RS_SIGMA, 256);  // the sigma model's update needs ~170 VGPRs: 256 threads (1024 would spill to scratch)
 #undef RS_ATTR
-  g_rs_attr_set[dev] = true;
-  return MLMCPI_OK;
+    return MLMCPI_OK;
+  });
 }
 
 // kind and extents; *act_out = the kernel's action, *n = the size of the index set

@@ -12,8 +12,6 @@
 //
 // Randomness: heat bath of vertex l in sweep s = ONE Philox call (site l, chain, step sweep0 + s, P_SIGMA_HB, sub 0) ->
 // (u, v); initialise: P_INIT, one uniform per state entry (entry 2l -> cos theta = 1 - 2u, 2l + 1 -> phi = 2 pi u - pi).
-#include <mutex>
-
 #include "lattice_sweep.hpp"
 
 #include "sigma_device.hpp"  // fp contraction is off from here on
@@ -228,8 +226,7 @@ namespace {
 
 uint32_t sigma_blocks(uint32_t N, uint32_t B) { return row_blocks((N + 255) / 256, B); }  // workgroups of 256 per chain
 
-std::mutex g_sigma_attr_mutex;
-bool g_sigma_attr_set[64] = {false};
+DeviceOnce g_sigma_attr_once;
 
 template <int OP>
 int sigma_reduce(uint32_t Mt, uint32_t Mx, const double *d_phi, uint32_t B, double scale, double *d_out, hipStream_t st) {
@@ -247,16 +244,12 @@ int sigma_reduce(uint32_t Mt, uint32_t Mx, const double *d_phi, uint32_t B, doub
 }  // namespace
 
 int sigma_init_sweep_kernels() {  // once per draw: the sweep kernel may take the whole LDS (of the current device)
-  int dev = 0;
-  MLMCPI_HIP_TRY(hipGetDevice(&dev));
-  if (dev < 0 || dev >= 64) return fail(MLMCPI_ERR_INVALID, "device index %d out of range", dev);
-  std::lock_guard<std::mutex> lock(g_sigma_attr_mutex);
-  if (g_sigma_attr_set[dev]) return MLMCPI_OK;
-  MLMCPI_HIP_TRY(hipFuncSetAttribute((const void *)sigma_sweep_kernel<256>, hipFuncAttributeMaxDynamicSharedMemorySize, kSigmaLdsMax));
-  MLMCPI_HIP_TRY(hipFuncSetAttribute((const void *)sigma_sweep_kernel<512>, hipFuncAttributeMaxDynamicSharedMemorySize, kSigmaLdsMax));
-  MLMCPI_HIP_TRY(hipFuncSetAttribute((const void *)sigma_sweep_kernel<1024>, hipFuncAttributeMaxDynamicSharedMemorySize, kSigmaLdsMax));
-  g_sigma_attr_set[dev] = true;
-  return MLMCPI_OK;
+  return once_per_device(g_sigma_attr_once, []() -> int {
+    MLMCPI_HIP_TRY(hipFuncSetAttribute((const void *)sigma_sweep_kernel<256>, hipFuncAttributeMaxDynamicSharedMemorySize, kSigmaLdsMax));
+    MLMCPI_HIP_TRY(hipFuncSetAttribute((const void *)sigma_sweep_kernel<512>, hipFuncAttributeMaxDynamicSharedMemorySize, kSigmaLdsMax));
+    MLMCPI_HIP_TRY(hipFuncSetAttribute((const void *)sigma_sweep_kernel<1024>, hipFuncAttributeMaxDynamicSharedMemorySize, kSigmaLdsMax));
+    return MLMCPI_OK;
+  });
 }
 
 int sigma_evaluate(const mlmcpi_lattice_action *act, const double *d_phi, uint32_t B, double *d_S, hipStream_t st) {

@@ -24,8 +24,6 @@
 //   P_SIGMA_REFLECT  site 0, sub 0: (u, v) -> r_z = 1 - 2 u, azimuth 2 pi v - pi;  sub 1: u -> seed vertex min(floor(u N), N - 1)
 //   P_SIGMA_BOND     unrotated: site l, sub 0: u decides link (l, 0), v decides link (l, 1)
 //                    rotated:   site e (the E end), sub d >> 1: u decides link (e, d) for d even, v for d odd
-#include <mutex>
-
 #include "internal.hpp"
 
 #include "sigma_cluster_device.hpp"  // the embedding and the geometries; fp contraction is off from here on
@@ -604,26 +602,21 @@ ScPlan sc_plan(uint32_t N, uint32_t B, const Tuning &tune) {
   return p;
 }
 
-std::mutex g_sc_attr_mutex;
-bool g_sc_attr_set[64] = {false};
+DeviceOnce g_sc_attr_once;
 
 // dynamic LDS above 64 KiB: the workgroup team's bitmap up to its bound, on either geometry
 int sc_init_attrs() {
-  int dev = 0;
-  MLMCPI_HIP_TRY(hipGetDevice(&dev));
-  if (dev < 0 || dev >= 64) return fail(MLMCPI_ERR_INVALID, "device index %d out of range", dev);
-  std::lock_guard<std::mutex> lock(g_sc_attr_mutex);
-  if (g_sc_attr_set[dev]) return MLMCPI_OK;
-  MLMCPI_HIP_TRY(hipFuncSetAttribute((const void *)sigma_cluster_kernel<true, true>,
-                                     hipFuncAttributeMaxDynamicSharedMemorySize, kScBlockLdsWords * sizeof(uint32_t)));
-  MLMCPI_HIP_TRY(hipFuncSetAttribute((const void *)sigma_rot_cluster_kernel<true, true>,
-                                     hipFuncAttributeMaxDynamicSharedMemorySize, kScBlockLdsWords * sizeof(uint32_t)));
-  MLMCPI_HIP_TRY(hipFuncSetAttribute((const void *)sigma_cluster_improved_kernel<WolffLatticeTasks, true, true>,
-                                     hipFuncAttributeMaxDynamicSharedMemorySize, kScBlockLdsWords * sizeof(uint32_t)));
-  MLMCPI_HIP_TRY(hipFuncSetAttribute((const void *)sigma_cluster_improved_kernel<WolffRotatedTasks, true, true>,
-                                     hipFuncAttributeMaxDynamicSharedMemorySize, kScBlockLdsWords * sizeof(uint32_t)));
-  g_sc_attr_set[dev] = true;
-  return MLMCPI_OK;
+  return once_per_device(g_sc_attr_once, []() -> int {
+    MLMCPI_HIP_TRY(hipFuncSetAttribute((const void *)sigma_cluster_kernel<true, true>,
+                                       hipFuncAttributeMaxDynamicSharedMemorySize, kScBlockLdsWords * sizeof(uint32_t)));
+    MLMCPI_HIP_TRY(hipFuncSetAttribute((const void *)sigma_rot_cluster_kernel<true, true>,
+                                       hipFuncAttributeMaxDynamicSharedMemorySize, kScBlockLdsWords * sizeof(uint32_t)));
+    MLMCPI_HIP_TRY(hipFuncSetAttribute((const void *)sigma_cluster_improved_kernel<WolffLatticeTasks, true, true>,
+                                       hipFuncAttributeMaxDynamicSharedMemorySize, kScBlockLdsWords * sizeof(uint32_t)));
+    MLMCPI_HIP_TRY(hipFuncSetAttribute((const void *)sigma_cluster_improved_kernel<WolffRotatedTasks, true, true>,
+                                       hipFuncAttributeMaxDynamicSharedMemorySize, kScBlockLdsWords * sizeof(uint32_t)));
+    return MLMCPI_OK;
+  });
 }
 
 int sc_check(const mlmcpi_lattice_action *act, const char *what) {

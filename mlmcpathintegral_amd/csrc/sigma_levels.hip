@@ -5,8 +5,6 @@
 // The rotated sweep keeps the canonical form of sigma2d.hip: neighbours are read as sigma(stored angles), what stays in LDS
 // after an update is sigma(angles_of(sigma')), and the file is compiled without fp contraction; so a draw gives the same bits
 // whatever tile, workgroup size, fuse depth or batch split the launch uses.
-#include <mutex>
-
 #include "internal.hpp"
 
 #include "sigma_level_device.hpp"  // fp contraction is off from here on
@@ -175,20 +173,15 @@ RotPlan rot_plan(const SigmaLevel &L, const Tuning &t) {
   return p;
 }
 
-std::mutex g_rot_attr_mutex;
-bool g_rot_attr_set[64] = {false};
+DeviceOnce g_rot_attr_once;
 
 int rot_init_sweep_kernels() {  // the sweep kernel may take the whole LDS (of the current device)
-  int dev = 0;
-  MLMCPI_HIP_TRY(hipGetDevice(&dev));
-  if (dev < 0 || dev >= 64) return fail(MLMCPI_ERR_INVALID, "device index %d out of range", dev);
-  std::lock_guard<std::mutex> lock(g_rot_attr_mutex);
-  if (g_rot_attr_set[dev]) return MLMCPI_OK;
-  MLMCPI_HIP_TRY(hipFuncSetAttribute((const void *)sigma_rot_sweep_kernel<256>, hipFuncAttributeMaxDynamicSharedMemorySize, kSigmaLdsMax));
-  MLMCPI_HIP_TRY(hipFuncSetAttribute((const void *)sigma_rot_sweep_kernel<512>, hipFuncAttributeMaxDynamicSharedMemorySize, kSigmaLdsMax));
-  MLMCPI_HIP_TRY(hipFuncSetAttribute((const void *)sigma_rot_sweep_kernel<1024>, hipFuncAttributeMaxDynamicSharedMemorySize, kSigmaLdsMax));
-  g_rot_attr_set[dev] = true;
-  return MLMCPI_OK;
+  return once_per_device(g_rot_attr_once, []() -> int {
+    MLMCPI_HIP_TRY(hipFuncSetAttribute((const void *)sigma_rot_sweep_kernel<256>, hipFuncAttributeMaxDynamicSharedMemorySize, kSigmaLdsMax));
+    MLMCPI_HIP_TRY(hipFuncSetAttribute((const void *)sigma_rot_sweep_kernel<512>, hipFuncAttributeMaxDynamicSharedMemorySize, kSigmaLdsMax));
+    MLMCPI_HIP_TRY(hipFuncSetAttribute((const void *)sigma_rot_sweep_kernel<1024>, hipFuncAttributeMaxDynamicSharedMemorySize, kSigmaLdsMax));
+    return MLMCPI_OK;
+  });
 }
 
 template <int OP>

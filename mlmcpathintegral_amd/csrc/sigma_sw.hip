@@ -20,7 +20,6 @@
 //   P_SIGMA_SW_REFLECT  site 0, sub 0: (u, v) -> r_z = 1 - 2 u, azimuth 2 pi v - pi (the map of P_SIGMA_REFLECT sub 0)
 //   P_SIGMA_SW_BOND     site l, sub 0: u decides link (l, 0), v decides link (l, 1)
 //   P_SIGMA_SW_FLIP     site root, sub 0: reflected iff u < 0.5
-#include <mutex>
 #include <stdio.h>
 #include <string.h>
 
@@ -93,20 +92,15 @@ int sw_layout(const Geometry &g, uint32_t B, SwFlavour flavour, SwWorkspace &ws)
 }
 
 // ---- the draw -------------------------------------------------------------------------------------------------------------------
-std::mutex g_sw_attr_mutex;
-bool g_sw_attr_set[64] = {false};
+DeviceOnce g_sw_attr_once;
 
 // dynamic LDS above 64 KiB, once per device: the chain kernels up to their bound, the rotated launch 1 at the largest tile
 int sw_init_attrs() {
-  int dev = 0;
-  MLMCPI_HIP_TRY(hipGetDevice(&dev));
-  if (dev < 0 || dev >= 64) return fail(MLMCPI_ERR_INVALID, "device index %d out of range", dev);
-  std::lock_guard<std::mutex> lock(g_sw_attr_mutex);
-  if (g_sw_attr_set[dev]) return MLMCPI_OK;
-  if (int rc = sw_chain_init_attrs()) return rc;
-  if (int rc = sw_tiled_init_attrs()) return rc;
-  g_sw_attr_set[dev] = true;
-  return MLMCPI_OK;
+  return once_per_device(g_sw_attr_once, []() -> int {
+    if (int rc = sw_chain_init_attrs()) return rc;
+    if (int rc = sw_tiled_init_attrs()) return rc;
+    return MLMCPI_OK;
+  });
 }
 
 inline const char *sw_chain_kernel_name(const LatticeGeometry &) { return "sigma_sw_chain_kernel"; }

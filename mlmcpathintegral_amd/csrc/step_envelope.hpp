@@ -1,7 +1,7 @@
 // step_envelope.hpp -- the von Mises sampler with a tabulated step envelope, for launches whose concentrations stay below
-// kVsKappaMax: the table's layout (host and device; runtime.hip builds it), one attempt pair, and the colour phases that draw
+// kVsKappaMax: the table's layout (host and device; step_envelope_tables.hip builds it), one attempt pair, and the colour phases that draw
 // a workgroup's cells with it.  Included by site_update.hpp and lattice_sweep.hpp, and by schwinger_sweeps.hip,
-// rotor_sweeps.hip, lattice2d.hip, random_sweep.hip and runtime.hip.
+// rotor_sweeps.hip, lattice2d.hip, random_sweep.hip, step_envelope_tables.hip and test_hooks.hip.
 #pragma once
 #include "device_common.hpp"
 #include "vonmises.hpp"
@@ -25,7 +25,7 @@ namespace mlmcpi {
 // kappa = scale |cos(2 pi t)| = scale sin(2 pi v), v = |t - 1/4| in [0, 1/4], class = floor(32 v): the table of class c
 // is built for kappa_min = scale sin(2 pi c / 32) and is a valid envelope for every larger kappa (the normalised target
 // only gets narrower).  Acceptance 0.70 ... 0.89 (0.79 on average; wrapped Cauchy: 0.82).  The tables are built by the
-// host for the action's scale (runtime.hip, vs_build_tables; exported as mlmcpi_vs_table so that the oracle's own
+// host for the action's scale (step_envelope_tables.hip, vs_build_tables; exported as mlmcpi_vs_table so that the oracle's own
 // construction can be compared with it) and copied to LDS by the kernels: 512 selector bytes + 8 x 16 floats.
 // The test is screened in fp32 (24 bits of |x|, one polynomial cosine, v_exp_f32) against the kVsU2Bits = 22 leading bits of
 // u2 with a guard band that covers every fp32 rounding on the way; when the band does not decide (one attempt in ~3 10^4),
@@ -54,7 +54,7 @@ constexpr uint32_t kVsU2Bits = 22;  // leading bits of the acceptance uniform ca
 //   lo[8..0]    the low 9 of the 35 position bits
 //   hi[31..26]  bin selector
 //   hi[25..0]   the high 26 position bits; (float)(hi << 6) is the position 2^32, rounded to 24 bits
-// Device image of the tables (bytes; built by the host for the action's scale, runtime.hip vs_device_image):
+// Device image of the tables (bytes; built by the host for the action's scale, step_envelope_tables.hip vs_device_image):
 //   code[class][64]   1 B   8 x (bin of the selector value): a byte offset into the next two tables
 //   scr[bin]          8 B   float2 {pi/2 - edge, -width 2^-32}: y = pi/2 - |x| = fma(scr.y, (float)(hi << 6), scr.x), cos|x| = sin y
 //   lw[class][bin]    8 B   float log2 of the bin's acceptance factor (+ 4 B of padding: lw and code share the class offset 64 cls)

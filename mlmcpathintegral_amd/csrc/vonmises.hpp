@@ -1,7 +1,7 @@
 // vonmises.hpp -- the exact von Mises sampler of the heat-bath updates (wrapped-Cauchy envelope), the conditionals built on it
 // (ExpCos, ExpSin2), the scaled Bessel I0, and the colour phase that draws a workgroup's cells with it (HbPool, heatbath_cells).
 // Included by step_envelope.hpp, site_update.hpp, fillin.hpp and lattice_sweep.hpp, and by schwinger_sweeps.hip,
-// rotor_sweeps.hip, path_twolevel.hip, lattice_twolevel.hip and runtime.hip.
+// rotor_sweeps.hip, path_twolevel.hip, lattice_twolevel.hip, test_hooks.hip and test_math.hip.
 #pragma once
 #include "device_common.hpp"
 

@@ -13,7 +13,7 @@ CSRC = os.path.join(ROOT, "mlmcpathintegral_amd", "csrc")
 SAMPLER_HEADERS = {"vonmises.hpp", "step_envelope.hpp", "site_update.hpp", "fillin.hpp"}
 UNITS_WITHOUT_SAMPLER = ("path1d", "path_hmc", "ho_exact", "lattice_reduce", "lattice_hmc", "gff_exact", "gff_levels", "cluster",
                          "sigma_cluster", "sigma_sw", "sigma_sw_tiled", "sigma_sw_chain", "sigma_sw_correlator", "sigma_levels",
-                         "sigma_twolevel", "schwinger_or_block")
+                         "sigma_twolevel", "schwinger_or_block", "runtime", "options", "schwinger_analytic", "index_maps")
 SW_UNITS = ("sigma_sw", "sigma_sw_tiled", "sigma_sw_chain", "sigma_sw_correlator")
 
 
@@ -65,3 +65,17 @@ def test_the_cluster_samplers_share_the_embedding_and_nothing_of_each_other():
         deps = _deps(build, unit)
         assert {"sigma_cluster_device.hpp", "sigma_sw_host.hpp"} <= deps, (unit, sorted(deps))
         assert "sigma_cluster.hip" not in deps, (unit, sorted(deps))
+
+
+def test_fillin_and_sigma_device_meet_in_test_math_only():
+    """sigma_device.hpp switches fp contraction off for the rest of the file that includes it, fillin.hpp's callers are compiled
+    with it on: the one unit that needs the primitives of both is test_math, whose kernel only calls functions compiled where
+    they are defined.  Every unit the Makefile compiles is looked at."""
+    build = os.path.join(CSRC, "build")
+    if not os.path.isdir(build):
+        pytest.skip("no built tree")
+    with open(os.path.join(CSRC, "Makefile")) as f:
+        units = [w[:-4] for w in re.search(r"^SRCS := (.*)$", f.read(), re.M).group(1).split()]
+    assert len(units) >= 33 and "test_math" in units and "runtime" in units
+    both = [u for u in units if {"fillin.hpp", "sigma_device.hpp"} <= _deps(build, u)]
+    assert both == ["test_math"], both
