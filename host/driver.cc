@@ -34,6 +34,10 @@
 //          (--path_correlator N, single-level runs of the three 1-D actions: all `batch` chains are sampled and after the statistics
 //           come C(tau) = <x(0) x(tau)> (rotor: <cos(x(0) - x(tau))>) for tau < N, the effective mass per interior lag with its
 //           jackknife error and the gap m_eff / a; for the harmonic oscillator the exact lattice values beside them)
+//   driver --action schwinger --Mt_lat 8 --beta 2 --sampler heatbath --batch 256 --n_samples 200 --wilson_loops 3
+//          (--wilson_loops N, single-level runs of the quenched Schwinger action: all `batch` chains are sampled and after the
+//           statistics come the Wilson loops W(r, s), r, s <= N, beside the exact values of the periodic lattice, and the Creutz
+//           ratios chi(r, r) with their jackknife error beside the string tension -log(I_1 / I_0))
 //   driver --action rotor --M_lat 256 --T_final 25.6 --m0 0.25 --sampler cluster --n_updates 10 --n_samples 20000
 //          (cluster samplers: rotor and schwinger; also --coarsesampler cluster for twolevel / hierarchical rotor runs)
 //   driver --method throughput --action schwinger --Mt_lat 1024 --sampler heatbath --batch 32 --n_samples 20
@@ -60,7 +64,7 @@ int main(int argc, char **argv) {
       {"n_sweep_heatbath", "1"}, {"autotune", "1"}, {"window", "20"}, {"method", "singlelevel"}, {"n_level", "3"},
       {"epsilon", "0.01"}, {"coarsening", "both"}, {"coarsesampler", "hmc"}, {"renormalisation", "none"}, {"n_meas", "200"},
       {"batch", "1"}, {"seed", "2481317"}, {"warmup", "5"}, {"random_order", "0"}, {"n_updates", "10"}, {"correlator", "0"},
-      {"path_correlator", "0"}};
+      {"path_correlator", "0"}, {"wilson_loops", "0"}};
   for (int i = 1; i + 1 < argc; i += 2) {
     if (std::strncmp(argv[i], "--", 2) || !o.count(argv[i] + 2)) fatal(std::string("unknown option ") + argv[i]);
     o[argv[i] + 2] = argv[i + 1];
@@ -92,6 +96,30 @@ int main(int argc, char **argv) {
       fatal("--path_correlator " + o["path_correlator"] + " is more than M_lat / 2 + 1 = " + std::to_string(M_lat / 2 + 1) +
             " lags (C(M_lat - tau) = C(tau))");
   }
+  // --wilson_loops N: the Wilson loops W(r, s), r, s <= N, of the quenched Schwinger action beside the QoI, and the Creutz ratios
+  // from them (qoi.hh WilsonLoops); 0: off.  Refused here, before any device call.
+  {
+    const std::string &v = o["wilson_loops"];
+    if (v.empty() || v.size() > 9 || v.find_first_not_of("0123456789") != std::string::npos)
+      fatal("--wilson_loops takes a non-negative integer (the largest loop side, 0: off), not " + v);
+  }
+  const unsigned wilson_n = (unsigned)std::stoul(o["wilson_loops"]);
+  if (wilson_n > 0) {
+    if (o["action"] != "schwinger")
+      fatal("--wilson_loops " + o["wilson_loops"] + " is not supported for chosen action: Wilson loops are built for schwinger only, not " +
+            o["action"] + " (the sigma model has --correlator 1, the 1-D actions --path_correlator N)");
+    if (o["method"] != "singlelevel")
+      fatal("--wilson_loops runs --method singlelevel only, not " + o["method"] + " (the two-level and multilevel estimators have "
+            "no difference estimator for W(r, s); the throughput loop measures the QoI alone)");
+    if (o["sampler"] == "hierarchical")
+      fatal("--wilson_loops takes a single-level sampler (hmc, heatbath or cluster), not hierarchical (Wilson loops are not built "
+            "on coarsened levels)");
+    if (world > 1) fatal("--wilson_loops runs on one rank (its sums are not exchanged)");
+    const unsigned Mt_lat = (unsigned)num("Mt_lat"), cap = std::min(Mt_lat, (unsigned)MLMCPI_WILSON_LOOPS_MAX);
+    if (wilson_n > cap)
+      fatal("--wilson_loops " + o["wilson_loops"] + " is more than min(Mt_lat, Mx_lat, " + std::to_string(MLMCPI_WILSON_LOOPS_MAX) + ") = " +
+            std::to_string(cap) + " links a side");
+  }
   std::shared_ptr<Exchange> exchange;
   if (world > 1) {
     check(mlmcpi_set_device(local_rank), "mlmcpi_set_device");
@@ -109,6 +137,7 @@ int main(int argc, char **argv) {
   std::shared_ptr<QoI> qoi;
   std::shared_ptr<SigmaCorrelator> correlator;
   std::shared_ptr<PathCorrelator> path_correlator;
+  std::shared_ptr<WilsonLoops> wilson_loops;
   std::shared_ptr<QoIFactory> qoi_factory;
   std::shared_ptr<ConditionedFineActionFactory> cfa_factory;
   double analytic = NAN;
@@ -247,6 +276,7 @@ int main(int argc, char **argv) {
       qoi = std::make_shared<QoIAvgPlaquette>(lat);
       qoi_factory = std::make_shared<QoIAvgPlaquetteFactory>();
       cfa_factory = std::make_shared<QuenchedSchwingerConditionedFineActionFactory>();
+      if (wilson_n > 0) wilson_loops = std::make_shared<WilsonLoops>(lat, wilson_n, wilson_n);
     } else {
       action = std::make_shared<GFFAction>(lat, nullptr, num("mass"));
       qoi = std::make_shared<QoI2DPhiSquared>(lat);
@@ -402,6 +432,7 @@ int main(int argc, char **argv) {
   // (--path_correlator N likewise)
   std::shared_ptr<CorrelatorMeasurement> measured = correlator;
   if (path_correlator) measured = path_correlator;
+  if (wilson_loops) measured = wilson_loops;  // --wilson_loops N likewise
   MonteCarloSingleLevel mc(action, qoi, factory, mp, exchange, measured ? batch : 1u, measured);
   mc.evaluate();
   std::cout << std::endl << "=== Single level MC ===" << std::endl;
@@ -505,6 +536,27 @@ int main(int argc, char **argv) {
       const double w = path_ho_lattice_omega(M_lat, T_final, num("mu2"));
       std::cout << " exact lattice gap: omega~ = " << w << ", omega~ / a = " << w / a_lat << std::endl;
     }
+  }
+  if (wilson_loops) {
+    const WilsonLoops::Estimate e = wilson_loops->means_and_errors();
+    const unsigned Mt = wilson_loops->Mt(), Mx = wilson_loops->Mx(), B = wilson_loops->batch();
+    const double beta = num("beta");
+    std::cout << std::endl << "=== Wilson loops ===" << std::endl
+              << " samples = " << wilson_loops->samples() << ", chains = " << B << ", errors: "
+              << (e.chain_spread ? "spread of the per-chain means" : "naive (one chain: autocorrelation ignored)") << std::endl
+              << std::setprecision(8) << std::fixed;
+    for (unsigned r = 1; r <= wilson_n; ++r)
+      for (unsigned s = 1; s <= wilson_n; ++s)
+        std::cout << " W(r = " << r << ", s = " << s << ") = " << e.mean[(r - 1) * wilson_n + s - 1] << " +/- "
+                  << e.error[(r - 1) * wilson_n + s - 1] << " exact = " << wilson_loop_exact(beta, Mt, Mx, r, s) << std::endl;
+    for (unsigned r = 1; r <= wilson_n; ++r) {
+      const WilsonLoops::Ratio c = wilson_loops->creutz(r, r);
+      std::cout << " chi(r = " << r << ", s = " << r << ") = " << c.value;
+      if (c.has_error) std::cout << " +/- " << c.error << " (jackknife over chains)";
+      else std::cout << " (one chain: no jackknife error)";
+      std::cout << std::endl;
+    }
+    std::cout << " exact string tension: -log(I_1(beta) / I_0(beta)) = " << string_tension_exact(beta) << std::endl;
   }
   return 0;
 }

@@ -63,5 +63,42 @@ inline double path_correlator_ho_exact(unsigned int M, double T_final, double m0
   return (a / m0) * std::cosh(w * (0.5 * M - (double)tau)) / (2.0 * std::sinh(w) * std::sinh(0.5 * w * M));
 }
 
+// ---- Wilson loops W(r, s) of the quenched Schwinger model (mlmcpi_schwinger_wilson_loops; the class that measures them is
+// WilsonLoops, qoi.hh) ----
+
+/** <W(r, s)> on the periodic Mt x Mx lattice, V = Mt Mx, A = r s <= V: sum_n I_n(beta)^(V-A) I_(n+1)(beta)^A / sum_n I_n(beta)^V over
+ *  all integers n (the character expansion; the sum over n carries the torus constraint sum theta_p = 0 mod 2 pi).  Evaluated with
+ *  rho_n = I_n / I_0 (the scaling of the Bessel functions cancels), n = 0, -1, 1, -2, .. until the terms fall below 1e-17 of the sum */
+inline double wilson_loop_exact(double beta, unsigned int Mt, unsigned int Mx, unsigned int r, unsigned int s) {
+  const double V = (double)Mt * Mx, A = (double)r * s;
+  const double i0 = std::cyl_bessel_i(0.0, beta);
+  auto rho = [&](int n) { return std::cyl_bessel_i((double)(n < 0 ? -n : n), beta) / i0; };
+  double num = 0.0, den = 0.0;
+  for (int m = 0; m < 400; ++m) {
+    double tn = 0.0, td = 0.0;
+    for (int n : {m, -m - 1}) {  // the pair (I_n, I_(n+1)) is (I_m, I_(m+1)) and, mirrored, (I_(m+1), I_m)
+      const double a = rho(n), b = rho(n + 1);
+      tn += std::pow(a, V - A) * std::pow(b, A);
+      td += std::pow(a, V);
+    }
+    num += tn;
+    den += td;
+    if (tn <= 1e-17 * num && td <= 1e-17 * den) break;
+  }
+  return num / den;
+}
+
+/** the string tension of the infinite lattice, sigma = -log(I_1(beta) / I_0(beta)): W -> exp(-sigma r s) */
+inline double string_tension_exact(double beta) { return -std::log(std::cyl_bessel_i(1.0, beta) / std::cyl_bessel_i(0.0, beta)); }
+
+/** the Creutz ratio chi(r, s) = -log[W(r,s) W(r-1,s-1) / (W(r-1,s) W(r,s-1))] of W [R][S] (entry [r-1][s-1]), 1 <= r <= R, 1 <= s <= S,
+ *  with W(0,.) = W(.,0) = 1: the string tension exactly for a pure area law.  NaN where the argument is not positive (noise) */
+inline double creutz_ratio(const std::vector<double> &W, unsigned int R, unsigned int S, unsigned int r, unsigned int s) {
+  (void)R;
+  auto w = [&](unsigned int a, unsigned int b) { return a == 0 || b == 0 ? 1.0 : W[(size_t)(a - 1) * S + (b - 1)]; };
+  const double q = w(r, s) * w(r - 1, s - 1) / (w(r - 1, s) * w(r, s - 1));
+  return q > 0.0 ? -std::log(q) : std::nan("");
+}
+
 }  // namespace mlmcpi
 #endif

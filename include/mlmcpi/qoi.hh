@@ -365,5 +365,123 @@ private:
   std::unique_ptr<DeviceVector> acc, out;
 };
 
+/** The Wilson loops W(r, s), 1 <= r <= R, 1 <= s <= S, of a quenched Schwinger state (mlmcpi_schwinger_wilson_loops; definitions in
+ *  mlmcpi_hip.h).  Not a QoI: R S numbers per chain, entry (r - 1) S + (s - 1).  accumulate() adds the sample's W and W^2 to
+ *  per-chain sums on the device; the means, their errors and the Creutz ratios (correlator.hh) are host arithmetic on those sums. */
+class WilsonLoops : public CorrelatorMeasurement {
+public:
+  struct Estimate {
+    std::vector<double> mean, error;
+    bool chain_spread;  // true: error = spread of the per-chain means (batch >= 2); false: the naive error of one chain
+  };
+  struct Ratio {
+    double value, error;
+    bool has_error;  // the jackknife over chains needs batch >= 2
+  };
+  WilsonLoops(const std::shared_ptr<Lattice2D> lattice, unsigned int R_, unsigned int S_)
+      : Mt_lat(lattice->getMt_lat()), Mx_lat(lattice->getMx_lat()), R_(R_), S_(S_), n_out_(R_ * S_) {}
+  unsigned int R() const { return R_; }
+  unsigned int S() const { return S_; }
+  unsigned int Mt() const { return Mt_lat; }
+  unsigned int Mx() const { return Mx_lat; }
+  /** d_out[b][R()][S()] = the loops of chain b, enqueued on the default stream */
+  void evaluate_device(const std::shared_ptr<SampleState> phi, double *d_out) { launch(phi, d_out, nullptr); }
+  /** one more sample: its loops are added to the per-chain sums (the batch is fixed by the first call) */
+  void accumulate(const std::shared_ptr<SampleState> phi) override {
+    if (!acc || B != phi->batch()) {
+      if (n_calls) fatal("WilsonLoops::accumulate: the batch changed between samples.");
+      B = phi->batch();
+      acc = std::make_unique<DeviceVector>(2 * (size_t)B * n_out_);
+      out = std::make_unique<DeviceVector>((size_t)B * n_out_);
+    }
+    launch(phi, (double *)out->ptr(), (double *)acc->ptr());
+    ++n_calls;
+  }
+  unsigned int samples() const override { return n_calls; }
+  unsigned int batch() const { return B; }
+  /** per-chain means of W over the accumulated samples, [batch][R() S()] */
+  std::vector<std::vector<double>> chain_means() const {
+    if (!n_calls) fatal("WilsonLoops: no samples accumulated.");
+    const std::vector<double> a = acc->download<double>();
+    std::vector<std::vector<double>> m(B, std::vector<double>(n_out_));
+    for (unsigned int b = 0; b < B; ++b)
+      for (unsigned int k = 0; k < n_out_; ++k) m[b][k] = a[2 * ((size_t)b * n_out_ + k)] / n_calls;
+    return m;
+  }
+  /** mean and error per loop.  batch >= 2: the error is the spread of the per-chain means over sqrt(batch), so autocorrelation
+   *  inside a chain cannot understate it; batch 1: the naive error of the samples (it ignores autocorrelation) */
+  Estimate means_and_errors() const {
+    if (!n_calls) fatal("WilsonLoops: no samples accumulated.");
+    return wilson_loops_estimate(acc->download<double>(), B, n_out_, n_calls);
+  }
+  /** the same arithmetic on downloaded sums a [batch][n_out][2] (W, W^2) of n samples */
+  static Estimate wilson_loops_estimate(const std::vector<double> &a, unsigned int B, unsigned int n_out, unsigned int n_calls) {
+    Estimate e{std::vector<double>(n_out, 0.0), std::vector<double>(n_out, 0.0), B >= 2};
+    const double n = n_calls;
+    for (unsigned int k = 0; k < n_out; ++k) {
+      if (B >= 2) {
+        double s = 0.0, s2 = 0.0;
+        for (unsigned int b = 0; b < B; ++b) s += a[2 * ((size_t)b * n_out + k)] / n;
+        const double m = s / B;
+        for (unsigned int b = 0; b < B; ++b) {
+          const double d = a[2 * ((size_t)b * n_out + k)] / n - m;
+          s2 += d * d;
+        }
+        e.mean[k] = m;
+        e.error[k] = std::sqrt(s2 / ((double)B * (B - 1.0)));
+      } else {
+        const double m = a[2 * k] / n, var = n_calls > 1 ? std::max(0.0, (a[2 * k + 1] / n - m * m) * n / (n - 1.0)) : 0.0;
+        e.mean[k] = m;
+        e.error[k] = std::sqrt(var / n);
+      }
+    }
+    return e;
+  }
+  /** the Creutz ratio chi(r, s), 1 <= r <= R(), 1 <= s <= S(), of the mean loops; batch >= 2: with the jackknife error over the chains */
+  Ratio creutz(unsigned int r, unsigned int s) const {
+    if (r < 1 || r > R_ || s < 1 || s > S_) fatal("WilsonLoops::creutz: loop outside 1 .. R x 1 .. S.");
+    return creutz_jackknife(chain_means(), R_, S_, r, s);
+  }
+  /** the same arithmetic on per-chain means m [batch][R S] */
+  static Ratio creutz_jackknife(const std::vector<std::vector<double>> &m, unsigned int R, unsigned int S, unsigned int r, unsigned int s) {
+    const unsigned int B = (unsigned int)m.size(), n_out = R * S;
+    std::vector<double> all(n_out, 0.0);
+    for (unsigned int b = 0; b < B; ++b)
+      for (unsigned int k = 0; k < n_out; ++k) all[k] += m[b][k];
+    std::vector<double> mean(all);
+    for (double &v : mean) v /= B;
+    Ratio res{creutz_ratio(mean, R, S, r, s), 0.0, B >= 2};
+    if (B >= 2) {
+      std::vector<double> x(B), leave(n_out);
+      double xm = 0.0, s2 = 0.0;
+      for (unsigned int b = 0; b < B; ++b) {
+        for (unsigned int k = 0; k < n_out; ++k) leave[k] = (all[k] - m[b][k]) / (B - 1.0);
+        x[b] = creutz_ratio(leave, R, S, r, s);
+        xm += x[b] / B;
+      }
+      for (unsigned int b = 0; b < B; ++b) s2 += (x[b] - xm) * (x[b] - xm);
+      res.error = std::sqrt((B - 1.0) / B * s2);
+    }
+    return res;
+  }
+
+private:
+  void launch(const std::shared_ptr<SampleState> phi, double *d_out, double *d_acc) {
+    if (phi->size() != 2 * Mt_lat * Mx_lat) fatal("Evaluating WilsonLoops on state of wrong size.");
+    if (!work || work_B != phi->batch()) {
+      check(mlmcpi_schwinger_wilson_loops_workspace_bytes(Mt_lat, Mx_lat, R_, S_, phi->batch(), &work_bytes), "schwinger_wilson_loops_workspace_bytes");
+      work = std::make_unique<DeviceBuffer>(work_bytes);
+      work_B = phi->batch();
+    }
+    check(mlmcpi_schwinger_wilson_loops(phi->device(), Mt_lat, Mx_lat, phi->batch(), R_, S_, d_out, d_acc, work->p, work_bytes, nullptr),
+          "schwinger_wilson_loops");
+  }
+  const unsigned int Mt_lat, Mx_lat, R_, S_, n_out_;
+  unsigned int B = 0, work_B = 0, n_calls = 0;
+  size_t work_bytes = 0;
+  std::unique_ptr<DeviceBuffer> work;
+  std::unique_ptr<DeviceVector> acc, out;
+};
+
 }  // namespace mlmcpi
 #endif

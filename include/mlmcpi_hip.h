@@ -795,6 +795,57 @@ int mlmcpi_qoi_avg_plaquette(const double *d_theta, uint32_t Mt, uint32_t Mx, ui
                              void *stream);
 int mlmcpi_qoi_2d_susceptibility(const double *d_theta, uint32_t Mt, uint32_t Mx, uint32_t B, double *d_out,
                                  void *stream);
+
+/* Wilson loops of the quenched Schwinger model (wilson_loops.hip).  With the state layout above,
+ * theta[b 2 Mt Mx + 2 (Mt j + i) + mu], and the plaquette orientation of the action (quenchedschwingeraction.cc:14-17): for a base
+ * vertex (i, j), 1 <= r <= R links along direction 0 and 1 <= s <= S links along direction 1, all indices periodic,
+ *   Theta(i,j;r,s) =  sum_{k<r} theta0(i+k, j)  +  sum_{l<s} theta1(i+r, j+l)  -  sum_{k<r} theta0(i+k, j+s)  -  sum_{l<s} theta1(i, j+l)
+ *                  =  the sum over the r x s cells (i+k, j+l) of the unreduced plaquette angle
+ *   W(r,s)         =  (1 / (Mt Mx)) sum_{i,j} cos Theta(i,j;r,s)
+ * into d_out [B][R][S], entry [r-1][s-1].  Identities: W(1,1) = mlmcpi_qoi_avg_plaquette; W(Mt,Mx) = 1 (every link cancels); W does
+ * not change under theta_mu(n) -> theta_mu(n) + g(n) - g(n + mu^).  On the periodic lattice, V = Mt Mx, A = r s <= V,
+ *   <W(r,s)> = sum_n I_n(beta)^(V-A) I_(n+1)(beta)^A / sum_n I_n(beta)^V   (n over the integers; -> (I_1/I_0)^A as V -> infinity)
+ * and the Creutz ratio chi(r,s) = -log[W(r,s) W(r-1,s-1) / (W(r-1,s) W(r,s-1))], W(0,.) = W(.,0) = 1, tends to the string tension
+ * -log(I_1(beta) / I_0(beta)) at every (r,s) (include/mlmcpi/correlator.hh).
+ * How it is computed: e^(i Theta) is the product of the cell phases e^(i theta_p), one sincos per plaquette; a strip of r cells is
+ * U(i,j;r) = U(i,j;r-1) z(i+r-1,j), a loop P(i,j;r,s) = P(i,j;r,s-1) U(i,j+s-1;r), and Re P is summed.
+ * Summation order: the lattice is cut into tiles of tile_w x tile_h = 32 x 32 base vertices (edge tiles clipped); thread t of the
+ * 256 of a workgroup adds the J = 4 base vertices (column t % 32, rows 4 (t / 32) .. + 3) ascending, the workgroup its threads by
+ * the lane tree (offsets 32, .., 1) and then its four waves ascending; the tiles (tile = ty tiles_w + tx) are added in ascending
+ * order and the sum is multiplied by 1 / (Mt Mx) last.  The geometry is a function of (Mt, Mx, R, S) alone, there are no atomics
+ * and no tuning knob: a chain's output is the same bits for every B, every split of the chains over calls and every stream.
+ * d_theta: 16-byte aligned, not written.  d_acc (may be NULL) [B][R][S][2]: W is ADDED to [.][.][.][0] and W^2 to [.][.][.][1] in the
+ * launch that writes d_out; the caller counts the calls.  d_work: _workspace_bytes(Mt, Mx, R, S, B) bytes, 256-byte aligned
+ * (one partial per chain, tile, r and s); content at entry ignored.
+ * Any Mt, Mx >= 2, odd extents included, Mt Mx <= 2^30.  Chains and tiles share one index of workgroups, B tiles of them, laid over
+ * grid x (2^31 / 256) and, beyond that, y: there is no 65535-chain limit (the bound, 2^23 x 65535 workgroups, is beyond any memory).
+ * MLMCPI_ERR_INVALID, with nothing launched and no output byte touched: a NULL pointer (d_acc excepted); Mt or Mx < 2 or Mt Mx >
+ * 2^30; B = 0; R = 0 or S = 0; R > Mt or S > Mx; more workgroups than above; work_bytes below _workspace_bytes.
+ * MLMCPI_ERR_UNSUPPORTED: R or S above MLMCPI_WILSON_LOOPS_MAX (the LDS image and the register window are sized by it).
+ * _plan (host only, touches no device) reports the geometry and returns the status the call would. */
+#ifdef __cplusplus
+constexpr uint32_t MLMCPI_WILSON_LOOPS_MAX = 16;
+#else
+#define MLMCPI_WILSON_LOOPS_MAX 16u
+#endif
+typedef struct mlmcpi_wilson_loops_plan_info {
+  uint64_t work_bytes;            /* what _workspace_bytes reports */
+  uint64_t grid;                  /* workgroups of the loop launch, B tiles; with work_bytes the only entries that depend on B */
+  uint32_t workgroup;             /* threads of a workgroup */
+  uint32_t tile_w, tile_h;        /* base vertices of a tile along direction 0 and 1; tile (tx, ty) owns the base vertices
+                                   * [tx tile_w, min(Mt, (tx + 1) tile_w)) x [ty tile_h, min(Mx, (ty + 1) tile_h)) */
+  uint32_t halo_w, halo_h;        /* R - 1 columns and S - 1 rows of cells beyond a tile in its LDS image */
+  uint32_t J;                     /* consecutive base rows of one column per thread */
+  uint32_t tiles_w, tiles_h;      /* ceil(Mt / tile_w), ceil(Mx / tile_h) */
+  uint32_t tiles;                 /* tiles per chain, tiles_w tiles_h */
+  uint32_t lds_bytes, lds_limit;  /* dynamic LDS of a workgroup, (min(tile_w, Mt) + R) (min(tile_h, Mx) + S) 16, and the limit the
+                                   * kernel is written for */
+} mlmcpi_wilson_loops_plan_info;
+int mlmcpi_schwinger_wilson_loops_workspace_bytes(uint32_t Mt, uint32_t Mx, uint32_t R, uint32_t S, uint32_t B, size_t *bytes);
+int mlmcpi_schwinger_wilson_loops(const double *d_theta, uint32_t Mt, uint32_t Mx, uint32_t B, uint32_t R, uint32_t S,
+                                  double *d_out /* [B][R][S] */, double *d_acc /* [B][R][S][2], may be NULL */, void *d_work,
+                                  size_t work_bytes, void *stream);
+int mlmcpi_schwinger_wilson_loops_plan(uint32_t Mt, uint32_t Mx, uint32_t R, uint32_t S, uint32_t B, mlmcpi_wilson_loops_plan_info *out);
 /* QoI2DMagneticSusceptibility (qoi/qft/qoi2dmagneticsusceptibility.cc:7-21): d_out[b] = |sum_n sigma_n|^2 / (Mt Mx) of a
  * sigma-model state */
 int mlmcpi_qoi_magnetic_susceptibility(const double *d_phi, uint32_t Mt, uint32_t Mx, uint32_t B, double *d_out, void *stream);

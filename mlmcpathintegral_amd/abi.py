@@ -72,6 +72,12 @@ class PathCorrelatorPlan(C.Structure):
         "components", "lds_bytes", "lds_limit")]
 
 
+class WilsonLoopsPlan(C.Structure):
+    """mlmcpi_wilson_loops_plan_info"""
+    _fields_ = [("work_bytes", C.c_uint64), ("grid", C.c_uint64)] + [(n, C.c_uint32) for n in (
+        "workgroup", "tile_w", "tile_h", "halo_w", "halo_h", "J", "tiles_w", "tiles_h", "tiles", "lds_bytes", "lds_limit")]
+
+
 _vp, _u32, _u64, _i, _d, _sz = C.c_void_p, C.c_uint32, C.c_uint64, C.c_int, C.c_double, C.c_size_t
 _PA, _LA = C.POINTER(PathAction), C.POINTER(LatticeAction)
 _SL = C.POINTER(SigmaLevel)
@@ -110,6 +116,9 @@ SIGNATURES = {
     "mlmcpi_path_correlator_workspace_bytes": (_i, [_PA, _u32, _u32, C.POINTER(_sz)]),
     "mlmcpi_path_correlator": (_i, [_PA, _vp, _u32, _u32, _vp, _vp, _vp, _sz, _vp]),
     "mlmcpi_path_correlator_plan": (_i, [_PA, _u32, _u32, C.POINTER(PathCorrelatorPlan)]),
+    "mlmcpi_schwinger_wilson_loops_workspace_bytes": (_i, [_u32, _u32, _u32, _u32, _u32, C.POINTER(_sz)]),
+    "mlmcpi_schwinger_wilson_loops": (_i, [_vp, _u32, _u32, _u32, _u32, _u32, _vp, _vp, _vp, _sz, _vp]),
+    "mlmcpi_schwinger_wilson_loops_plan": (_i, [_u32, _u32, _u32, _u32, _u32, C.POINTER(WilsonLoopsPlan)]),
     "mlmcpi_path_sweep_draw": (_i, [_PA, _vp, _vp, _u32, _u32, _u32, _u64, _u32, _u32, _vp]),
     "mlmcpi_path_sweep_draw_from": (_i, [_PA, _vp, _vp, _vp, _u32, _u32, _u32, _u64, _u32, _u32, _vp, _vp]),
     "mlmcpi_path_sweep_draw_qoi": (_i, [_PA, _vp, _vp, _vp, _u32, _u32, _u32, _u64, _u32, _u32, _vp, _vp, _vp, _vp]),

@@ -725,6 +725,33 @@ def qoi_avg_plaquette(theta, Mt, Mx):
     return out
 
 
+def wilson_loops_plan(Mt, Mx, R, S, B):
+    """The launch geometry of wilson_loops for these arguments (mlmcpi_schwinger_wilson_loops_plan; no device needed): a dict
+    of the fields of mlmcpi_wilson_loops_plan_info"""
+    info = abi.WilsonLoopsPlan()
+    abi.call("mlmcpi_schwinger_wilson_loops_plan", Mt, Mx, R, S, B, C.byref(info))
+    return {n: getattr(info, n) for n, _ in abi.WilsonLoopsPlan._fields_}
+
+
+def wilson_loops_workspace(Mt, Mx, R, S, B, device="cuda"):
+    """workspace of wilson_loops for B chains and loops up to R x S (uint8 tensor)"""
+    return _workspace("mlmcpi_schwinger_wilson_loops_workspace_bytes", Mt, Mx, R, S, B, device=device)
+
+
+def wilson_loops(theta, Mt, Mx, R, S, acc=None, work=None):
+    """W(r, s), r <= R, s <= S, of every chain of theta [B, 2 Mt Mx] (mlmcpi_schwinger_wilson_loops): returns [B, R, S], entry
+    [r - 1, s - 1]; acc [B, R, S, 2] (optional) is added to: W and W^2"""
+    _check_state(theta, 2 * Mt * Mx)
+    B = theta.shape[0]
+    if work is None:
+        work = wilson_loops_workspace(Mt, Mx, R, S, B, theta.device)
+    if acc is not None:
+        assert acc.dtype == torch.float64 and tuple(acc.shape) == (B, R, S, 2), acc.shape
+    out = torch.empty((B, R, S), dtype=torch.float64, device=theta.device)
+    abi.call("mlmcpi_schwinger_wilson_loops", _p(theta), Mt, Mx, B, R, S, _p(out), _p(acc), _p(work), work.numel(), _stream())
+    return out
+
+
 def qoi_2d_susceptibility(theta, Mt, Mx):
     out = torch.empty(theta.shape[0], dtype=torch.float64, device=theta.device)
     abi.call("mlmcpi_qoi_2d_susceptibility", _p(theta), Mt, Mx, theta.shape[0], _p(out), _stream())
