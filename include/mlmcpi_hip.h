@@ -32,6 +32,36 @@
  *     sweep-by-sweep kernels (GFF and the sigma model always) agree bit for bit whatever the plan.  A QoI fused into the last launch of a
  *     draw (mlmcpi_lattice_sweep_draw_qoi*) sums per-tile partials in the tile order of that launch: under another plan
  *     (MLMCPI_OR_HEAT=split, MLMCPI_OR_KERNEL=block) it agrees to rounding (1e-13).  Spelled out in DESIGN.md 3 / 9.
+ *   - CHAINS PER CALL.  B is the number of chains of one call; where the chains ride in the launch grid decides the largest B.
+ *     The HIP runtime on the MI355X launches gridDim.y and gridDim.z beyond 65535 and every workgroup of such a grid runs with the
+ *     right index (measured at 65535, 65536 and 65581 through mlmcpi_path_initialise: DESIGN.md "Chains per call"), so an entry
+ *     point without a guard takes any B its buffers hold ("unbounded" below; batches whose element count B * n passes 2^32, 32 GB of
+ *     state, have not been run and want an index audit first).  Four units refuse
+ *     B > 65535 by name, with nothing launched; the guards are conservative and stay until someone needs them lifted.  Every entry
+ *     point is run at B = 65535 and, where it takes it, at B = 65581 by tests/test_chain_count_gpu.py.
+ *       entry points                                                                   chains ride on        largest B
+ *       mlmcpi_path_evaluate / _force / _initialise, mlmcpi_qoi_xsquared /             grid y                unbounded
+ *         _susceptibility, mlmcpi_path_copy_from_*, mlmcpi_path_hmc_draw
+ *       mlmcpi_path_hmc_run                                                            grid x, 1 per         unbounded
+ *                                                                                      workgroup (M a multiple of 64, <= 8192); else
+ *                                                                                      grid y + x, 256 per workgroup
+ *       mlmcpi_path_sweep_draw / _from / _qoi                                          grid y; QoI: x, 256   65535 (refused by name)
+ *       mlmcpi_path_site_updates, mlmcpi_lattice_site_updates                          grid x, 64 per wg     unbounded
+ *       mlmcpi_path_twolevel_draw / _masked                                            grid x, 1 per wg      unbounded
+ *       mlmcpi_path_exact_draw                                                         grid y, 16 per row    unbounded
+ *       mlmcpi_path_cluster_draw, mlmcpi_schwinger_cluster_*                           grid x, 4 per wg      unbounded
+ *       mlmcpi_path_correlator, mlmcpi_schwinger_wilson_loops                          linear index, x then y 2^23 x 65535 workgroups
+ *       mlmcpi_lattice_evaluate / _force / _initialise / _sweep_draw* / _copy_from_* / grid y (finish kernels: unbounded
+ *         _twolevel_draw* / _exact_draw / _hmc_draw, mlmcpi_qoi_phi_squared /          x, 4 or 1 per wg)
+ *         _avg_plaquette / _2d_susceptibility / _magnetic_susceptibility
+ *       mlmcpi_lattice_random_sweep_draw, mlmcpi_sigma_cluster_draw,                   grid x, 1 or more     unbounded
+ *         mlmcpi_sigma_sw_draw, mlmcpi_sigma_level_cluster_* / _sw_*                   workgroups per chain
+ *       mlmcpi_gff_level_evaluate / _draw, mlmcpi_gff_cfa_*                            grid x, 1 per wg      unbounded
+ *       mlmcpi_gff_copy_from_*, mlmcpi_gff_twolevel_draw                               grid y                unbounded
+ *       mlmcpi_sigma_level_initialise / _evaluate / _magnetic_susceptibility /         grid y                65535 (refused)
+ *         _sweep_draw / _copy_from_*, mlmcpi_sigma_cfa_*, mlmcpi_sigma_twolevel_*
+ *       mlmcpi_sigma_level_correlator                                                  grid y and z          65535 (refused by name)
+ *       mlmcpi_stats_accumulate, mlmcpi_stats_window_record                            grid x, 256 per wg    unbounded
  */
 #ifndef MLMCPI_HIP_H
 #define MLMCPI_HIP_H
@@ -196,7 +226,7 @@ int mlmcpi_path_hmc_plan(const mlmcpi_path_action *act, uint32_t B, uint32_t nt,
  * d_acc (may be NULL) [B][n_lag][2]: C is ADDED to [.][.][0] and C^2 to [.][.][1] in the launch that writes d_out; the caller
  * counts the calls.  d_work: _workspace_bytes(act, n_lag, B) bytes (never 0), 256-byte aligned; content at entry ignored.
  * Chains and segments share one index of workgroups, ceil(B / chains_per_workgroup) nseg of them, laid over grid x (2^31 / 256) and,
- * beyond that, y: there is no 65535-chain limit (the bound, 2^23 x 65535 workgroups, is beyond any memory).
+ * beyond that, y: there is no 65535-chain limit (the bound, 2^23 x 65535 workgroups, is beyond any memory; CHAINS PER CALL above).
  * MLMCPI_ERR_INVALID, with nothing launched and no output byte touched: NULL act, d_x, d_out or d_work; kind outside 0 .. 2; M = 0,
  * B = 0 or n_lag = 0; n_lag > M/2 + 1; more workgroups than above; work_bytes below _workspace_bytes.
  * _plan (host only, touches no device) reports the geometry and returns the status the call would. */
@@ -224,7 +254,8 @@ int mlmcpi_path_correlator_plan(const mlmcpi_path_action *act, uint32_t n_lag, u
  * n_overrelax sweeps of RotorAction::overrelaxation_update (rotoraction.cc:40-56) then n_heatbath
  * sweeps of heatbath_update (:20-37), even sites then odd sites within each sweep.  Sweep s of
  * this call uses Philox step sweep0 + s.  d_x is updated in place; d_scratch is B*M doubles.
- * At most 65535 chains per call (they are one grid dimension of every launch; _from and _qoi too): more is an error.
+ * At most 65535 chains per call (they are one grid dimension of every launch; _from and _qoi too): more is an error (the
+ * table under CHAINS PER CALL at the top of this header).
  * Up to 16 overrelaxation sweeps of a launch are applied in closed form (more: launches of equal depth);
  * MLMCPI_OR_KERNEL=block sweeps one by one, 8 per launch.  The two agree to <= 2e-15 without a heat bath
  * behind (the same map, other rounding), NOT bit for bit: see "bit reproducibility across launch plans"
@@ -633,7 +664,7 @@ int mlmcpi_sigma_level_copy_from_coarse(const mlmcpi_sigma_level *fine, const do
  * counts the calls.  d_work: _correlator_workspace_bytes(level, B) bytes, 256-byte aligned; content at entry ignored.  The state
  * is read once (one sincos pair per vertex); every sum is taken in an order fixed by the level alone, without atomics, so a
  * chain's output is the same bits whatever B and however the chains are split over calls.  The launch geometry takes B <= 65535
- * chains per call.  MLMCPI_ERR_INVALID, with nothing launched: NULL level, odd or zero extents, Mt Mx > 2^30, NULL d_state, d_out
+ * chains per call (CHAINS PER CALL above).  MLMCPI_ERR_INVALID, with nothing launched: NULL level, odd or zero extents, Mt Mx > 2^30, NULL d_state, d_out
  * or d_work, B = 0 or B > 65535, work_bytes below _correlator_workspace_bytes. */
 int mlmcpi_sigma_level_correlator_size(const mlmcpi_sigma_level *level, uint32_t *n_out);
 int mlmcpi_sigma_level_correlator_workspace_bytes(const mlmcpi_sigma_level *level, uint32_t B, size_t *bytes);
@@ -818,8 +849,8 @@ int mlmcpi_qoi_2d_susceptibility(const double *d_theta, uint32_t Mt, uint32_t Mx
  * launch that writes d_out; the caller counts the calls.  d_work: _workspace_bytes(Mt, Mx, R, S, B) bytes, 256-byte aligned
  * (one partial per chain, tile, r and s); content at entry ignored.
  * Any Mt, Mx >= 2, odd extents included, Mt Mx <= 2^30.  Chains and tiles share one index of workgroups, B tiles of them, laid over
- * grid x (2^31 / 256) and, beyond that, y: there is no 65535-chain limit (the bound, 2^23 x 65535 workgroups, is beyond any memory).
- * MLMCPI_ERR_INVALID, with nothing launched and no output byte touched: a NULL pointer (d_acc excepted); Mt or Mx < 2 or Mt Mx >
+ * grid x (2^31 / 256) and, beyond that, y: there is no 65535-chain limit (the bound, 2^23 x 65535 workgroups, is beyond any memory;
+ * CHAINS PER CALL above).  MLMCPI_ERR_INVALID, with nothing launched and no output byte touched: a NULL pointer (d_acc excepted); Mt or Mx < 2 or Mt Mx >
  * 2^30; B = 0; R = 0 or S = 0; R > Mt or S > Mx; more workgroups than above; work_bytes below _workspace_bytes.
  * MLMCPI_ERR_UNSUPPORTED: R or S above MLMCPI_WILSON_LOOPS_MAX (the LDS image and the register window are sized by it).
  * _plan (host only, touches no device) reports the geometry and returns the status the call would. */
