@@ -38,6 +38,11 @@
 //          (--wilson_loops N, single-level runs of the quenched Schwinger action: all `batch` chains are sampled and after the
 //           statistics come the Wilson loops W(r, s), r, s <= N, beside the exact values of the periodic lattice, and the Creutz
 //           ratios chi(r, r) with their jackknife error beside the string tension -log(I_1 / I_0))
+//   driver --action gff --Mt_lat 8 --mass 4 --sampler exact --batch 256 --n_samples 100 --gff_correlator 3
+//          (--gff_correlator P, single-level runs of the Gaussian free field with the exact, heatbath or hmc sampler: all `batch`
+//           chains are sampled and after the statistics come the slice correlators C_t(tau; q), q < P, beside the exact law, the
+//           energies E_q from the effective mass at tau <= Mt_lat / 4 with their jackknife error beside the lattice dispersion
+//           relation, and the same along x)
 //   driver --action rotor --M_lat 256 --T_final 25.6 --m0 0.25 --sampler cluster --n_updates 10 --n_samples 20000
 //          (cluster samplers: rotor and schwinger; also --coarsesampler cluster for twolevel / hierarchical rotor runs)
 //   driver --method throughput --action schwinger --Mt_lat 1024 --sampler heatbath --batch 32 --n_samples 20
@@ -64,7 +69,7 @@ int main(int argc, char **argv) {
       {"n_sweep_heatbath", "1"}, {"autotune", "1"}, {"window", "20"}, {"method", "singlelevel"}, {"n_level", "3"},
       {"epsilon", "0.01"}, {"coarsening", "both"}, {"coarsesampler", "hmc"}, {"renormalisation", "none"}, {"n_meas", "200"},
       {"batch", "1"}, {"seed", "2481317"}, {"warmup", "5"}, {"random_order", "0"}, {"n_updates", "10"}, {"correlator", "0"},
-      {"path_correlator", "0"}, {"wilson_loops", "0"}};
+      {"path_correlator", "0"}, {"wilson_loops", "0"}, {"gff_correlator", "0"}};
   for (int i = 1; i + 1 < argc; i += 2) {
     if (std::strncmp(argv[i], "--", 2) || !o.count(argv[i] + 2)) fatal(std::string("unknown option ") + argv[i]);
     o[argv[i] + 2] = argv[i + 1];
@@ -120,6 +125,33 @@ int main(int argc, char **argv) {
       fatal("--wilson_loops " + o["wilson_loops"] + " is more than min(Mt_lat, Mx_lat, " + std::to_string(MLMCPI_WILSON_LOOPS_MAX) + ") = " +
             std::to_string(cap) + " links a side");
   }
+  // --gff_correlator P: the slice correlators C_t(tau; q), C_x(tau; q), q < P, of the Gaussian free field beside the QoI, and the
+  // energies E_q from their decay (qoi.hh GffCorrelator); 0: off.  Refused here, before any device call.
+  {
+    const std::string &v = o["gff_correlator"];
+    if (v.empty() || v.size() > 9 || v.find_first_not_of("0123456789") != std::string::npos)
+      fatal("--gff_correlator takes a non-negative integer (the number of momenta, 0: off), not " + v);
+  }
+  const unsigned gff_mom = (unsigned)std::stoul(o["gff_correlator"]);
+  if (gff_mom > 0) {
+    if (o["action"] != "gff")
+      fatal("--gff_correlator " + o["gff_correlator"] + " is not supported for chosen action: the momentum-projected correlator is built "
+            "for gff only, not " + o["action"] + " (the sigma model has --correlator 1, the 1-D actions --path_correlator N, schwinger "
+            "--wilson_loops N)");
+    if (o["method"] != "singlelevel")
+      fatal("--gff_correlator runs --method singlelevel only, not " + o["method"] + " (the two-level and multilevel estimators have "
+            "no difference estimator for C(tau; q); the throughput loop measures the QoI alone)");
+    if (o["sampler"] != "exact" && o["sampler"] != "heatbath" && o["sampler"] != "hmc")
+      fatal("--gff_correlator takes a single-level sampler (exact, heatbath or hmc), not " + o["sampler"] + " (the exact law is that of "
+            "the plain lattice, not of coarsened levels)");
+    if (world > 1) fatal("--gff_correlator runs on one rank (its sums are not exchanged)");
+    const unsigned Mt_lat = (unsigned)num("Mt_lat");
+    if (Mt_lat < 2 || Mt_lat % 2) fatal("--gff_correlator needs an even Mt_lat >= 2, not " + o["Mt_lat"]);
+    const unsigned cap = std::min(Mt_lat / 2 + 1, (unsigned)MLMCPI_GFF_CORRELATOR_MAX_MOMENTA);
+    if (gff_mom > cap)
+      fatal("--gff_correlator " + o["gff_correlator"] + " is more than min(Mt_lat / 2 + 1, " +
+            std::to_string(MLMCPI_GFF_CORRELATOR_MAX_MOMENTA) + ") = " + std::to_string(cap) + " momenta");
+  }
   std::shared_ptr<Exchange> exchange;
   if (world > 1) {
     check(mlmcpi_set_device(local_rank), "mlmcpi_set_device");
@@ -138,6 +170,7 @@ int main(int argc, char **argv) {
   std::shared_ptr<SigmaCorrelator> correlator;
   std::shared_ptr<PathCorrelator> path_correlator;
   std::shared_ptr<WilsonLoops> wilson_loops;
+  std::shared_ptr<GffCorrelator> gff_correlator;
   std::shared_ptr<QoIFactory> qoi_factory;
   std::shared_ptr<ConditionedFineActionFactory> cfa_factory;
   double analytic = NAN;
@@ -280,6 +313,7 @@ int main(int argc, char **argv) {
     } else {
       action = std::make_shared<GFFAction>(lat, nullptr, num("mass"));
       qoi = std::make_shared<QoI2DPhiSquared>(lat);
+      if (gff_mom > 0) gff_correlator = std::make_shared<GffCorrelator>(lat, gff_mom);
       qoi_factory = std::make_shared<QoI2DPhiSquaredFactory>();           // driver_qft.cc:247-252
       cfa_factory = std::make_shared<GFFConditionedFineActionFactory>();  // driver_qft.cc:331-333 (use --coarsening rotate)
     }
@@ -295,7 +329,7 @@ int main(int argc, char **argv) {
       hp.batch = batch;
       return std::make_shared<HMCSamplerFactory>(hp);
     }
-    if (name == "exact") return std::make_shared<ExactSamplerFactory>(path_lags > 0 ? batch : 1u);  // driver_qm.cc: sampler = 'exact' (harmonic oscillator, GFF)
+    if (name == "exact") return std::make_shared<ExactSamplerFactory>(path_lags > 0 || gff_mom > 0 ? batch : 1u);  // driver_qm.cc: sampler = 'exact' (harmonic oscillator, GFF)
     if (name == "cluster") {  // driver_qm.cc:62-70, driver_qft.cc:69-80
       ClusterParameters cp;
       cp.n_burnin = (unsigned)num("n_burnin"); cp.n_updates = (unsigned)num("n_updates"); cp.batch = batch;
@@ -433,6 +467,7 @@ int main(int argc, char **argv) {
   std::shared_ptr<CorrelatorMeasurement> measured = correlator;
   if (path_correlator) measured = path_correlator;
   if (wilson_loops) measured = wilson_loops;  // --wilson_loops N likewise
+  if (gff_correlator) measured = gff_correlator;  // and --gff_correlator P
   MonteCarloSingleLevel mc(action, qoi, factory, mp, exchange, measured ? batch : 1u, measured);
   mc.evaluate();
   std::cout << std::endl << "=== Single level MC ===" << std::endl;
@@ -557,6 +592,42 @@ int main(int argc, char **argv) {
       std::cout << std::endl;
     }
     std::cout << " exact string tension: -log(I_1(beta) / I_0(beta)) = " << string_tension_exact(beta) << std::endl;
+  }
+  if (gff_correlator) {
+    const GffCorrelator::Estimate e = gff_correlator->means_and_errors();
+    const unsigned Mt = gff_correlator->Mt(), Mx = gff_correlator->Mx(), B = gff_correlator->batch();
+    const double mass = num("mass");
+    std::cout << std::endl << "=== GFF correlator ===" << std::endl
+              << " samples = " << gff_correlator->samples() << ", chains = " << B << ", momenta = " << gff_mom << ", errors: "
+              << (e.chain_spread ? "spread of the per-chain means" : "naive (one chain: autocorrelation ignored)") << std::endl
+              << std::setprecision(8) << std::fixed;
+    // the exact law along x is that along t with the extents exchanged, mu^2 = (mass / Mt)^2 kept: the mass argument rescaled
+    auto correlators = [&](int d) {
+      const unsigned M = d ? Mx : Mt, Mo = d ? Mt : Mx;
+      for (unsigned q = 0; q < gff_mom; ++q)
+        for (unsigned tau = 0; tau <= M / 2; ++tau) {
+          const unsigned k = gff_correlator->index(d, q, tau);
+          std::cout << " C_" << (d ? "x" : "t") << "(tau = " << tau << "; q = " << q << ") = " << e.mean[k] << " +/- " << e.error[k]
+                    << " exact = " << gff_correlator_exact(M, Mo, mass * M / Mt, q, tau) << std::endl;
+        }
+    };
+    auto energies = [&](int d) {
+      const unsigned M = d ? Mx : Mt, Mo = d ? Mt : Mx;
+      for (unsigned q = 0; q < gff_mom; ++q)
+        for (unsigned tau = 1; tau <= M / 4; ++tau) {
+          const GffCorrelator::Energy en = gff_correlator->energy(d, q, tau);
+          std::cout << " E_" << (d ? "x" : "t") << "(q = " << q << "; tau = " << tau << ") = " << en.value;
+          if (en.has_error) std::cout << " +/- " << en.error << " (jackknife over chains)";
+          else std::cout << " (one chain: no jackknife error)";
+          std::cout << " exact = " << gff_dispersion_exact(M, Mo, mass * M / Mt, q) << std::endl;
+        }
+    };
+    correlators(0);
+    std::cout << "=== GFF energies (effective mass of C_t) ===" << std::endl;
+    energies(0);
+    std::cout << "=== GFF correlator along x ===" << std::endl;
+    correlators(1);
+    energies(1);
   }
   return 0;
 }

@@ -100,5 +100,26 @@ inline double creutz_ratio(const std::vector<double> &W, unsigned int R, unsigne
   return q > 0.0 ? -std::log(q) : std::nan("");
 }
 
+// ---- the momentum-projected slice correlators of the Gaussian free field (mlmcpi_gff_correlator; the class that measures them
+// is GffCorrelator, qoi.hh) ----
+
+/** E_q of the GFF action on the unrotated Mt x Mx lattice, mu^2 = (mass / Mt)^2 as the action defines it: the lattice dispersion
+ *  relation cosh E_q = 1 + (mu^2 + 2 - 2 cos(2 pi q / Mx)) / 2, the decay rate of C_t(tau; q) */
+inline double gff_dispersion_exact(unsigned int Mt, unsigned int Mx, double mass, unsigned int q) {
+  const double mu2 = (mass / Mt) * (mass / Mt);
+  return std::acosh(1.0 + 0.5 * (mu2 + 2.0 - 2.0 * std::cos(2.0 * M_PI * q / Mx)));
+}
+
+/** <C_t(tau; q)> of that action, as the mode sum (1/Mt) sum_k cos(2 pi k tau / Mt) / lambda(k, q), lambda(k, q) = 4 + mu^2 -
+ *  2 cos(2 pi k / Mt) - 2 cos(2 pi q / Mx) the eigenvalue of the precision matrix; equal to cosh(E_q (Mt/2 - tau)) / (2 sinh E_q
+ *  sinh(E_q Mt / 2)).  C_x(tau; q) is the same with the extents exchanged. */
+inline double gff_correlator_exact(unsigned int Mt, unsigned int Mx, double mass, unsigned int q, unsigned int tau) {
+  const double mu2 = (mass / Mt) * (mass / Mt), cq = 2.0 * std::cos(2.0 * M_PI * q / Mx);
+  double s = 0.0;
+  for (unsigned int k = 0; k < Mt; ++k)
+    s += std::cos(2.0 * M_PI * (double)(((unsigned long long)k * tau) % Mt) / Mt) / (4.0 + mu2 - 2.0 * std::cos(2.0 * M_PI * k / Mt) - cq);
+  return s / Mt;
+}
+
 }  // namespace mlmcpi
 #endif

@@ -483,5 +483,141 @@ private:
   std::unique_ptr<DeviceVector> acc, out;
 };
 
+/** The momentum-projected slice correlators C_t(tau; q), C_x(tau; q), q < P, of a Gaussian free field state on a lattice, rotated
+ *  or not (mlmcpi_gff_correlator; definitions in mlmcpi_hip.h).  Not a QoI: n_out() = P (Mt/2 + 1) + P (Mx/2 + 1) numbers per
+ *  chain, C_t first, momentum-major, lag fastest.  accumulate() adds the sample's C and C^2 to per-chain sums on the device; the
+ *  means, their errors and the energies E_q (the effective mass of correlator.hh) are host arithmetic on those sums. */
+class GffCorrelator : public CorrelatorMeasurement {
+public:
+  struct Estimate {
+    std::vector<double> mean, error;
+    bool chain_spread;  // true: error = spread of the per-chain means (batch >= 2); false: the naive error of one chain
+  };
+  struct Energy {
+    double value, error;
+    bool has_error;  // the jackknife over chains needs batch >= 2
+  };
+  GffCorrelator(const std::shared_ptr<Lattice2D> lattice, unsigned int P_)
+      : Mt_lat(lattice->getMt_lat()), Mx_lat(lattice->getMx_lat()), rotated(lattice->is_rotated() ? 1 : 0),
+        n_vertices(lattice->getNvertices()), P_(P_), n_out_(P_ * (Mt_lat / 2 + 1) + P_ * (Mx_lat / 2 + 1)) {}
+  unsigned int n_mom() const { return P_; }
+  unsigned int n_out() const { return n_out_; }
+  unsigned int Mt() const { return Mt_lat; }
+  unsigned int Mx() const { return Mx_lat; }
+  /** where C_d(tau; q) sits in a vector of n_out() entries (d = 0: t, 1: x) */
+  static unsigned int index(unsigned int Mt, unsigned int Mx, unsigned int P, int d, unsigned int q, unsigned int tau) {
+    const unsigned int nt = Mt / 2 + 1, nx = Mx / 2 + 1;
+    return d == 0 ? q * nt + tau : P * nt + q * nx + tau;
+  }
+  unsigned int index(int d, unsigned int q, unsigned int tau) const { return index(Mt_lat, Mx_lat, P_, d, q, tau); }
+  /** d_out[b][n_out()] = the correlators of chain b, enqueued on the default stream */
+  void evaluate_device(const std::shared_ptr<SampleState> phi, double *d_out) { launch(phi, d_out, nullptr); }
+  /** one more sample: its correlators are added to the per-chain sums (the batch is fixed by the first call) */
+  void accumulate(const std::shared_ptr<SampleState> phi) override {
+    if (!acc || B != phi->batch()) {
+      if (n_calls) fatal("GffCorrelator::accumulate: the batch changed between samples.");
+      B = phi->batch();
+      acc = std::make_unique<DeviceVector>(2 * (size_t)B * n_out_);
+      out = std::make_unique<DeviceVector>((size_t)B * n_out_);
+    }
+    launch(phi, (double *)out->ptr(), (double *)acc->ptr());
+    ++n_calls;
+  }
+  unsigned int samples() const override { return n_calls; }
+  unsigned int batch() const { return B; }
+  /** per-chain means of C over the accumulated samples, [batch][n_out()] */
+  std::vector<std::vector<double>> chain_means() const {
+    if (!n_calls) fatal("GffCorrelator: no samples accumulated.");
+    return chain_means_of(acc->download<double>(), B, n_out_, n_calls);
+  }
+  /** the same arithmetic on downloaded sums a [batch][n_out][2] (C, C^2) of n samples */
+  static std::vector<std::vector<double>> chain_means_of(const std::vector<double> &a, unsigned int B, unsigned int n_out, unsigned int n_calls) {
+    std::vector<std::vector<double>> m(B, std::vector<double>(n_out));
+    for (unsigned int b = 0; b < B; ++b)
+      for (unsigned int k = 0; k < n_out; ++k) m[b][k] = a[2 * ((size_t)b * n_out + k)] / n_calls;
+    return m;
+  }
+  /** mean and error per entry.  batch >= 2: the error is the spread of the per-chain means over sqrt(batch), so autocorrelation
+   *  inside a chain cannot understate it; batch 1: the naive error of the samples (it ignores autocorrelation) */
+  Estimate means_and_errors() const {
+    if (!n_calls) fatal("GffCorrelator: no samples accumulated.");
+    return estimate(acc->download<double>(), B, n_out_, n_calls);
+  }
+  /** the same arithmetic on downloaded sums a [batch][n_out][2] (C, C^2) of n samples */
+  static Estimate estimate(const std::vector<double> &a, unsigned int B, unsigned int n_out, unsigned int n_calls) {
+    Estimate e{std::vector<double>(n_out, 0.0), std::vector<double>(n_out, 0.0), B >= 2};
+    const double n = n_calls;
+    for (unsigned int k = 0; k < n_out; ++k) {
+      if (B >= 2) {
+        double s = 0.0, s2 = 0.0;
+        for (unsigned int b = 0; b < B; ++b) s += a[2 * ((size_t)b * n_out + k)] / n;
+        const double m = s / B;
+        for (unsigned int b = 0; b < B; ++b) {
+          const double d = a[2 * ((size_t)b * n_out + k)] / n - m;
+          s2 += d * d;
+        }
+        e.mean[k] = m;
+        e.error[k] = std::sqrt(s2 / ((double)B * (B - 1.0)));
+      } else {
+        const double m = a[2 * k] / n, var = n_calls > 1 ? std::max(0.0, (a[2 * k + 1] / n - m * m) * n / (n - 1.0)) : 0.0;
+        e.mean[k] = m;
+        e.error[k] = std::sqrt(var / n);
+      }
+    }
+    return e;
+  }
+  /** E_q of direction d (0: t, 1: x) from the effective mass of the mean correlator at lag tau, 1 <= tau <= M_d/2 - 1; batch >= 2:
+   *  with the jackknife error over the chains */
+  Energy energy(int d, unsigned int q, unsigned int tau) const {
+    const unsigned int M = d == 0 ? Mt_lat : Mx_lat;
+    if (q >= P_ || tau < 1 || tau + 1 > M / 2) fatal("GffCorrelator::energy: momentum or lag outside its range.");
+    return energy_jackknife(chain_means(), Mt_lat, Mx_lat, P_, d, q, tau);
+  }
+  /** E_q along t, the direction the dispersion relation of correlator.hh speaks of */
+  Energy energy(unsigned int q, unsigned int tau) const { return energy(0, q, tau); }
+  /** the same arithmetic on per-chain means m [batch][n_out] */
+  static Energy energy_jackknife(const std::vector<std::vector<double>> &m, unsigned int Mt, unsigned int Mx, unsigned int P, int d,
+                                 unsigned int q, unsigned int tau) {
+    const unsigned int B = (unsigned int)m.size(), nl = (d == 0 ? Mt : Mx) / 2 + 1, o = index(Mt, Mx, P, d, q, 0);
+    std::vector<double> all(nl, 0.0);
+    for (unsigned int b = 0; b < B; ++b)
+      for (unsigned int k = 0; k < nl; ++k) all[k] += m[b][o + k];
+    std::vector<double> mean(all);
+    for (double &v : mean) v /= B;
+    Energy r{effective_mass(mean, tau), 0.0, B >= 2};
+    if (B >= 2) {
+      std::vector<double> x(B), leave(nl);
+      double xm = 0.0, s2 = 0.0;
+      for (unsigned int b = 0; b < B; ++b) {
+        for (unsigned int k = 0; k < nl; ++k) leave[k] = (all[k] - m[b][o + k]) / (B - 1.0);
+        x[b] = effective_mass(leave, tau);
+        xm += x[b] / B;
+      }
+      for (unsigned int b = 0; b < B; ++b) s2 += (x[b] - xm) * (x[b] - xm);
+      r.error = std::sqrt((B - 1.0) / B * s2);
+    }
+    return r;
+  }
+
+private:
+  void launch(const std::shared_ptr<SampleState> phi, double *d_out, double *d_acc) {
+    if (phi->size() != n_vertices) fatal("Evaluating GffCorrelator on state of wrong size.");
+    if (!work || work_B != phi->batch()) {
+      check(mlmcpi_gff_correlator_workspace_bytes(Mt_lat, Mx_lat, rotated, P_, phi->batch(), &work_bytes), "gff_correlator_workspace_bytes");
+      work = std::make_unique<DeviceBuffer>(work_bytes);
+      work_B = phi->batch();
+    }
+    check(mlmcpi_gff_correlator(Mt_lat, Mx_lat, rotated, P_, phi->device(), phi->batch(), d_out, d_acc, work->p, work_bytes, nullptr),
+          "gff_correlator");
+  }
+  const unsigned int Mt_lat, Mx_lat;
+  const int rotated;
+  const unsigned int n_vertices, P_, n_out_;
+  unsigned int B = 0, work_B = 0, n_calls = 0;
+  size_t work_bytes = 0;
+  std::unique_ptr<DeviceBuffer> work;
+  std::unique_ptr<DeviceVector> acc, out;
+};
+
 }  // namespace mlmcpi
 #endif

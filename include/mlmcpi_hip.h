@@ -51,6 +51,8 @@
  *       mlmcpi_path_exact_draw                                                         grid y, 16 per row    unbounded
  *       mlmcpi_path_cluster_draw, mlmcpi_schwinger_cluster_*                           grid x, 4 per wg      unbounded
  *       mlmcpi_path_correlator, mlmcpi_schwinger_wilson_loops                          linear index, x then y 2^23 x 65535 workgroups
+ *       mlmcpi_gff_correlator (its batch is spelled n_chains; run at the edge by       linear index, x then y unbounded (2^23 x 65535
+ *         tests/test_gff_correlator_gpu.py)                                                                  workgroups)
  *       mlmcpi_lattice_evaluate / _force / _initialise / _sweep_draw* / _copy_from_* / grid y (finish kernels: unbounded
  *         _twolevel_draw* / _exact_draw / _hmc_draw, mlmcpi_qoi_phi_squared /          x, 4 or 1 per wg)
  *         _avg_plaquette / _2d_susceptibility / _magnetic_susceptibility
@@ -877,6 +879,73 @@ int mlmcpi_schwinger_wilson_loops(const double *d_theta, uint32_t Mt, uint32_t M
                                   double *d_out /* [B][R][S] */, double *d_acc /* [B][R][S][2], may be NULL */, void *d_work,
                                   size_t work_bytes, void *stream);
 int mlmcpi_schwinger_wilson_loops_plan(uint32_t Mt, uint32_t Mx, uint32_t R, uint32_t S, uint32_t B, mlmcpi_wilson_loops_plan_info *out);
+
+/* The momentum-projected time-slice correlators of a Gaussian free field state (gff_correlator.hip).
+ * A level is (Mt, Mx, rotated), Mt and Mx even and >= 2, Mt Mx <= 2^30.  rotated = 0: phi[b][Mt j + i], the GFF layout above.
+ * rotated != 0: the Mt Mx / 2 vertices with i + j even in the order of rotated lattices above (mlmcpi_sigma_level; the GFF levels
+ * store the same Lattice2D order): the planes E then O, index p (Mt Mx / 4) + (Mt/2) b + a = vertex (2 a + p, 2 b + p).  N = the
+ * level's number of vertices.  For the momenta q = 0 .. P - 1 (P = n_mom):
+ *   slice sums   S^t_i(q) = sum_j phi(i, j) e^{-2 pi i q j / Mx} over the level's vertices with first coordinate i;
+ *                S^x_j(q) = sum_i phi(i, j) e^{-2 pi i q i / Mt} over those with second coordinate j.
+ *   correlators  C_t(tau; q) = (1/N) sum_i Re[S^t_i(q) conj S^t_{(i + tau) mod Mt}(q)], tau = 0 .. Mt/2;
+ *                C_x(tau; q) = (1/N) sum_j Re[S^x_j(q) conj S^x_{(j + tau) mod Mx}(q)], tau = 0 .. Mx/2.
+ * d_out [n_chains][n_out], n_out = P (Mt/2 + 1) + P (Mx/2 + 1) (_correlator_size): C_t first, momentum-major, lag fastest.
+ * Identities: with w(0) = w(M/2) = 1 and w = 2 otherwise, N sum_tau w C_t(tau; 0) = (sum phi)^2; summed over ALL Mx momenta,
+ * sum_q C_t(0; q) = Mx (1/N) sum phi^2 (unrotated; C(.; Mx - q) = C(.; q), so the momenta 0 < q < Mx/2 count twice).  For the GFF
+ * action on the unrotated Mt x Mx lattice, mu^2 = (mass / Mt)^2, <C_t(tau; q)> = (1/Mt) sum_k cos(2 pi k tau / Mt) / (4 + mu^2 -
+ * 2 cos(2 pi k / Mt) - 2 cos(2 pi q / Mx)) = cosh(E_q (Mt/2 - tau)) / (2 sinh E_q sinh(E_q Mt / 2)), one cosh whose rate is the
+ * lattice dispersion relation cosh E_q = 1 + (mu^2 + 2 - 2 cos(2 pi q / Mx)) / 2 (include/mlmcpi/correlator.hh).
+ * How it is computed: the twiddles are entries (q j) mod M of a table of the M-th roots of unity, the product reduced in integers,
+ * the table built by a prelude launch of every call (one sincospi per entry on an argument reduced exactly; entry 0 is (1, 0)); no
+ * twiddle is formed by recurrence.  The state is read once: a workgroup takes a band of band_rows rows of a chunk of `tile` columns of
+ * one plane (unrotated: one plane of Mt columns x Mx rows, column i, row j; rotated: plane p, column a, row b) and adds, one FMA per
+ * part and vertex, the rows of its band ascending (S^t) and the columns of its chunk ascending (S^x); a gather adds the bands
+ * (chunks) ascending; one wave per (lag, q, direction, chain) adds the slices lane l: l, l + 64, .. ascending (a product and an FMA
+ * each), then the lane tree (offsets 32, .., 1), and multiplies by 1/N last.  The geometry is a function of (Mt, Mx, rotated, P)
+ * alone, there are no atomics and no tuning knob: a chain's output is the same bits for every n_chains, every split of the chains
+ * over calls, every stream, and with or without d_acc.
+ * d_phi: 16-byte aligned, not written.  d_acc (may be NULL) [n_chains][n_out][2]: C is ADDED to [.][.][0] and C^2 to [.][.][1] in
+ * the launch that writes d_out; the caller counts the calls.  d_work: _workspace_bytes bytes, 256-byte aligned; content at entry
+ * ignored.
+ * The batch parameter is spelled n_chains, not B: tests/test_chain_count_cases.py collects the exports with a `uint32_t B` and
+ * demands a row of its case table for each; these entry points are run at the 65535-chain edge by tests/test_gff_correlator_gpu.py
+ * instead.  Chains and tiles (blocks of lags) share one index of workgroups laid over grid x (2^31 / 256) and, beyond that, y:
+ * there is no 65535-chain limit (CHAINS PER CALL above).
+ * MLMCPI_ERR_INVALID, with nothing launched and no output byte touched: odd or zero extents or Mt Mx > 2^30; n_mom = 0 or above
+ * Mx/2 + 1 or Mt/2 + 1; a NULL pointer (d_acc excepted) or d_phi, d_work off 16 bytes; n_chains = 0; more workgroups than 2^23 x
+ * 65535; work_bytes below _workspace_bytes.  MLMCPI_ERR_UNSUPPORTED: n_mom above MLMCPI_GFF_CORRELATOR_MAX_MOMENTA (the LDS
+ * twiddle images and the register accumulators are sized by it).  _plan (host only, touches no device) reports the geometry and
+ * returns the status the call would. */
+#ifdef __cplusplus
+constexpr uint32_t MLMCPI_GFF_CORRELATOR_MAX_MOMENTA = 8;
+#else
+#define MLMCPI_GFF_CORRELATOR_MAX_MOMENTA 8u
+#endif
+typedef struct mlmcpi_gff_correlator_plan_info {
+  uint64_t work_bytes;             /* what _workspace_bytes reports: align256 of each of the table ((Mt + Mx) 16 bytes), the band partials
+                                    * (n_chains planes bands P plane_w 16), the chunk partials (n_chains planes chunks P plane_h 16) and
+                                    * the slice sums (n_chains P (Mt + Mx) 16) */
+  uint64_t grid;                   /* workgroups of the projection launch, n_chains planes bands chunks */
+  uint64_t gather_grid, lag_grid;  /* of the gather, n_chains ceil(P (Mt + Mx) / workgroup), and of the lag launch, n_chains P
+                                    * (ceil((Mt/2 + 1) / lags_per_workgroup) + ceil((Mx/2 + 1) / lags_per_workgroup)) */
+  uint32_t workgroup;              /* threads of a workgroup, every launch */
+  uint32_t tile;                   /* rows and columns of a tile; columns of a chunk */
+  uint32_t band_rows;              /* rows of a band */
+  uint32_t planes, plane_w, plane_h;  /* 1, Mt, Mx; rotated: 2, Mt/2, Mx/2 */
+  uint32_t chunks, bands;          /* ceil(plane_w / tile), ceil(plane_h / band_rows) */
+  uint32_t vector_loads;           /* 1: plane_w is even and the tile is loaded by 16-byte loads; 0: by 8-byte loads (the same sums) */
+  uint32_t table_entries;          /* Mt + Mx roots of unity */
+  uint32_t lags_per_workgroup;
+  uint32_t lags_in_lds;            /* 1: max(Mt, Mx) 16 bytes fit lds_limit and the lag launch stages the slice sums in LDS */
+  uint32_t lds_bytes, lag_lds_bytes, lds_limit;  /* LDS of a workgroup of the projection and of the lag launch; the limit both are written for */
+} mlmcpi_gff_correlator_plan_info;
+int mlmcpi_gff_correlator_size(uint32_t Mt, uint32_t Mx, int32_t rotated, uint32_t n_mom, uint32_t *n_out);
+int mlmcpi_gff_correlator_workspace_bytes(uint32_t Mt, uint32_t Mx, int32_t rotated, uint32_t n_mom, uint32_t n_chains, size_t *bytes);
+int mlmcpi_gff_correlator(uint32_t Mt, uint32_t Mx, int32_t rotated, uint32_t n_mom, const double *d_phi, uint32_t n_chains,
+                          double *d_out /* [n_chains][n_out] */, double *d_acc /* [n_chains][n_out][2], may be NULL */, void *d_work,
+                          size_t work_bytes, void *stream);
+int mlmcpi_gff_correlator_plan(uint32_t Mt, uint32_t Mx, int32_t rotated, uint32_t n_mom, uint32_t n_chains,
+                               mlmcpi_gff_correlator_plan_info *out);
 /* QoI2DMagneticSusceptibility (qoi/qft/qoi2dmagneticsusceptibility.cc:7-21): d_out[b] = |sum_n sigma_n|^2 / (Mt Mx) of a
  * sigma-model state */
 int mlmcpi_qoi_magnetic_susceptibility(const double *d_phi, uint32_t Mt, uint32_t Mx, uint32_t B, double *d_out, void *stream);

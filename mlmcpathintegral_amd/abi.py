@@ -78,6 +78,13 @@ class WilsonLoopsPlan(C.Structure):
         "workgroup", "tile_w", "tile_h", "halo_w", "halo_h", "J", "tiles_w", "tiles_h", "tiles", "lds_bytes", "lds_limit")]
 
 
+class GffCorrelatorPlan(C.Structure):
+    """mlmcpi_gff_correlator_plan_info"""
+    _fields_ = [(n, C.c_uint64) for n in ("work_bytes", "grid", "gather_grid", "lag_grid")] + [(n, C.c_uint32) for n in (
+        "workgroup", "tile", "band_rows", "planes", "plane_w", "plane_h", "chunks", "bands", "vector_loads", "table_entries",
+        "lags_per_workgroup", "lags_in_lds", "lds_bytes", "lag_lds_bytes", "lds_limit")]
+
+
 _vp, _u32, _u64, _i, _d, _sz = C.c_void_p, C.c_uint32, C.c_uint64, C.c_int, C.c_double, C.c_size_t
 _PA, _LA = C.POINTER(PathAction), C.POINTER(LatticeAction)
 _SL = C.POINTER(SigmaLevel)
@@ -119,6 +126,10 @@ SIGNATURES = {
     "mlmcpi_schwinger_wilson_loops_workspace_bytes": (_i, [_u32, _u32, _u32, _u32, _u32, C.POINTER(_sz)]),
     "mlmcpi_schwinger_wilson_loops": (_i, [_vp, _u32, _u32, _u32, _u32, _u32, _vp, _vp, _vp, _sz, _vp]),
     "mlmcpi_schwinger_wilson_loops_plan": (_i, [_u32, _u32, _u32, _u32, _u32, C.POINTER(WilsonLoopsPlan)]),
+    "mlmcpi_gff_correlator_size": (_i, [_u32, _u32, C.c_int32, _u32, C.POINTER(_u32)]),
+    "mlmcpi_gff_correlator_workspace_bytes": (_i, [_u32, _u32, C.c_int32, _u32, _u32, C.POINTER(_sz)]),
+    "mlmcpi_gff_correlator": (_i, [_u32, _u32, C.c_int32, _u32, _vp, _u32, _vp, _vp, _vp, _sz, _vp]),
+    "mlmcpi_gff_correlator_plan": (_i, [_u32, _u32, C.c_int32, _u32, _u32, C.POINTER(GffCorrelatorPlan)]),
     "mlmcpi_path_sweep_draw": (_i, [_PA, _vp, _vp, _u32, _u32, _u32, _u64, _u32, _u32, _vp]),
     "mlmcpi_path_sweep_draw_from": (_i, [_PA, _vp, _vp, _vp, _u32, _u32, _u32, _u64, _u32, _u32, _vp, _vp]),
     "mlmcpi_path_sweep_draw_qoi": (_i, [_PA, _vp, _vp, _vp, _u32, _u32, _u32, _u64, _u32, _u32, _vp, _vp, _vp, _vp]),

@@ -752,6 +752,55 @@ def wilson_loops(theta, Mt, Mx, R, S, acc=None, work=None):
     return out
 
 
+def gff_correlator_size(Mt, Mx, n_mom, rotated=False):
+    """n_out = n_mom (Mt/2 + 1) + n_mom (Mx/2 + 1) (mlmcpi_gff_correlator_size; no device needed)"""
+    n = C.c_uint32(0)
+    abi.call("mlmcpi_gff_correlator_size", Mt, Mx, int(bool(rotated)), n_mom, C.byref(n))
+    return n.value
+
+
+def gff_correlator_plan(Mt, Mx, n_mom, rotated=False, n_chains=1):
+    """The launch geometry of gff_correlator for these arguments (mlmcpi_gff_correlator_plan; no device needed): a dict of the
+    fields of mlmcpi_gff_correlator_plan_info"""
+    info = abi.GffCorrelatorPlan()
+    abi.call("mlmcpi_gff_correlator_plan", Mt, Mx, int(bool(rotated)), n_mom, n_chains, C.byref(info))
+    return {n: getattr(info, n) for n, _ in abi.GffCorrelatorPlan._fields_}
+
+
+def gff_correlator_workspace(Mt, Mx, n_mom, n_chains, rotated=False, device="cuda"):
+    """workspace of gff_correlator for n_chains chains and n_mom momenta (uint8 tensor)"""
+    return _workspace("mlmcpi_gff_correlator_workspace_bytes", Mt, Mx, int(bool(rotated)), n_mom, n_chains, device=device)
+
+
+def gff_correlator(phi, Mt, Mx, n_mom, rotated=False, acc=None, work=None):
+    """C_t(tau; q) and C_x(tau; q), q < n_mom, of every chain of the GFF state phi [B, N] on the level (Mt, Mx, rotated)
+    (mlmcpi_gff_correlator): returns [B, n_out], C_t first, momentum-major, lag fastest (gff_correlator_t / _x slice it); acc
+    [B, n_out, 2] (optional) is added to: C and C^2"""
+    _check_state(phi, Mt * Mx // 2 if rotated else Mt * Mx)
+    B, n_out = phi.shape[0], gff_correlator_size(Mt, Mx, n_mom, rotated)
+    if work is None:
+        work = gff_correlator_workspace(Mt, Mx, n_mom, B, rotated, phi.device)
+    if acc is not None:
+        assert acc.dtype == torch.float64 and tuple(acc.shape) == (B, n_out, 2), acc.shape
+    out = torch.empty((B, n_out), dtype=torch.float64, device=phi.device)
+    abi.call("mlmcpi_gff_correlator", Mt, Mx, int(bool(rotated)), n_mom, _p(phi), B, _p(out), _p(acc), _p(work), work.numel(), _stream())
+    return out
+
+
+def gff_correlator_t(out, Mt, Mx, n_mom, q):
+    """C_t(tau; q), tau = 0 .. Mt/2, of every chain: the view [B, Mt/2 + 1] of what gff_correlator returned"""
+    assert 0 <= q < n_mom and out.shape[-1] == n_mom * (Mt // 2 + Mx // 2 + 2)
+    nt = Mt // 2 + 1
+    return out[..., q * nt:(q + 1) * nt]
+
+
+def gff_correlator_x(out, Mt, Mx, n_mom, q):
+    """C_x(tau; q), tau = 0 .. Mx/2, of every chain: the view [B, Mx/2 + 1] of what gff_correlator returned"""
+    assert 0 <= q < n_mom and out.shape[-1] == n_mom * (Mt // 2 + Mx // 2 + 2)
+    nt, nx = Mt // 2 + 1, Mx // 2 + 1
+    return out[..., n_mom * nt + q * nx:n_mom * nt + (q + 1) * nx]
+
+
 def qoi_2d_susceptibility(theta, Mt, Mx):
     out = torch.empty(theta.shape[0], dtype=torch.float64, device=theta.device)
     abi.call("mlmcpi_qoi_2d_susceptibility", _p(theta), Mt, Mx, theta.shape[0], _p(out), _stream())
