@@ -62,6 +62,26 @@
 
 using namespace mlmcpi;
 
+/** the value v of --name, a count (0: off); anything but a non-negative integer is refused, before any device call */
+static unsigned count_option(const std::string &name, const std::string &v, const char *counted) {
+  if (v.empty() || v.size() > 9 || v.find_first_not_of("0123456789") != std::string::npos)
+    fatal("--" + name + " takes a non-negative integer (" + counted + ", 0: off), not " + v);
+  return (unsigned)std::stoul(v);
+}
+
+/** the first lines of a measurement's block: its title, then samples, chains, `more` and what its errors are */
+static void measurement_header(const char *title, const CorrelatorMeasurement &m, const ChainEstimate &e, const std::string &more = "") {
+  std::cout << std::endl << "=== " << title << " ===" << std::endl
+            << " samples = " << m.samples() << ", chains = " << m.batch() << more << ", errors: "
+            << (e.chain_spread ? "spread of the per-chain means" : "naive (one chain: autocorrelation ignored)") << std::endl;
+}
+
+/** what follows the value of a quantity derived from the mean over chains */
+static void jackknife_suffix(const ChainScalar &s) {
+  if (s.has_error) std::cout << " +/- " << s.error << " (jackknife over chains)";
+  else std::cout << " (one chain: no jackknife error)";
+}
+
 int main(int argc, char **argv) {
   std::map<std::string, std::string> o = {{"action", "harmonicoscillator"}, {"M_lat", "128"}, {"T_final", "4.0"},
       {"Mt_lat", "16"}, {"m0", "1.0"}, {"mu2", "1.0"}, {"lambda", "1.0"}, {"x0", "1.0"}, {"beta", "1.0"}, {"mass", "10.0"},
@@ -81,12 +101,7 @@ int main(int argc, char **argv) {
   const unsigned batch = (unsigned)num("batch");
   // --path_correlator N: the time correlator C(tau), tau = 0 .. N - 1, of a 1-D path action beside the QoI, and the energy gap from
   // its decay (qoi.hh PathCorrelator); 0: off.  Refused here, before any device call.
-  {
-    const std::string &v = o["path_correlator"];
-    if (v.empty() || v.size() > 9 || v.find_first_not_of("0123456789") != std::string::npos)
-      fatal("--path_correlator takes a non-negative integer (the number of lags, 0: off), not " + v);
-  }
-  const unsigned path_lags = (unsigned)std::stoul(o["path_correlator"]);
+  const unsigned path_lags = count_option("path_correlator", o["path_correlator"], "the number of lags");
   if (path_lags > 0) {
     const std::string &pa = o["action"];
     if (pa != "harmonicoscillator" && pa != "quarticoscillator" && pa != "rotor")
@@ -103,12 +118,7 @@ int main(int argc, char **argv) {
   }
   // --wilson_loops N: the Wilson loops W(r, s), r, s <= N, of the quenched Schwinger action beside the QoI, and the Creutz ratios
   // from them (qoi.hh WilsonLoops); 0: off.  Refused here, before any device call.
-  {
-    const std::string &v = o["wilson_loops"];
-    if (v.empty() || v.size() > 9 || v.find_first_not_of("0123456789") != std::string::npos)
-      fatal("--wilson_loops takes a non-negative integer (the largest loop side, 0: off), not " + v);
-  }
-  const unsigned wilson_n = (unsigned)std::stoul(o["wilson_loops"]);
+  const unsigned wilson_n = count_option("wilson_loops", o["wilson_loops"], "the largest loop side");
   if (wilson_n > 0) {
     if (o["action"] != "schwinger")
       fatal("--wilson_loops " + o["wilson_loops"] + " is not supported for chosen action: Wilson loops are built for schwinger only, not " +
@@ -127,12 +137,7 @@ int main(int argc, char **argv) {
   }
   // --gff_correlator P: the slice correlators C_t(tau; q), C_x(tau; q), q < P, of the Gaussian free field beside the QoI, and the
   // energies E_q from their decay (qoi.hh GffCorrelator); 0: off.  Refused here, before any device call.
-  {
-    const std::string &v = o["gff_correlator"];
-    if (v.empty() || v.size() > 9 || v.find_first_not_of("0123456789") != std::string::npos)
-      fatal("--gff_correlator takes a non-negative integer (the number of momenta, 0: off), not " + v);
-  }
-  const unsigned gff_mom = (unsigned)std::stoul(o["gff_correlator"]);
+  const unsigned gff_mom = count_option("gff_correlator", o["gff_correlator"], "the number of momenta");
   if (gff_mom > 0) {
     if (o["action"] != "gff")
       fatal("--gff_correlator " + o["gff_correlator"] + " is not supported for chosen action: the momentum-projected correlator is built "
@@ -491,10 +496,8 @@ int main(int argc, char **argv) {
         avg_err[tau] = std::sqrt(s2 / ((double)B * (B - 1.0)));
       }
     }
-    std::cout << std::endl << "=== Time-slice correlator ===" << std::endl
-              << " samples = " << correlator->samples() << ", chains = " << B << ", errors: "
-              << (e.chain_spread ? "spread of the per-chain means" : "naive (one chain: autocorrelation ignored)") << std::endl
-              << std::setprecision(6) << std::fixed;
+    measurement_header("Time-slice correlator", *correlator, e);
+    std::cout << std::setprecision(6) << std::fixed;
     for (unsigned tau = 0; tau < std::max(nt, nx); ++tau) {
       std::cout << " C(tau = " << tau << "):";
       if (tau < nt) std::cout << " C_t = " << Ct[tau] << " +/- " << Et[tau];
@@ -507,8 +510,7 @@ int main(int argc, char **argv) {
     for (int d = 0; d < 2; ++d) {
       const SigmaCorrelator::Xi xi = correlator->xi(d);
       std::cout << " xi_2 (" << (d ? "x" : "t") << ") = " << xi.value;
-      if (xi.has_error) std::cout << " +/- " << xi.error << " (jackknife over chains)";
-      else std::cout << " (one chain: no jackknife error)";
+      jackknife_suffix(xi);
       std::cout << ", xi_2 / M = " << xi.value / (d ? Mx : Mt) << std::endl;
     }
     // --sampler swendsenwang or wolff: the same two numbers from the cluster sums of the updates (the field BEFORE each update);
@@ -548,13 +550,11 @@ int main(int argc, char **argv) {
   }
   if (path_correlator) {
     const PathCorrelator::Estimate e = path_correlator->means_and_errors();
-    const unsigned M_lat = path_correlator->M(), B = path_correlator->batch();
+    const unsigned M_lat = path_correlator->M();
     const double T_final = num("T_final"), a_lat = T_final / M_lat;
     const bool ho = a == "harmonicoscillator";
-    std::cout << std::endl << "=== Path correlator ===" << std::endl
-              << " samples = " << path_correlator->samples() << ", chains = " << B << ", errors: "
-              << (e.chain_spread ? "spread of the per-chain means" : "naive (one chain: autocorrelation ignored)") << std::endl
-              << std::setprecision(8) << std::fixed;
+    measurement_header("Path correlator", *path_correlator, e);
+    std::cout << std::setprecision(8) << std::fixed;
     for (unsigned tau = 0; tau < path_lags; ++tau) {
       std::cout << " C(tau = " << tau << ") = " << e.mean[tau] << " +/- " << e.error[tau];
       if (ho) std::cout << " exact = " << path_correlator_ho_exact(M_lat, T_final, num("m0"), num("mu2"), tau);
@@ -563,8 +563,7 @@ int main(int argc, char **argv) {
     for (unsigned tau = 1; tau + 1 < path_lags; ++tau) {
       const PathCorrelator::Mass m = path_correlator->effective_mass(tau);
       std::cout << " m_eff(tau = " << tau << ") = " << m.value;
-      if (m.has_error) std::cout << " +/- " << m.error << " (jackknife over chains)";
-      else std::cout << " (one chain: no jackknife error)";
+      jackknife_suffix(m);
       std::cout << ", Delta E = m_eff / a = " << m.value / a_lat << std::endl;
     }
     if (ho) {
@@ -574,12 +573,10 @@ int main(int argc, char **argv) {
   }
   if (wilson_loops) {
     const WilsonLoops::Estimate e = wilson_loops->means_and_errors();
-    const unsigned Mt = wilson_loops->Mt(), Mx = wilson_loops->Mx(), B = wilson_loops->batch();
+    const unsigned Mt = wilson_loops->Mt(), Mx = wilson_loops->Mx();
     const double beta = num("beta");
-    std::cout << std::endl << "=== Wilson loops ===" << std::endl
-              << " samples = " << wilson_loops->samples() << ", chains = " << B << ", errors: "
-              << (e.chain_spread ? "spread of the per-chain means" : "naive (one chain: autocorrelation ignored)") << std::endl
-              << std::setprecision(8) << std::fixed;
+    measurement_header("Wilson loops", *wilson_loops, e);
+    std::cout << std::setprecision(8) << std::fixed;
     for (unsigned r = 1; r <= wilson_n; ++r)
       for (unsigned s = 1; s <= wilson_n; ++s)
         std::cout << " W(r = " << r << ", s = " << s << ") = " << e.mean[(r - 1) * wilson_n + s - 1] << " +/- "
@@ -587,20 +584,17 @@ int main(int argc, char **argv) {
     for (unsigned r = 1; r <= wilson_n; ++r) {
       const WilsonLoops::Ratio c = wilson_loops->creutz(r, r);
       std::cout << " chi(r = " << r << ", s = " << r << ") = " << c.value;
-      if (c.has_error) std::cout << " +/- " << c.error << " (jackknife over chains)";
-      else std::cout << " (one chain: no jackknife error)";
+      jackknife_suffix(c);
       std::cout << std::endl;
     }
     std::cout << " exact string tension: -log(I_1(beta) / I_0(beta)) = " << string_tension_exact(beta) << std::endl;
   }
   if (gff_correlator) {
     const GffCorrelator::Estimate e = gff_correlator->means_and_errors();
-    const unsigned Mt = gff_correlator->Mt(), Mx = gff_correlator->Mx(), B = gff_correlator->batch();
+    const unsigned Mt = gff_correlator->Mt(), Mx = gff_correlator->Mx();
     const double mass = num("mass");
-    std::cout << std::endl << "=== GFF correlator ===" << std::endl
-              << " samples = " << gff_correlator->samples() << ", chains = " << B << ", momenta = " << gff_mom << ", errors: "
-              << (e.chain_spread ? "spread of the per-chain means" : "naive (one chain: autocorrelation ignored)") << std::endl
-              << std::setprecision(8) << std::fixed;
+    measurement_header("GFF correlator", *gff_correlator, e, ", momenta = " + std::to_string(gff_mom));
+    std::cout << std::setprecision(8) << std::fixed;
     // the exact law along x is that along t with the extents exchanged, mu^2 = (mass / Mt)^2 kept: the mass argument rescaled
     auto correlators = [&](int d) {
       const unsigned M = d ? Mx : Mt, Mo = d ? Mt : Mx;
@@ -617,8 +611,7 @@ int main(int argc, char **argv) {
         for (unsigned tau = 1; tau <= M / 4; ++tau) {
           const GffCorrelator::Energy en = gff_correlator->energy(d, q, tau);
           std::cout << " E_" << (d ? "x" : "t") << "(q = " << q << "; tau = " << tau << ") = " << en.value;
-          if (en.has_error) std::cout << " +/- " << en.error << " (jackknife over chains)";
-          else std::cout << " (one chain: no jackknife error)";
+          jackknife_suffix(en);
           std::cout << " exact = " << gff_dispersion_exact(M, Mo, mass * M / Mt, q) << std::endl;
         }
     };

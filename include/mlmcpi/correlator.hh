@@ -1,6 +1,7 @@
 // correlator.hh -- host arithmetic on a mean time-slice correlator C(tau), tau = 0 .. M/2, of a periodic direction of even
 // extent M (mlmcpi_sigma_level_correlator; the class that measures it is SigmaCorrelator, qoi.hh), and on the time correlator of
-// a 1-D path (below).  No device code.
+// a 1-D path, on Wilson loops and on the slice correlators of the Gaussian free field (below): the functions of a mean vector whose
+// error over chains chain_estimate.hh forms (chain_jackknife).  No device code.
 #ifndef MLMCPI_CORRELATOR_HH
 #define MLMCPI_CORRELATOR_HH
 #include <cmath>

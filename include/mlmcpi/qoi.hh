@@ -2,12 +2,16 @@
 // path as device reductions.  evaluate() returns chain 0; evaluate_batch() all chains of the state;
 // evaluate_device() leaves the per-chain values on the device (asynchronous: no host round trip per sample, for
 // loops that accumulate statistics on the device with mlmcpi_stats_accumulate).
+// After the QoIs, the measurements beside the QoI (SigmaCorrelator, PathCorrelator, WilsonLoops, GffCorrelator): each is its ABI
+// call and its one derived quantity on top of CorrelatorMeasurement, which keeps the per-chain sums on the device; the arithmetic
+// on those sums is chain_estimate.hh, the derived quantities themselves correlator.hh.
 #ifndef MLMCPI_QOI_HH
 #define MLMCPI_QOI_HH
 #include <algorithm>
 #include <cmath>
 
 #include "action.hh"
+#include "chain_estimate.hh"
 #include "correlator.hh"
 
 namespace mlmcpi {
@@ -125,44 +129,21 @@ private:
   const bool rotated;
 };
 
-/** What MonteCarloSingleLevel asks of a correlator it measures beside the QoI: one more sample of the state at hand, and how
- *  many it has taken (SigmaCorrelator, PathCorrelator). */
+/** A measurement beside the QoI: not a QoI, its value is a vector of n_out() numbers per chain.  MonteCarloSingleLevel asks it for
+ *  one more sample of the state at hand (accumulate) and how many it has taken (samples).  accumulate() adds the sample's values and
+ *  their squares to per-chain sums on the device; the means and their errors are host arithmetic on those sums (chain_estimate.hh).
+ *  A measurement supplies its name (the fatal messages carry it), the size of the state it takes, and its two ABI calls. */
 class CorrelatorMeasurement {
 public:
+  using Estimate = ChainEstimate;
   virtual ~CorrelatorMeasurement() {}
-  virtual void accumulate(const std::shared_ptr<SampleState> phi) = 0;
-  virtual unsigned int samples() const = 0;
-};
-
-/** The time-slice correlators C_t(tau), C_x(tau) of the O(3) sigma model on a lattice, rotated or not
- *  (mlmcpi_sigma_level_correlator; definitions in mlmcpi_hip.h).  Not a QoI: its value is a vector of n_out() =
- *  (Mt/2 + 1) + (Mx/2 + 1) numbers per chain, C_t first.  accumulate() adds the sample's C and C^2 to per-chain sums on the
- *  device; the means, their errors and xi_2 (correlator.hh) are host arithmetic on those sums. */
-class SigmaCorrelator : public CorrelatorMeasurement {
-public:
-  struct Estimate {
-    std::vector<double> mean, error;
-    bool chain_spread;  // true: error = spread of the per-chain means (batch >= 2); false: the naive error of one chain
-  };
-  struct Xi {
-    double value, error;
-    bool has_error;  // the jackknife over chains needs batch >= 2
-  };
-  explicit SigmaCorrelator(const std::shared_ptr<Lattice2D> lattice)
-      : level{lattice->getMt_lat(), lattice->getMx_lat(), lattice->is_rotated() ? 1 : 0, 0.0}, n_vertices(lattice->getNvertices()) {
-    uint32_t n = 0;
-    check(mlmcpi_sigma_level_correlator_size(&level, &n), "sigma_level_correlator_size");
-    n_out_ = n;
-  }
   unsigned int n_out() const { return n_out_; }
-  unsigned int Mt() const { return level.Mt; }
-  unsigned int Mx() const { return level.Mx; }
-  /** d_out[b][n_out()] = the correlators of chain b, enqueued on the default stream */
+  /** d_out[b][n_out()] = the values of chain b, enqueued on the default stream */
   void evaluate_device(const std::shared_ptr<SampleState> phi, double *d_out) { launch(phi, d_out, nullptr); }
-  /** one more sample: its correlators are added to the per-chain sums (the batch is fixed by the first call) */
-  void accumulate(const std::shared_ptr<SampleState> phi) override {
+  /** one more sample: its values are added to the per-chain sums (the batch is fixed by the first call) */
+  void accumulate(const std::shared_ptr<SampleState> phi) {
     if (!acc || B != phi->batch()) {
-      if (n_calls) fatal("SigmaCorrelator::accumulate: the batch changed between samples.");
+      if (n_calls) fatal(name + "::accumulate: the batch changed between samples.");
       B = phi->batch();
       acc = std::make_unique<DeviceVector>(2 * (size_t)B * n_out_);
       out = std::make_unique<DeviceVector>((size_t)B * n_out_);
@@ -170,43 +151,52 @@ public:
     launch(phi, (double *)out->ptr(), (double *)acc->ptr());
     ++n_calls;
   }
-  unsigned int samples() const override { return n_calls; }
+  unsigned int samples() const { return n_calls; }
   unsigned int batch() const { return B; }
-  /** per-chain means of C over the accumulated samples, [batch][n_out()] */
-  std::vector<std::vector<double>> chain_means() const {
-    if (!n_calls) fatal("SigmaCorrelator: no samples accumulated.");
-    const std::vector<double> a = acc->download<double>();
-    std::vector<std::vector<double>> m(B, std::vector<double>(n_out_));
-    for (unsigned int b = 0; b < B; ++b)
-      for (unsigned int k = 0; k < n_out_; ++k) m[b][k] = a[2 * ((size_t)b * n_out_ + k)] / n_calls;
-    return m;
+  /** per-chain means over the accumulated samples, [batch][n_out()] */
+  std::vector<std::vector<double>> chain_means() const { return chain_means_of(sums(), B, n_out_, n_calls); }
+  /** mean and error per entry: the spread of the per-chain means for batch >= 2, the naive error of one chain (chain_estimate) */
+  Estimate means_and_errors() const { return chain_estimate(sums(), B, n_out_, n_calls); }
+
+protected:
+  CorrelatorMeasurement(const char *name_, unsigned int n_out_) : name(name_), n_out_(n_out_) {}
+  /** fatal, with the measurement's own message, unless n is the size of the states it takes */
+  virtual void check_size(unsigned int n) const = 0;
+  virtual void workspace_bytes(unsigned int batch, size_t *bytes) const = 0;
+  virtual void run(const double *d_state, unsigned int batch, double *d_out, double *d_acc, void *d_work, size_t work_bytes) const = 0;
+
+private:
+  std::vector<double> sums() const {
+    if (!n_calls) fatal(name + ": no samples accumulated.");
+    return acc->download<double>();
   }
-  /** mean and error per entry.  batch >= 2: the error is the spread of the per-chain means over sqrt(batch), so
-   *  autocorrelation inside a chain cannot understate it; batch 1: the naive error of the samples (it ignores autocorrelation) */
-  Estimate means_and_errors() const {
-    if (!n_calls) fatal("SigmaCorrelator: no samples accumulated.");
-    const std::vector<double> a = acc->download<double>();
-    Estimate e{std::vector<double>(n_out_, 0.0), std::vector<double>(n_out_, 0.0), B >= 2};
-    const double n = n_calls;
-    for (unsigned int k = 0; k < n_out_; ++k) {
-      if (B >= 2) {
-        double s = 0.0, s2 = 0.0;
-        for (unsigned int b = 0; b < B; ++b) s += a[2 * ((size_t)b * n_out_ + k)] / n;
-        const double m = s / B;
-        for (unsigned int b = 0; b < B; ++b) {
-          const double d = a[2 * ((size_t)b * n_out_ + k)] / n - m;
-          s2 += d * d;
-        }
-        e.mean[k] = m;
-        e.error[k] = std::sqrt(s2 / ((double)B * (B - 1.0)));
-      } else {
-        const double m = a[2 * k] / n, var = n_calls > 1 ? std::max(0.0, (a[2 * k + 1] / n - m * m) * n / (n - 1.0)) : 0.0;
-        e.mean[k] = m;
-        e.error[k] = std::sqrt(var / n);
-      }
+  void launch(const std::shared_ptr<SampleState> phi, double *d_out, double *d_acc) {
+    check_size(phi->size());
+    if (!work || work_B != phi->batch()) {
+      workspace_bytes(phi->batch(), &work_bytes);
+      work = std::make_unique<DeviceBuffer>(work_bytes);
+      work_B = phi->batch();
     }
-    return e;
+    run(phi->device(), phi->batch(), d_out, d_acc, work->p, work_bytes);
   }
+  const std::string name;
+  const unsigned int n_out_;
+  unsigned int B = 0, work_B = 0, n_calls = 0;
+  size_t work_bytes = 0;
+  std::unique_ptr<DeviceBuffer> work;
+  std::unique_ptr<DeviceVector> acc, out;
+};
+
+/** The time-slice correlators C_t(tau), C_x(tau) of the O(3) sigma model on a lattice, rotated or not
+ *  (mlmcpi_sigma_level_correlator; definitions in mlmcpi_hip.h): n_out() = (Mt/2 + 1) + (Mx/2 + 1) numbers per chain, C_t first.
+ *  xi_2 (correlator.hh) is host arithmetic on their means. */
+class SigmaCorrelator : public CorrelatorMeasurement {
+public:
+  using Xi = ChainScalar;
+  explicit SigmaCorrelator(const std::shared_ptr<Lattice2D> lattice)
+      : CorrelatorMeasurement("SigmaCorrelator", size_of(level_of(lattice))), level(level_of(lattice)), n_vertices(lattice->getNvertices()) {}
+  unsigned int Mt() const { return level.Mt; }
+  unsigned int Mx() const { return level.Mx; }
   /** the part of a vector of n_out() entries that belongs to direction d (0: t, 1: x) */
   std::vector<double> direction(const std::vector<double> &v, int d) const {
     const unsigned int nt = level.Mt / 2 + 1;
@@ -215,227 +205,79 @@ public:
   /** xi_2 of direction d from the mean correlator; batch >= 2: with the jackknife error over the chains */
   Xi xi(int d) const {
     const unsigned int M = d == 0 ? level.Mt : level.Mx;
-    const std::vector<std::vector<double>> m = chain_means();
-    std::vector<double> all(n_out_, 0.0);
-    for (unsigned int b = 0; b < B; ++b)
-      for (unsigned int k = 0; k < n_out_; ++k) all[k] += m[b][k];
-    std::vector<double> mean(all);
-    for (double &v : mean) v /= B;
-    Xi r{xi_second_moment(direction(mean, d), M), 0.0, B >= 2};
-    if (B >= 2) {
-      std::vector<double> x(B), leave(n_out_);
-      double xm = 0.0, s2 = 0.0;
-      for (unsigned int b = 0; b < B; ++b) {
-        for (unsigned int k = 0; k < n_out_; ++k) leave[k] = (all[k] - m[b][k]) / (B - 1.0);
-        x[b] = xi_second_moment(direction(leave, d), M);
-        xm += x[b] / B;
-      }
-      for (unsigned int b = 0; b < B; ++b) s2 += (x[b] - xm) * (x[b] - xm);
-      r.error = std::sqrt((B - 1.0) / B * s2);
-    }
-    return r;
+    return chain_jackknife(chain_means(), [&](const std::vector<double> &C) { return xi_second_moment(direction(C, d), M); });
+  }
+
+protected:
+  void check_size(unsigned int n) const override {
+    if (n != 2 * n_vertices) fatal("Evaluating SigmaCorrelator on state of wrong size.");
+  }
+  void workspace_bytes(unsigned int batch, size_t *bytes) const override {
+    check(mlmcpi_sigma_level_correlator_workspace_bytes(&level, batch, bytes), "sigma_level_correlator_workspace_bytes");
+  }
+  void run(const double *d_state, unsigned int batch, double *d_out, double *d_acc, void *d_work, size_t work_bytes) const override {
+    check(mlmcpi_sigma_level_correlator(&level, d_state, batch, d_out, d_acc, d_work, work_bytes, nullptr), "sigma_level_correlator");
   }
 
 private:
-  void launch(const std::shared_ptr<SampleState> phi, double *d_out, double *d_acc) {
-    if (phi->size() != 2 * n_vertices) fatal("Evaluating SigmaCorrelator on state of wrong size.");
-    if (!work || work_B != phi->batch()) {
-      check(mlmcpi_sigma_level_correlator_workspace_bytes(&level, phi->batch(), &work_bytes), "sigma_level_correlator_workspace_bytes");
-      work = std::make_unique<DeviceBuffer>(work_bytes);
-      work_B = phi->batch();
-    }
-    check(mlmcpi_sigma_level_correlator(&level, phi->device(), phi->batch(), d_out, d_acc, work->p, work_bytes, nullptr),
-          "sigma_level_correlator");
+  static mlmcpi_sigma_level level_of(const std::shared_ptr<Lattice2D> lattice) {
+    return mlmcpi_sigma_level{lattice->getMt_lat(), lattice->getMx_lat(), lattice->is_rotated() ? 1 : 0, 0.0};
+  }
+  static unsigned int size_of(const mlmcpi_sigma_level &level) {
+    uint32_t n = 0;
+    check(mlmcpi_sigma_level_correlator_size(&level, &n), "sigma_level_correlator_size");
+    return n;
   }
   const mlmcpi_sigma_level level;
   const unsigned int n_vertices;
-  unsigned int n_out_ = 0, B = 0, work_B = 0, n_calls = 0;
-  size_t work_bytes = 0;
-  std::unique_ptr<DeviceBuffer> work;
-  std::unique_ptr<DeviceVector> acc, out;
 };
 
 /** The time correlator C(tau), tau = 0 .. n_lag - 1, of a 1-D path action (mlmcpi_path_correlator; definitions in
- *  mlmcpi_hip.h): x_j x_{j+tau} averaged over the path for the oscillators, cos(x_j - x_{j+tau}) for the rotor.  Not a QoI: n_lag
- *  numbers per chain.  accumulate() adds the sample's C and C^2 to per-chain sums on the device; the means, their errors and the
- *  effective mass (correlator.hh) are host arithmetic on those sums. */
+ *  mlmcpi_hip.h): x_j x_{j+tau} averaged over the path for the oscillators, cos(x_j - x_{j+tau}) for the rotor; n_lag numbers per
+ *  chain.  The effective mass (correlator.hh) is host arithmetic on their means. */
 class PathCorrelator : public CorrelatorMeasurement {
 public:
-  struct Estimate {
-    std::vector<double> mean, error;
-    bool chain_spread;  // true: error = spread of the per-chain means (batch >= 2); false: the naive error of one chain
-  };
-  struct Mass {
-    double value, error;
-    bool has_error;  // the jackknife over chains needs batch >= 2
-  };
+  using Mass = ChainScalar;
   PathCorrelator(const std::shared_ptr<Lattice1D> lattice, int kind, unsigned int n_lag_)
-      : act{kind, lattice->getM_lat(), lattice->getT_final(), 1.0, 1.0, 0.0, 0.0}, n_lag_(n_lag_) {}
-  unsigned int n_lag() const { return n_lag_; }
+      : CorrelatorMeasurement("PathCorrelator", n_lag_), act{kind, lattice->getM_lat(), lattice->getT_final(), 1.0, 1.0, 0.0, 0.0} {}
+  unsigned int n_lag() const { return n_out(); }
   unsigned int M() const { return act.M; }
-  /** d_out[b][n_lag()] = the correlator of chain b, enqueued on the default stream */
-  void evaluate_device(const std::shared_ptr<SampleState> x, double *d_out) { launch(x, d_out, nullptr); }
-  /** one more sample: its correlator is added to the per-chain sums (the batch is fixed by the first call) */
-  void accumulate(const std::shared_ptr<SampleState> x) override {
-    if (!acc || B != x->batch()) {
-      if (n_calls) fatal("PathCorrelator::accumulate: the batch changed between samples.");
-      B = x->batch();
-      acc = std::make_unique<DeviceVector>(2 * (size_t)B * n_lag_);
-      out = std::make_unique<DeviceVector>((size_t)B * n_lag_);
-    }
-    launch(x, (double *)out->ptr(), (double *)acc->ptr());
-    ++n_calls;
-  }
-  unsigned int samples() const override { return n_calls; }
-  unsigned int batch() const { return B; }
-  /** per-chain means of C over the accumulated samples, [batch][n_lag()] */
-  std::vector<std::vector<double>> chain_means() const {
-    if (!n_calls) fatal("PathCorrelator: no samples accumulated.");
-    const std::vector<double> a = acc->download<double>();
-    std::vector<std::vector<double>> m(B, std::vector<double>(n_lag_));
-    for (unsigned int b = 0; b < B; ++b)
-      for (unsigned int k = 0; k < n_lag_; ++k) m[b][k] = a[2 * ((size_t)b * n_lag_ + k)] / n_calls;
-    return m;
-  }
-  /** mean and error per lag.  batch >= 2: the error is the spread of the per-chain means over sqrt(batch), so autocorrelation
-   *  inside a chain cannot understate it; batch 1: the naive error of the samples (it ignores autocorrelation) */
-  Estimate means_and_errors() const {
-    if (!n_calls) fatal("PathCorrelator: no samples accumulated.");
-    const std::vector<double> a = acc->download<double>();
-    Estimate e{std::vector<double>(n_lag_, 0.0), std::vector<double>(n_lag_, 0.0), B >= 2};
-    const double n = n_calls;
-    for (unsigned int k = 0; k < n_lag_; ++k) {
-      if (B >= 2) {
-        double s = 0.0, s2 = 0.0;
-        for (unsigned int b = 0; b < B; ++b) s += a[2 * ((size_t)b * n_lag_ + k)] / n;
-        const double m = s / B;
-        for (unsigned int b = 0; b < B; ++b) {
-          const double d = a[2 * ((size_t)b * n_lag_ + k)] / n - m;
-          s2 += d * d;
-        }
-        e.mean[k] = m;
-        e.error[k] = std::sqrt(s2 / ((double)B * (B - 1.0)));
-      } else {
-        const double m = a[2 * k] / n, var = n_calls > 1 ? std::max(0.0, (a[2 * k + 1] / n - m * m) * n / (n - 1.0)) : 0.0;
-        e.mean[k] = m;
-        e.error[k] = std::sqrt(var / n);
-      }
-    }
-    return e;
-  }
   /** m_eff(tau), 1 <= tau <= n_lag() - 2, from the mean correlator; batch >= 2: with the jackknife error over the chains */
   Mass effective_mass(unsigned int tau) const {
-    if (tau < 1 || tau + 1 >= n_lag_) fatal("PathCorrelator::effective_mass: lag outside 1 .. n_lag - 2.");
-    const std::vector<std::vector<double>> m = chain_means();
-    std::vector<double> all(n_lag_, 0.0);
-    for (unsigned int b = 0; b < B; ++b)
-      for (unsigned int k = 0; k < n_lag_; ++k) all[k] += m[b][k];
-    std::vector<double> mean(all);
-    for (double &v : mean) v /= B;
-    Mass r{mlmcpi::effective_mass(mean, tau), 0.0, B >= 2};
-    if (B >= 2) {
-      std::vector<double> x(B), leave(n_lag_);
-      double xm = 0.0, s2 = 0.0;
-      for (unsigned int b = 0; b < B; ++b) {
-        for (unsigned int k = 0; k < n_lag_; ++k) leave[k] = (all[k] - m[b][k]) / (B - 1.0);
-        x[b] = mlmcpi::effective_mass(leave, tau);
-        xm += x[b] / B;
-      }
-      for (unsigned int b = 0; b < B; ++b) s2 += (x[b] - xm) * (x[b] - xm);
-      r.error = std::sqrt((B - 1.0) / B * s2);
-    }
-    return r;
+    if (tau < 1 || tau + 1 >= n_lag()) fatal("PathCorrelator::effective_mass: lag outside 1 .. n_lag - 2.");
+    return chain_jackknife(chain_means(), [&](const std::vector<double> &C) { return mlmcpi::effective_mass(C, tau); });
+  }
+
+protected:
+  void check_size(unsigned int n) const override {
+    if (n != act.M) fatal("Evaluating PathCorrelator on path of wrong size.");
+  }
+  void workspace_bytes(unsigned int batch, size_t *bytes) const override {
+    check(mlmcpi_path_correlator_workspace_bytes(&act, n_lag(), batch, bytes), "path_correlator_workspace_bytes");
+  }
+  void run(const double *d_x, unsigned int batch, double *d_out, double *d_acc, void *d_work, size_t work_bytes) const override {
+    check(mlmcpi_path_correlator(&act, d_x, batch, n_lag(), d_out, d_acc, d_work, work_bytes, nullptr), "path_correlator");
   }
 
 private:
-  void launch(const std::shared_ptr<SampleState> x, double *d_out, double *d_acc) {
-    if (x->size() != act.M) fatal("Evaluating PathCorrelator on path of wrong size.");
-    if (!work || work_B != x->batch()) {
-      check(mlmcpi_path_correlator_workspace_bytes(&act, n_lag_, x->batch(), &work_bytes), "path_correlator_workspace_bytes");
-      work = std::make_unique<DeviceBuffer>(work_bytes);
-      work_B = x->batch();
-    }
-    check(mlmcpi_path_correlator(&act, x->device(), x->batch(), n_lag_, d_out, d_acc, work->p, work_bytes, nullptr), "path_correlator");
-  }
   const mlmcpi_path_action act;  // kind and M are all the correlator reads
-  const unsigned int n_lag_;
-  unsigned int B = 0, work_B = 0, n_calls = 0;
-  size_t work_bytes = 0;
-  std::unique_ptr<DeviceBuffer> work;
-  std::unique_ptr<DeviceVector> acc, out;
 };
 
 /** The Wilson loops W(r, s), 1 <= r <= R, 1 <= s <= S, of a quenched Schwinger state (mlmcpi_schwinger_wilson_loops; definitions in
- *  mlmcpi_hip.h).  Not a QoI: R S numbers per chain, entry (r - 1) S + (s - 1).  accumulate() adds the sample's W and W^2 to
- *  per-chain sums on the device; the means, their errors and the Creutz ratios (correlator.hh) are host arithmetic on those sums. */
+ *  mlmcpi_hip.h): R S numbers per chain, entry (r - 1) S + (s - 1).  The Creutz ratios (correlator.hh) are host arithmetic on
+ *  their means. */
 class WilsonLoops : public CorrelatorMeasurement {
 public:
-  struct Estimate {
-    std::vector<double> mean, error;
-    bool chain_spread;  // true: error = spread of the per-chain means (batch >= 2); false: the naive error of one chain
-  };
-  struct Ratio {
-    double value, error;
-    bool has_error;  // the jackknife over chains needs batch >= 2
-  };
+  using Ratio = ChainScalar;
   WilsonLoops(const std::shared_ptr<Lattice2D> lattice, unsigned int R_, unsigned int S_)
-      : Mt_lat(lattice->getMt_lat()), Mx_lat(lattice->getMx_lat()), R_(R_), S_(S_), n_out_(R_ * S_) {}
+      : CorrelatorMeasurement("WilsonLoops", R_ * S_), Mt_lat(lattice->getMt_lat()), Mx_lat(lattice->getMx_lat()), R_(R_), S_(S_) {}
   unsigned int R() const { return R_; }
   unsigned int S() const { return S_; }
   unsigned int Mt() const { return Mt_lat; }
   unsigned int Mx() const { return Mx_lat; }
-  /** d_out[b][R()][S()] = the loops of chain b, enqueued on the default stream */
-  void evaluate_device(const std::shared_ptr<SampleState> phi, double *d_out) { launch(phi, d_out, nullptr); }
-  /** one more sample: its loops are added to the per-chain sums (the batch is fixed by the first call) */
-  void accumulate(const std::shared_ptr<SampleState> phi) override {
-    if (!acc || B != phi->batch()) {
-      if (n_calls) fatal("WilsonLoops::accumulate: the batch changed between samples.");
-      B = phi->batch();
-      acc = std::make_unique<DeviceVector>(2 * (size_t)B * n_out_);
-      out = std::make_unique<DeviceVector>((size_t)B * n_out_);
-    }
-    launch(phi, (double *)out->ptr(), (double *)acc->ptr());
-    ++n_calls;
-  }
-  unsigned int samples() const override { return n_calls; }
-  unsigned int batch() const { return B; }
-  /** per-chain means of W over the accumulated samples, [batch][R() S()] */
-  std::vector<std::vector<double>> chain_means() const {
-    if (!n_calls) fatal("WilsonLoops: no samples accumulated.");
-    const std::vector<double> a = acc->download<double>();
-    std::vector<std::vector<double>> m(B, std::vector<double>(n_out_));
-    for (unsigned int b = 0; b < B; ++b)
-      for (unsigned int k = 0; k < n_out_; ++k) m[b][k] = a[2 * ((size_t)b * n_out_ + k)] / n_calls;
-    return m;
-  }
-  /** mean and error per loop.  batch >= 2: the error is the spread of the per-chain means over sqrt(batch), so autocorrelation
-   *  inside a chain cannot understate it; batch 1: the naive error of the samples (it ignores autocorrelation) */
-  Estimate means_and_errors() const {
-    if (!n_calls) fatal("WilsonLoops: no samples accumulated.");
-    return wilson_loops_estimate(acc->download<double>(), B, n_out_, n_calls);
-  }
-  /** the same arithmetic on downloaded sums a [batch][n_out][2] (W, W^2) of n samples */
+  /** means_and_errors() on downloaded sums a [batch][n_out][2] (W, W^2) of n samples */
   static Estimate wilson_loops_estimate(const std::vector<double> &a, unsigned int B, unsigned int n_out, unsigned int n_calls) {
-    Estimate e{std::vector<double>(n_out, 0.0), std::vector<double>(n_out, 0.0), B >= 2};
-    const double n = n_calls;
-    for (unsigned int k = 0; k < n_out; ++k) {
-      if (B >= 2) {
-        double s = 0.0, s2 = 0.0;
-        for (unsigned int b = 0; b < B; ++b) s += a[2 * ((size_t)b * n_out + k)] / n;
-        const double m = s / B;
-        for (unsigned int b = 0; b < B; ++b) {
-          const double d = a[2 * ((size_t)b * n_out + k)] / n - m;
-          s2 += d * d;
-        }
-        e.mean[k] = m;
-        e.error[k] = std::sqrt(s2 / ((double)B * (B - 1.0)));
-      } else {
-        const double m = a[2 * k] / n, var = n_calls > 1 ? std::max(0.0, (a[2 * k + 1] / n - m * m) * n / (n - 1.0)) : 0.0;
-        e.mean[k] = m;
-        e.error[k] = std::sqrt(var / n);
-      }
-    }
-    return e;
+    return chain_estimate(a, B, n_out, n_calls);
   }
   /** the Creutz ratio chi(r, s), 1 <= r <= R(), 1 <= s <= S(), of the mean loops; batch >= 2: with the jackknife error over the chains */
   Ratio creutz(unsigned int r, unsigned int s) const {
@@ -444,64 +286,35 @@ public:
   }
   /** the same arithmetic on per-chain means m [batch][R S] */
   static Ratio creutz_jackknife(const std::vector<std::vector<double>> &m, unsigned int R, unsigned int S, unsigned int r, unsigned int s) {
-    const unsigned int B = (unsigned int)m.size(), n_out = R * S;
-    std::vector<double> all(n_out, 0.0);
-    for (unsigned int b = 0; b < B; ++b)
-      for (unsigned int k = 0; k < n_out; ++k) all[k] += m[b][k];
-    std::vector<double> mean(all);
-    for (double &v : mean) v /= B;
-    Ratio res{creutz_ratio(mean, R, S, r, s), 0.0, B >= 2};
-    if (B >= 2) {
-      std::vector<double> x(B), leave(n_out);
-      double xm = 0.0, s2 = 0.0;
-      for (unsigned int b = 0; b < B; ++b) {
-        for (unsigned int k = 0; k < n_out; ++k) leave[k] = (all[k] - m[b][k]) / (B - 1.0);
-        x[b] = creutz_ratio(leave, R, S, r, s);
-        xm += x[b] / B;
-      }
-      for (unsigned int b = 0; b < B; ++b) s2 += (x[b] - xm) * (x[b] - xm);
-      res.error = std::sqrt((B - 1.0) / B * s2);
-    }
-    return res;
+    return chain_jackknife(m, [&](const std::vector<double> &W) { return creutz_ratio(W, R, S, r, s); }, 0, (size_t)R * S);
+  }
+
+protected:
+  void check_size(unsigned int n) const override {
+    if (n != 2 * Mt_lat * Mx_lat) fatal("Evaluating WilsonLoops on state of wrong size.");
+  }
+  void workspace_bytes(unsigned int batch, size_t *bytes) const override {
+    check(mlmcpi_schwinger_wilson_loops_workspace_bytes(Mt_lat, Mx_lat, R_, S_, batch, bytes), "schwinger_wilson_loops_workspace_bytes");
+  }
+  void run(const double *d_theta, unsigned int batch, double *d_out, double *d_acc, void *d_work, size_t work_bytes) const override {
+    check(mlmcpi_schwinger_wilson_loops(d_theta, Mt_lat, Mx_lat, batch, R_, S_, d_out, d_acc, d_work, work_bytes, nullptr), "schwinger_wilson_loops");
   }
 
 private:
-  void launch(const std::shared_ptr<SampleState> phi, double *d_out, double *d_acc) {
-    if (phi->size() != 2 * Mt_lat * Mx_lat) fatal("Evaluating WilsonLoops on state of wrong size.");
-    if (!work || work_B != phi->batch()) {
-      check(mlmcpi_schwinger_wilson_loops_workspace_bytes(Mt_lat, Mx_lat, R_, S_, phi->batch(), &work_bytes), "schwinger_wilson_loops_workspace_bytes");
-      work = std::make_unique<DeviceBuffer>(work_bytes);
-      work_B = phi->batch();
-    }
-    check(mlmcpi_schwinger_wilson_loops(phi->device(), Mt_lat, Mx_lat, phi->batch(), R_, S_, d_out, d_acc, work->p, work_bytes, nullptr),
-          "schwinger_wilson_loops");
-  }
-  const unsigned int Mt_lat, Mx_lat, R_, S_, n_out_;
-  unsigned int B = 0, work_B = 0, n_calls = 0;
-  size_t work_bytes = 0;
-  std::unique_ptr<DeviceBuffer> work;
-  std::unique_ptr<DeviceVector> acc, out;
+  const unsigned int Mt_lat, Mx_lat, R_, S_;
 };
 
 /** The momentum-projected slice correlators C_t(tau; q), C_x(tau; q), q < P, of a Gaussian free field state on a lattice, rotated
- *  or not (mlmcpi_gff_correlator; definitions in mlmcpi_hip.h).  Not a QoI: n_out() = P (Mt/2 + 1) + P (Mx/2 + 1) numbers per
- *  chain, C_t first, momentum-major, lag fastest.  accumulate() adds the sample's C and C^2 to per-chain sums on the device; the
- *  means, their errors and the energies E_q (the effective mass of correlator.hh) are host arithmetic on those sums. */
+ *  or not (mlmcpi_gff_correlator; definitions in mlmcpi_hip.h): n_out() = P (Mt/2 + 1) + P (Mx/2 + 1) numbers per chain, C_t
+ *  first, momentum-major, lag fastest.  The energies E_q (the effective mass of correlator.hh) are host arithmetic on their means. */
 class GffCorrelator : public CorrelatorMeasurement {
 public:
-  struct Estimate {
-    std::vector<double> mean, error;
-    bool chain_spread;  // true: error = spread of the per-chain means (batch >= 2); false: the naive error of one chain
-  };
-  struct Energy {
-    double value, error;
-    bool has_error;  // the jackknife over chains needs batch >= 2
-  };
+  using Energy = ChainScalar;
   GffCorrelator(const std::shared_ptr<Lattice2D> lattice, unsigned int P_)
-      : Mt_lat(lattice->getMt_lat()), Mx_lat(lattice->getMx_lat()), rotated(lattice->is_rotated() ? 1 : 0),
-        n_vertices(lattice->getNvertices()), P_(P_), n_out_(P_ * (Mt_lat / 2 + 1) + P_ * (Mx_lat / 2 + 1)) {}
+      : CorrelatorMeasurement("GffCorrelator", P_ * (lattice->getMt_lat() / 2 + 1) + P_ * (lattice->getMx_lat() / 2 + 1)),
+        Mt_lat(lattice->getMt_lat()), Mx_lat(lattice->getMx_lat()), rotated(lattice->is_rotated() ? 1 : 0),
+        n_vertices(lattice->getNvertices()), P_(P_) {}
   unsigned int n_mom() const { return P_; }
-  unsigned int n_out() const { return n_out_; }
   unsigned int Mt() const { return Mt_lat; }
   unsigned int Mx() const { return Mx_lat; }
   /** where C_d(tau; q) sits in a vector of n_out() entries (d = 0: t, 1: x) */
@@ -510,61 +323,12 @@ public:
     return d == 0 ? q * nt + tau : P * nt + q * nx + tau;
   }
   unsigned int index(int d, unsigned int q, unsigned int tau) const { return index(Mt_lat, Mx_lat, P_, d, q, tau); }
-  /** d_out[b][n_out()] = the correlators of chain b, enqueued on the default stream */
-  void evaluate_device(const std::shared_ptr<SampleState> phi, double *d_out) { launch(phi, d_out, nullptr); }
-  /** one more sample: its correlators are added to the per-chain sums (the batch is fixed by the first call) */
-  void accumulate(const std::shared_ptr<SampleState> phi) override {
-    if (!acc || B != phi->batch()) {
-      if (n_calls) fatal("GffCorrelator::accumulate: the batch changed between samples.");
-      B = phi->batch();
-      acc = std::make_unique<DeviceVector>(2 * (size_t)B * n_out_);
-      out = std::make_unique<DeviceVector>((size_t)B * n_out_);
-    }
-    launch(phi, (double *)out->ptr(), (double *)acc->ptr());
-    ++n_calls;
-  }
-  unsigned int samples() const override { return n_calls; }
-  unsigned int batch() const { return B; }
-  /** per-chain means of C over the accumulated samples, [batch][n_out()] */
-  std::vector<std::vector<double>> chain_means() const {
-    if (!n_calls) fatal("GffCorrelator: no samples accumulated.");
-    return chain_means_of(acc->download<double>(), B, n_out_, n_calls);
-  }
-  /** the same arithmetic on downloaded sums a [batch][n_out][2] (C, C^2) of n samples */
+  /** chain_means() and means_and_errors() on downloaded sums a [batch][n_out][2] (C, C^2) of n samples */
   static std::vector<std::vector<double>> chain_means_of(const std::vector<double> &a, unsigned int B, unsigned int n_out, unsigned int n_calls) {
-    std::vector<std::vector<double>> m(B, std::vector<double>(n_out));
-    for (unsigned int b = 0; b < B; ++b)
-      for (unsigned int k = 0; k < n_out; ++k) m[b][k] = a[2 * ((size_t)b * n_out + k)] / n_calls;
-    return m;
+    return mlmcpi::chain_means_of(a, B, n_out, n_calls);
   }
-  /** mean and error per entry.  batch >= 2: the error is the spread of the per-chain means over sqrt(batch), so autocorrelation
-   *  inside a chain cannot understate it; batch 1: the naive error of the samples (it ignores autocorrelation) */
-  Estimate means_and_errors() const {
-    if (!n_calls) fatal("GffCorrelator: no samples accumulated.");
-    return estimate(acc->download<double>(), B, n_out_, n_calls);
-  }
-  /** the same arithmetic on downloaded sums a [batch][n_out][2] (C, C^2) of n samples */
   static Estimate estimate(const std::vector<double> &a, unsigned int B, unsigned int n_out, unsigned int n_calls) {
-    Estimate e{std::vector<double>(n_out, 0.0), std::vector<double>(n_out, 0.0), B >= 2};
-    const double n = n_calls;
-    for (unsigned int k = 0; k < n_out; ++k) {
-      if (B >= 2) {
-        double s = 0.0, s2 = 0.0;
-        for (unsigned int b = 0; b < B; ++b) s += a[2 * ((size_t)b * n_out + k)] / n;
-        const double m = s / B;
-        for (unsigned int b = 0; b < B; ++b) {
-          const double d = a[2 * ((size_t)b * n_out + k)] / n - m;
-          s2 += d * d;
-        }
-        e.mean[k] = m;
-        e.error[k] = std::sqrt(s2 / ((double)B * (B - 1.0)));
-      } else {
-        const double m = a[2 * k] / n, var = n_calls > 1 ? std::max(0.0, (a[2 * k + 1] / n - m * m) * n / (n - 1.0)) : 0.0;
-        e.mean[k] = m;
-        e.error[k] = std::sqrt(var / n);
-      }
-    }
-    return e;
+    return chain_estimate(a, B, n_out, n_calls);
   }
   /** E_q of direction d (0: t, 1: x) from the effective mass of the mean correlator at lag tau, 1 <= tau <= M_d/2 - 1; batch >= 2:
    *  with the jackknife error over the chains */
@@ -575,48 +339,28 @@ public:
   }
   /** E_q along t, the direction the dispersion relation of correlator.hh speaks of */
   Energy energy(unsigned int q, unsigned int tau) const { return energy(0, q, tau); }
-  /** the same arithmetic on per-chain means m [batch][n_out] */
+  /** the same arithmetic on per-chain means m [batch][n_out]: the jackknife sees the lags of (d, q) alone */
   static Energy energy_jackknife(const std::vector<std::vector<double>> &m, unsigned int Mt, unsigned int Mx, unsigned int P, int d,
                                  unsigned int q, unsigned int tau) {
-    const unsigned int B = (unsigned int)m.size(), nl = (d == 0 ? Mt : Mx) / 2 + 1, o = index(Mt, Mx, P, d, q, 0);
-    std::vector<double> all(nl, 0.0);
-    for (unsigned int b = 0; b < B; ++b)
-      for (unsigned int k = 0; k < nl; ++k) all[k] += m[b][o + k];
-    std::vector<double> mean(all);
-    for (double &v : mean) v /= B;
-    Energy r{effective_mass(mean, tau), 0.0, B >= 2};
-    if (B >= 2) {
-      std::vector<double> x(B), leave(nl);
-      double xm = 0.0, s2 = 0.0;
-      for (unsigned int b = 0; b < B; ++b) {
-        for (unsigned int k = 0; k < nl; ++k) leave[k] = (all[k] - m[b][o + k]) / (B - 1.0);
-        x[b] = effective_mass(leave, tau);
-        xm += x[b] / B;
-      }
-      for (unsigned int b = 0; b < B; ++b) s2 += (x[b] - xm) * (x[b] - xm);
-      r.error = std::sqrt((B - 1.0) / B * s2);
-    }
-    return r;
+    return chain_jackknife(m, [&](const std::vector<double> &C) { return effective_mass(C, tau); }, index(Mt, Mx, P, d, q, 0),
+                           (d == 0 ? Mt : Mx) / 2 + 1);
+  }
+
+protected:
+  void check_size(unsigned int n) const override {
+    if (n != n_vertices) fatal("Evaluating GffCorrelator on state of wrong size.");
+  }
+  void workspace_bytes(unsigned int batch, size_t *bytes) const override {
+    check(mlmcpi_gff_correlator_workspace_bytes(Mt_lat, Mx_lat, rotated, P_, batch, bytes), "gff_correlator_workspace_bytes");
+  }
+  void run(const double *d_phi, unsigned int batch, double *d_out, double *d_acc, void *d_work, size_t work_bytes) const override {
+    check(mlmcpi_gff_correlator(Mt_lat, Mx_lat, rotated, P_, d_phi, batch, d_out, d_acc, d_work, work_bytes, nullptr), "gff_correlator");
   }
 
 private:
-  void launch(const std::shared_ptr<SampleState> phi, double *d_out, double *d_acc) {
-    if (phi->size() != n_vertices) fatal("Evaluating GffCorrelator on state of wrong size.");
-    if (!work || work_B != phi->batch()) {
-      check(mlmcpi_gff_correlator_workspace_bytes(Mt_lat, Mx_lat, rotated, P_, phi->batch(), &work_bytes), "gff_correlator_workspace_bytes");
-      work = std::make_unique<DeviceBuffer>(work_bytes);
-      work_B = phi->batch();
-    }
-    check(mlmcpi_gff_correlator(Mt_lat, Mx_lat, rotated, P_, phi->device(), phi->batch(), d_out, d_acc, work->p, work_bytes, nullptr),
-          "gff_correlator");
-  }
   const unsigned int Mt_lat, Mx_lat;
   const int rotated;
-  const unsigned int n_vertices, P_, n_out_;
-  unsigned int B = 0, work_B = 0, n_calls = 0;
-  size_t work_bytes = 0;
-  std::unique_ptr<DeviceBuffer> work;
-  std::unique_ptr<DeviceVector> acc, out;
+  const unsigned int n_vertices, P_;
 };
 
 }  // namespace mlmcpi
