@@ -45,6 +45,9 @@
 //           relation, and the same along x)
 //   driver --action rotor --M_lat 256 --T_final 25.6 --m0 0.25 --sampler cluster --n_updates 10 --n_samples 20000
 //          (cluster samplers: rotor and schwinger; also --coarsesampler cluster for twolevel / hierarchical rotor runs)
+//   driver --action nonlinearsigma --Mt_lat 8 --beta 1.2 --sampler heatbath --batch 64 --n_samples 200 --qoi topological
+//          (--qoi magnetic|topological, nonlinearsigma only: chi_m, the default, or the topological susceptibility chi_t = Q^2 / n
+//           of the geometric charge, in single-level, --method twolevel and --sampler hierarchical runs)
 //   driver --method throughput --action schwinger --Mt_lat 1024 --sampler heatbath --batch 32 --n_samples 20
 //          (the sampling loop of MonteCarloSingleLevel on a batch of chains, statistics accumulated on the device:
 //           prints link-updates/s of the C++ path)
@@ -89,7 +92,7 @@ int main(int argc, char **argv) {
       {"n_sweep_heatbath", "1"}, {"autotune", "1"}, {"window", "20"}, {"method", "singlelevel"}, {"n_level", "3"},
       {"epsilon", "0.01"}, {"coarsening", "both"}, {"coarsesampler", "hmc"}, {"renormalisation", "none"}, {"n_meas", "200"},
       {"batch", "1"}, {"seed", "2481317"}, {"warmup", "5"}, {"random_order", "0"}, {"n_updates", "10"}, {"correlator", "0"},
-      {"path_correlator", "0"}, {"wilson_loops", "0"}, {"gff_correlator", "0"}};
+      {"path_correlator", "0"}, {"wilson_loops", "0"}, {"gff_correlator", "0"}, {"qoi", "magnetic"}};
   for (int i = 1; i + 1 < argc; i += 2) {
     if (std::strncmp(argv[i], "--", 2) || !o.count(argv[i] + 2)) fatal(std::string("unknown option ") + argv[i]);
     o[argv[i] + 2] = argv[i + 1];
@@ -157,6 +160,14 @@ int main(int argc, char **argv) {
       fatal("--gff_correlator " + o["gff_correlator"] + " is more than min(Mt_lat / 2 + 1, " +
             std::to_string(MLMCPI_GFF_CORRELATOR_MAX_MOMENTA) + ") = " + std::to_string(cap) + " momenta");
   }
+  // --qoi magnetic|topological: the QoI of the O(3) sigma model, chi_m (the default) or the topological susceptibility chi_t = Q^2 / n
+  // of the geometric charge (qoi.hh QoI2DSigmaTopologicalSusceptibility), on every level of a single-level,
+  // twolevel or hierarchical run.  Refused here, before any device call.
+  if (o["qoi"] != "magnetic" && o["qoi"] != "topological") fatal("--qoi takes magnetic or topological, not " + o["qoi"]);
+  const bool topological = o["qoi"] == "topological";
+  if (topological && o["action"] != "nonlinearsigma")
+    fatal("--qoi topological is not supported for chosen action: the geometric topological charge is built for nonlinearsigma only, "
+          "not " + o["action"] + " (the rotor and schwinger measure their own topological susceptibility by default)");
   std::shared_ptr<Exchange> exchange;
   if (world > 1) {
     check(mlmcpi_set_device(local_rank), "mlmcpi_set_device");
@@ -303,9 +314,14 @@ int main(int argc, char **argv) {
     if (o["renormalisation"] == "exact" && levels)
       fatal("nonlinearsigma: non-perturbative renormalisation not implemented for non-linear sigma model.");
     action = std::make_shared<NonlinearSigmaAction>(lat, nullptr, renorm, num("beta"));
-    qoi = std::make_shared<QoI2DMagneticSusceptibility>(lat);
+    if (topological) {
+      qoi = std::make_shared<QoI2DSigmaTopologicalSusceptibility>(lat);
+      qoi_factory = std::make_shared<QoI2DSigmaTopologicalSusceptibilityFactory>();
+    } else {
+      qoi = std::make_shared<QoI2DMagneticSusceptibility>(lat);
+      qoi_factory = std::make_shared<QoI2DMagneticSusceptibilityFactory>();
+    }
     if (wants_correlator) correlator = std::make_shared<SigmaCorrelator>(lat);
-    qoi_factory = std::make_shared<QoI2DMagneticSusceptibilityFactory>();
     cfa_factory = std::make_shared<NonlinearSigmaConditionedFineActionFactory>();
   } else if (a == "schwinger" || a == "gff") {
     auto lat = std::make_shared<Lattice2D>((unsigned)num("Mt_lat"), (unsigned)num("Mt_lat"), coarsenings.at(o["coarsening"]));
@@ -327,6 +343,8 @@ int main(int argc, char **argv) {
   }
   action->set_seed((uint64_t)num("seed"), (uint32_t)rank * batch);  // chain index = Philox counter word: distinct per rank
   std::cout << "Action: " << action->info_string() << std::endl;
+  if (topological)
+    std::cout << "QoI: topological susceptibility chi_t = Q^2 / n of the geometric (Berg-Luescher) charge" << std::endl;
   auto basic_factory = [&](const std::string &name) -> std::shared_ptr<SamplerFactory> {
     if (name == "hmc") {
       HMCParameters hp;
@@ -405,6 +423,7 @@ int main(int argc, char **argv) {
     TwoLevelMCParameters tp;
     tp.n_burnin = (unsigned)num("n_burnin"); tp.n_samples = (unsigned)num("n_samples"); tp.n_meas = (unsigned)num("n_meas");
     tp.n_autocorr_window = (unsigned)num("window");
+    if (topological) tp.batch = batch;  // --qoi topological: every state holds the samplers' `batch` chains, Q is their mean
     MonteCarloTwoLevel two(action, qoi_factory, basic_factory(o["coarsesampler"]), cfa_factory, tp);
     two.evaluate_difference();
     std::cout << std::endl << "=== Two level MC ===" << std::endl;
@@ -473,7 +492,8 @@ int main(int argc, char **argv) {
   if (path_correlator) measured = path_correlator;
   if (wilson_loops) measured = wilson_loops;  // --wilson_loops N likewise
   if (gff_correlator) measured = gff_correlator;  // and --gff_correlator P
-  MonteCarloSingleLevel mc(action, qoi, factory, mp, exchange, measured ? batch : 1u, measured);
+  // (--qoi topological likewise: Q is the mean of chi_t over the chains)
+  MonteCarloSingleLevel mc(action, qoi, factory, mp, exchange, measured || topological ? batch : 1u, measured);
   mc.evaluate();
   std::cout << std::endl << "=== Single level MC ===" << std::endl;
   mc.show_statistics();

@@ -454,6 +454,7 @@ struct TwoLevelMCParameters {
   unsigned int n_coarse_autocorr_window = 10, n_fine_autocorr_window = 10, n_delta_autocorr_window = 10;
   unsigned int n_autocorr_window = 20;  // statistics of the coarse sampler (StatisticsParameters)
   unsigned int n_meas = 200;            // draws timed for the two-level step's cost_per_sample
+  unsigned int batch = 1;               // chains of every state (the samplers' batch); > 1: a sample's Q is the mean of the QoI over them
 };
 
 /** montecarlo/montecarlotwolevel.{hh,cc}: mean and variance of Q_fine, Q_coarse and of their difference over the
@@ -469,13 +470,13 @@ public:
         stats_coarse_sampler("QoI[coarsesampler]", p.n_autocorr_window) {
     coarse_action->set_seed(fine_action->get_seed() + 7919, fine_action->get_chain0());
     coarse_sampler = sampler_factory->get(coarse_action);
-    twolevel_step = std::make_shared<TwoLevelMetropolisStep>(coarse_action, fine_action, cfa_factory->get(fine_action), 1, p.n_meas);
+    twolevel_step = std::make_shared<TwoLevelMetropolisStep>(coarse_action, fine_action, cfa_factory->get(fine_action), p.batch, p.n_meas);
   }
 
   /** montecarlotwolevel.cc:39-84 */
   void evaluate_difference() {
-    auto phi_state = std::make_shared<SampleState>(fine_action->sample_size());
-    auto phi_coarse_state = std::make_shared<SampleState>(coarse_action->sample_size());
+    auto phi_state = std::make_shared<SampleState>(fine_action->sample_size(), param.batch);
+    auto phi_coarse_state = std::make_shared<SampleState>(coarse_action->sample_size(), param.batch);
     stats_coarse.hard_reset(); stats_coarse_sampler.hard_reset(); stats_fine.hard_reset(); stats_diff.hard_reset();
     for (unsigned int k = 0; k < param.n_burnin; ++k) record_pair(phi_coarse_state, phi_state);
     stats_coarse_sampler.reset();
@@ -499,10 +500,16 @@ private:
   void record_pair(std::shared_ptr<SampleState> phi_coarse_state, std::shared_ptr<SampleState> phi_state) {
     draw_coarse_sample(phi_coarse_state);
     twolevel_step->draw(phi_coarse_state, phi_state);
-    const double qf = qoi_fine->evaluate(phi_state), qc = qoi_coarse->evaluate(phi_coarse_state);
+    const double qf = measure(qoi_fine, phi_state), qc = measure(qoi_coarse, phi_coarse_state);
     stats_fine.record_sample(qf);
     stats_coarse.record_sample(qc);
     stats_diff.record_sample(qf - qc);
+  }
+  double measure(const std::shared_ptr<QoI> &qoi, const std::shared_ptr<SampleState> state) const {
+    if (param.batch == 1) return qoi->evaluate(state);
+    double s = 0.0;
+    for (double q : qoi->evaluate_batch(state)) s += q;
+    return s / param.batch;
   }
   /** montecarlotwolevel.cc:87-98: ceil(2 tau_int) <= 100 draws of the coarse sampler between uses */
   void draw_coarse_sample(std::shared_ptr<SampleState> phi_state) {
@@ -510,7 +517,7 @@ private:
     if (!(two_tau_int >= 1.)) two_tau_int = 1.;  // NaN from a degenerate first window
     while (t_sampler < two_tau_int) {
       coarse_sampler->draw(phi_state);
-      stats_coarse_sampler.record_sample(qoi_coarse->evaluate(phi_state));
+      stats_coarse_sampler.record_sample(measure(qoi_coarse, phi_state));
       t_sampler++;
     }
     t_indep = (n_indep * t_indep + t_sampler) / (1.0 + n_indep);
@@ -780,6 +787,7 @@ typedef QFTQoIFactory<QoI2DSusceptibility> QoI2DSusceptibilityFactory;
 typedef QFTQoIFactory<QoIAvgPlaquette> QoIAvgPlaquetteFactory;
 typedef QFTQoIFactory<QoI2DPhiSquared> QoI2DPhiSquaredFactory;
 typedef QFTQoIFactory<QoI2DMagneticSusceptibility> QoI2DMagneticSusceptibilityFactory;
+typedef QFTQoIFactory<QoI2DSigmaTopologicalSusceptibility> QoI2DSigmaTopologicalSusceptibilityFactory;
 
 }  // namespace mlmcpi
 #endif

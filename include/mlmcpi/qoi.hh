@@ -129,6 +129,23 @@ private:
   const bool rotated;
 };
 
+/** The topological susceptibility chi_t = Q^2 / N of the O(3) sigma model, Q the geometric (Berg-Luescher) charge, on any level of
+ *  its hierarchy (mlmcpi_sigma_level_topological_charge; definitions in mlmcpi_hip.h).  Not a QoI of the
+ *  reference.  No sweep launch sums it (fused_kind 0): the samplers take the unfused path. */
+class QoI2DSigmaTopologicalSusceptibility : public QoI {
+public:
+  explicit QoI2DSigmaTopologicalSusceptibility(const std::shared_ptr<Lattice2D> lattice)
+      : level{lattice->getMt_lat(), lattice->getMx_lat(), lattice->is_rotated() ? 1 : 0, 0.0}, n_vertices(lattice->getNvertices()) {}
+  void evaluate_device(const std::shared_ptr<SampleState> phi, double *d_out) override {
+    if (phi->size() != 2 * n_vertices) fatal("Evaluating QoI2DSigmaTopologicalSusceptibility on state of wrong size.");
+    check(mlmcpi_sigma_level_topological_charge(&level, phi->device(), phi->batch(), nullptr, d_out, nullptr, nullptr),
+          "sigma_level_topological_charge");
+  }
+private:
+  const mlmcpi_sigma_level level;
+  const unsigned int n_vertices;
+};
+
 /** A measurement beside the QoI: not a QoI, its value is a vector of n_out() numbers per chain.  MonteCarloSingleLevel asks it for
  *  one more sample of the state at hand (accumulate) and how many it has taken (samples).  accumulate() adds the sample's values and
  *  their squares to per-chain sums on the device; the means and their errors are host arithmetic on those sums (chain_estimate.hh).

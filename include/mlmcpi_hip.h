@@ -63,6 +63,8 @@
  *       mlmcpi_sigma_level_initialise / _evaluate / _magnetic_susceptibility /         grid y                65535 (refused)
  *         _sweep_draw / _copy_from_*, mlmcpi_sigma_cfa_*, mlmcpi_sigma_twolevel_*
  *       mlmcpi_sigma_level_correlator                                                  grid y and z          65535 (refused by name)
+ *       mlmcpi_sigma_level_topological_charge (its batch is spelled n_chains; run at   linear index, x then y unbounded (2^23 x 65535
+ *         the edge by tests/test_sigma_topology_gpu.py)                                                      workgroups)
  *       mlmcpi_stats_accumulate, mlmcpi_stats_window_record                            grid x, 256 per wg    unbounded
  */
 #ifndef MLMCPI_HIP_H
@@ -672,6 +674,24 @@ int mlmcpi_sigma_level_correlator_size(const mlmcpi_sigma_level *level, uint32_t
 int mlmcpi_sigma_level_correlator_workspace_bytes(const mlmcpi_sigma_level *level, uint32_t B, size_t *bytes);
 int mlmcpi_sigma_level_correlator(const mlmcpi_sigma_level *level, const double *d_state, uint32_t B, double *d_out,
                                   double *d_acc /* may be NULL */, void *d_work, size_t work_bytes, void *stream);
+/* The geometric (Berg-Luescher) topological charge on a level and its susceptibility (sigma_topology.hip);
+ * rotated = 0 is the plain lattice, `beta` is ignored.  With sigma = (sin theta cos phi, sin theta sin phi, cos theta) and, for an
+ * ordered triple of unit vectors, A(a, b, c) = 2 atan2(a . (b x c), 1 + a . b + b . c + c . a):
+ *   plain level    one face per vertex (i, j): corners s1 = (i, j), s2 = (i+1, j), s3 = (i+1, j+1), s4 = (i, j+1), periodic;
+ *                  triangles (s1, s2, s3) and (s1, s3, s4)
+ *   rotated level  one face per site (i, j) with i + j odd (n faces for n vertices): corners W = (i-1, j), S = (i, j-1),
+ *                  E = (i+1, j), N = (i, j+1), all level vertices, periodic in the Cartesian frame; triangles (W, S, E), (W, E, N)
+ *   Q = (1 / 4 pi) sum over faces (A_1 + A_2), not rounded;  chi = Q^2 / n with the level's n.
+ * d_q [n_chains] and d_chi [n_chains]: either may be NULL, not both.  d_acc (may be NULL) [n_chains][5]: stats->record_sample of
+ * chi in the launch that finishes it (mlmcpi_stats_accumulate's recurrence).  The state is read once (one sincos pair per vertex,
+ * staged in LDS tile by tile with the halo the tile's faces reach); lane, wave and tile partials are added in an order fixed by
+ * the level alone, without atomics; the partials live in the library's scratch.  A chain's outputs are the same bits for every
+ * n_chains, every split of the chains over calls, every stream and whichever outputs are asked for.  Any n_chains runs (CHAINS
+ * PER CALL above).  MLMCPI_ERR_INVALID, with nothing launched: NULL level or d_state, d_q and d_chi both NULL, odd or zero
+ * extents, Mt Mx > 2^30, n_chains = 0. */
+int mlmcpi_sigma_level_topological_charge(const mlmcpi_sigma_level *level, const double *d_state, uint32_t n_chains,
+                                          double *d_q /* may be NULL */, double *d_chi /* may be NULL */,
+                                          double *d_acc /* may be NULL: record_sample moments of chi, [n_chains][5] */, void *stream);
 /* The Wolff single-cluster update on a level (sigma_cluster.hip): n_updates updates of every chain of
  * d_state [B][2 n], in place.  Unrotated: mlmcpi_sigma_cluster_* on (Mt, Mx, beta), the same bits.  Rotated: the level is
  * bipartite, every link has one E end; its 2 n links are (e, d), e an E vertex (e < n / 2), d its direction in the order above;

@@ -206,6 +206,7 @@ SIGNATURES = {
     "mlmcpi_sigma_level_initialise": (_i, [_SL, _vp, _u32, _u64, _u32, _vp]),
     "mlmcpi_sigma_level_evaluate": (_i, [_SL, _vp, _u32, _vp, _vp]),
     "mlmcpi_sigma_level_magnetic_susceptibility": (_i, [_SL, _vp, _u32, _vp, _vp]),
+    "mlmcpi_sigma_level_topological_charge": (_i, [_SL, _vp, _u32, _vp, _vp, _vp, _vp]),
     "mlmcpi_sigma_level_sweep_draw": (_i, [_SL, _vp, _vp, _u32, _u32, _u32, _u64, _u32, _u32, _vp]),
     "mlmcpi_sigma_level_copy_from_fine": (_i, [_SL, _vp, _vp, _u32, _vp]),
     "mlmcpi_sigma_level_copy_from_coarse": (_i, [_SL, _vp, _vp, _u32, _vp]),

@@ -471,6 +471,19 @@ def sigma_level_magnetic_susceptibility(level, x):
     return out
 
 
+def sigma_level_topological_charge(level, x, acc=None):
+    """geometric topological charge of every chain of x [B, 2 n] on a level, rotated or not (mlmcpi_sigma_level_topological_charge):
+    returns (Q [B], chi = Q^2 / n [B]); acc [B, 5] (optional): record_sample of chi in the same call"""
+    _check_state(x, sigma_level_size(level))
+    B = x.shape[0]
+    if acc is not None:
+        assert acc.dtype == torch.float64 and tuple(acc.shape) == (B, 5), acc.shape
+    q = torch.empty(B, dtype=torch.float64, device=x.device)
+    chi = torch.empty(B, dtype=torch.float64, device=x.device)
+    abi.call("mlmcpi_sigma_level_topological_charge", C.byref(level), _p(x), B, _p(q), _p(chi), _p(acc), _stream())
+    return q, chi
+
+
 def sigma_level_correlator_size(level):
     """n_out = (Mt/2 + 1) + (Mx/2 + 1): the lags of C_t, then those of C_x"""
     n = C.c_uint32(0)
