@@ -61,6 +61,7 @@
 #include <cstring>
 #include <map>
 
+#include "mlmcpi/cluster_sampler.hh"
 #include "mlmcpi/multilevel.hh"
 
 using namespace mlmcpi;
@@ -215,7 +216,7 @@ int main(int argc, char **argv) {
     fatal(" cluster not supported for chosen action: nonlinearsigma needs the generic 2-D cluster update (connected components "
           "on the lattice), which is not built (DESIGN.md 8)");
   if (wants_cluster && a != "rotor" && a != "schwinger") fatal(" cluster not supported for chosen action.");
-  // --sampler wolff: the Wolff single-cluster sampler of the sigma model (sampler.hh WolffClusterSampler)
+  // --sampler wolff: the Wolff single-cluster sampler of the sigma model (cluster_sampler.hh WolffClusterSampler)
   if (o["sampler"] == "wolff" && a != "nonlinearsigma")
     fatal(" wolff sampler not supported for chosen action: it is built for nonlinearsigma only (the rotor and schwinger have "
           "--sampler cluster; the other actions have no reflection the bond form is symmetric under)");
@@ -241,7 +242,7 @@ int main(int argc, char **argv) {
       fatal("nonlinearsigma: --coarsesampler levelwolff needs --coarsening rotate, not " + o["coarsening"] +
             ": this action coarsens by rotate only (nonlinearsigmaaction.hh:143-149)");
   }
-  // --sampler swendsenwang: the multi-cluster sampler of the sigma model (sampler.hh SwendsenWangSampler)
+  // --sampler swendsenwang: the multi-cluster sampler of the sigma model (cluster_sampler.hh SwendsenWangSampler)
   if (o["sampler"] == "swendsenwang" && a != "nonlinearsigma")
     fatal(" swendsenwang sampler not supported for chosen action: it is built for nonlinearsigma only (the rotor and schwinger have "
           "--sampler cluster; the other actions have no reflection the bond form is symmetric under)");

@@ -7,6 +7,7 @@
 #include <cstring>
 #include <thread>
 
+#include "mlmcpi/cluster_sampler.hh"
 #include "mlmcpi/multilevel.hh"
 
 using namespace mlmcpi;

@@ -17,6 +17,7 @@
 #include <numeric>
 #include <utility>
 
+#include "mlmcpi/cluster_sampler.hh"
 #include "mlmcpi/multilevel.hh"
 
 using namespace mlmcpi;
@@ -651,6 +652,51 @@ static void held_samples(const std::string &name, Sampler &sampler, unsigned M, 
   std::printf(" %s: 6 draws, %d failures so far\n", name.c_str(), failures);
 }
 
+/** what the replay side keeps of the improved outputs of the sigma model's cluster draws since its last reset: the sum over the
+ *  draws of a draw's chi_m (the sum over the chains over B n_updates) and, per chain, the sums of F_d and of C; structure_factor(d)
+ *  and correlator() reduce them in the order ClusterImprovedSums documents: every chain's sum over the updates counted, then over
+ *  B, added chain by chain */
+struct ImprovedReplay {
+  ImprovedReplay(unsigned B_, unsigned n_updates_, unsigned n_out_, unsigned Mt_, unsigned Mx_)
+      : B(B_), n_updates(n_updates_), n_out(n_out_), Mt(Mt_), Mx(Mx_), chain_F(2 * B_, 0.0), chain_C((size_t)B_ * n_out_, 0.0) {}
+  /** one draw: imp [B], F [B][2] or NULL, C [B][n_out] or NULL; F_from_C: without F, F_d of the draw is structure_factor() of its C_d */
+  void add(const Vec &imp, const Vec *F, const Vec *C, bool F_from_C = false) {
+    double v = 0.0;
+    for (double q : imp) v += q;
+    v /= (double)B * n_updates;
+    improved_sum += v;
+    ++draws;
+    for (size_t k = 0; C && k < chain_C.size(); ++k) chain_C[k] += (*C)[k];
+    for (unsigned b = 0; b < B; ++b) {
+      if (F) {
+        chain_F[2 * b] += (*F)[2 * b];
+        chain_F[2 * b + 1] += (*F)[2 * b + 1];
+      } else if (F_from_C && C) {
+        const Vec::const_iterator c = C->begin() + (size_t)b * n_out;
+        chain_F[2 * b] += mlmcpi::structure_factor(Vec(c, c + Mt / 2 + 1), Mt);
+        chain_F[2 * b + 1] += mlmcpi::structure_factor(Vec(c + Mt / 2 + 1, c + n_out), Mx);
+      }
+    }
+  }
+  double improved_mean() const { return improved_sum / draws; }
+  double structure_factor(int d) const {
+    const double n = (double)draws * n_updates;
+    double m = 0.0;
+    for (unsigned b = 0; b < B; ++b) m += chain_F[2 * b + d] / n / B;
+    return m;
+  }
+  Vec correlator() const {
+    const double n = (double)draws * n_updates;
+    Vec m(n_out, 0.0);
+    for (unsigned k = 0; k < n_out; ++k)
+      for (unsigned b = 0; b < B; ++b) m[k] += chain_C[(size_t)b * n_out + k] / n / B;
+    return m;
+  }
+  unsigned B, n_updates, n_out, Mt, Mx, draws = 0;
+  double improved_sum = 0.0;
+  Vec chain_F, chain_C;
+};
+
 static void case_exact_and_cluster() {
   const unsigned B = 3;
   {  // HarmonicOscillatorExactSampler, M = 32
@@ -824,6 +870,94 @@ static void case_exact_and_cluster() {
       EXPECT(sampler.mean_clusters_per_update() == clusters_total / (6.0 * n_updates), "swendsen-wang, %s: clusters per update %.17g vs %.17g", where.c_str(),
              sampler.mean_clusters_per_update(), clusters_total / (6.0 * n_updates));
       EXPECT(sampler.improved_mean() == improved_sum / 6, "swendsen-wang, %s: improved chi_m %.17g vs %.17g", where.c_str(), sampler.improved_mean(), improved_sum / 6);
+    }
+    // the option paths: the improved entry points, their outputs kept by the replay per chain
+    uint32_t n_out = 0;
+    check(mlmcpi_sigma_level_correlator_size(&lv, &n_out), "sigma_level_correlator_size");
+    struct Options {
+      const char *name;
+      bool improved, structure, correlator;
+    };
+    auto with_options = [&](const Options &o) {
+      ClusterParameters q = cp;
+      q.improved = o.improved;
+      q.structure = o.structure;
+      q.correlator = o.correlator;
+      return q;
+    };
+    for (const Options &o : {Options{"improved", true, false, false}, Options{"structure", false, true, false}, Options{"correlator", false, false, true},
+                             Options{"structure + correlator", false, true, true}}) {
+      const std::string name = std::string("wolff (") + o.name + "), " + where;
+      WolffClusterSampler sampler(make(), with_options(o));
+      size_t bytes = 0;
+      check(mlmcpi_sigma_level_cluster_improved_workspace_bytes(&lv, B, &bytes), "sigma_level_cluster_improved_workspace_bytes");
+      Dev x((size_t)M * B * sizeof(double)), sites(B * sizeof(uint32_t)), improved(B * sizeof(double)), structure(2 * B * sizeof(double)),
+          corr((size_t)B * n_out * sizeof(double)), work(bytes);
+      init(x.d());
+      uint32_t update = 0;
+      ImprovedReplay kept(B, n_updates, n_out, lv.Mt, lv.Mx);
+      auto draw = [&]() {
+        improved.zero();
+        structure.zero();
+        corr.zero();
+        check(mlmcpi_sigma_level_cluster_improved_draw(&lv, x.d(), B, n_updates, SEED, CHAIN0, update, (uint32_t *)sites.p, improved.d(),
+                                                       o.structure ? structure.d() : nullptr, o.correlator ? corr.d() : nullptr, work.p, bytes, nullptr),
+              "sigma_level_cluster_improved_draw");
+        update += n_updates;
+        const Vec F = structure.get<double>(), C = corr.get<double>();
+        kept.add(improved.get<double>(), o.structure ? &F : nullptr, o.correlator ? &C : nullptr);
+        return x.get<double>();
+      };
+      for (unsigned k = 0; k < n_ctor; ++k) draw();
+      sites.zero();
+      kept = ImprovedReplay(B, n_updates, n_out, lv.Mt, lv.Mx);  // the constructor resets after its draws
+      held_samples(name, sampler, M, B, draw);
+      double total = 0.0, held = sampler.flipped_sites_folded();
+      for (uint32_t v : sites.get<uint32_t>()) total += v;
+      for (uint32_t v : sampler.flipped_sites_unfolded()) held += v;
+      EXPECT(held == total, "%s: flipped sites %.17g, the replay's counters sum to %.17g", name.c_str(), held, total);
+      EXPECT(sampler.improved_mean() == kept.improved_mean(), "%s: improved chi_m %.17g vs %.17g", name.c_str(), sampler.improved_mean(), kept.improved_mean());
+      for (int d = 0; o.structure && d < 2; ++d)
+        EXPECT(sampler.improved_structure_factor(d).value == kept.structure_factor(d), "%s: improved F_%d %.17g vs %.17g", name.c_str(), d,
+               sampler.improved_structure_factor(d).value, kept.structure_factor(d));
+      if (o.correlator) EXPECT_SAME(sampler.improved_correlator().mean, kept.correlator(), "%s: improved correlator", name.c_str());
+    }
+    for (const Options &o : {Options{"structure", false, true, false}, Options{"correlator", false, false, true}, Options{"structure + correlator", false, true, true}}) {
+      const std::string name = std::string("swendsen-wang (") + o.name + "), " + where;
+      SwendsenWangSampler sampler(make(), with_options(o));
+      size_t bytes = 0;
+      if (o.correlator) check(mlmcpi_sigma_level_sw_correlator_workspace_bytes(&lv, B, &bytes), "sigma_level_sw_correlator_workspace_bytes");
+      else check(mlmcpi_sigma_level_sw_structure_workspace_bytes(&lv, B, &bytes), "sigma_level_sw_structure_workspace_bytes");
+      Dev x((size_t)M * B * sizeof(double)), clusters(B * sizeof(uint32_t)), improved(B * sizeof(double)), structure(2 * B * sizeof(double)),
+          corr((size_t)B * n_out * sizeof(double)), work(bytes);
+      init(x.d());
+      uint32_t update = 0;
+      ImprovedReplay kept(B, n_updates, n_out, lv.Mt, lv.Mx);
+      auto draw = [&]() {
+        clusters.zero();
+        improved.zero();
+        structure.zero();
+        corr.zero();
+        // with the correlator the library returns C alone: F of the draw, where asked for, is structure_factor() of its C
+        if (o.correlator)
+          check(mlmcpi_sigma_level_sw_correlator_draw(&lv, x.d(), B, n_updates, SEED, CHAIN0, update, nullptr, (uint32_t *)clusters.p, improved.d(), corr.d(),
+                                                      work.p, bytes, nullptr), "sigma_level_sw_correlator_draw");
+        else
+          check(mlmcpi_sigma_level_sw_structure_draw(&lv, x.d(), B, n_updates, SEED, CHAIN0, update, nullptr, (uint32_t *)clusters.p, improved.d(),
+                                                     structure.d(), work.p, bytes, nullptr), "sigma_level_sw_structure_draw");
+        update += n_updates;
+        const Vec F = structure.get<double>(), C = corr.get<double>();
+        kept.add(improved.get<double>(), o.correlator ? nullptr : &F, o.correlator ? &C : nullptr, o.structure);
+        return x.get<double>();
+      };
+      for (unsigned k = 0; k < n_ctor; ++k) draw();
+      kept = ImprovedReplay(B, n_updates, n_out, lv.Mt, lv.Mx);  // reset_improved() at the end of the constructor
+      held_samples(name, sampler, M, B, draw);
+      EXPECT(sampler.improved_mean() == kept.improved_mean(), "%s: improved chi_m %.17g vs %.17g", name.c_str(), sampler.improved_mean(), kept.improved_mean());
+      for (int d = 0; o.structure && d < 2; ++d)
+        EXPECT(sampler.improved_structure_factor(d).value == kept.structure_factor(d), "%s: improved F_%d %.17g vs %.17g", name.c_str(), d,
+               sampler.improved_structure_factor(d).value, kept.structure_factor(d));
+      if (o.correlator) EXPECT_SAME(sampler.improved_correlator().mean, kept.correlator(), "%s: improved correlator", name.c_str());
     }
   }
 }

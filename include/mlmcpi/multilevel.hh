@@ -12,7 +12,6 @@
 // copy of accepted states) is one ABI call, mlmcpi_path_twolevel_draw.
 #ifndef MLMCPI_MULTILEVEL_HH
 #define MLMCPI_MULTILEVEL_HH
-#include <chrono>
 #include <cmath>
 
 #include "montecarlo.hh"
@@ -28,28 +27,15 @@ public:
   virtual int cfa_kind() const { return 0; }
 };
 
-/** Gaussian fill-in x_{2j+1} ~ N(Wminimum(x_2j, x_2j+2), 1/Wcurvature): harmonic and quartic oscillator.
- *  fill_fine_points / evaluate run inside mlmcpi_path_twolevel_draw. */
-class GaussianConditionedFineAction : public ConditionedFineAction {
+/** a conditioned fine action that holds its fine action as an ActionT */
+template <class ActionT>
+class ConditionedFineActionOf : public ConditionedFineAction {
 public:
-  explicit GaussianConditionedFineAction(const std::shared_ptr<QMAction> action_) : action(action_) {
-    if (action->abi_action().kind == MLMCPI_ROTOR) fatal("Gaussian conditioned fine action not defined for the rotor action");
-  }
+  explicit ConditionedFineActionOf(const std::shared_ptr<ActionT> action_) : action(action_) {}
   std::shared_ptr<Action> fine_action() const override { return action; }
 
-private:
-  const std::shared_ptr<QMAction> action;
-};
-
-/** action/qm/rotorconditionedfineaction.{hh,cc}: fill-in x_{2j+1} = mod_2pi(Wminimum + ExpSin2(2 Wcurvature)).
- *  fill_fine_points / evaluate run inside mlmcpi_path_twolevel_draw. */
-class RotorConditionedFineAction : public ConditionedFineAction {
-public:
-  explicit RotorConditionedFineAction(const std::shared_ptr<RotorAction> action_) : action(action_) {}
-  std::shared_ptr<Action> fine_action() const override { return action; }
-
-private:
-  const std::shared_ptr<RotorAction> action;
+protected:
+  const std::shared_ptr<ActionT> action;
 };
 
 class ConditionedFineActionFactory {
@@ -58,71 +44,66 @@ public:
   virtual std::shared_ptr<ConditionedFineAction> get(std::shared_ptr<Action> action) = 0;
 };
 
-class GaussianConditionedFineActionFactory : public ConditionedFineActionFactory {
+/** the factory of a CfaT that takes an ActionT: casts the action, fatal with CfaT::needs where it is none */
+template <class ActionT, class CfaT>
+class CastingConditionedFineActionFactory : public ConditionedFineActionFactory {
 public:
   std::shared_ptr<ConditionedFineAction> get(std::shared_ptr<Action> action) override {
-    auto qm = std::dynamic_pointer_cast<QMAction>(action);
-    if (!qm) fatal("Gaussian conditioned fine action needs a 1-D action");
-    return std::make_shared<GaussianConditionedFineAction>(qm);
+    auto cast = std::dynamic_pointer_cast<ActionT>(action);
+    if (!cast) fatal(CfaT::needs);
+    return std::make_shared<CfaT>(cast);
   }
 };
 
-class RotorConditionedFineActionFactory : public ConditionedFineActionFactory {
+/** Gaussian fill-in x_{2j+1} ~ N(Wminimum(x_2j, x_2j+2), 1/Wcurvature): harmonic and quartic oscillator.
+ *  fill_fine_points / evaluate run inside mlmcpi_path_twolevel_draw. */
+class GaussianConditionedFineAction : public ConditionedFineActionOf<QMAction> {
 public:
-  std::shared_ptr<ConditionedFineAction> get(std::shared_ptr<Action> action) override {
-    auto rotor = std::dynamic_pointer_cast<RotorAction>(action);
-    if (!rotor) fatal("rotor conditioned fine action needs a RotorAction");
-    return std::make_shared<RotorConditionedFineAction>(rotor);
+  static constexpr const char *needs = "Gaussian conditioned fine action needs a 1-D action";
+  explicit GaussianConditionedFineAction(const std::shared_ptr<QMAction> action_) : ConditionedFineActionOf(action_) {
+    if (action->abi_action().kind == MLMCPI_ROTOR) fatal("Gaussian conditioned fine action not defined for the rotor action");
   }
 };
+typedef CastingConditionedFineActionFactory<QMAction, GaussianConditionedFineAction> GaussianConditionedFineActionFactory;
+
+/** action/qm/rotorconditionedfineaction.{hh,cc}: fill-in x_{2j+1} = mod_2pi(Wminimum + ExpSin2(2 Wcurvature)).
+ *  fill_fine_points / evaluate run inside mlmcpi_path_twolevel_draw. */
+class RotorConditionedFineAction : public ConditionedFineActionOf<RotorAction> {
+public:
+  static constexpr const char *needs = "rotor conditioned fine action needs a RotorAction";
+  using ConditionedFineActionOf::ConditionedFineActionOf;
+};
+typedef CastingConditionedFineActionFactory<RotorAction, RotorConditionedFineAction> RotorConditionedFineActionFactory;
 
 /** action/qft/quenchedschwingerconditionedfineaction.hh:134-170 (QuenchedSchwingerSemiConditionedFineAction):
  *  semi-coarsened lattices; uniform shifts of the split links and an ExpCos draw of the links in between run
  *  inside mlmcpi_lattice_twolevel_draw. */
-class QuenchedSchwingerSemiConditionedFineAction : public ConditionedFineAction {
+class QuenchedSchwingerSemiConditionedFineAction : public ConditionedFineActionOf<QuenchedSchwingerAction> {
 public:
-  explicit QuenchedSchwingerSemiConditionedFineAction(const std::shared_ptr<QuenchedSchwingerAction> action_) : action(action_) {}
-  std::shared_ptr<Action> fine_action() const override { return action; }
-
-private:
-  const std::shared_ptr<QuenchedSchwingerAction> action;
+  using ConditionedFineActionOf::ConditionedFineActionOf;
 };
 
 /** quenchedschwingerconditionedfineaction.hh:44-96 (QuenchedSchwingerConditionedFineAction): lattices coarsened in
  *  both directions; Bessel-product fill-in (beta <= 8) or its approximation, inside mlmcpi_lattice_twolevel_draw. */
-class QuenchedSchwingerConditionedFineAction : public ConditionedFineAction {
+class QuenchedSchwingerConditionedFineAction : public ConditionedFineActionOf<QuenchedSchwingerAction> {
 public:
-  explicit QuenchedSchwingerConditionedFineAction(const std::shared_ptr<QuenchedSchwingerAction> action_) : action(action_) {}
-  std::shared_ptr<Action> fine_action() const override { return action; }
-
-private:
-  const std::shared_ptr<QuenchedSchwingerAction> action;
+  using ConditionedFineActionOf::ConditionedFineActionOf;
 };
 
 /** quenchedschwingerconditionedfineaction.hh:98-131 (QuenchedSchwingerGaussianConditionedFineAction): the Gaussian variant
  *  of the fill-in for lattices coarsened in both directions (GaussianFillinDistribution); the reference's factory never
  *  selects it, a caller can (QuenchedSchwingerGaussianConditionedFineActionFactory).  Runs inside
  *  mlmcpi_lattice_twolevel_draw_cfa(cfa_kind = 1). */
-class QuenchedSchwingerGaussianConditionedFineAction : public ConditionedFineAction {
+class QuenchedSchwingerGaussianConditionedFineAction : public ConditionedFineActionOf<QuenchedSchwingerAction> {
 public:
-  explicit QuenchedSchwingerGaussianConditionedFineAction(const std::shared_ptr<QuenchedSchwingerAction> action_) : action(action_) {
+  static constexpr const char *needs = "Schwinger conditioned fine action needs a QuenchedSchwingerAction";
+  explicit QuenchedSchwingerGaussianConditionedFineAction(const std::shared_ptr<QuenchedSchwingerAction> action_) : ConditionedFineActionOf(action_) {
     if (action->get_lattice()->get_coarsening_type() != CoarsenBoth) fatal("Gaussian conditioned fine action needs CoarsenBoth");
   }
-  std::shared_ptr<Action> fine_action() const override { return action; }
   int cfa_kind() const override { return 1; }
-
-private:
-  const std::shared_ptr<QuenchedSchwingerAction> action;
 };
-
-class QuenchedSchwingerGaussianConditionedFineActionFactory : public ConditionedFineActionFactory {
-public:
-  std::shared_ptr<ConditionedFineAction> get(std::shared_ptr<Action> action) override {
-    auto schwinger = std::dynamic_pointer_cast<QuenchedSchwingerAction>(action);
-    if (!schwinger) fatal("Schwinger conditioned fine action needs a QuenchedSchwingerAction");
-    return std::make_shared<QuenchedSchwingerGaussianConditionedFineAction>(schwinger);
-  }
-};
+typedef CastingConditionedFineActionFactory<QuenchedSchwingerAction, QuenchedSchwingerGaussianConditionedFineAction>
+    QuenchedSchwingerGaussianConditionedFineActionFactory;
 
 /** quenchedschwingerconditionedfineaction.hh:218-238: the fill-in follows the coarsening type of the lattice */
 class QuenchedSchwingerConditionedFineActionFactory : public ConditionedFineActionFactory {
@@ -139,10 +120,10 @@ public:
 /** action/qft/gffconditionedfineaction.{hh,cc}: a fine-only vertex is Gaussian around the mean of its four nearest
  *  neighbours, all of them coarse vertices (red-black coarsening, CoarsenRotate); fill_fine_points / evaluate run inside
  *  mlmcpi_gff_twolevel_draw, and are exposed here for direct use. */
-class GFFConditionedFineAction : public ConditionedFineAction {
+class GFFConditionedFineAction : public ConditionedFineActionOf<GFFAction> {
 public:
-  explicit GFFConditionedFineAction(const std::shared_ptr<GFFAction> action_) : action(action_) {}
-  std::shared_ptr<Action> fine_action() const override { return action; }
+  static constexpr const char *needs = "GFF conditioned fine action needs a GFFAction";
+  using ConditionedFineActionOf::ConditionedFineActionOf;
   void fill_fine_points(std::shared_ptr<SampleState> phi_state, uint32_t step = 0) const {
     DeviceVector S(phi_state->batch());
     check(mlmcpi_gff_cfa_fill(action->level_handle(), phi_state->device_mutable(), phi_state->batch(), action->get_seed() ^ 0x115147ull,
@@ -153,27 +134,16 @@ public:
     check(mlmcpi_gff_cfa_evaluate(action->level_handle(), phi_state->device(), phi_state->batch(), (double *)S.ptr(), nullptr), "gff_cfa_evaluate");
     return S.download<double>()[0];
   }
-
-private:
-  const std::shared_ptr<GFFAction> action;
 };
-
-class GFFConditionedFineActionFactory : public ConditionedFineActionFactory {
-public:
-  std::shared_ptr<ConditionedFineAction> get(std::shared_ptr<Action> action) override {
-    auto gff = std::dynamic_pointer_cast<GFFAction>(action);
-    if (!gff) fatal("GFF conditioned fine action needs a GFFAction");
-    return std::make_shared<GFFConditionedFineAction>(gff);
-  }
-};
+typedef CastingConditionedFineActionFactory<GFFAction, GFFConditionedFineAction> GFFConditionedFineActionFactory;
 
 /** action/qft/nonlinearsigmaconditionedfineaction.{hh,cc}: every fine-only vertex of a CoarsenRotate level has its four
  *  neighbours among the coarse vertices, so the fill is one independent heat-bath draw per fine-only vertex and evaluate is minus
  *  the log of its density; both run inside mlmcpi_sigma_twolevel_draw, and are exposed here for direct use. */
-class NonlinearSigmaConditionedFineAction : public ConditionedFineAction {
+class NonlinearSigmaConditionedFineAction : public ConditionedFineActionOf<NonlinearSigmaAction> {
 public:
-  explicit NonlinearSigmaConditionedFineAction(const std::shared_ptr<NonlinearSigmaAction> action_) : action(action_) {}
-  std::shared_ptr<Action> fine_action() const override { return action; }
+  static constexpr const char *needs = "nonlinear sigma conditioned fine action needs a NonlinearSigmaAction";
+  using ConditionedFineActionOf::ConditionedFineActionOf;
   void fill_fine_points(std::shared_ptr<SampleState> phi_state, uint32_t step = 0) const {
     const mlmcpi_sigma_level lv = action->level();
     check(mlmcpi_sigma_cfa_fill(&lv, phi_state->device_mutable(), phi_state->batch(), action->get_seed() ^ 0x115147ull, action->get_chain0(),
@@ -185,19 +155,8 @@ public:
     check(mlmcpi_sigma_cfa_evaluate(&lv, phi_state->device(), phi_state->batch(), (double *)S.ptr(), nullptr), "sigma_cfa_evaluate");
     return S.download<double>()[0];
   }
-
-private:
-  const std::shared_ptr<NonlinearSigmaAction> action;
 };
-
-class NonlinearSigmaConditionedFineActionFactory : public ConditionedFineActionFactory {
-public:
-  std::shared_ptr<ConditionedFineAction> get(std::shared_ptr<Action> action) override {
-    auto sigma = std::dynamic_pointer_cast<NonlinearSigmaAction>(action);
-    if (!sigma) fatal("nonlinear sigma conditioned fine action needs a NonlinearSigmaAction");
-    return std::make_shared<NonlinearSigmaConditionedFineAction>(sigma);
-  }
-};
+typedef CastingConditionedFineActionFactory<NonlinearSigmaAction, NonlinearSigmaConditionedFineAction> NonlinearSigmaConditionedFineActionFactory;
 
 /** twolevelmetropolisstep.{hh,cc}: draws a fine-level sample from a coarse-level proposal. */
 class TwoLevelMetropolisStep : public MCMCStep {
@@ -225,10 +184,7 @@ public:
     // twolevelmetropolisstep.cc:23-31: cost per sample by timing draws (10 000 in the reference)
     auto phi_fine = std::make_shared<SampleState>(fine->sample_size(), B);
     auto phi_coarse = std::make_shared<SampleState>(coarse->sample_size(), B);
-    const auto t0 = std::chrono::steady_clock::now();
-    for (unsigned int k = 0; k < n_meas; ++k) draw(phi_coarse, phi_fine);
-    check(mlmcpi_stream_synchronize(nullptr), "synchronize");
-    cost_per_sample_ = 1.E6 * std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count() / (n_meas ? n_meas : 1);
+    cost_per_sample_ = timed_cost_per_sample(n_meas, [&]() { draw(phi_coarse, phi_fine); });
     theta_fine->data = std::make_shared<SampleState>(fine->sample_size(), B)->data;  // back to zeros
     reset_stats();
   }
@@ -252,12 +208,8 @@ public:
       check(mlmcpi_lattice_twolevel_draw_cfa(&qft_fine->abi_action(), &qft_coarse->abi_action(), cfa->cfa_kind(), phi_coarse_state->device(),
                                              theta_fine->device_mutable(), B, level_seed(), fine->get_chain0(), step++, work,
                                              (int32_t *)accept_flags.ptr(), nullptr, nullptr), "lattice_twolevel_draw");
-    std::vector<int32_t> flags = accept_flags.download<int32_t>();
-    double acc = 0;
-    for (int32_t f : flags) acc += f;
-    accept = flags[0] != 0;
     n_total_samples++;
-    n_accepted_samples += acc / B;
+    n_accepted_samples += mean_accept_flags(accept_flags, B, accept);
     if (copy_if_rejected || accept || B > 1) phi_state->data = theta_fine->data;
   }
   void set_state(std::shared_ptr<SampleState> phi_state) override { theta_fine->data = phi_state->data; }
@@ -311,10 +263,7 @@ public:
       phi_sampler_state.push_back(std::make_shared<SampleState>(action[ell]->sample_size(), p.batch));
     coarse_sampler = coarse_sampler_factory->get(action[n_level - 1]);
     auto meas_state = std::make_shared<SampleState>(fine_action->sample_size(), p.batch);
-    const auto t0 = std::chrono::steady_clock::now();
-    for (unsigned int k = 0; k < p.n_meas; ++k) draw(meas_state);
-    check(mlmcpi_stream_synchronize(nullptr), "synchronize");
-    cost_per_sample_ = 1.E6 * std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count() / (p.n_meas ? p.n_meas : 1);
+    cost_per_sample_ = timed_cost_per_sample(p.n_meas, [&]() { draw(meas_state); });
   }
 
   /** hierarchicalsampler.cc:55-81 */
@@ -396,10 +345,7 @@ public:
     }
     coarse_sampler = coarse_sampler_factory->get(action[n_level - 1]);
     auto meas_state = std::make_shared<SampleState>(fine_action->sample_size());
-    const auto t0 = std::chrono::steady_clock::now();
-    for (unsigned int k = 0; k < p.n_meas; ++k) draw(meas_state);
-    check(mlmcpi_stream_synchronize(nullptr), "synchronize");
-    cost_per_sample_ = 1.E6 * std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count() / (p.n_meas ? p.n_meas : 1);
+    cost_per_sample_ = timed_cost_per_sample(p.n_meas, [&]() { draw(meas_state); });
   }
 
   void draw(std::shared_ptr<SampleState> phi_state) override {
