@@ -48,6 +48,12 @@
 //   driver --action nonlinearsigma --Mt_lat 8 --beta 1.2 --sampler heatbath --batch 64 --n_samples 200 --qoi topological
 //          (--qoi magnetic|topological, nonlinearsigma only: chi_m, the default, or the topological susceptibility chi_t = Q^2 / n
 //           of the geometric charge, in single-level, --method twolevel and --sampler hierarchical runs)
+//   driver --action nonlinearsigma --Mt_lat 8 --beta 1.2 --sampler heatbath --batch 64 --n_samples 200 --qoi topological --n_cool 3
+//          (--n_cool k with --qoi topological: chi_t is read from the field after k cooling sweeps, each level cooling its own
+//           field, wherever --qoi topological runs; the chain's state is not touched)
+//   driver --action nonlinearsigma --Mt_lat 8 --beta 1.2 --sampler heatbath --batch 64 --n_samples 200 --qoi topological --cooling_profile 0,1,3
+//          (--cooling_profile d0,d1,.. with --qoi topological, --method singlelevel: after the run, per depth chi_t and <E> / 4 pi
+//           of the cooled field with their jackknife error over the chains)
 //   driver --method throughput --action schwinger --Mt_lat 1024 --sampler heatbath --batch 32 --n_samples 20
 //          (the sampling loop of MonteCarloSingleLevel on a batch of chains, statistics accumulated on the device:
 //           prints link-updates/s of the C++ path)
@@ -60,6 +66,7 @@
 #include <chrono>
 #include <cstring>
 #include <map>
+#include <set>
 
 #include "mlmcpi/cluster_sampler.hh"
 #include "mlmcpi/multilevel.hh"
@@ -93,10 +100,12 @@ int main(int argc, char **argv) {
       {"n_sweep_heatbath", "1"}, {"autotune", "1"}, {"window", "20"}, {"method", "singlelevel"}, {"n_level", "3"},
       {"epsilon", "0.01"}, {"coarsening", "both"}, {"coarsesampler", "hmc"}, {"renormalisation", "none"}, {"n_meas", "200"},
       {"batch", "1"}, {"seed", "2481317"}, {"warmup", "5"}, {"random_order", "0"}, {"n_updates", "10"}, {"correlator", "0"},
-      {"path_correlator", "0"}, {"wilson_loops", "0"}, {"gff_correlator", "0"}, {"qoi", "magnetic"}};
+      {"path_correlator", "0"}, {"wilson_loops", "0"}, {"gff_correlator", "0"}, {"qoi", "magnetic"}, {"n_cool", "0"}, {"cooling_profile", ""}};
+  std::set<std::string> given;  // the options on the command line
   for (int i = 1; i + 1 < argc; i += 2) {
     if (std::strncmp(argv[i], "--", 2) || !o.count(argv[i] + 2)) fatal(std::string("unknown option ") + argv[i]);
     o[argv[i] + 2] = argv[i + 1];
+    given.insert(argv[i] + 2);
   }
   auto num = [&](const char *k) { return std::stod(o[k]); };
   // ranks: one process per GPU, the launcher's environment names them
@@ -169,6 +178,44 @@ int main(int argc, char **argv) {
   if (topological && o["action"] != "nonlinearsigma")
     fatal("--qoi topological is not supported for chosen action: the geometric topological charge is built for nonlinearsigma only, "
           "not " + o["action"] + " (the rotor and schwinger measure their own topological susceptibility by default)");
+  // --n_cool k: chi_t of the field after k cooling sweeps (qoi.hh QoI2DSigmaCooledTopologicalSusceptibility),
+  // wherever --qoi topological runs.  --cooling_profile d0,d1,..: per depth chi_t and <E> / 4 pi after a single-level run
+  // (qoi.hh SigmaCoolingProfile).  Both refused here, before any device call.
+  const bool cooled = given.count("n_cool") != 0, wants_profile = given.count("cooling_profile") != 0;
+  const unsigned n_cool = cooled ? count_option("n_cool", o["n_cool"], "the number of cooling sweeps") : 0u;
+  std::vector<uint32_t> profile_depths;
+  for (const char *flag : {"n_cool", "cooling_profile"}) {
+    if (!given.count(flag)) continue;
+    const std::string f = std::string("--") + flag;
+    if (o["action"] != "nonlinearsigma")
+      fatal(f + " " + o[flag] + " is not supported for chosen action: cooling is built for nonlinearsigma only, not " + o["action"]);
+    if (!topological) fatal(f + " needs --qoi topological (cooling serves the topological charge), not --qoi " + o["qoi"]);
+  }
+  if (n_cool > MLMCPI_SIGMA_COOLING_MAX_DEPTH)
+    fatal("--n_cool " + o["n_cool"] + " is more than " + std::to_string(MLMCPI_SIGMA_COOLING_MAX_DEPTH) + " cooling sweeps");
+  if (wants_profile) {
+    if (o["method"] != "singlelevel")
+      fatal("--cooling_profile runs --method singlelevel only, not " + o["method"] + " (the two-level estimator takes --n_cool k)");
+    if (o["correlator"] == "1") fatal("--cooling_profile and --correlator 1 do not run together (one measurement beside the QoI per run)");
+    if (world > 1) fatal("--cooling_profile runs on one rank (its sums are not exchanged)");
+    const std::string &v = o["cooling_profile"];
+    if (v.empty() || v.find_first_not_of("0123456789,") != std::string::npos || v.front() == ',' || v.back() == ',' ||
+        v.find(",,") != std::string::npos)
+      fatal("--cooling_profile takes a comma-separated list of depths d0,d1,.., not " + v);
+    for (size_t at = 0; at < v.size();) {
+      const size_t end = std::min(v.find(',', at), v.size());
+      if (end - at > 9) fatal("--cooling_profile takes depths up to " + std::to_string(MLMCPI_SIGMA_COOLING_MAX_DEPTH) + ", not " + v.substr(at, end - at));
+      profile_depths.push_back((uint32_t)std::stoul(v.substr(at, end - at)));
+      at = end + 1;
+    }
+    for (size_t k = 0; k < profile_depths.size(); ++k) {
+      if (k && profile_depths[k] <= profile_depths[k - 1]) fatal("--cooling_profile takes strictly ascending depths, not " + v);
+      if (profile_depths[k] > MLMCPI_SIGMA_COOLING_MAX_DEPTH)
+        fatal("--cooling_profile takes depths up to " + std::to_string(MLMCPI_SIGMA_COOLING_MAX_DEPTH) + ", not " + std::to_string(profile_depths[k]));
+    }
+    if (profile_depths.size() > MLMCPI_SIGMA_COOLING_MAX_DEPTHS)
+      fatal("--cooling_profile takes at most " + std::to_string(MLMCPI_SIGMA_COOLING_MAX_DEPTHS) + " depths, not " + std::to_string(profile_depths.size()));
+  }
   std::shared_ptr<Exchange> exchange;
   if (world > 1) {
     check(mlmcpi_set_device(local_rank), "mlmcpi_set_device");
@@ -185,6 +232,7 @@ int main(int argc, char **argv) {
   std::shared_ptr<Action> action;
   std::shared_ptr<QoI> qoi;
   std::shared_ptr<SigmaCorrelator> correlator;
+  std::shared_ptr<SigmaCoolingProfile> cooling_profile;
   std::shared_ptr<PathCorrelator> path_correlator;
   std::shared_ptr<WilsonLoops> wilson_loops;
   std::shared_ptr<GffCorrelator> gff_correlator;
@@ -315,7 +363,10 @@ int main(int argc, char **argv) {
     if (o["renormalisation"] == "exact" && levels)
       fatal("nonlinearsigma: non-perturbative renormalisation not implemented for non-linear sigma model.");
     action = std::make_shared<NonlinearSigmaAction>(lat, nullptr, renorm, num("beta"));
-    if (topological) {
+    if (topological && cooled) {  // --n_cool 0 is the uncooled chi_t through the cooling call: the same bits
+      qoi = std::make_shared<QoI2DSigmaCooledTopologicalSusceptibility>(lat, n_cool);
+      qoi_factory = std::make_shared<QoI2DSigmaCooledTopologicalSusceptibilityFactory>(n_cool);
+    } else if (topological) {
       qoi = std::make_shared<QoI2DSigmaTopologicalSusceptibility>(lat);
       qoi_factory = std::make_shared<QoI2DSigmaTopologicalSusceptibilityFactory>();
     } else {
@@ -323,6 +374,7 @@ int main(int argc, char **argv) {
       qoi_factory = std::make_shared<QoI2DMagneticSusceptibilityFactory>();
     }
     if (wants_correlator) correlator = std::make_shared<SigmaCorrelator>(lat);
+    if (wants_profile) cooling_profile = std::make_shared<SigmaCoolingProfile>(lat, profile_depths);
     cfa_factory = std::make_shared<NonlinearSigmaConditionedFineActionFactory>();
   } else if (a == "schwinger" || a == "gff") {
     auto lat = std::make_shared<Lattice2D>((unsigned)num("Mt_lat"), (unsigned)num("Mt_lat"), coarsenings.at(o["coarsening"]));
@@ -346,6 +398,7 @@ int main(int argc, char **argv) {
   std::cout << "Action: " << action->info_string() << std::endl;
   if (topological)
     std::cout << "QoI: topological susceptibility chi_t = Q^2 / n of the geometric (Berg-Luescher) charge" << std::endl;
+  if (n_cool > 0) std::cout << "Cooling: chi_t is read after " << n_cool << " cooling sweeps of a copy of the field" << std::endl;
   auto basic_factory = [&](const std::string &name) -> std::shared_ptr<SamplerFactory> {
     if (name == "hmc") {
       HMCParameters hp;
@@ -493,12 +546,27 @@ int main(int argc, char **argv) {
   if (path_correlator) measured = path_correlator;
   if (wilson_loops) measured = wilson_loops;  // --wilson_loops N likewise
   if (gff_correlator) measured = gff_correlator;  // and --gff_correlator P
+  if (cooling_profile) measured = cooling_profile;  // and --cooling_profile d0,d1,..
   // (--qoi topological likewise: Q is the mean of chi_t over the chains)
   MonteCarloSingleLevel mc(action, qoi, factory, mp, exchange, measured || topological ? batch : 1u, measured);
   mc.evaluate();
   std::cout << std::endl << "=== Single level MC ===" << std::endl;
   mc.show_statistics();
   mc.get_sampler()->show_stats();
+  if (cooling_profile) {
+    const SigmaCoolingProfile::Estimate e = cooling_profile->means_and_errors();
+    const std::vector<uint32_t> &depths = cooling_profile->get_depths();
+    measurement_header("Cooling profile", *cooling_profile, e);
+    std::cout << std::setprecision(8) << std::scientific;
+    for (unsigned k = 0; k < depths.size(); ++k) {
+      const ChainScalar chi = cooling_profile->entry(k), en = cooling_profile->entry((unsigned)depths.size() + k);
+      std::cout << " depth " << depths[k] << ": chi_t = " << chi.value;
+      jackknife_suffix(chi);
+      std::cout << ", <E> / 4 pi = " << en.value;
+      jackknife_suffix(en);
+      std::cout << std::endl;
+    }
+  }
   if (correlator) {
     const SigmaCorrelator::Estimate e = correlator->means_and_errors();
     const unsigned Mt = correlator->Mt(), Mx = correlator->Mx(), nt = Mt / 2 + 1, nx = Mx / 2 + 1, B = correlator->batch();

@@ -734,6 +734,18 @@ typedef QFTQoIFactory<QoIAvgPlaquette> QoIAvgPlaquetteFactory;
 typedef QFTQoIFactory<QoI2DPhiSquared> QoI2DPhiSquaredFactory;
 typedef QFTQoIFactory<QoI2DMagneticSusceptibility> QoI2DMagneticSusceptibilityFactory;
 typedef QFTQoIFactory<QoI2DSigmaTopologicalSusceptibility> QoI2DSigmaTopologicalSusceptibilityFactory;
+/** every level cools its own field n_cool sweeps */
+class QoI2DSigmaCooledTopologicalSusceptibilityFactory : public QoIFactory {
+public:
+  explicit QoI2DSigmaCooledTopologicalSusceptibilityFactory(unsigned int n_cool_) : n_cool(n_cool_) {}
+  std::shared_ptr<QoI> get(std::shared_ptr<Action> action) override {
+    auto qft = std::dynamic_pointer_cast<QFTAction>(action);
+    if (!qft) fatal("this QoI needs a 2-D action");
+    return std::make_shared<QoI2DSigmaCooledTopologicalSusceptibility>(qft->get_lattice(), n_cool);
+  }
+private:
+  const unsigned int n_cool;
+};
 
 }  // namespace mlmcpi
 #endif

@@ -146,6 +146,34 @@ private:
   const unsigned int n_vertices;
 };
 
+/** chi_t of the field after n_cool cooling sweeps (mlmcpi_sigma_level_cooled_charge at the one depth n_cool), on
+ *  plain and rotated lattices.  The state is only read: cooling runs on a copy in this QoI's own workspace, sized for the batch at
+ *  hand.  n_cool = 0 returns what QoI2DSigmaTopologicalSusceptibility returns, bit for bit.  fused_kind 0. */
+class QoI2DSigmaCooledTopologicalSusceptibility : public QoI {
+public:
+  QoI2DSigmaCooledTopologicalSusceptibility(const std::shared_ptr<Lattice2D> lattice, unsigned int n_cool_)
+      : level{lattice->getMt_lat(), lattice->getMx_lat(), lattice->is_rotated() ? 1 : 0, 0.0}, n_vertices(lattice->getNvertices()),
+        n_cool(n_cool_) {}
+  void evaluate_device(const std::shared_ptr<SampleState> phi, double *d_out) override {
+    if (phi->size() != 2 * n_vertices) fatal("Evaluating QoI2DSigmaCooledTopologicalSusceptibility on state of wrong size.");
+    if (!work || work_B != phi->batch()) {
+      check(mlmcpi_sigma_level_cooling_workspace_bytes(&level, phi->batch(), &work_bytes), "sigma_level_cooling_workspace_bytes");
+      work = std::make_unique<DeviceBuffer>(work_bytes);
+      work_B = phi->batch();
+    }
+    const uint32_t depth = n_cool;
+    check(mlmcpi_sigma_level_cooled_charge(&level, phi->device(), phi->batch(), &depth, 1, nullptr, d_out, nullptr, nullptr, work->p,
+                                           work_bytes, nullptr),
+          "sigma_level_cooled_charge");
+  }
+private:
+  const mlmcpi_sigma_level level;
+  const unsigned int n_vertices, n_cool;
+  unsigned int work_B = 0;
+  size_t work_bytes = 0;
+  std::unique_ptr<DeviceBuffer> work;
+};
+
 /** A measurement beside the QoI: not a QoI, its value is a vector of n_out() numbers per chain.  MonteCarloSingleLevel asks it for
  *  one more sample of the state at hand (accumulate) and how many it has taken (samples).  accumulate() adds the sample's values and
  *  their squares to per-chain sums on the device; the means and their errors are host arithmetic on those sums (chain_estimate.hh).
@@ -247,6 +275,63 @@ private:
   }
   const mlmcpi_sigma_level level;
   const unsigned int n_vertices;
+};
+
+/** The cooling profile of the O(3) sigma model on a lattice, rotated or not (mlmcpi_sigma_level_cooled_charge): per
+ *  chain and sample chi_t = Q^2 / n at each of the ascending `depths`, then E / 4 pi at each of them, n_out() = 2 depths.size()
+ *  numbers.  The call has no accumulator argument, so a sample's 2 n_depths numbers per chain make one round trip through the host,
+ *  where E is divided by 4 pi and the value and its square are added to the per-chain sums. */
+class SigmaCoolingProfile : public CorrelatorMeasurement {
+public:
+  SigmaCoolingProfile(const std::shared_ptr<Lattice2D> lattice, const std::vector<uint32_t> &depths_)
+      : CorrelatorMeasurement("SigmaCoolingProfile", 2 * (unsigned int)depths_.size()),
+        level{lattice->getMt_lat(), lattice->getMx_lat(), lattice->is_rotated() ? 1 : 0, 0.0}, n_vertices(lattice->getNvertices()),
+        depths(depths_) {}
+  const std::vector<uint32_t> &get_depths() const { return depths; }
+  /** entry k of the mean over chains; batch >= 2: with the jackknife error over the chains */
+  ChainScalar entry(unsigned int k) const {
+    return chain_jackknife(chain_means(), [](const std::vector<double> &v) { return v[0]; }, k, 1);
+  }
+
+protected:
+  void check_size(unsigned int n) const override {
+    if (n != 2 * n_vertices) fatal("Evaluating SigmaCoolingProfile on state of wrong size.");
+  }
+  void workspace_bytes(unsigned int batch, size_t *bytes) const override {
+    check(mlmcpi_sigma_level_cooling_workspace_bytes(&level, batch, bytes), "sigma_level_cooling_workspace_bytes");
+    *bytes += raw_bytes(batch);
+  }
+  void run(const double *d_state, unsigned int batch, double *d_out, double *d_acc, void *d_work, size_t work_bytes) const override {
+    const size_t nd = depths.size(), raw = raw_bytes(batch), count = (size_t)batch * nd;
+    double *d_chi = (double *)((char *)d_work + (work_bytes - raw)), *d_e = d_chi + count;
+    check(mlmcpi_sigma_level_cooled_charge(&level, d_state, batch, depths.data(), (uint32_t)nd, nullptr, d_chi, d_e, nullptr, d_work,
+                                           work_bytes - raw, nullptr),
+          "sigma_level_cooled_charge");
+    std::vector<double> h(2 * count), v(2 * count);
+    check(mlmcpi_copy_d2h(h.data(), d_chi, 2 * count * sizeof(double), nullptr), "copy_d2h");
+    const double four_pi = 4.0 * std::acos(-1.0);
+    for (size_t b = 0; b < batch; ++b)
+      for (size_t k = 0; k < nd; ++k) {
+        v[b * 2 * nd + k] = h[b * nd + k];
+        v[b * 2 * nd + nd + k] = h[count + b * nd + k] / four_pi;
+      }
+    check(mlmcpi_copy_h2d(d_out, v.data(), v.size() * sizeof(double), nullptr), "copy_h2d");
+    if (d_acc) {
+      std::vector<double> a(2 * v.size());
+      check(mlmcpi_copy_d2h(a.data(), d_acc, a.size() * sizeof(double), nullptr), "copy_d2h");
+      for (size_t i = 0; i < v.size(); ++i) {
+        a[2 * i] += v[i];
+        a[2 * i + 1] += v[i] * v[i];
+      }
+      check(mlmcpi_copy_h2d(d_acc, a.data(), a.size() * sizeof(double), nullptr), "copy_h2d");
+    }
+  }
+
+private:
+  size_t raw_bytes(unsigned int batch) const { return (2 * (size_t)batch * depths.size() * sizeof(double) + 255) & ~(size_t)255; }
+  const mlmcpi_sigma_level level;
+  const unsigned int n_vertices;
+  const std::vector<uint32_t> depths;
 };
 
 /** The time correlator C(tau), tau = 0 .. n_lag - 1, of a 1-D path action (mlmcpi_path_correlator; definitions in

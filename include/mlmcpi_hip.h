@@ -65,6 +65,8 @@
  *       mlmcpi_sigma_level_correlator                                                  grid y and z          65535 (refused by name)
  *       mlmcpi_sigma_level_topological_charge (its batch is spelled n_chains; run at   linear index, x then y unbounded (2^23 x 65535
  *         the edge by tests/test_sigma_topology_gpu.py)                                                      workgroups)
+ *       mlmcpi_sigma_level_cooled_charge (n_chains; run at the edge by                 linear index, x then y unbounded (2^23 x 65535
+ *         tests/test_sigma_cooling_gpu.py)                                                                   workgroups)
  *       mlmcpi_stats_accumulate, mlmcpi_stats_window_record                            grid x, 256 per wg    unbounded
  */
 #ifndef MLMCPI_HIP_H
@@ -692,6 +694,48 @@ int mlmcpi_sigma_level_correlator(const mlmcpi_sigma_level *level, const double 
 int mlmcpi_sigma_level_topological_charge(const mlmcpi_sigma_level *level, const double *d_state, uint32_t n_chains,
                                           double *d_q /* may be NULL */, double *d_chi /* may be NULL */,
                                           double *d_acc /* may be NULL: record_sample moments of chi, [n_chains][5] */, void *stream);
+/* Cooling on a level and the cooled charge (sigma_cooling.hip); `beta` is ignored.  Cooling is the deterministic
+ * beta -> infinity limit of the heat bath: sigma_l <- Delta_l / |Delta_l|, Delta_l = add4 of the four neighbours in the order of
+ * mlmcpi_sigma_level_sweep_draw, |Delta| = sqrt((x^2 + y^2) + z^2), three divisions; Delta_l = 0 leaves sigma_l as it is.  One
+ * cooling sweep updates the two colour classes in the sweeps' order: plain level (i + j) even, then odd; rotated level phase E,
+ * then phase O.  Depth d is the field after d sweeps, starting from sigma_of(d_state); between sweeps the field lives as unit
+ * vectors and is never converted back to angles.  For every depth d = depths[k]:
+ *   d_q      [n_chains][n_depths]  Q_d, the charge above on the field of depth d (same faces, triangles and sum order)
+ *   d_chi    [n_chains][n_depths]  Q_d^2 / n
+ *   d_energy [n_chains][n_depths]  E_d = 2 n - (1/2) sum_l sigma_l . Delta_l, the bond energy sum_bonds (1 - sigma . sigma'),
+ *                                  coinciding neighbours of tiny levels counted as often as they occur
+ * any of the three may be NULL, not all.  d_cooled (may be NULL) [n_chains][2 n]: the angles (atan2(sqrt(x^2 + y^2), z),
+ * atan2(y, x)) of the field at the LAST depth.  depths (HOST memory) is strictly ascending, may start at 0, 1 <= n_depths <=
+ * MLMCPI_SIGMA_COOLING_MAX_DEPTHS, last depth <= MLMCPI_SIGMA_COOLING_MAX_DEPTH.  d_state is read once and never written.
+ * d_work: _cooling_workspace_bytes(level, n_chains) bytes, 256-byte aligned, content at entry ignored: two buffers of unit
+ * vectors ([n_chains][3][n] doubles each, ping-pong) and the partial sums of the charge (one per 32 x 32 tile) and of the energy
+ * (one per group of 256 vertices).  The library does not chunk: a caller short of memory splits the chains.
+ * An update is a function of four stored vectors and every sum is taken in an order fixed by the level alone, without atomics: a
+ * chain's Q_d, chi_d, E_d and cooled state are the same bits under every MLMCPI_SIGMA_COOL_PLAN=TWxTHxNTxK (tile, workgroup size,
+ * sweeps fused per launch; a launch never runs past the next listed depth), every n_chains, split of the chains over calls and
+ * stream, every choice of outputs and EVERY DEPTH LIST CONTAINING d; Q_0 and chi_0 are the bits of
+ * mlmcpi_sigma_level_topological_charge.  Any n_chains runs (CHAINS PER CALL above).  MLMCPI_ERR_INVALID, with nothing launched:
+ * NULL level, d_state, depths or d_work; d_q, d_chi and d_energy all NULL; odd or zero extents, Mt Mx > 2^30; n_chains = 0;
+ * n_depths outside 1 .. 32; depths not strictly ascending or beyond 4096; work_bytes below the query.
+ * _cooling_plan (host only, touches no device) reports the launches of such a call and returns the status the call would for the
+ * arguments it sees. */
+#define MLMCPI_SIGMA_COOLING_MAX_DEPTHS 32
+#define MLMCPI_SIGMA_COOLING_MAX_DEPTH 4096
+typedef struct mlmcpi_sigma_cooling_plan {
+  uint32_t tw, th, nt, fuse;  /* tile (plain: vertices, rotated: plane cells; never larger than the plane), workgroup size, sweeps per launch at most */
+  uint32_t tiles;             /* cooling workgroups per chain and launch */
+  uint32_t lds_bytes;         /* LDS image of the deepest launch */
+  uint32_t n_launches;        /* cooling launches of the call */
+  uint32_t n_measurements;    /* = n_depths */
+  uint8_t launch_sweeps[MLMCPI_SIGMA_COOLING_MAX_DEPTH]; /* [n_launches] sweeps of each; they sum to the last depth, none crosses a listed depth */
+} mlmcpi_sigma_cooling_plan;
+int mlmcpi_sigma_level_cooling_workspace_bytes(const mlmcpi_sigma_level *level, uint32_t n_chains, size_t *bytes);
+int mlmcpi_sigma_level_cooled_charge(const mlmcpi_sigma_level *level, const double *d_state, uint32_t n_chains,
+                                     const uint32_t *depths /* host */, uint32_t n_depths, double *d_q /* may be NULL */,
+                                     double *d_chi /* may be NULL */, double *d_energy /* may be NULL */,
+                                     double *d_cooled /* may be NULL */, void *d_work, size_t work_bytes, void *stream);
+int mlmcpi_sigma_level_cooling_plan(const mlmcpi_sigma_level *level, uint32_t n_chains, const uint32_t *depths, uint32_t n_depths,
+                                    mlmcpi_sigma_cooling_plan *plan);
 /* The Wolff single-cluster update on a level (sigma_cluster.hip): n_updates updates of every chain of
  * d_state [B][2 n], in place.  Unrotated: mlmcpi_sigma_cluster_* on (Mt, Mx, beta), the same bits.  Rotated: the level is
  * bipartite, every link has one E end; its 2 n links are (e, d), e an E vertex (e < n / 2), d its direction in the order above;

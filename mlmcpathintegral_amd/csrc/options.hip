@@ -87,6 +87,19 @@ const Option kOptions[] = {
     }
     return false;
   }},
+  {"MLMCPI_SIGMA_COOL_PLAN", [](Tuning &t, const std::string &v) {  // the LDS image of a rotated level (halo K cells, 48 B) and of a plain one (halo 2 K vertices, 24 B)
+    unsigned a = 0, b = 0, c = 0, k = 0;
+    char rest = 0;
+    t.sigma_cool_tw = t.sigma_cool_th = t.sigma_cool_nt = t.sigma_cool_fuse = 0;
+    if (v.empty()) return true;
+    if (sscanf(v.c_str(), "%ux%ux%ux%u%c", &a, &b, &c, &k, &rest) == 4 && a >= 1 && a <= 128 && b >= 1 && b <= 128 &&
+        (c == 256 || c == 512 || c == 1024) && k >= 1 && k <= kMaxFuse && (size_t)(a + 2 * k) * (b + 2 * k) * 48 <= kSigmaLdsMax &&
+        (size_t)(a + 4 * k) * (b + 4 * k) * 24 <= kSigmaLdsMax) {
+      t.sigma_cool_tw = a; t.sigma_cool_th = b; t.sigma_cool_nt = c; t.sigma_cool_fuse = k;
+      return true;
+    }
+    return false;
+  }},
   {"MLMCPI_SIGMA_TWOLEVEL_GROUPS", [](Tuning &t, const std::string &v) {
     unsigned g = 0;
     char rest = 0;

@@ -29,48 +29,9 @@
 // The two atan2 of a face stay two: the product of the triangles' complex numbers would lose the 2 pi the sum can wind by.
 #include "internal.hpp"
 
-#include "sigma_level_device.hpp"  // fp contraction is off from here on
+#include "sigma_topology_device.hpp"  // the face code; fp contraction is off from here on
 
 namespace mlmcpi {
-
-constexpr uint32_t kTopoThreads = kGroup;                 // 256: chain_sum's workgroup
-constexpr uint32_t kTopoTile = 32;                        // cells along a side of a tile
-constexpr uint32_t kTopoLd = kTopoTile + 1;               // staged entries along a side, and the row stride in LDS (doubles)
-constexpr uint32_t kTopoPlane = kTopoLd * kTopoLd;        // doubles of one component of one staged plane
-constexpr uint32_t kTopoGridX = (1u << 31) / kTopoThreads;  // workgroups along x of a launch; beyond, the grid grows along y
-constexpr uint64_t kTopoMaxBlocks = (uint64_t)kTopoGridX * 65535;
-
-struct TopoPlan {
-  uint32_t W, H;            // a vertex plane: W columns (the contiguous index), H rows
-  uint32_t tiles_a, tiles;  // tiles along W; tiles of a chain
-  uint32_t nvert;           // n
-};
-
-inline TopoPlan topo_plan(const SigmaLevel &L) {
-  TopoPlan G;
-  G.W = L.rot ? L.ht : L.Mt;
-  G.H = L.rot ? L.hx : L.Mx;
-  G.tiles_a = (G.W + kTopoTile - 1) / kTopoTile;
-  G.tiles = G.tiles_a * ((G.H + kTopoTile - 1) / kTopoTile);
-  G.nvert = L.nvert();
-  return G;
-}
-
-__device__ __forceinline__ uint64_t topo_block() { return (uint64_t)blockIdx.y * gridDim.x + blockIdx.x; }
-
-__device__ __forceinline__ V3 topo_load(const double *s, uint32_t c) { return V3{s[c], s[kTopoPlane + c], s[2 * kTopoPlane + c]}; }
-
-__device__ __forceinline__ double topo_triple(const V3 &a, const V3 &b, const V3 &c) {
-  return dot3(a, V3{b.y * c.z - b.z * c.y, b.z * c.x - b.x * c.z, b.x * c.y - b.y * c.x});
-}
-
-// half the signed area of the face (c1, c2, c3, c4): atan2 of the triangle (c1, c2, c3) plus atan2 of (c1, c3, c4)
-__device__ __forceinline__ double topo_face(const V3 &c1, const V3 &c2, const V3 &c3, const V3 &c4) {
-  const double d13 = dot3(c1, c3);
-  const double x1 = ((1.0 + dot3(c1, c2)) + dot3(c2, c3)) + d13, y1 = topo_triple(c1, c2, c3);
-  const double x2 = ((1.0 + d13) + dot3(c3, c4)) + dot3(c4, c1), y2 = topo_triple(c1, c3, c4);
-  return atan2(y1, x1) + atan2(y2, x2);
-}
 
 template <int ROT>
 __global__ void __launch_bounds__(kTopoThreads)
@@ -80,27 +41,16 @@ __global__ void __launch_bounds__(kTopoThreads)
   __shared__ double red[kTopoThreads / kWave];
   const uint64_t wg = topo_block();
   if (wg >= nblocks) return;
-  const uint32_t tile = (uint32_t)(wg % G.tiles), tid = threadIdx.x;
-  const uint64_t b = wg / G.tiles;
-  const uint32_t a0 = (tile % G.tiles_a) * kTopoTile, b0 = (tile / G.tiles_a) * kTopoTile;
-  const uint32_t tw = G.W - a0 < kTopoTile ? G.W - a0 : kTopoTile, th = G.H - b0 < kTopoTile ? G.H - b0 : kTopoTile;
-  const uint32_t sw = tw + 1, ns = sw * (th + 1);
-  const double2 *s = phi + (size_t)b * G.nvert;
+  const uint32_t tid = threadIdx.x;
+  const TopoTile T = topo_tile(G, (uint32_t)(wg % G.tiles));
+  const double2 *s = phi + (size_t)(wg / G.tiles) * G.nvert;
 
-  for (uint32_t c = tid; c < NP * ns; c += kTopoThreads) {
-    const uint32_t p = c / ns, r = c - p * ns, la = r % sw, lb = r / sw;
-    // plain and E: entry (a0 + la, b0 + lb); O: (a0 - 1 + la, b0 - 1 + lb); a0 + la <= W, so one subtraction wraps either
-    uint32_t a = a0 + la + (p ? G.W - 1 : 0), bb = b0 + lb + (p ? G.H - 1 : 0);
-    if (a >= G.W) a -= G.W;
-    if (bb >= G.H) bb -= G.H;
-    const V3 v = sigma_of(s[(size_t)p * G.W * G.H + (size_t)bb * G.W + a]);
-    double *d = sig + p * 3 * kTopoPlane + lb * kTopoLd + la;
-    d[0] = v.x;
-    d[kTopoPlane] = v.y;
-    d[2 * kTopoPlane] = v.z;
-  }
+  topo_stage<ROT>(G, T, sig, [s](size_t l) { return sigma_of(s[l]); });
   __syncthreads();
 
+  // topo_faces<ROT>(T, sig), written out: called here it flips the polarity of one branch of block_sum, and this kernel's
+  // instructions are pinned (tools/kernel_digest.py)
+  const uint32_t tw = T.tw, th = T.th;
   double acc[1] = {0.0};
   for (uint32_t t = tid; t < tw * th; t += kTopoThreads) {
     const uint32_t c = (t / tw) * kTopoLd + t % tw;
@@ -134,14 +84,6 @@ __global__ void __launch_bounds__(kTopoThreads)
   if (acc) record_moments(acc + 5 * b, X);
 }
 
-namespace {
-
-inline dim3 topo_grid(uint64_t blocks) {
-  const uint32_t gx = blocks < kTopoGridX ? (uint32_t)blocks : kTopoGridX;
-  return dim3(gx, (uint32_t)((blocks + gx - 1) / gx));
-}
-
-}  // namespace
 }  // namespace mlmcpi
 
 using namespace mlmcpi;

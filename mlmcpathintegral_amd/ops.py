@@ -484,6 +484,38 @@ def sigma_level_topological_charge(level, x, acc=None):
     return q, chi
 
 
+def sigma_level_cooling_workspace(level, B, device="cuda"):
+    """workspace of sigma_level_cooled_charge for B chains (uint8 tensor)"""
+    return _workspace("mlmcpi_sigma_level_cooling_workspace_bytes", C.byref(level), B, device=device)
+
+
+def sigma_level_cooling_plan(level, B, depths):
+    """the launches mlmcpi_sigma_level_cooled_charge would make (abi.SigmaCoolingPlan; host only)"""
+    d = (C.c_uint32 * len(depths))(*depths)
+    plan = abi.SigmaCoolingPlan()
+    abi.call("mlmcpi_sigma_level_cooling_plan", C.byref(level), B, d, len(depths), C.byref(plan))
+    return plan
+
+
+def sigma_level_cooled_charge(level, x, depths, *, energy=False, cooled=False, stream=None, work=None):
+    """cooling of every chain of x [B, 2 n] on a level, rotated or not, measured at the ascending list `depths` of sweep counts
+    (mlmcpi_sigma_level_cooled_charge; x is not written): returns (Q [B, n_depths], chi = Q^2 / n [B, n_depths]), then with
+    energy=True the bond energy E [B, n_depths] and with cooled=True the angles [B, 2 n] of the field at the last depth.  Runs,
+    and allocates, on `stream` (a torch.cuda.Stream; default: the current one)."""
+    _check_state(x, sigma_level_size(level))
+    B, nd = x.shape[0], len(depths)
+    d = (C.c_uint32 * nd)(*depths)
+    with torch.cuda.stream(stream if stream is not None else torch.cuda.current_stream()):
+        if work is None:
+            work = sigma_level_cooling_workspace(level, B, x.device)
+        q, chi = _f64(B, nd, x), _f64(B, nd, x)
+        e = _f64(B, nd, x) if energy else None
+        out = torch.empty_like(x) if cooled else None
+        abi.call("mlmcpi_sigma_level_cooled_charge", C.byref(level), _p(x), B, d, nd, _p(q), _p(chi), _p(e), _p(out), _p(work),
+                 work.numel(), _stream())
+    return (q, chi) + ((e,) if energy else ()) + ((out,) if cooled else ())
+
+
 def sigma_level_correlator_size(level):
     """n_out = (Mt/2 + 1) + (Mx/2 + 1): the lags of C_t, then those of C_x"""
     n = C.c_uint32(0)
