@@ -54,6 +54,12 @@
 //   driver --action nonlinearsigma --Mt_lat 8 --beta 1.2 --sampler heatbath --batch 64 --n_samples 200 --qoi topological --cooling_profile 0,1,3
 //          (--cooling_profile d0,d1,.. with --qoi topological, --method singlelevel: after the run, per depth chi_t and <E> / 4 pi
 //           of the cooled field with their jackknife error over the chains)
+//   driver --action nonlinearsigma --Mt_lat 8 --beta 1.2 --sampler heatbath --batch 64 --n_samples 200 --qoi topological --flow_time 0.5 --flow_eps 0.05
+//          (--flow_time t [--flow_eps e, default 0.05] with --qoi topological: chi_t is read from the field after t / e gradient-flow
+//           steps of size e, each level flowing its own field to the same t, wherever --n_cool runs)
+//   driver --action nonlinearsigma --Mt_lat 8 --beta 1.2 --sampler heatbath --batch 64 --n_samples 200 --qoi topological --flow_profile 0,0.25,1 --flow_scale 0.03
+//          (--flow_profile t0,t1,.. with --qoi topological, --method singlelevel: after the run, per flow time chi_t, <E> / 4 pi and
+//           t <E> / n with their jackknife error over the chains; with --flow_scale c the time at which t <E> / n = c)
 //   driver --method throughput --action schwinger --Mt_lat 1024 --sampler heatbath --batch 32 --n_samples 20
 //          (the sampling loop of MonteCarloSingleLevel on a batch of chains, statistics accumulated on the device:
 //           prints link-updates/s of the C++ path)
@@ -100,7 +106,8 @@ int main(int argc, char **argv) {
       {"n_sweep_heatbath", "1"}, {"autotune", "1"}, {"window", "20"}, {"method", "singlelevel"}, {"n_level", "3"},
       {"epsilon", "0.01"}, {"coarsening", "both"}, {"coarsesampler", "hmc"}, {"renormalisation", "none"}, {"n_meas", "200"},
       {"batch", "1"}, {"seed", "2481317"}, {"warmup", "5"}, {"random_order", "0"}, {"n_updates", "10"}, {"correlator", "0"},
-      {"path_correlator", "0"}, {"wilson_loops", "0"}, {"gff_correlator", "0"}, {"qoi", "magnetic"}, {"n_cool", "0"}, {"cooling_profile", ""}};
+      {"path_correlator", "0"}, {"wilson_loops", "0"}, {"gff_correlator", "0"}, {"qoi", "magnetic"}, {"n_cool", "0"}, {"cooling_profile", ""},
+      {"flow_time", "0"}, {"flow_eps", "0.05"}, {"flow_profile", ""}, {"flow_scale", ""}};
   std::set<std::string> given;  // the options on the command line
   for (int i = 1; i + 1 < argc; i += 2) {
     if (std::strncmp(argv[i], "--", 2) || !o.count(argv[i] + 2)) fatal(std::string("unknown option ") + argv[i]);
@@ -216,6 +223,68 @@ int main(int argc, char **argv) {
     if (profile_depths.size() > MLMCPI_SIGMA_COOLING_MAX_DEPTHS)
       fatal("--cooling_profile takes at most " + std::to_string(MLMCPI_SIGMA_COOLING_MAX_DEPTHS) + " depths, not " + std::to_string(profile_depths.size()));
   }
+  // --flow_time t [--flow_eps e]: chi_t of the field after t / e gradient-flow steps (qoi.hh QoI2DSigmaFlowedTopologicalSusceptibility,
+  // DESIGN.md 4.1h), wherever --n_cool runs.  --flow_profile t0,t1,.. [--flow_scale c]: per flow time chi_t, <E> / 4 pi and t <E> / n
+  // after a single-level run (qoi.hh SigmaFlowProfile).  All refused here, before any device call.
+  const bool flowed = given.count("flow_time") != 0, wants_flow_profile = given.count("flow_profile") != 0;
+  double flow_eps = 0.05;
+  unsigned flow_steps = 0;
+  std::vector<uint32_t> flow_profile_steps;
+  std::vector<double> flow_profile_times;
+  double flow_scale_c = NAN;
+  for (const char *flag : {"flow_time", "flow_eps", "flow_profile", "flow_scale"}) {
+    if (!given.count(flag)) continue;
+    const std::string f = std::string("--") + flag;
+    if (o["action"] != "nonlinearsigma")
+      fatal(f + " " + o[flag] + " is not supported for chosen action: the gradient flow is built for nonlinearsigma only, not " + o["action"]);
+    if (!topological) fatal(f + " needs --qoi topological (the flow serves the topological charge), not --qoi " + o["qoi"]);
+  }
+  if (given.count("flow_eps") && !flowed && !wants_flow_profile) fatal("--flow_eps needs --flow_time t or --flow_profile t0,t1,..");
+  if (given.count("flow_scale") && !wants_flow_profile) fatal("--flow_scale needs --flow_profile t0,t1,..");
+  if (flowed && cooled) fatal("--flow_time and --n_cool do not run together (one smoothing of the field per QoI)");
+  if (flowed || wants_flow_profile) {
+    auto real = [&](const char *flag, const std::string &v, double &out) {
+      char *end = nullptr;
+      out = v.empty() ? NAN : std::strtod(v.c_str(), &end);
+      return !v.empty() && end && *end == 0 && std::isfinite(out);
+    };
+    if (!real("flow_eps", o["flow_eps"], flow_eps) || !(flow_eps > 0.0 && flow_eps <= 0.25))
+      fatal("--flow_eps takes a step size 0 < eps <= 0.25, not " + o["flow_eps"]);
+    // t / eps must be an integer to 1e-9
+    auto steps_of = [&](const std::string &flag, const std::string &v) {
+      double t = 0.0;
+      if (!real(flag.c_str(), v, t) || t < 0.0) fatal("--" + flag + " takes flow times t >= 0, not " + v);
+      const double s = t / flow_eps, r = std::floor(s + 0.5);
+      if (std::fabs(s - r) > 1e-9) fatal("--" + flag + " " + v + " is not a whole number of steps of --flow_eps " + o["flow_eps"]);
+      if (r > MLMCPI_SIGMA_FLOW_MAX_STEPS)
+        fatal("--" + flag + " " + v + " is more than " + std::to_string(MLMCPI_SIGMA_FLOW_MAX_STEPS) + " steps of --flow_eps " + o["flow_eps"]);
+      return (uint32_t)r;
+    };
+    if (flowed) flow_steps = steps_of("flow_time", o["flow_time"]);
+    if (wants_flow_profile) {
+      if (o["method"] != "singlelevel")
+        fatal("--flow_profile runs --method singlelevel only, not " + o["method"] + " (the two-level estimator takes --flow_time t)");
+      if (o["correlator"] == "1") fatal("--flow_profile and --correlator 1 do not run together (one measurement beside the QoI per run)");
+      if (wants_profile) fatal("--flow_profile and --cooling_profile do not run together (one measurement beside the QoI per run)");
+      if (world > 1) fatal("--flow_profile runs on one rank (its sums are not exchanged)");
+      const std::string &v = o["flow_profile"];
+      if (v.empty() || v.find_first_not_of("0123456789.,eE+-") != std::string::npos || v.front() == ',' || v.back() == ',' ||
+          v.find(",,") != std::string::npos)
+        fatal("--flow_profile takes a comma-separated list of flow times t0,t1,.., not " + v);
+      for (size_t at = 0; at < v.size();) {
+        const size_t end = std::min(v.find(',', at), v.size());
+        flow_profile_steps.push_back(steps_of("flow_profile", v.substr(at, end - at)));
+        flow_profile_times.push_back(flow_profile_steps.back() * flow_eps);
+        at = end + 1;
+      }
+      for (size_t k = 1; k < flow_profile_steps.size(); ++k)
+        if (flow_profile_steps[k] <= flow_profile_steps[k - 1]) fatal("--flow_profile takes strictly ascending flow times, not " + v);
+      if (flow_profile_steps.size() > MLMCPI_SIGMA_FLOW_MAX_TIMES)
+        fatal("--flow_profile takes at most " + std::to_string(MLMCPI_SIGMA_FLOW_MAX_TIMES) + " flow times, not " + std::to_string(flow_profile_steps.size()));
+      if (given.count("flow_scale") && !real("flow_scale", o["flow_scale"], flow_scale_c))
+        fatal("--flow_scale takes the value c of t <E> / n that sets the scale, not " + o["flow_scale"]);
+    }
+  }
   std::shared_ptr<Exchange> exchange;
   if (world > 1) {
     check(mlmcpi_set_device(local_rank), "mlmcpi_set_device");
@@ -233,6 +302,7 @@ int main(int argc, char **argv) {
   std::shared_ptr<QoI> qoi;
   std::shared_ptr<SigmaCorrelator> correlator;
   std::shared_ptr<SigmaCoolingProfile> cooling_profile;
+  std::shared_ptr<SigmaFlowProfile> flow_profile;
   std::shared_ptr<PathCorrelator> path_correlator;
   std::shared_ptr<WilsonLoops> wilson_loops;
   std::shared_ptr<GffCorrelator> gff_correlator;
@@ -366,6 +436,9 @@ int main(int argc, char **argv) {
     if (topological && cooled) {  // --n_cool 0 is the uncooled chi_t through the cooling call: the same bits
       qoi = std::make_shared<QoI2DSigmaCooledTopologicalSusceptibility>(lat, n_cool);
       qoi_factory = std::make_shared<QoI2DSigmaCooledTopologicalSusceptibilityFactory>(n_cool);
+    } else if (topological && flowed) {  // --flow_time 0 is the uncooled chi_t through the flow call: the same bits
+      qoi = std::make_shared<QoI2DSigmaFlowedTopologicalSusceptibility>(lat, flow_eps, flow_steps);
+      qoi_factory = std::make_shared<QoI2DSigmaFlowedTopologicalSusceptibilityFactory>(flow_eps, flow_steps);
     } else if (topological) {
       qoi = std::make_shared<QoI2DSigmaTopologicalSusceptibility>(lat);
       qoi_factory = std::make_shared<QoI2DSigmaTopologicalSusceptibilityFactory>();
@@ -375,6 +448,7 @@ int main(int argc, char **argv) {
     }
     if (wants_correlator) correlator = std::make_shared<SigmaCorrelator>(lat);
     if (wants_profile) cooling_profile = std::make_shared<SigmaCoolingProfile>(lat, profile_depths);
+    if (wants_flow_profile) flow_profile = std::make_shared<SigmaFlowProfile>(lat, flow_eps, flow_profile_steps);
     cfa_factory = std::make_shared<NonlinearSigmaConditionedFineActionFactory>();
   } else if (a == "schwinger" || a == "gff") {
     auto lat = std::make_shared<Lattice2D>((unsigned)num("Mt_lat"), (unsigned)num("Mt_lat"), coarsenings.at(o["coarsening"]));
@@ -399,6 +473,9 @@ int main(int argc, char **argv) {
   if (topological)
     std::cout << "QoI: topological susceptibility chi_t = Q^2 / n of the geometric (Berg-Luescher) charge" << std::endl;
   if (n_cool > 0) std::cout << "Cooling: chi_t is read after " << n_cool << " cooling sweeps of a copy of the field" << std::endl;
+  if (flow_steps > 0)
+    std::cout << "Gradient flow: chi_t is read at flow time " << flow_steps * flow_eps << " (" << flow_steps << " steps of " << flow_eps
+              << ") of a copy of the field" << std::endl;
   auto basic_factory = [&](const std::string &name) -> std::shared_ptr<SamplerFactory> {
     if (name == "hmc") {
       HMCParameters hp;
@@ -547,6 +624,7 @@ int main(int argc, char **argv) {
   if (wilson_loops) measured = wilson_loops;  // --wilson_loops N likewise
   if (gff_correlator) measured = gff_correlator;  // and --gff_correlator P
   if (cooling_profile) measured = cooling_profile;  // and --cooling_profile d0,d1,..
+  if (flow_profile) measured = flow_profile;        // and --flow_profile t0,t1,..
   // (--qoi topological likewise: Q is the mean of chi_t over the chains)
   MonteCarloSingleLevel mc(action, qoi, factory, mp, exchange, measured || topological ? batch : 1u, measured);
   mc.evaluate();
@@ -564,6 +642,29 @@ int main(int argc, char **argv) {
       jackknife_suffix(chi);
       std::cout << ", <E> / 4 pi = " << en.value;
       jackknife_suffix(en);
+      std::cout << std::endl;
+    }
+  }
+  if (flow_profile) {
+    const SigmaFlowProfile::Estimate e = flow_profile->means_and_errors();
+    const unsigned nt = (unsigned)flow_profile->get_steps().size();
+    measurement_header("Flow profile", *flow_profile, e, ", eps = " + o["flow_eps"]);
+    std::cout << std::setprecision(8) << std::scientific;
+    for (unsigned k = 0; k < nt; ++k) {
+      const ChainScalar chi = flow_profile->entry(k), en = flow_profile->entry(nt + k), te = flow_profile->t_energy(k);
+      std::cout << " t " << flow_profile->time(k) << " (step " << flow_profile->get_steps()[k] << "): chi_t = " << chi.value;
+      jackknife_suffix(chi);
+      std::cout << ", <E> / 4 pi = " << en.value;
+      jackknife_suffix(en);
+      std::cout << ", t <E> / n = " << te.value;
+      jackknife_suffix(te);
+      std::cout << std::endl;
+    }
+    if (given.count("flow_scale")) {
+      const ChainScalar sc = flow_profile->scale(flow_scale_c);
+      std::cout << " flow scale: t <E> / n = " << flow_scale_c << " at t = " << sc.value;
+      if (std::isnan(sc.value)) std::cout << " (the listed flow times do not bracket it)";
+      else jackknife_suffix(sc);
       std::cout << std::endl;
     }
   }

@@ -122,5 +122,19 @@ inline double gff_correlator_exact(unsigned int Mt, unsigned int Mx, double mass
   return s / Mt;
 }
 
+// ---- the gradient flow of the O(3) sigma model (mlmcpi_sigma_level_flowed_charge; the class that measures it is
+// SigmaFlowProfile, qoi.hh) ----
+
+/** the reference scale of the flow: the flow time at which t <E(t)> / n, given as tE[k] at the ascending times[k], first reaches
+ *  c, by linear interpolation between the neighbouring pair of times that brackets c; NaN when no pair does */
+inline double flow_scale(const std::vector<double> &times, const std::vector<double> &tE, double c) {
+  for (size_t k = 0; k + 1 < times.size() && k + 1 < tE.size(); ++k) {
+    const double lo = tE[k], hi = tE[k + 1];
+    if (((lo <= c && c <= hi) || (hi <= c && c <= lo)) && lo != hi)
+      return times[k] + (times[k + 1] - times[k]) * (c - lo) / (hi - lo);
+  }
+  return std::nan("");
+}
+
 }  // namespace mlmcpi
 #endif

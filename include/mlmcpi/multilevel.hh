@@ -746,6 +746,19 @@ public:
 private:
   const unsigned int n_cool;
 };
+/** every level flows its own field n_steps steps of size eps: the same flow time on every level */
+class QoI2DSigmaFlowedTopologicalSusceptibilityFactory : public QoIFactory {
+public:
+  QoI2DSigmaFlowedTopologicalSusceptibilityFactory(double eps_, unsigned int n_steps_) : eps(eps_), n_steps(n_steps_) {}
+  std::shared_ptr<QoI> get(std::shared_ptr<Action> action) override {
+    auto qft = std::dynamic_pointer_cast<QFTAction>(action);
+    if (!qft) fatal("this QoI needs a 2-D action");
+    return std::make_shared<QoI2DSigmaFlowedTopologicalSusceptibility>(qft->get_lattice(), eps, n_steps);
+  }
+private:
+  const double eps;
+  const unsigned int n_steps;
+};
 
 }  // namespace mlmcpi
 #endif

@@ -174,6 +174,37 @@ private:
   std::unique_ptr<DeviceBuffer> work;
 };
 
+/** chi_t of the field after n_steps gradient-flow steps of size eps, flow time t = n_steps eps
+ *  (mlmcpi_sigma_level_flowed_charge at the one step count n_steps), on plain and rotated lattices.  The state is
+ *  only read: the flow runs on a copy in this QoI's own workspace, sized for the batch at hand.  n_steps = 0 returns what
+ *  QoI2DSigmaTopologicalSusceptibility returns, bit for bit.  fused_kind 0. */
+class QoI2DSigmaFlowedTopologicalSusceptibility : public QoI {
+public:
+  QoI2DSigmaFlowedTopologicalSusceptibility(const std::shared_ptr<Lattice2D> lattice, double eps_, unsigned int n_steps_)
+      : level{lattice->getMt_lat(), lattice->getMx_lat(), lattice->is_rotated() ? 1 : 0, 0.0}, n_vertices(lattice->getNvertices()),
+        eps(eps_), n_steps(n_steps_) {}
+  void evaluate_device(const std::shared_ptr<SampleState> phi, double *d_out) override {
+    if (phi->size() != 2 * n_vertices) fatal("Evaluating QoI2DSigmaFlowedTopologicalSusceptibility on state of wrong size.");
+    if (!work || work_B != phi->batch()) {
+      check(mlmcpi_sigma_level_flow_workspace_bytes(&level, phi->batch(), &work_bytes), "sigma_level_flow_workspace_bytes");
+      work = std::make_unique<DeviceBuffer>(work_bytes);
+      work_B = phi->batch();
+    }
+    const uint32_t steps = n_steps;
+    check(mlmcpi_sigma_level_flowed_charge(&level, phi->device(), phi->batch(), eps, &steps, 1, nullptr, d_out, nullptr, nullptr, work->p,
+                                           work_bytes, nullptr),
+          "sigma_level_flowed_charge");
+  }
+private:
+  const mlmcpi_sigma_level level;
+  const unsigned int n_vertices;
+  const double eps;
+  const unsigned int n_steps;
+  unsigned int work_B = 0;
+  size_t work_bytes = 0;
+  std::unique_ptr<DeviceBuffer> work;
+};
+
 /** A measurement beside the QoI: not a QoI, its value is a vector of n_out() numbers per chain.  MonteCarloSingleLevel asks it for
  *  one more sample of the state at hand (accumulate) and how many it has taken (samples).  accumulate() adds the sample's values and
  *  their squares to per-chain sums on the device; the means and their errors are host arithmetic on those sums (chain_estimate.hh).
@@ -277,36 +308,37 @@ private:
   const unsigned int n_vertices;
 };
 
-/** The cooling profile of the O(3) sigma model on a lattice, rotated or not (mlmcpi_sigma_level_cooled_charge): per
- *  chain and sample chi_t = Q^2 / n at each of the ascending `depths`, then E / 4 pi at each of them, n_out() = 2 depths.size()
- *  numbers.  The call has no accumulator argument, so a sample's 2 n_depths numbers per chain make one round trip through the host,
- *  where E is divided by 4 pi and the value and its square are added to the per-chain sums. */
-class SigmaCoolingProfile : public CorrelatorMeasurement {
+/** What the cooling and the flow profile share: per chain and sample chi_t = Q^2 / n at each of the ascending `points` (depths
+ *  or step counts), then E / 4 pi at each of them, n_out() = 2 points.size() numbers.  The device calls have no accumulator
+ *  argument, so a sample's 2 n_points numbers per chain make one round trip through the host, where E is divided by 4 pi and the
+ *  value and its square are added to the per-chain sums.  A profile supplies its two ABI calls. */
+class SigmaSmoothingProfile : public CorrelatorMeasurement {
 public:
-  SigmaCoolingProfile(const std::shared_ptr<Lattice2D> lattice, const std::vector<uint32_t> &depths_)
-      : CorrelatorMeasurement("SigmaCoolingProfile", 2 * (unsigned int)depths_.size()),
-        level{lattice->getMt_lat(), lattice->getMx_lat(), lattice->is_rotated() ? 1 : 0, 0.0}, n_vertices(lattice->getNvertices()),
-        depths(depths_) {}
-  const std::vector<uint32_t> &get_depths() const { return depths; }
   /** entry k of the mean over chains; batch >= 2: with the jackknife error over the chains */
   ChainScalar entry(unsigned int k) const {
     return chain_jackknife(chain_means(), [](const std::vector<double> &v) { return v[0]; }, k, 1);
   }
 
 protected:
+  SigmaSmoothingProfile(const char *name_, const std::shared_ptr<Lattice2D> lattice, const std::vector<uint32_t> &points_)
+      : CorrelatorMeasurement(name_, 2 * (unsigned int)points_.size()),
+        level{lattice->getMt_lat(), lattice->getMx_lat(), lattice->is_rotated() ? 1 : 0, 0.0}, n_vertices(lattice->getNvertices()),
+        points(points_), name(name_) {}
+  /** bytes of the device call's own workspace */
+  virtual void call_workspace_bytes(unsigned int batch, size_t *bytes) const = 0;
+  /** d_chi, d_e [batch][points.size()] of the states d_state */
+  virtual void measure(const double *d_state, unsigned int batch, double *d_chi, double *d_e, void *d_work, size_t work_bytes) const = 0;
   void check_size(unsigned int n) const override {
-    if (n != 2 * n_vertices) fatal("Evaluating SigmaCoolingProfile on state of wrong size.");
+    if (n != 2 * n_vertices) fatal("Evaluating " + name + " on state of wrong size.");
   }
   void workspace_bytes(unsigned int batch, size_t *bytes) const override {
-    check(mlmcpi_sigma_level_cooling_workspace_bytes(&level, batch, bytes), "sigma_level_cooling_workspace_bytes");
+    call_workspace_bytes(batch, bytes);
     *bytes += raw_bytes(batch);
   }
   void run(const double *d_state, unsigned int batch, double *d_out, double *d_acc, void *d_work, size_t work_bytes) const override {
-    const size_t nd = depths.size(), raw = raw_bytes(batch), count = (size_t)batch * nd;
+    const size_t nd = points.size(), raw = raw_bytes(batch), count = (size_t)batch * nd;
     double *d_chi = (double *)((char *)d_work + (work_bytes - raw)), *d_e = d_chi + count;
-    check(mlmcpi_sigma_level_cooled_charge(&level, d_state, batch, depths.data(), (uint32_t)nd, nullptr, d_chi, d_e, nullptr, d_work,
-                                           work_bytes - raw, nullptr),
-          "sigma_level_cooled_charge");
+    measure(d_state, batch, d_chi, d_e, d_work, work_bytes - raw);
     std::vector<double> h(2 * count), v(2 * count);
     check(mlmcpi_copy_d2h(h.data(), d_chi, 2 * count * sizeof(double), nullptr), "copy_d2h");
     const double four_pi = 4.0 * std::acos(-1.0);
@@ -326,12 +358,74 @@ protected:
       check(mlmcpi_copy_h2d(d_acc, a.data(), a.size() * sizeof(double), nullptr), "copy_h2d");
     }
   }
-
-private:
-  size_t raw_bytes(unsigned int batch) const { return (2 * (size_t)batch * depths.size() * sizeof(double) + 255) & ~(size_t)255; }
   const mlmcpi_sigma_level level;
   const unsigned int n_vertices;
-  const std::vector<uint32_t> depths;
+  const std::vector<uint32_t> points;
+
+private:
+  size_t raw_bytes(unsigned int batch) const { return (2 * (size_t)batch * points.size() * sizeof(double) + 255) & ~(size_t)255; }
+  const std::string name;
+};
+
+/** The cooling profile of the O(3) sigma model on a lattice, rotated or not (mlmcpi_sigma_level_cooled_charge): chi_t
+ *  and E / 4 pi at each of the ascending `depths` (SigmaSmoothingProfile). */
+class SigmaCoolingProfile : public SigmaSmoothingProfile {
+public:
+  SigmaCoolingProfile(const std::shared_ptr<Lattice2D> lattice, const std::vector<uint32_t> &depths_)
+      : SigmaSmoothingProfile("SigmaCoolingProfile", lattice, depths_) {}
+  const std::vector<uint32_t> &get_depths() const { return points; }
+
+protected:
+  void call_workspace_bytes(unsigned int batch, size_t *bytes) const override {
+    check(mlmcpi_sigma_level_cooling_workspace_bytes(&level, batch, bytes), "sigma_level_cooling_workspace_bytes");
+  }
+  void measure(const double *d_state, unsigned int batch, double *d_chi, double *d_e, void *d_work, size_t work_bytes) const override {
+    check(mlmcpi_sigma_level_cooled_charge(&level, d_state, batch, points.data(), (uint32_t)points.size(), nullptr, d_chi, d_e, nullptr,
+                                           d_work, work_bytes, nullptr),
+          "sigma_level_cooled_charge");
+  }
+};
+
+/** The flow profile of the O(3) sigma model on a lattice, rotated or not (mlmcpi_sigma_level_flowed_charge): chi_t
+ *  and E / 4 pi at each of the ascending step counts `steps` of size eps, flow time t = steps[k] eps (SigmaSmoothingProfile).  The
+ *  dimensionless t <E> / n and the reference scale at which it reaches c (correlator.hh flow_scale) are host arithmetic on the
+ *  per-chain means. */
+class SigmaFlowProfile : public SigmaSmoothingProfile {
+public:
+  SigmaFlowProfile(const std::shared_ptr<Lattice2D> lattice, double eps_, const std::vector<uint32_t> &steps_)
+      : SigmaSmoothingProfile("SigmaFlowProfile", lattice, steps_), eps(eps_) {}
+  const std::vector<uint32_t> &get_steps() const { return points; }
+  double time(unsigned int k) const { return points[k] * eps; }
+  /** t <E> / n at step count k of the list; batch >= 2: with the jackknife error over the chains */
+  ChainScalar t_energy(unsigned int k) const {
+    const double f = time(k) * 4.0 * std::acos(-1.0) / n_vertices;  // the entries hold E / 4 pi
+    return chain_jackknife(chain_means(), [f](const std::vector<double> &v) { return f * v[0]; }, points.size() + k, 1);
+  }
+  /** the flow time at which t <E> / n = c (flow_scale; NaN where the listed times do not bracket c), jackknife over the chains */
+  ChainScalar scale(double c) const {
+    const size_t nd = points.size();
+    std::vector<double> times(nd);
+    for (size_t k = 0; k < nd; ++k) times[k] = time((unsigned int)k);
+    const double four_pi_n = 4.0 * std::acos(-1.0) / n_vertices;
+    return chain_jackknife(chain_means(), [&](const std::vector<double> &v) {
+      std::vector<double> tE(nd);
+      for (size_t k = 0; k < nd; ++k) tE[k] = times[k] * four_pi_n * v[k];
+      return flow_scale(times, tE, c);
+    }, nd, nd);
+  }
+
+protected:
+  void call_workspace_bytes(unsigned int batch, size_t *bytes) const override {
+    check(mlmcpi_sigma_level_flow_workspace_bytes(&level, batch, bytes), "sigma_level_flow_workspace_bytes");
+  }
+  void measure(const double *d_state, unsigned int batch, double *d_chi, double *d_e, void *d_work, size_t work_bytes) const override {
+    check(mlmcpi_sigma_level_flowed_charge(&level, d_state, batch, eps, points.data(), (uint32_t)points.size(), nullptr, d_chi, d_e, nullptr,
+                                           d_work, work_bytes, nullptr),
+          "sigma_level_flowed_charge");
+  }
+
+private:
+  const double eps;
 };
 
 /** The time correlator C(tau), tau = 0 .. n_lag - 1, of a 1-D path action (mlmcpi_path_correlator; definitions in

@@ -67,6 +67,8 @@
  *         the edge by tests/test_sigma_topology_gpu.py)                                                      workgroups)
  *       mlmcpi_sigma_level_cooled_charge (n_chains; run at the edge by                 linear index, x then y unbounded (2^23 x 65535
  *         tests/test_sigma_cooling_gpu.py)                                                                   workgroups)
+ *       mlmcpi_sigma_level_flowed_charge (n_chains; run at the edge by                 linear index, x then y unbounded (2^23 x 65535
+ *         tests/test_sigma_flow_gpu.py)                                                                      workgroups)
  *       mlmcpi_stats_accumulate, mlmcpi_stats_window_record                            grid x, 256 per wg    unbounded
  */
 #ifndef MLMCPI_HIP_H
@@ -736,6 +738,45 @@ int mlmcpi_sigma_level_cooled_charge(const mlmcpi_sigma_level *level, const doub
                                      double *d_cooled /* may be NULL */, void *d_work, size_t work_bytes, void *stream);
 int mlmcpi_sigma_level_cooling_plan(const mlmcpi_sigma_level *level, uint32_t n_chains, const uint32_t *depths, uint32_t n_depths,
                                     mlmcpi_sigma_cooling_plan *plan);
+/* Gradient flow on a level and the flowed charge (sigma_flow.hip); `beta` is ignored.  With F(Y)_l = Delta_l -
+ * (Y_l . Delta_l) Y_l, Delta_l = add4 of the four neighbours' Y in the order of mlmcpi_sigma_level_sweep_draw and the dot product
+ * (x x' + y y') + z z', one step of size eps is the 2N-storage third-order Runge-Kutta scheme, on ALL sites from the previous
+ * stage's Y, starting from A = 0, Y = sigma:  A <- a_i A + eps F(Y), Y <- Y + b_i A, i = 1, 2, 3, a = (0, -17/32, -32/27), b =
+ * (1/4, 8/9, 3/4); then sigma <- Y / |Y|, |Y| = sqrt((x^2 + y^2) + z^2), three divisions.  Stage values are not normalised.
+ * Step count s is the field after s steps, flow time t = s eps, starting from sigma_of(d_state); between steps the field lives
+ * as unit vectors and is never converted back to angles.  For every s = steps[k], d_q, d_chi and d_energy [n_chains][n_steps]
+ * are Q_s, Q_s^2 / n and E_s as in mlmcpi_sigma_level_cooled_charge (any may be NULL, not all); d_flowed (may be NULL)
+ * [n_chains][2 n]: the angles of the field at the LAST step count.  steps (HOST memory) is strictly ascending, may start at 0,
+ * 1 <= n_steps <= MLMCPI_SIGMA_FLOW_MAX_TIMES, last entry <= MLMCPI_SIGMA_FLOW_MAX_STEPS; eps is finite, 0 < eps <= 0.25 (the
+ * energy never rose for eps <= 0.3 and blew up at 0.4).  d_state is read once and never written.  d_work:
+ * _flow_workspace_bytes(level, n_chains) bytes, 256-byte aligned, content at entry ignored, the layout of cooling's workspace.
+ * A stage update is a function of the stored Y and A of the site and the stored Y of four neighbours, and every sum is taken in
+ * an order fixed by the level alone, without atomics: a chain's Q_s, chi_s, E_s and flowed state are the same bits under every
+ * MLMCPI_SIGMA_FLOW_PLAN=TWxTHxNTxK (tile, workgroup size, steps fused per launch; a launch never runs past the next listed step
+ * count), every n_chains, split of the chains over calls and stream, every choice of outputs and EVERY STEP LIST CONTAINING s;
+ * Q_0 and chi_0 are the bits of mlmcpi_sigma_level_topological_charge.  Any n_chains runs (CHAINS PER CALL above).
+ * MLMCPI_ERR_INVALID, with nothing launched: NULL level, d_state, steps or d_work; d_q, d_chi and d_energy all NULL; odd or zero
+ * extents, Mt Mx > 2^30; n_chains = 0; eps outside (0, 0.25] or not finite; n_steps outside 1 .. 32; steps not strictly
+ * ascending or beyond 4096; work_bytes below the query; more workgroups in a launch than the grid holds.
+ * _flow_plan (host only, touches no device) reports the launches of such a call and returns the status the call would for the
+ * arguments it sees. */
+#define MLMCPI_SIGMA_FLOW_MAX_TIMES 32
+#define MLMCPI_SIGMA_FLOW_MAX_STEPS 4096
+typedef struct mlmcpi_sigma_flow_plan {
+  uint32_t tw, th, nt, fuse;  /* tile (plain: vertices, rotated: plane cells; never larger than the plane), workgroup size, steps per launch at most */
+  uint32_t tiles;             /* flow workgroups per chain and launch */
+  uint32_t lds_bytes;         /* LDS image of the deepest launch: (tw + 6 K)(th + 6 K) x 72 B (rotated: 144 B) */
+  uint32_t n_launches;        /* flow launches of the call */
+  uint32_t n_measurements;    /* = n_steps */
+  uint8_t launch_steps[MLMCPI_SIGMA_FLOW_MAX_STEPS]; /* [n_launches] steps of each; they sum to the last step count, none crosses a listed one */
+} mlmcpi_sigma_flow_plan;
+int mlmcpi_sigma_level_flow_workspace_bytes(const mlmcpi_sigma_level *level, uint32_t n_chains, size_t *bytes);
+int mlmcpi_sigma_level_flowed_charge(const mlmcpi_sigma_level *level, const double *d_state, uint32_t n_chains, double eps,
+                                     const uint32_t *steps /* host */, uint32_t n_steps, double *d_q /* may be NULL */,
+                                     double *d_chi /* may be NULL */, double *d_energy /* may be NULL */,
+                                     double *d_flowed /* may be NULL */, void *d_work, size_t work_bytes, void *stream);
+int mlmcpi_sigma_level_flow_plan(const mlmcpi_sigma_level *level, uint32_t n_chains, double eps, const uint32_t *steps,
+                                 uint32_t n_steps, mlmcpi_sigma_flow_plan *plan);
 /* The Wolff single-cluster update on a level (sigma_cluster.hip): n_updates updates of every chain of
  * d_state [B][2 n], in place.  Unrotated: mlmcpi_sigma_cluster_* on (Mt, Mx, beta), the same bits.  Rotated: the level is
  * bipartite, every link has one E end; its 2 n links are (e, d), e an E vertex (e < n / 2), d its direction in the order above;

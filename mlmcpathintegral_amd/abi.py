@@ -91,6 +91,12 @@ class SigmaCoolingPlan(C.Structure):
         ("launch_sweeps", C.c_uint8 * 4096)]
 
 
+class SigmaFlowPlan(C.Structure):
+    """mlmcpi_sigma_flow_plan"""
+    _fields_ = [(n, C.c_uint32) for n in ("tw", "th", "nt", "fuse", "tiles", "lds_bytes", "n_launches", "n_measurements")] + [
+        ("launch_steps", C.c_uint8 * 4096)]
+
+
 _vp, _u32, _u64, _i, _d, _sz = C.c_void_p, C.c_uint32, C.c_uint64, C.c_int, C.c_double, C.c_size_t
 _PA, _LA = C.POINTER(PathAction), C.POINTER(LatticeAction)
 _SL = C.POINTER(SigmaLevel)
@@ -216,6 +222,9 @@ SIGNATURES = {
     "mlmcpi_sigma_level_cooling_workspace_bytes": (_i, [_SL, _u32, C.POINTER(_sz)]),
     "mlmcpi_sigma_level_cooled_charge": (_i, [_SL, _vp, _u32, C.POINTER(_u32), _u32, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
     "mlmcpi_sigma_level_cooling_plan": (_i, [_SL, _u32, C.POINTER(_u32), _u32, C.POINTER(SigmaCoolingPlan)]),
+    "mlmcpi_sigma_level_flow_workspace_bytes": (_i, [_SL, _u32, C.POINTER(_sz)]),
+    "mlmcpi_sigma_level_flowed_charge": (_i, [_SL, _vp, _u32, _d, C.POINTER(_u32), _u32, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "mlmcpi_sigma_level_flow_plan": (_i, [_SL, _u32, _d, C.POINTER(_u32), _u32, C.POINTER(SigmaFlowPlan)]),
     "mlmcpi_sigma_level_sweep_draw": (_i, [_SL, _vp, _vp, _u32, _u32, _u32, _u64, _u32, _u32, _vp]),
     "mlmcpi_sigma_level_copy_from_fine": (_i, [_SL, _vp, _vp, _u32, _vp]),
     "mlmcpi_sigma_level_copy_from_coarse": (_i, [_SL, _vp, _vp, _u32, _vp]),

@@ -67,7 +67,8 @@ struct Tuning {
   uint32_t sigma_sw_tile_w = 0, sigma_sw_tile_h = 0;  // MLMCPI_SIGMA_SW_TILE=WxH: tile of its tiled plan, W, H in {8, 16, 32, 64} (0: 64x32 vertices; on a rotated level: 32x32 cells)
   uint32_t sigma_level_tw = 0, sigma_level_th = 0, sigma_level_nt = 0, sigma_level_fuse = 0;  // MLMCPI_SIGMA_LEVEL_PLAN=TWxTHxNTxK: rotated sigma sweep (0: 32x32x512x2)
   uint32_t sigma_cool_tw = 0, sigma_cool_th = 0, sigma_cool_nt = 0, sigma_cool_fuse = 0;  // MLMCPI_SIGMA_COOL_PLAN=TWxTHxNTxK: sigma cooling, plain and rotated levels (0: 32x32x512x2)
-  uint32_t sigma_twolevel_groups = 0;             // MLMCPI_SIGMA_TWOLEVEL_GROUPS=g: groups of 256 vertices per workgroup of the sigma two-level pass (0: 1)
+  uint32_t sigma_flow_tw = 0, sigma_flow_th = 0, sigma_flow_nt = 0, sigma_flow_fuse = 0;  // MLMCPI_SIGMA_FLOW_PLAN=TWxTHxNTxK: sigma gradient flow, plain and rotated levels (0: 16x16x512x1)
+  uint32_t sigma_twolevel_groups = 0;            // MLMCPI_SIGMA_TWOLEVEL_GROUPS=g: groups of 256 vertices per workgroup of the sigma two-level pass (0: 1)
 };
 Tuning tuning();  // a copy taken under the lock: callers snapshot it once per call
 

@@ -100,6 +100,19 @@ const Option kOptions[] = {
     }
     return false;
   }},
+  {"MLMCPI_SIGMA_FLOW_PLAN", [](Tuning &t, const std::string &v) {  // the LDS image of a rotated level (halo 3 K cells, 144 B) and of a plain one (halo 3 K vertices, 72 B)
+    unsigned a = 0, b = 0, c = 0, k = 0;
+    char rest = 0;
+    t.sigma_flow_tw = t.sigma_flow_th = t.sigma_flow_nt = t.sigma_flow_fuse = 0;
+    if (v.empty()) return true;
+    if (sscanf(v.c_str(), "%ux%ux%ux%u%c", &a, &b, &c, &k, &rest) == 4 && a >= 1 && a <= 128 && b >= 1 && b <= 128 &&
+        (c == 256 || c == 512 || c == 1024) && k >= 1 && k <= kMaxFuse && (size_t)(a + 6 * k) * (b + 6 * k) * 144 <= kSigmaLdsMax &&
+        (size_t)(a + 6 * k) * (b + 6 * k) * 72 <= kSigmaLdsMax) {
+      t.sigma_flow_tw = a; t.sigma_flow_th = b; t.sigma_flow_nt = c; t.sigma_flow_fuse = k;
+      return true;
+    }
+    return false;
+  }},
   {"MLMCPI_SIGMA_TWOLEVEL_GROUPS", [](Tuning &t, const std::string &v) {
     unsigned g = 0;
     char rest = 0;

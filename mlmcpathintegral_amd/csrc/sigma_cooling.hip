@@ -25,7 +25,7 @@
 // No atomics; workgroups of every launch ride one linear index over grid x and then y (topo_grid).
 #include "internal.hpp"
 
-#include "sigma_topology_device.hpp"  // the face code; fp contraction is off from here on
+#include "sigma_field_device.hpp"  // the field's layout and the face code; fp contraction is off from here on
 
 namespace mlmcpi {
 
@@ -34,15 +34,6 @@ __device__ __forceinline__ V3 sigma_cool(const V3 &sig, const V3 &Dl) {
   if (!(n2 > 0.0)) return sig;
   const double nrm = sqrt(n2);
   return V3{Dl.x / nrm, Dl.y / nrm, Dl.z / nrm};
-}
-
-// vertex l of a chain's buffer v[3][n]
-__device__ __forceinline__ V3 cool_fetch(const double *v, uint32_t n, size_t l) { return V3{v[l], v[n + l], v[2 * (size_t)n + l]}; }
-
-__device__ __forceinline__ void cool_store(double *v, uint32_t n, size_t l, const V3 &s) {
-  v[l] = s.x;
-  v[n + l] = s.y;
-  v[2 * (size_t)n + l] = s.z;
 }
 
 // workgroup (chain, group g of 256 vertices): depth 0 of the field
@@ -234,6 +225,51 @@ __global__ void __launch_bounds__(kGroup)
   }
 }
 
+// ---- what the gradient flow shares (sigma_field_device.hpp) ---------------------------------------------------------------------
+CoolWork cool_work(const SigmaLevel &L, uint32_t n_chains) {
+  CoolWork w;
+  w.ngroups = (L.nvert() + kGroup - 1) / kGroup;
+  w.vec = align256((size_t)n_chains * 3 * L.nvert() * sizeof(double));
+  w.part_q = align256((size_t)n_chains * topo_plan(L).tiles * sizeof(double));
+  w.part_e = align256((size_t)n_chains * w.ngroups * sizeof(double));
+  w.total = 2 * w.vec + w.part_q + w.part_e;
+  return w;
+}
+
+int cool_stage(const SigmaLevel &L, const CoolWork &w, uint32_t n_chains, const double *d_state, double *vec, hipStream_t st) {
+  const uint64_t vblocks = (uint64_t)n_chains * w.ngroups;
+  hipLaunchKernelGGL(sigma_cool_stage_kernel, topo_grid(vblocks), dim3(kGroup), 0, st, L.nvert(), w.ngroups, vblocks, (const double2 *)d_state, vec);
+  MLMCPI_LAUNCH_CHECK("sigma_cool_stage_kernel");
+  return MLMCPI_OK;
+}
+
+int cool_measure(const SigmaLevel &L, const CoolWork &w, uint32_t n_chains, const double *vec, double *part_q, double *part_e,
+                 uint32_t n_cols, uint32_t k, double *d_q, double *d_chi, double *d_energy, hipStream_t st) {
+  const TopoPlan G = topo_plan(L);
+  const uint64_t vblocks = (uint64_t)n_chains * w.ngroups, qblocks = (uint64_t)n_chains * G.tiles;
+  if (d_q || d_chi) {
+    if (L.rot) hipLaunchKernelGGL(sigma_cool_charge_kernel<1>, topo_grid(qblocks), dim3(kTopoThreads), 0, st, G, qblocks, vec, part_q);
+    else hipLaunchKernelGGL(sigma_cool_charge_kernel<0>, topo_grid(qblocks), dim3(kTopoThreads), 0, st, G, qblocks, vec, part_q);
+    MLMCPI_LAUNCH_CHECK("sigma_cool_charge_kernel");
+  }
+  if (d_energy) {
+    if (L.rot) hipLaunchKernelGGL(sigma_cool_energy_kernel<1>, topo_grid(vblocks), dim3(kGroup), 0, st, L, w.ngroups, vblocks, vec, part_e);
+    else hipLaunchKernelGGL(sigma_cool_energy_kernel<0>, topo_grid(vblocks), dim3(kGroup), 0, st, L, w.ngroups, vblocks, vec, part_e);
+    MLMCPI_LAUNCH_CHECK("sigma_cool_energy_kernel");
+  }
+  hipLaunchKernelGGL(sigma_cool_finish_kernel, topo_grid(n_chains), dim3(kGroup), 0, st, (const double *)part_q, G.tiles, (const double *)part_e,
+                     w.ngroups, (uint64_t)n_chains, (double)L.nvert(), n_cols, k, d_q, d_chi, d_energy);
+  MLMCPI_LAUNCH_CHECK("sigma_cool_finish_kernel");
+  return MLMCPI_OK;
+}
+
+int cool_angles(const SigmaLevel &L, const CoolWork &w, uint32_t n_chains, const double *vec, double *d_out, hipStream_t st) {
+  const uint64_t vblocks = (uint64_t)n_chains * w.ngroups;
+  hipLaunchKernelGGL(sigma_cool_angles_kernel, topo_grid(vblocks), dim3(kGroup), 0, st, L.nvert(), w.ngroups, vblocks, vec, (double2 *)d_out);
+  MLMCPI_LAUNCH_CHECK("sigma_cool_angles_kernel");
+  return MLMCPI_OK;
+}
+
 namespace {
 
 struct CoolPlan {
@@ -256,21 +292,6 @@ CoolPlan cool_plan(const SigmaLevel &L, const Tuning &t) {
 inline size_t cool_lds(const SigmaLevel &L, const CoolPlan &p, uint32_t K) {
   const uint32_t H = L.rot ? K : 2 * K;
   return (size_t)(p.tw + 2 * H) * (p.th + 2 * H) * (L.rot ? 6 : 3) * sizeof(double);
-}
-
-struct CoolWork {
-  size_t vec, part_q, part_e, total;  // bytes of one vector buffer, of the charge partials, of the energy partials
-  uint32_t ngroups;
-};
-
-CoolWork cool_work(const SigmaLevel &L, uint32_t n_chains) {
-  CoolWork w;
-  w.ngroups = (L.nvert() + kGroup - 1) / kGroup;
-  w.vec = align256((size_t)n_chains * 3 * L.nvert() * sizeof(double));
-  w.part_q = align256((size_t)n_chains * topo_plan(L).tiles * sizeof(double));
-  w.part_e = align256((size_t)n_chains * w.ngroups * sizeof(double));
-  w.total = 2 * w.vec + w.part_q + w.part_e;
-  return w;
 }
 
 // what the call and its plan query refuse alike; the plan (one snapshot of the knobs per call) comes back through `plan`.  Its LDS
@@ -374,15 +395,12 @@ int mlmcpi_sigma_level_cooled_charge(const mlmcpi_sigma_level *level, const doub
   const CoolWork w = cool_work(L, n_chains);
   MLMCPI_REQUIRE(work_bytes >= w.total, "the cooling workspace is too small: %zu bytes given, %zu needed", work_bytes, w.total);
   if (int rc = cool_init_kernels()) return rc;
-  const TopoPlan G = topo_plan(L);
   hipStream_t st = as_stream(stream);
-  const uint32_t n = L.nvert();
   double *cur = (double *)d_work, *other = (double *)((char *)d_work + w.vec);
   double *part_q = (double *)((char *)d_work + 2 * w.vec), *part_e = (double *)((char *)d_work + 2 * w.vec + w.part_q);
-  const uint64_t vblocks = (uint64_t)n_chains * w.ngroups, cblocks = (uint64_t)n_chains * p.tiles, qblocks = (uint64_t)n_chains * G.tiles;
+  const uint64_t cblocks = (uint64_t)n_chains * p.tiles;
 
-  hipLaunchKernelGGL(sigma_cool_stage_kernel, topo_grid(vblocks), dim3(kGroup), 0, st, n, w.ngroups, vblocks, (const double2 *)d_state, cur);
-  MLMCPI_LAUNCH_CHECK("sigma_cool_stage_kernel");
+  if (int rc = cool_stage(L, w, n_chains, d_state, cur, st)) return rc;
   uint32_t done = 0;
   for (uint32_t k = 0; k < n_depths; ++k) {
     while (done < depths[k]) {
@@ -393,24 +411,10 @@ int mlmcpi_sigma_level_cooled_charge(const mlmcpi_sigma_level *level, const doub
       other = t;
       done += K;
     }
-    if (d_q || d_chi) {
-      if (L.rot) hipLaunchKernelGGL(sigma_cool_charge_kernel<1>, topo_grid(qblocks), dim3(kTopoThreads), 0, st, G, qblocks, (const double *)cur, part_q);
-      else hipLaunchKernelGGL(sigma_cool_charge_kernel<0>, topo_grid(qblocks), dim3(kTopoThreads), 0, st, G, qblocks, (const double *)cur, part_q);
-      MLMCPI_LAUNCH_CHECK("sigma_cool_charge_kernel");
-    }
-    if (d_energy) {
-      if (L.rot) hipLaunchKernelGGL(sigma_cool_energy_kernel<1>, topo_grid(vblocks), dim3(kGroup), 0, st, L, w.ngroups, vblocks, (const double *)cur, part_e);
-      else hipLaunchKernelGGL(sigma_cool_energy_kernel<0>, topo_grid(vblocks), dim3(kGroup), 0, st, L, w.ngroups, vblocks, (const double *)cur, part_e);
-      MLMCPI_LAUNCH_CHECK("sigma_cool_energy_kernel");
-    }
-    hipLaunchKernelGGL(sigma_cool_finish_kernel, topo_grid(n_chains), dim3(kGroup), 0, st, (const double *)part_q, G.tiles, (const double *)part_e,
-                       w.ngroups, (uint64_t)n_chains, (double)n, n_depths, k, d_q, d_chi, d_energy);
-    MLMCPI_LAUNCH_CHECK("sigma_cool_finish_kernel");
+    if (int rc = cool_measure(L, w, n_chains, cur, part_q, part_e, n_depths, k, d_q, d_chi, d_energy, st)) return rc;
   }
-  if (d_cooled) {
-    hipLaunchKernelGGL(sigma_cool_angles_kernel, topo_grid(vblocks), dim3(kGroup), 0, st, n, w.ngroups, vblocks, (const double *)cur, (double2 *)d_cooled);
-    MLMCPI_LAUNCH_CHECK("sigma_cool_angles_kernel");
-  }
+  if (d_cooled)
+    if (int rc = cool_angles(L, w, n_chains, cur, d_cooled, st)) return rc;
   return MLMCPI_OK;
 }
 

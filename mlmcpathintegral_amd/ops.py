@@ -516,6 +516,39 @@ def sigma_level_cooled_charge(level, x, depths, *, energy=False, cooled=False, s
     return (q, chi) + ((e,) if energy else ()) + ((out,) if cooled else ())
 
 
+def sigma_level_flow_workspace(level, B, device="cuda"):
+    """workspace of sigma_level_flowed_charge for B chains (uint8 tensor)"""
+    return _workspace("mlmcpi_sigma_level_flow_workspace_bytes", C.byref(level), B, device=device)
+
+
+def sigma_level_flow_plan(level, B, eps, steps):
+    """the launches mlmcpi_sigma_level_flowed_charge would make (abi.SigmaFlowPlan; host only)"""
+    d = (C.c_uint32 * len(steps))(*steps)
+    plan = abi.SigmaFlowPlan()
+    abi.call("mlmcpi_sigma_level_flow_plan", C.byref(level), B, eps, d, len(steps), C.byref(plan))
+    return plan
+
+
+def sigma_level_flowed_charge(level, x, eps, steps, *, energy=False, flowed=False, stream=None, work=None):
+    """gradient flow of every chain of x [B, 2 n] on a level, rotated or not, in steps of size eps (0 < eps <= 0.25), measured at
+    the ascending list `steps` of step counts, flow time t = s eps (mlmcpi_sigma_level_flowed_charge; x is not written): returns
+    (Q [B, n_steps], chi = Q^2 / n [B, n_steps]), then with energy=True the bond energy E [B, n_steps] and with flowed=True the
+    angles [B, 2 n] of the field at the last step count.  Runs, and allocates, on `stream` (a torch.cuda.Stream; default: the
+    current one)."""
+    _check_state(x, sigma_level_size(level))
+    B, nd = x.shape[0], len(steps)
+    d = (C.c_uint32 * nd)(*steps)
+    with torch.cuda.stream(stream if stream is not None else torch.cuda.current_stream()):
+        if work is None:
+            work = sigma_level_flow_workspace(level, B, x.device)
+        q, chi = _f64(B, nd, x), _f64(B, nd, x)
+        e = _f64(B, nd, x) if energy else None
+        out = torch.empty_like(x) if flowed else None
+        abi.call("mlmcpi_sigma_level_flowed_charge", C.byref(level), _p(x), B, eps, d, nd, _p(q), _p(chi), _p(e), _p(out), _p(work),
+                 work.numel(), _stream())
+    return (q, chi) + ((e,) if energy else ()) + ((out,) if flowed else ())
+
+
 def sigma_level_correlator_size(level):
     """n_out = (Mt/2 + 1) + (Mx/2 + 1): the lags of C_t, then those of C_x"""
     n = C.c_uint32(0)
