@@ -175,78 +175,85 @@ __device__ __forceinline__ void perm_build_rows(const PP &P, double *plane, cons
 }
 
 // The tasks of a half and who takes them.  A task is a column pair (mu = 0: rows r, r + 1 of column c) or a row pair
-// (mu = 1: columns c, c + 1 of row r), coordinates inside the half.  r05: whole WAVES take whole rows -- wave-task m of a
-// half is, for m < HR / 2, the mu = 0 tasks of row pair m in columns 0 .. 63 (lane l: the even columns on lanes 0 .. 31,
-// the odd ones on 32 .. 63: a 32-lane group of a gather read stays inside one quadrant of the plane, contiguous banks),
-// and for m >= HR / 2 the mu = 1 tasks of rows 2 (m - HR / 2) + (l >> 5) in column pairs l & 31; wave w takes m = w, w + NW,
-// ... (slot k: m = w + NW k).  The kind of a slot and the row of its tasks are then wave-uniform and the column of a lane
-// is the same in every slot: what was ~65 vector instructions of index arithmetic per task in the three places that need
-// coordinates (own angles, gather, image) is scalar work plus a few additions.  The columns beyond 64 of the 68-wide
-// output of the fused launch (4 x HR / 2 mu = 0 tasks, 2 x HR mu = 1 tasks) are left-over wave-tasks of one kind each, in
-// the last slot of waves that have no main task there.  Which lane computes a task does not enter its result.
+// (mu = 1: columns c, c + 1 of row r), coordinates inside the half.  Whole WAVES take whole rows (r05): a mu = 0 wave-task is
+// the mu = 0 tasks of row pair m in columns 0 .. 63 (lane l: the even columns on lanes 0 .. 31, the odd ones on 32 .. 63: a
+// 32-lane group of a gather read stays inside one quadrant of the plane, contiguous banks), a mu = 1 wave-task the mu = 1
+// tasks of rows 2 m + (l >> 5) in column pairs l & 31; there are H2 = HR / 2 of either kind, m = 0 .. H2 - 1.
+// A wave has ONE kind -- the first half of the waves mu = 0, the second mu = 1 -- and wave j of its kind takes a BLOCK of
+// consecutive m: Q + 1 = H2 / (NW / 2) + 1 of them for j < R = H2 mod (NW / 2), Q for the others, slot k = the block's k-th.
+// So the slots of a mu = 0 thread are consecutive row pairs of ONE column, and the third stream of slot k is the second of
+// slot k + 1 -- the same plaquettes in the same order: perm_sweeps sums it once and hands it down the block.
+// The kind of a wave and the row of a slot are wave-uniform (scalar), slots 0 .. Q - 1 are full in every wave (known at
+// compile time), and the column of a lane is the same in every slot.  The columns beyond 64 of the 68-wide output of the
+// fused launch (4 x HR / 2 mu = 0 tasks, 2 x HR mu = 1 tasks) are left-over wave-tasks in the last slot of the waves of
+// their kind whose block is the shorter one.  Which lane computes a task does not enter its result.
 template <int NT, int RING, int TH = 64>
 struct PermTasks {
   using PG = PermGeom<NT, RING, TH>;
-  static constexpr int OW = PG::OW, HR = PG::HR, H2 = HR / 2, NW = NT / kWave, NS = (HR + NW - 1) / NW;
+  static constexpr int OW = PG::OW, HR = PG::HR, H2 = HR / 2, NW = NT / kWave, NS = PG::NV;
+  static constexpr int NWK = NW / 2, Q = H2 / NWK, R = H2 % NWK;      // waves of a kind; the block: Q + 1 (wave j < R of its kind) or Q slots
   static constexpr int XC = OW - 64;                                   // columns beyond a wave's 64 (0 or 4)
   static constexpr int L0 = XC * H2, L1 = (XC / 2) * HR;               // left-over tasks, mu = 0 and mu = 1
   static constexpr int NL0 = (L0 + 63) / 64, NL1 = (L1 + 63) / 64;     // ... as wave-tasks
-  static constexpr int WF = HR - NW * (NS - 1);                        // the first wave without a main task in slot NS - 1
-  static_assert(PG::NV == NS, "slots per thread");
-  static_assert(NL0 + NL1 <= NW - WF, "the left-over wave-tasks fit the free last slots");
+  static_assert(NW % 2 == 0 && NS == Q + (R > 0 ? 1 : 0), "slots per thread: the longer block");
+  static_assert(XC == 0 || (R > 0 && NL0 <= NWK - R && NL1 <= NWK - R), "the left-over wave-tasks fit the free last slots of their kind");
   uint32_t wave, lane, c_mu0, c_mu1, r_lo;
+  uint32_t j, m0, len;   // wave j of its kind: the wave-tasks m0 .. m0 + len - 1 (scalar)
+  bool kind;             // mu = 1 (scalar)
   __device__ PermTasks() {
     wave = __builtin_amdgcn_readfirstlane(threadIdx.x / kWave);
     lane = threadIdx.x % kWave;
     c_mu0 = lane < 32 ? 2 * lane : 2 * (lane - 32) + 1;
     c_mu1 = 2 * (lane & 31u);
     r_lo = lane >> 5;
+    kind = wave >= (uint32_t)NWK;
+    j = kind ? wave - (uint32_t)NWK : wave;
+    m0 = j * (uint32_t)Q + min(j, (uint32_t)R);
+    len = (uint32_t)Q + (j < (uint32_t)R ? 1u : 0u);
   }
-  // slot k of this thread: false when there is no task in it; mu1 is wave-uniform
-  __device__ __forceinline__ bool task(int k, bool &mu1, uint32_t &r, uint32_t &c) const {
-    const uint32_t m = wave + (uint32_t)(NW * k);
-    mu1 = false; r = 0; c = 0;
-    if (NW * k + NW - 1 < H2 || m < (uint32_t)H2) {            // (the first clause: known at compile time for the early slots)
-      r = 2 * m;
-      c = c_mu0;
-      return true;
-    }
-    if (m < (uint32_t)HR) {
-      mu1 = true;
-      r = 2 * (m - H2) + r_lo;
-      c = c_mu1;
-      return true;
-    }
-    if (XC > 0 && k == NS - 1) {
-      const uint32_t j = wave - (uint32_t)WF;
-      if (j < (uint32_t)NL0) {                                // mu = 0, columns 64 ..: task L = row pair L / XC, column 64 + L % XC
-        const uint32_t L = 64 * j + lane;
+  // f(std::true_type) in the mu = 1 waves, f(std::false_type) in the mu = 0 ones: one scalar branch around all of a wave's slots
+  template <class F>
+  __device__ __forceinline__ void by_kind(F &&f) const {
+    if (kind) f(std::true_type{}); else f(std::false_type{});
+  }
+  // slot k of the block (0 <= k < NS): is there a wave-task in it?  (k < Q: yes, at compile time)
+  __device__ __forceinline__ bool in_block(int k) const { return k < Q || (uint32_t)k < len; }
+  // slot k of this thread, a wave of kind MU1: false when there is no task in it
+  template <bool MU1>
+  __device__ __forceinline__ bool task(int k, uint32_t &r, uint32_t &c) const {
+    if (main_task<MU1>(k, r, c)) return true;
+    return XC > 0 && k == NS - 1 && left_task<MU1>(r, c);
+  }
+  // ... when it is one of the block
+  template <bool MU1>
+  __device__ __forceinline__ bool main_task(int k, uint32_t &r, uint32_t &c) const {
+    r = 0; c = 0;
+    if (!in_block(k)) return false;
+    const uint32_t m = m0 + (uint32_t)k;
+    r = MU1 ? 2 * m + r_lo : 2 * m;
+    c = MU1 ? c_mu1 : c_mu0;
+    return true;
+  }
+  // the left-over task in slot NS - 1, if the thread has one
+  template <bool MU1>
+  __device__ __forceinline__ bool left_task(uint32_t &r, uint32_t &c) const {
+    r = 0; c = 0;
+    if (XC > 0 && !in_block(NS - 1)) {
+      const uint32_t jl = j - (uint32_t)R;
+      if (!MU1 && jl < (uint32_t)NL0) {                       // mu = 0, columns 64 ..: task L = row pair L / XC, column 64 + L % XC
+        const uint32_t L = 64 * jl + lane;
         r = 2 * (L / (XC ? XC : 1));
         c = 64 + L % (XC ? XC : 1);
         return L < (uint32_t)L0;
       }
-      if (j < (uint32_t)(NL0 + NL1)) {                        // mu = 1, column pairs 32 ..: row L / (XC / 2), column 64 + 2 (L % (XC / 2))
-        const uint32_t L = 64 * (j - NL0) + lane;
-        mu1 = true;
+      if (MU1 && jl < (uint32_t)NL1) {                        // mu = 1, column pairs 32 ..: row L / (XC / 2), column 64 + 2 (L % (XC / 2))
+        const uint32_t L = 64 * jl + lane;
         r = L / (XC > 1 ? XC / 2 : 1);
         c = 64 + 2 * (L % (XC > 1 ? XC / 2 : 1));
         return L < (uint32_t)L1;
       }
     }
     return false;
-  }
-  __device__ __forceinline__ bool valid(int k) const {
-    bool mu1; uint32_t r, c;
-    return task(k, mu1, r, c);
-  }
-  __device__ __forceinline__ bool is_mu1(int k) const {
-    bool mu1; uint32_t r, c;
-    task(k, mu1, r, c);
-    return mu1;
-  }
-  __device__ __forceinline__ void coords(int k, uint32_t &r, uint32_t &c) const {
-    bool mu1;
-    task(k, mu1, r, c);
   }
 };
 
@@ -276,6 +283,29 @@ __device__ __forceinline__ void perm_gather1(uint32_t pa, uint32_t px, uint32_t 
   asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(a0), "+v"(x0), "+v"(y0) : : "memory");
   S += a0; X += x0; X2 += y0;
 }
+// ... and of two streams, for a task whose third one the task before it in the block has summed: ten reads, one wait
+template <int STEP>
+__device__ __forceinline__ void perm_gather5(uint32_t pa, uint32_t px2, double &S, double &X2) {
+  double a0 = lds_read_f64<0>(pa), y0 = lds_read_f64<0>(px2);
+  double a1 = lds_read_f64<STEP>(pa), y1 = lds_read_f64<STEP>(px2);
+  double a2 = lds_read_f64<2 * STEP>(pa), y2 = lds_read_f64<2 * STEP>(px2);
+  double a3 = lds_read_f64<3 * STEP>(pa), y3 = lds_read_f64<3 * STEP>(px2);
+  double a4 = lds_read_f64<4 * STEP>(pa), y4 = lds_read_f64<4 * STEP>(px2);
+  asm volatile("s_waitcnt lgkmcnt(0)"
+               : "+v"(a0), "+v"(y0), "+v"(a1), "+v"(y1), "+v"(a2), "+v"(y2), "+v"(a3), "+v"(y3), "+v"(a4), "+v"(y4)
+               :
+               : "memory");
+  S += a0; X2 += y0;
+  S += a1; X2 += y1;
+  S += a2; X2 += y2;
+  S += a3; X2 += y3;
+  S += a4; X2 += y4;
+}
+__device__ __forceinline__ void perm_gather1(uint32_t pa, uint32_t px2, double &S, double &X2) {
+  double a0 = lds_read_f64<0>(pa), y0 = lds_read_f64<0>(px2);
+  asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(a0), "+v"(y0) : : "memory");
+  S += a0; X2 += y0;
+}
 
 // res[h][k] = the new angles of the two links of task k of half h
 template <int NT, int RING, int TH = 64>
@@ -295,19 +325,20 @@ __device__ __forceinline__ void perm_sweeps(double *plane, const double2 *__rest
   auto back = [](uint32_t x, uint32_t h, uint32_t n) { return h <= n ? (x >= h ? x - h : x + n - h) : (x + n - h % n) % n; };
   const uint32_t gi0 = back(i0, H, Mt), gj0 = back(j0, H, Mx);
   const uint32_t oi0 = back(i0, RING, Mt), oj0 = back(j0, RING, Mx);
-  const PermTasks<NT, RING, TH> tasks;
+  using PT = PermTasks<NT, RING, TH>;
+  const PT tasks;
   // the links of a half as they are now (HR, RING, 2 K and the tile origins are even: output parity = plane parity = lattice parity)
   // (32-bit byte offsets from the chain's base pointer -- the host admits lattices of less than 2^28 vertices to these
   // kernels --, wraps by the unsigned-minimum trick: v >= n ? v - n : v = min(v, v - n); twice more for extents below
   // the output window's, a uniform branch.  The 64-bit pointer form this replaces cost 30 vector instructions per task.)
   const char *const src_b = reinterpret_cast<const char *>(src);
   const bool small_lattice = Mx < (uint32_t)(2 * HR + 2) || Mt < (uint32_t)(PG::OW + 2);   // (uniform: two copies of the loop)
-  auto load_theta_of = [&](int h, double2 (&th)[NV], auto small) {
+  auto load_theta_of = [&](int h, double2 (&th)[NV], auto small, auto kind) {
+    constexpr bool MU1 = decltype(kind)::value;
 #pragma unroll
     for (int k = 0; k < NV; ++k) {
-      if (!tasks.valid(k)) continue;
       uint32_t r, c;
-      tasks.coords(k, r, c);
+      if (!tasks.template task<MU1>(k, r, c)) continue;
       uint32_t gr = oj0 + r + h * HR, gc = oi0 + c;
       gr = min(gr, gr - Mx);
       gc = min(gc, gc - Mt);
@@ -316,7 +347,7 @@ __device__ __forceinline__ void perm_sweeps(double *plane, const double2 *__rest
         gc = min(gc, gc - Mt); gc = min(gc, gc - Mt);
       }
       const uint32_t o = (gr * Mt + gc) * 16u;
-      if (!tasks.is_mu1(k)) {
+      if (!MU1) {
         const uint32_t o2 = gr + 1 == Mx ? o - gr * Mt * 16u : o + Mt * 16u;
         th[k] = make_double2(*reinterpret_cast<const double *>(src_b + o), *reinterpret_cast<const double *>(src_b + o2));
       } else {
@@ -325,17 +356,19 @@ __device__ __forceinline__ void perm_sweeps(double *plane, const double2 *__rest
       }
     }
   };
-  auto load_theta = [&](int h, double2 (&th)[NV]) {
-    if (small_lattice) load_theta_of(h, th, std::true_type{}); else load_theta_of(h, th, std::false_type{});
+  auto load_theta = [&](int h, double2 (&th)[NV], auto kind) {
+    if (small_lattice) load_theta_of(h, th, std::true_type{}, kind); else load_theta_of(h, th, std::false_type{}, kind);
   };
-  // what K sweeps add to them
-  auto gather = [&](int h, double2 (&d)[NV]) {
+  // what K sweeps add to them.  In a mu = 0 wave the third stream of slot k - 1 of the block IS the second of slot k -- the
+  // next row pair of the same column: the same address, the same K reads, added in the same order from 0.0 -- so it is
+  // summed once, by slot k - 1, and slot k sums two streams: a block of n row pairs costs 2 n + 1 streams, not 3 n.
+  auto gather = [&](int h, double2 (&d)[NV], auto kind) {
+    constexpr bool MU1 = decltype(kind)::value;
     const uint32_t lds0 = (uint32_t)(uintptr_t)plane;   // the LDS byte address of the plane (lds_read_f64)
-#pragma unroll
-    for (int k = 0; k < NV; ++k) {
-      if (!tasks.valid(k)) continue;
-      uint32_t r, c;
-      tasks.coords(k, r, c);
+    double Xnext = 0.0;                                 // mu = 0: the third stream of the slot before
+    // task (r, c) of slot k; chained: its second stream is Xnext
+    auto one = [&](int k, uint32_t r, uint32_t c, auto chained_t) {
+      constexpr bool chained = decltype(chained_t)::value;
       // the shared stream, the first of the two others and the second, at s = 0 (plane coordinates C = c + 2 K, R = r + h HR + 2 K):
       //   mu = 0 (R even): A_s = P(C + 2 s e_C, R - 1 - 2 s), B_s = P(C + 2 s e_C, R + 2 s), B'_s two rows above B_s;
       //   mu = 1 (C even): D_s = P(C - 1 - 2 s, J_s), J_s = R + 2 (s + 1) e_R, C_s = P(C + 2 s, J_s), C'_s two columns on;
@@ -343,7 +376,7 @@ __device__ __forceinline__ void perm_sweeps(double *plane, const double2 *__rest
       // read set begins at the tasks (PermGeom::col_u, row_v with C = c + 2 K, R = ro + 2 K written out in c and ro)
       const uint32_t ro = r + (uint32_t)(h * HR), cq = c >> 1, rq = ro >> 1;
       uint32_t a, x, x2;
-      if (!tasks.is_mu1(k)) {
+      if (!MU1) {
         const uint32_t cb = (c & 1u) ? PP::QB + ((uint32_t)(PG::OW / 2 - 1) - cq) * 8u : cq * 8u;   // = P.col(C)
         x = cb + rq * (uint32_t)PP::kRow;                                             // row R, even: v = ro / 2
         x2 = x + (uint32_t)PP::kRow;
@@ -358,39 +391,71 @@ __device__ __forceinline__ void perm_sweeps(double *plane, const double2 *__rest
       uint32_t pa = lds0 + a, px = lds0 + x, px2 = lds0 + x2;
       double S = 0.0, X = 0.0, X2 = 0.0;
       uint32_t s = 0;
-      for (; s + 5 <= K; s += 5) {
-        perm_gather5<PP::kStep>(pa, px, px2, S, X, X2);
-        pa += 5 * PP::kStep;
-        px += 5 * PP::kStep;
-        px2 += 5 * PP::kStep;
+      if (chained) {
+        X = Xnext;
+        for (; s + 5 <= K; s += 5) {
+          perm_gather5<PP::kStep>(pa, px2, S, X2);
+          pa += 5 * PP::kStep;
+          px2 += 5 * PP::kStep;
+        }
+        for (; s < K; ++s) {
+          perm_gather1(pa, px2, S, X2);
+          pa += PP::kStep;
+          px2 += PP::kStep;
+        }
+      } else {
+        for (; s + 5 <= K; s += 5) {
+          perm_gather5<PP::kStep>(pa, px, px2, S, X, X2);
+          pa += 5 * PP::kStep;
+          px += 5 * PP::kStep;
+          px2 += 5 * PP::kStep;
+        }
+        for (; s < K; ++s) {
+          perm_gather1(pa, px, px2, S, X, X2);
+          pa += PP::kStep;
+          px += PP::kStep;
+          px2 += PP::kStep;
+        }
       }
-      for (; s < K; ++s) {
-        perm_gather1(pa, px, px2, S, X, X2);
-        pa += PP::kStep;
-        px += PP::kStep;
-        px2 += PP::kStep;
-      }
-      d[k] = tasks.is_mu1(k) ? make_double2(X - S, X2 - S) : make_double2(S - X, S - X2);
+      Xnext = X2;
+      double2 dk = MU1 ? make_double2(X - S, X2 - S) : make_double2(S - X, S - X2);
+      // (the differences HERE: moved behind the last task by the scheduler, every task kept three sums live instead of two
+      // differences, and the fused launch spilled)
+      asm volatile("" : "+v"(dk.x), "+v"(dk.y));
+      d[k] = dk;
+    };
+    // the left-over wave-task first, while few results are live (it takes all three streams), then the block in order
+    uint32_t r, c;
+    if (PT::XC > 0)
+      if (tasks.template left_task<MU1>(r, c)) one(NV - 1, r, c, std::false_type{});
+#pragma unroll
+    for (int k = 0; k < NV; ++k) {
+      if (!tasks.template main_task<MU1>(k, r, c)) continue;   // (scalar; k < Q: at compile time)
+      if (!MU1 && k > 0) one(k, r, c, std::true_type{}); else one(k, r, c, std::false_type{});
     }
   };
-  auto finish = [&](const double2 (&th)[NV], double2 (&d)[NV]) {
+  auto finish = [&](const double2 (&th)[NV], double2 (&d)[NV], auto kind) {
 #pragma unroll
-    for (int k = 0; k < NV; ++k)
-      if (tasks.valid(k)) d[k] = make_double2(mod_2pi_fast(th[k].x + d[k].x), mod_2pi_fast(th[k].y + d[k].y));
+    for (int k = 0; k < NV; ++k) {
+      uint32_t r, c;
+      if (tasks.template task<decltype(kind)::value>(k, r, c)) d[k] = make_double2(mod_2pi_fast(th[k].x + d[k].x), mod_2pi_fast(th[k].y + d[k].y));
+    }
   };
 
   perm_build_rows<NT, U, MLMCPI_PERM_U == 0>(P, plane, src, Mt, Mx, gi0, gj0, W, rows);
   // one plane: first half (its angles are in flight across the barrier and the first reads of the plane), second half
   double2 th[NV];
-  load_theta(0, th);
+  tasks.by_kind([&](auto kind) { load_theta(0, th, kind); });
   __syncthreads();
   MLMCPI_STAMP(1);  // plane built
-  gather(0, res[0]);
-  finish(th, res[0]);
-  MLMCPI_STAMP(2);  // first half gathered
-  load_theta(1, th);
-  gather(1, res[1]);
-  finish(th, res[1]);
+  tasks.by_kind([&](auto kind) {
+    gather(0, res[0], kind);
+    finish(th, res[0], kind);
+    MLMCPI_STAMP(2);  // first half gathered
+    load_theta(1, th, kind);
+    gather(1, res[1], kind);
+    finish(th, res[1], kind);
+  });
 }
 
 // the angles of perm_sweeps into the planes th0, th1 of an OW x 2 HR image (the caller puts barriers around it)
@@ -399,22 +464,24 @@ __device__ __forceinline__ void perm_store_image(double *th0, double *th1, const
   using PG = PermGeom<NT, RING, TH>;
   constexpr int OW = PG::OW, HR = PG::HR, NV = PG::NV;
   const PermTasks<NT, RING, TH> tasks;
+  tasks.by_kind([&](auto kind) {
+    constexpr bool MU1 = decltype(kind)::value;
 #pragma unroll
-  for (int h = 0; h < 2; ++h)
+    for (int h = 0; h < 2; ++h)
 #pragma unroll
-    for (int k = 0; k < NV; ++k) {
-      if (!tasks.valid(k)) continue;
-      uint32_t r, c;
-      tasks.coords(k, r, c);
-      const uint32_t o = (r + h * HR) * OW + c;
-      if (!tasks.is_mu1(k)) {
-        th0[o] = res[h][k].x;
-        th0[o + OW] = res[h][k].y;
-      } else {
-        th1[o] = res[h][k].x;
-        th1[o + 1] = res[h][k].y;
+      for (int k = 0; k < NV; ++k) {
+        uint32_t r, c;
+        if (!tasks.template task<MU1>(k, r, c)) continue;
+        const uint32_t o = (r + h * HR) * OW + c;
+        if (!MU1) {
+          th0[o] = res[h][k].x;
+          th0[o + OW] = res[h][k].y;
+        } else {
+          th1[o] = res[h][k].x;
+          th1[o + 1] = res[h][k].y;
+        }
       }
-    }
+  });
 }
 
 }  // namespace mlmcpi
