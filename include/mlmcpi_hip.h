@@ -696,7 +696,8 @@ int mlmcpi_sigma_level_correlator(const mlmcpi_sigma_level *level, const double 
 int mlmcpi_sigma_level_topological_charge(const mlmcpi_sigma_level *level, const double *d_state, uint32_t n_chains,
                                           double *d_q /* may be NULL */, double *d_chi /* may be NULL */,
                                           double *d_acc /* may be NULL: record_sample moments of chi, [n_chains][5] */, void *stream);
-/* Cooling on a level and the cooled charge (sigma_cooling.hip); `beta` is ignored.  Cooling is the deterministic
+/* Cooling on a level and the cooled charge (sigma_cooling.hip, a smoother of sigma_smooth.hip on the field of sigma_field.hip;
+ * DESIGN.md 4.1g); `beta` is ignored.  Cooling is the deterministic
  * beta -> infinity limit of the heat bath: sigma_l <- Delta_l / |Delta_l|, Delta_l = add4 of the four neighbours in the order of
  * mlmcpi_sigma_level_sweep_draw, |Delta| = sqrt((x^2 + y^2) + z^2), three divisions; Delta_l = 0 leaves sigma_l as it is.  One
  * cooling sweep updates the two colour classes in the sweeps' order: plain level (i + j) even, then odd; rotated level phase E,
@@ -718,7 +719,8 @@ int mlmcpi_sigma_level_topological_charge(const mlmcpi_sigma_level *level, const
  * stream, every choice of outputs and EVERY DEPTH LIST CONTAINING d; Q_0 and chi_0 are the bits of
  * mlmcpi_sigma_level_topological_charge.  Any n_chains runs (CHAINS PER CALL above).  MLMCPI_ERR_INVALID, with nothing launched:
  * NULL level, d_state, depths or d_work; d_q, d_chi and d_energy all NULL; odd or zero extents, Mt Mx > 2^30; n_chains = 0;
- * n_depths outside 1 .. 32; depths not strictly ascending or beyond 4096; work_bytes below the query.
+ * n_depths outside 1 .. 32; depths not strictly ascending or beyond 4096; work_bytes below the query; more workgroups in a launch
+ * than the grid holds.
  * _cooling_plan (host only, touches no device) reports the launches of such a call and returns the status the call would for the
  * arguments it sees. */
 #define MLMCPI_SIGMA_COOLING_MAX_DEPTHS 32
@@ -738,7 +740,8 @@ int mlmcpi_sigma_level_cooled_charge(const mlmcpi_sigma_level *level, const doub
                                      double *d_cooled /* may be NULL */, void *d_work, size_t work_bytes, void *stream);
 int mlmcpi_sigma_level_cooling_plan(const mlmcpi_sigma_level *level, uint32_t n_chains, const uint32_t *depths, uint32_t n_depths,
                                     mlmcpi_sigma_cooling_plan *plan);
-/* Gradient flow on a level and the flowed charge (sigma_flow.hip); `beta` is ignored.  With F(Y)_l = Delta_l -
+/* Gradient flow on a level and the flowed charge (sigma_flow.hip, the other smoother of sigma_smooth.hip); `beta`
+ * is ignored.  With F(Y)_l = Delta_l -
  * (Y_l . Delta_l) Y_l, Delta_l = add4 of the four neighbours' Y in the order of mlmcpi_sigma_level_sweep_draw and the dot product
  * (x x' + y y') + z z', one step of size eps is the 2N-storage third-order Runge-Kutta scheme, on ALL sites from the previous
  * stage's Y, starting from A = 0, Y = sigma:  A <- a_i A + eps F(Y), Y <- Y + b_i A, i = 1, 2, 3, a = (0, -17/32, -32/27), b =

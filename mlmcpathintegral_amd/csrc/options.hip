@@ -15,6 +15,20 @@ std::mutex g_tuning_mutex;
 Tuning g_tuning;
 bool g_tuning_loaded = false;
 
+// TWxTHxNTxK: tile extents 1 .. 128, workgroup size, 1 .. kMaxFuse units fused per launch, and an LDS image that fits
+bool parse_plan(const std::string &v, uint32_t &tw, uint32_t &th, uint32_t &nt, uint32_t &fuse, bool (*fits)(size_t a, size_t b, size_t k)) {
+  unsigned a = 0, b = 0, c = 0, k = 0;
+  char rest = 0;
+  tw = th = nt = fuse = 0;
+  if (v.empty()) return true;
+  if (sscanf(v.c_str(), "%ux%ux%ux%u%c", &a, &b, &c, &k, &rest) == 4 && a >= 1 && a <= 128 && b >= 1 && b <= 128 &&
+      (c == 256 || c == 512 || c == 1024) && k >= 1 && k <= kMaxFuse && fits(a, b, k)) {
+    tw = a; th = b; nt = c; fuse = k;
+    return true;
+  }
+  return false;
+}
+
 // A parser puts its knob back to the default first, then takes the value: false (value refused) leaves the default in force.
 struct Option { const char *name; bool (*parse)(Tuning &t, const std::string &v); };
 const Option kOptions[] = {
@@ -76,42 +90,13 @@ const Option kOptions[] = {
     return false;
   }},
   {"MLMCPI_SIGMA_LEVEL_PLAN", [](Tuning &t, const std::string &v) {
-    unsigned a = 0, b = 0, c = 0, k = 0;
-    char rest = 0;
-    t.sigma_level_tw = t.sigma_level_th = t.sigma_level_nt = t.sigma_level_fuse = 0;
-    if (v.empty()) return true;
-    if (sscanf(v.c_str(), "%ux%ux%ux%u%c", &a, &b, &c, &k, &rest) == 4 && a >= 1 && a <= 128 && b >= 1 && b <= 128 &&
-        (c == 256 || c == 512 || c == 1024) && k >= 1 && k <= kMaxFuse && (size_t)(a + 2 * k) * (b + 2 * k) * 48 <= kSigmaLdsMax) {
-      t.sigma_level_tw = a; t.sigma_level_th = b; t.sigma_level_nt = c; t.sigma_level_fuse = k;
-      return true;
-    }
-    return false;
+    return parse_plan(v, t.sigma_level_tw, t.sigma_level_th, t.sigma_level_nt, t.sigma_level_fuse, [](size_t a, size_t b, size_t k) { return (a + 2 * k) * (b + 2 * k) * 48 <= kSigmaLdsMax; });
   }},
   {"MLMCPI_SIGMA_COOL_PLAN", [](Tuning &t, const std::string &v) {  // the LDS image of a rotated level (halo K cells, 48 B) and of a plain one (halo 2 K vertices, 24 B)
-    unsigned a = 0, b = 0, c = 0, k = 0;
-    char rest = 0;
-    t.sigma_cool_tw = t.sigma_cool_th = t.sigma_cool_nt = t.sigma_cool_fuse = 0;
-    if (v.empty()) return true;
-    if (sscanf(v.c_str(), "%ux%ux%ux%u%c", &a, &b, &c, &k, &rest) == 4 && a >= 1 && a <= 128 && b >= 1 && b <= 128 &&
-        (c == 256 || c == 512 || c == 1024) && k >= 1 && k <= kMaxFuse && (size_t)(a + 2 * k) * (b + 2 * k) * 48 <= kSigmaLdsMax &&
-        (size_t)(a + 4 * k) * (b + 4 * k) * 24 <= kSigmaLdsMax) {
-      t.sigma_cool_tw = a; t.sigma_cool_th = b; t.sigma_cool_nt = c; t.sigma_cool_fuse = k;
-      return true;
-    }
-    return false;
+    return parse_plan(v, t.sigma_cool_tw, t.sigma_cool_th, t.sigma_cool_nt, t.sigma_cool_fuse, [](size_t a, size_t b, size_t k) { return (a + 2 * k) * (b + 2 * k) * 48 <= kSigmaLdsMax && (a + 4 * k) * (b + 4 * k) * 24 <= kSigmaLdsMax; });
   }},
   {"MLMCPI_SIGMA_FLOW_PLAN", [](Tuning &t, const std::string &v) {  // the LDS image of a rotated level (halo 3 K cells, 144 B) and of a plain one (halo 3 K vertices, 72 B)
-    unsigned a = 0, b = 0, c = 0, k = 0;
-    char rest = 0;
-    t.sigma_flow_tw = t.sigma_flow_th = t.sigma_flow_nt = t.sigma_flow_fuse = 0;
-    if (v.empty()) return true;
-    if (sscanf(v.c_str(), "%ux%ux%ux%u%c", &a, &b, &c, &k, &rest) == 4 && a >= 1 && a <= 128 && b >= 1 && b <= 128 &&
-        (c == 256 || c == 512 || c == 1024) && k >= 1 && k <= kMaxFuse && (size_t)(a + 6 * k) * (b + 6 * k) * 144 <= kSigmaLdsMax &&
-        (size_t)(a + 6 * k) * (b + 6 * k) * 72 <= kSigmaLdsMax) {
-      t.sigma_flow_tw = a; t.sigma_flow_th = b; t.sigma_flow_nt = c; t.sigma_flow_fuse = k;
-      return true;
-    }
-    return false;
+    return parse_plan(v, t.sigma_flow_tw, t.sigma_flow_th, t.sigma_flow_nt, t.sigma_flow_fuse, [](size_t a, size_t b, size_t k) { return (a + 6 * k) * (b + 6 * k) * 144 <= kSigmaLdsMax && (a + 6 * k) * (b + 6 * k) * 72 <= kSigmaLdsMax; });
   }},
   {"MLMCPI_SIGMA_TWOLEVEL_GROUPS", [](Tuning &t, const std::string &v) {
     unsigned g = 0;

@@ -7,28 +7,25 @@
 //   then sigma <- Y / |Y|, |Y| = sqrt((x^2 + y^2) + z^2), three divisions.  Stage values are not normalised.
 //
 // The third-order 2N-storage Runge-Kutta scheme; flow time after s steps t = s eps.  The Markov chain's state is only read: the
-// field lives in the caller's workspace as unit vectors in the layout of cooling (sigma_field_device.hpp) and is never converted
+// field lives in the caller's workspace as unit vectors in the layout of sigma_field_device.hpp and is never converted
 // back to angles between steps; A and the stage fields never leave a launch.
 //
-// Launches of a call:
-//   1. sigma_cool_stage_kernel (cool_stage): sigma_of(angles) -> buffer A (step 0).
-//   2. sigma_flow_kernel<ROT, NT>: one workgroup per tile per chain loads TW x TH vertices (rotated: plane cells, E and O) plus a
-//      halo of 3 K (vertices or cells: a stage consumes one) from one buffer with modular loads, runs the 3 K stages of K steps in
-//      LDS, one barrier per stage, stage m = 1 .. 3 K on the sites at least m from the edge of the loaded region, whose inputs
-//      are still exact, the last stage exactly on the tile, and writes the tile to the other buffer.  K <= the plan's fuse depth
-//      and a launch never runs past the next listed step.
-//   3. at each listed step: the charge, energy and finish launches of cooling (cool_measure).
-//   4. sigma_cool_angles_kernel (cool_angles) with d_flowed.
+// The smoother of a call of the smoothing driver (sigma_smooth.hip: the field is staged, smoothed between two buffers, measured at
+// each listed step count and turned back into angles by sigma_field.hip's launches) is
+//   sigma_flow_kernel<ROT, NT>: one workgroup per tile per chain loads TW x TH vertices (rotated: plane cells, E and O) plus a
+//   halo of 3 K (vertices or cells: a stage consumes one) from one buffer with modular loads, runs the 3 K stages of K steps in
+//   LDS, one barrier per stage, stage m = 1 .. 3 K on the sites at least m from the edge of the loaded region, whose inputs
+//   are still exact, the last stage exactly on the tile, and writes the tile to the other buffer.
 // LDS image per site: Y, the next Y (a stage reads the OLD Y of its neighbours) and A, 9 doubles = 72 B per vertex, 144 B per
 // rotated cell.  A stage update is a pure function of the stored Y and A of the site and the stored Y of four neighbours, so a
 // halo vertex recomputed by a neighbouring tile gets the bits its owner computes, and a vertex written to the buffer and loaded
 // again is the vertex that stayed in LDS: the field of step s does not depend on the tile, the workgroup size, the fuse depth or
-// the steps listed before s.  No atomics; workgroups of every launch ride one linear index over grid x and then y (topo_grid).
+// the steps listed before s.  No atomics; workgroups ride one linear index over grid x and then y (topo_grid).
 #include <math.h>
 
-#include "internal.hpp"
+#include "sigma_smooth_host.hpp"  // the driver; includes sigma_level_device.hpp: fp contraction is off from here on
 
-#include "sigma_field_device.hpp"  // the field's layout, cooling's launches; fp contraction is off from here on
+#include "sigma_field_device.hpp"  // the field's layout
 
 namespace mlmcpi {
 
@@ -92,7 +89,7 @@ __device__ __forceinline__ void flow_stage(const FlowRegion &R, uint32_t m, cons
     flow_keep(yn, S, s, v);
     if constexpr (I == 2) {
       if (out && la >= R.H && la < R.H + R.TW && lb >= R.H && lb < R.H + R.TH && R.a0 + (la - R.H) < R.PW && R.b0 + (lb - R.H) < R.PH)
-        cool_store(out, n, (size_t)p * q + (size_t)((R.sb + lb) % R.PH) * R.PW + (R.sa + la) % R.PW, v);
+        field_store(out, n, (size_t)p * q + (size_t)((R.sb + lb) % R.PH) * R.PW + (R.sa + la) % R.PW, v);
     }
   }
 }
@@ -128,8 +125,8 @@ __global__ void __launch_bounds__(NT)
   for (uint32_t c = tid; c < R.P; c += NT) {
     const uint32_t la = c % R.W, lb = c / R.W;
     const uint32_t l = ((R.sb + lb) % R.PH) * R.PW + (R.sa + la) % R.PW;
-    flow_keep(lds, S, c, cool_fetch(s, n, l));
-    if constexpr (ROT) flow_keep(lds, S, R.P + c, cool_fetch(s, n, L.q + l));
+    flow_keep(lds, S, c, field_fetch(s, n, l));
+    if constexpr (ROT) flow_keep(lds, S, R.P + c, field_fetch(s, n, L.q + l));
   }
   __syncthreads();
 
@@ -151,69 +148,13 @@ __global__ void __launch_bounds__(NT)
 
 namespace {
 
-struct FlowPlan {
-  uint32_t tw, th, nt, fuse, tiles_a, tiles;
-};
-
-// Tile, workgroup size and fuse depth: the option, else 16 x 16 (vertices or cells), 512 threads, one step per launch (DESIGN.md
-// 4.1h: 34 KB of LDS on a plain level, 68 KB on a rotated one); the tile never exceeds the plane.
-FlowPlan flow_plan(const SigmaLevel &L, const Tuning &t) {
-  FlowPlan p{t.sigma_flow_tw ? t.sigma_flow_tw : 16u, t.sigma_flow_th ? t.sigma_flow_th : 16u, t.sigma_flow_nt ? t.sigma_flow_nt : 512u,
-             t.sigma_flow_fuse ? t.sigma_flow_fuse : 1u, 0, 0};
-  const uint32_t PW = L.rot ? L.ht : L.Mt, PH = L.rot ? L.hx : L.Mx;
-  if (p.tw > PW) p.tw = PW;
-  if (p.th > PH) p.th = PH;
-  p.tiles_a = (PW + p.tw - 1) / p.tw;
-  p.tiles = p.tiles_a * ((PH + p.th - 1) / p.th);
-  return p;
-}
-
-inline size_t flow_lds(const SigmaLevel &L, const FlowPlan &p, uint32_t K) {
+// the default 16 x 16 x 512 x 1 takes 34 KB of LDS on a plain level, 68 KB on a rotated one
+size_t flow_lds(const SigmaLevel &L, const SmoothPlan &p, uint32_t K) {
   return (size_t)(p.tw + 6 * K) * (p.th + 6 * K) * (L.rot ? 18 : 9) * sizeof(double);
 }
 
-// what the call and its plan query refuse alike; the plan (one snapshot of the knobs per call) comes back through `plan`.  Its LDS
-// image fits: the option table takes no plan whose images do not, the default's do, and flow_plan only shrinks tiles.
-int flow_check(const mlmcpi_sigma_level *level, uint32_t n_chains, double eps, const uint32_t *steps, uint32_t n_steps, FlowPlan *plan) {
-  if (int rc = check_sigma_level(level)) return rc;
-  MLMCPI_REQUIRE(n_chains > 0, "the flow needs n_chains > 0");
-  MLMCPI_REQUIRE(std::isfinite(eps) && eps > 0.0 && eps <= 0.25, "the flow takes a step size 0 < eps <= 0.25 (got %g)", eps);
-  MLMCPI_REQUIRE(steps, "the flow needs a list of step counts (steps is NULL)");
-  MLMCPI_REQUIRE(n_steps >= 1 && n_steps <= MLMCPI_SIGMA_FLOW_MAX_TIMES, "the flow takes 1 .. %d step counts (got %u)",
-                 MLMCPI_SIGMA_FLOW_MAX_TIMES, n_steps);
-  for (uint32_t k = 0; k < n_steps; ++k) {
-    MLMCPI_REQUIRE(k == 0 || steps[k] > steps[k - 1], "the flow step counts must be strictly ascending (steps[%u] = %u after %u)", k,
-                   steps[k], k ? steps[k - 1] : 0);
-    MLMCPI_REQUIRE(steps[k] <= MLMCPI_SIGMA_FLOW_MAX_STEPS, "a flow step count is at most %d (steps[%u] = %u)", MLMCPI_SIGMA_FLOW_MAX_STEPS,
-                   k, steps[k]);
-  }
-  const SigmaLevel L = make_level(*level);
-  const FlowPlan p = *plan = flow_plan(L, tuning());
-  uint32_t per_chain = (L.nvert() + kGroup - 1) / kGroup;
-  if (p.tiles > per_chain) per_chain = p.tiles;
-  if (topo_plan(L).tiles > per_chain) per_chain = topo_plan(L).tiles;
-  const uint64_t most = (uint64_t)n_chains * per_chain;
-  MLMCPI_REQUIRE(most <= kTopoMaxBlocks, "the flow takes at most %llu workgroups per launch (these chains need %llu)",
-                 (unsigned long long)kTopoMaxBlocks, (unsigned long long)most);
-  return MLMCPI_OK;
-}
-
-DeviceOnce g_flow_attr_once;
-
-int flow_init_kernels() {  // the flow kernel may take the whole LDS (of the current device)
-  return once_per_device(g_flow_attr_once, []() -> int {
-    MLMCPI_HIP_TRY(hipFuncSetAttribute((const void *)sigma_flow_kernel<0, 256>, hipFuncAttributeMaxDynamicSharedMemorySize, kSigmaLdsMax));
-    MLMCPI_HIP_TRY(hipFuncSetAttribute((const void *)sigma_flow_kernel<0, 512>, hipFuncAttributeMaxDynamicSharedMemorySize, kSigmaLdsMax));
-    MLMCPI_HIP_TRY(hipFuncSetAttribute((const void *)sigma_flow_kernel<0, 1024>, hipFuncAttributeMaxDynamicSharedMemorySize, kSigmaLdsMax));
-    MLMCPI_HIP_TRY(hipFuncSetAttribute((const void *)sigma_flow_kernel<1, 256>, hipFuncAttributeMaxDynamicSharedMemorySize, kSigmaLdsMax));
-    MLMCPI_HIP_TRY(hipFuncSetAttribute((const void *)sigma_flow_kernel<1, 512>, hipFuncAttributeMaxDynamicSharedMemorySize, kSigmaLdsMax));
-    MLMCPI_HIP_TRY(hipFuncSetAttribute((const void *)sigma_flow_kernel<1, 1024>, hipFuncAttributeMaxDynamicSharedMemorySize, kSigmaLdsMax));
-    return MLMCPI_OK;
-  });
-}
-
 template <int ROT>
-int flow_launch(const SigmaLevel &L, const FlowPlan &p, uint32_t K, double eps, uint64_t blocks, const double *src, double *dst, hipStream_t st) {
+int flow_launch(const SigmaLevel &L, const SmoothPlan &p, uint32_t K, double eps, uint64_t blocks, const double *src, double *dst, hipStream_t st) {
   const size_t lds = flow_lds(L, p, K);
 #define MLMCPI_FLOW(NT) \
   hipLaunchKernelGGL((sigma_flow_kernel<ROT, NT>), topo_grid(blocks), dim3(NT), lds, st, L, blocks, src, dst, p.tw, p.th, p.tiles_a, p.tiles, K, eps)
@@ -225,6 +166,21 @@ int flow_launch(const SigmaLevel &L, const FlowPlan &p, uint32_t K, double eps, 
   return MLMCPI_OK;
 }
 
+DeviceOnce g_flow_attr_once;
+
+const Smoother kFlow = {
+    "the flow", "flow", "step count", "steps", MLMCPI_SIGMA_FLOW_MAX_TIMES, MLMCPI_SIGMA_FLOW_MAX_STEPS,
+    {&Tuning::sigma_flow_tw, &Tuning::sigma_flow_th, &Tuning::sigma_flow_nt, &Tuning::sigma_flow_fuse}, {16, 16, 512, 1},
+    flow_lds, {flow_launch<0>, flow_launch<1>},
+    {(const void *)sigma_flow_kernel<0, 256>, (const void *)sigma_flow_kernel<0, 512>, (const void *)sigma_flow_kernel<0, 1024>,
+     (const void *)sigma_flow_kernel<1, 256>, (const void *)sigma_flow_kernel<1, 512>, (const void *)sigma_flow_kernel<1, 1024>}, &g_flow_attr_once};
+
+// the flow's own argument, checked before the driver's
+int flow_check_eps(double eps) {
+  MLMCPI_REQUIRE(std::isfinite(eps) && eps > 0.0 && eps <= 0.25, "the flow takes a step size 0 < eps <= 0.25 (got %g)", eps);
+  return MLMCPI_OK;
+}
+
 }  // namespace
 }  // namespace mlmcpi
 
@@ -233,71 +189,20 @@ using namespace mlmcpi;
 extern "C" {
 
 int mlmcpi_sigma_level_flow_workspace_bytes(const mlmcpi_sigma_level *level, uint32_t n_chains, size_t *bytes) {
-  if (int rc = check_sigma_level(level)) return rc;
-  MLMCPI_REQUIRE(bytes, "the flow workspace query needs somewhere to write (bytes is NULL)");
-  MLMCPI_REQUIRE(n_chains > 0, "the flow needs n_chains > 0");
-  *bytes = cool_work(make_level(*level), n_chains).total;
-  return MLMCPI_OK;
+  return smooth_workspace_bytes(kFlow, level, n_chains, bytes);
 }
 
 int mlmcpi_sigma_level_flow_plan(const mlmcpi_sigma_level *level, uint32_t n_chains, double eps, const uint32_t *steps, uint32_t n_steps,
                                  mlmcpi_sigma_flow_plan *plan) {
-  MLMCPI_REQUIRE(plan, "the flow plan query needs somewhere to write (plan is NULL)");
-  FlowPlan p;
-  if (int rc = flow_check(level, n_chains, eps, steps, n_steps, &p)) return rc;
-  const SigmaLevel L = make_level(*level);
-  *plan = mlmcpi_sigma_flow_plan{};
-  plan->tw = p.tw;
-  plan->th = p.th;
-  plan->nt = p.nt;
-  plan->fuse = p.fuse;
-  plan->tiles = p.tiles;
-  plan->n_measurements = n_steps;
-  uint32_t done = 0, deepest = 0;
-  for (uint32_t k = 0; k < n_steps; ++k)
-    while (done < steps[k]) {
-      const uint32_t K = steps[k] - done < p.fuse ? steps[k] - done : p.fuse;
-      plan->launch_steps[plan->n_launches++] = (uint8_t)K;
-      if (K > deepest) deepest = K;
-      done += K;
-    }
-  plan->lds_bytes = deepest ? (uint32_t)flow_lds(L, p, deepest) : 0;
-  return MLMCPI_OK;
+  if (int rc = flow_check_eps(eps)) return rc;
+  return smooth_plan_query(kFlow, level, n_chains, steps, n_steps, plan, &mlmcpi_sigma_flow_plan::launch_steps);
 }
 
 int mlmcpi_sigma_level_flowed_charge(const mlmcpi_sigma_level *level, const double *d_state, uint32_t n_chains, double eps,
                                      const uint32_t *steps, uint32_t n_steps, double *d_q, double *d_chi, double *d_energy, double *d_flowed,
                                      void *d_work, size_t work_bytes, void *stream) {
-  FlowPlan p;
-  if (int rc = flow_check(level, n_chains, eps, steps, n_steps, &p)) return rc;
-  MLMCPI_REQUIRE(d_state, "the flow needs a state (d_state is NULL)");
-  MLMCPI_REQUIRE(d_q || d_chi || d_energy, "the flow needs d_q, d_chi or d_energy (all three are NULL)");
-  MLMCPI_REQUIRE(d_work, "the flow needs its workspace (d_work is NULL)");
-  const SigmaLevel L = make_level(*level);
-  const CoolWork w = cool_work(L, n_chains);
-  MLMCPI_REQUIRE(work_bytes >= w.total, "the flow workspace is too small: %zu bytes given, %zu needed", work_bytes, w.total);
-  if (int rc = flow_init_kernels()) return rc;
-  hipStream_t st = as_stream(stream);
-  double *cur = (double *)d_work, *other = (double *)((char *)d_work + w.vec);
-  double *part_q = (double *)((char *)d_work + 2 * w.vec), *part_e = (double *)((char *)d_work + 2 * w.vec + w.part_q);
-  const uint64_t fblocks = (uint64_t)n_chains * p.tiles;
-
-  if (int rc = cool_stage(L, w, n_chains, d_state, cur, st)) return rc;
-  uint32_t done = 0;
-  for (uint32_t k = 0; k < n_steps; ++k) {
-    while (done < steps[k]) {
-      const uint32_t K = steps[k] - done < p.fuse ? steps[k] - done : p.fuse;
-      if (int rc = L.rot ? flow_launch<1>(L, p, K, eps, fblocks, cur, other, st) : flow_launch<0>(L, p, K, eps, fblocks, cur, other, st)) return rc;
-      double *t = cur;
-      cur = other;
-      other = t;
-      done += K;
-    }
-    if (int rc = cool_measure(L, w, n_chains, cur, part_q, part_e, n_steps, k, d_q, d_chi, d_energy, st)) return rc;
-  }
-  if (d_flowed)
-    if (int rc = cool_angles(L, w, n_chains, cur, d_flowed, st)) return rc;
-  return MLMCPI_OK;
+  if (int rc = flow_check_eps(eps)) return rc;
+  return smooth_run(kFlow, level, d_state, n_chains, eps, steps, n_steps, d_q, d_chi, d_energy, d_flowed, d_work, work_bytes, stream);
 }
 
 }  // extern "C"

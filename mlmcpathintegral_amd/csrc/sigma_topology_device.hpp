@@ -1,5 +1,5 @@
 // sigma_topology_device.hpp -- the face code of the geometric topological charge of the O(3) sigma model, shared by the charge of a
-// state of angles (sigma_topology.hip) and the charge of a cooled field of unit vectors (sigma_cooling.hip): the tile and its plan,
+// state of angles (sigma_topology.hip) and the charge of a smoothed field of unit vectors (sigma_field.hip): the tile and its plan,
 // the staging geometry, the faces of a staged tile and their sum order.  The two units differ in one thing only:
 // where a staged vertex comes from (`fetch`).  Includes sigma_level_device.hpp, so the including file is compiled without fp
 // contraction.

@@ -497,23 +497,28 @@ def sigma_level_cooling_plan(level, B, depths):
     return plan
 
 
+def _sigma_level_smoothed_charge(name, workspace, level, x, lead, counts, energy, field, stream, work):
+    """what sigma_level_cooled_charge and sigma_level_flowed_charge share; lead: the arguments between B and the list (eps)"""
+    _check_state(x, sigma_level_size(level))
+    B, nd = x.shape[0], len(counts)
+    d = (C.c_uint32 * nd)(*counts)
+    with torch.cuda.stream(stream if stream is not None else torch.cuda.current_stream()):
+        if work is None:
+            work = workspace(level, B, x.device)
+        q, chi = _f64(B, nd, x), _f64(B, nd, x)
+        e = _f64(B, nd, x) if energy else None
+        out = torch.empty_like(x) if field else None
+        abi.call(name, C.byref(level), _p(x), B, *lead, d, nd, _p(q), _p(chi), _p(e), _p(out), _p(work), work.numel(), _stream())
+    return (q, chi) + ((e,) if energy else ()) + ((out,) if field else ())
+
+
 def sigma_level_cooled_charge(level, x, depths, *, energy=False, cooled=False, stream=None, work=None):
     """cooling of every chain of x [B, 2 n] on a level, rotated or not, measured at the ascending list `depths` of sweep counts
     (mlmcpi_sigma_level_cooled_charge; x is not written): returns (Q [B, n_depths], chi = Q^2 / n [B, n_depths]), then with
     energy=True the bond energy E [B, n_depths] and with cooled=True the angles [B, 2 n] of the field at the last depth.  Runs,
     and allocates, on `stream` (a torch.cuda.Stream; default: the current one)."""
-    _check_state(x, sigma_level_size(level))
-    B, nd = x.shape[0], len(depths)
-    d = (C.c_uint32 * nd)(*depths)
-    with torch.cuda.stream(stream if stream is not None else torch.cuda.current_stream()):
-        if work is None:
-            work = sigma_level_cooling_workspace(level, B, x.device)
-        q, chi = _f64(B, nd, x), _f64(B, nd, x)
-        e = _f64(B, nd, x) if energy else None
-        out = torch.empty_like(x) if cooled else None
-        abi.call("mlmcpi_sigma_level_cooled_charge", C.byref(level), _p(x), B, d, nd, _p(q), _p(chi), _p(e), _p(out), _p(work),
-                 work.numel(), _stream())
-    return (q, chi) + ((e,) if energy else ()) + ((out,) if cooled else ())
+    return _sigma_level_smoothed_charge("mlmcpi_sigma_level_cooled_charge", sigma_level_cooling_workspace, level, x, (), depths, energy,
+                                        cooled, stream, work)
 
 
 def sigma_level_flow_workspace(level, B, device="cuda"):
@@ -535,18 +540,8 @@ def sigma_level_flowed_charge(level, x, eps, steps, *, energy=False, flowed=Fals
     (Q [B, n_steps], chi = Q^2 / n [B, n_steps]), then with energy=True the bond energy E [B, n_steps] and with flowed=True the
     angles [B, 2 n] of the field at the last step count.  Runs, and allocates, on `stream` (a torch.cuda.Stream; default: the
     current one)."""
-    _check_state(x, sigma_level_size(level))
-    B, nd = x.shape[0], len(steps)
-    d = (C.c_uint32 * nd)(*steps)
-    with torch.cuda.stream(stream if stream is not None else torch.cuda.current_stream()):
-        if work is None:
-            work = sigma_level_flow_workspace(level, B, x.device)
-        q, chi = _f64(B, nd, x), _f64(B, nd, x)
-        e = _f64(B, nd, x) if energy else None
-        out = torch.empty_like(x) if flowed else None
-        abi.call("mlmcpi_sigma_level_flowed_charge", C.byref(level), _p(x), B, eps, d, nd, _p(q), _p(chi), _p(e), _p(out), _p(work),
-                 work.numel(), _stream())
-    return (q, chi) + ((e,) if energy else ()) + ((out,) if flowed else ())
+    return _sigma_level_smoothed_charge("mlmcpi_sigma_level_flowed_charge", sigma_level_flow_workspace, level, x, (eps,), steps, energy,
+                                        flowed, stream, work)
 
 
 def sigma_level_correlator_size(level):

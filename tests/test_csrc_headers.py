@@ -13,7 +13,8 @@ CSRC = os.path.join(ROOT, "mlmcpathintegral_amd", "csrc")
 SAMPLER_HEADERS = {"vonmises.hpp", "step_envelope.hpp", "site_update.hpp", "fillin.hpp"}
 UNITS_WITHOUT_SAMPLER = ("path1d", "path_hmc", "ho_exact", "lattice_reduce", "lattice_hmc", "gff_exact", "gff_levels", "cluster",
                          "sigma_cluster", "sigma_sw", "sigma_sw_tiled", "sigma_sw_chain", "sigma_sw_correlator", "sigma_levels",
-                         "sigma_twolevel", "schwinger_or_block", "runtime", "options", "schwinger_analytic", "index_maps")
+                         "sigma_twolevel", "schwinger_or_block", "runtime", "options", "schwinger_analytic", "index_maps", "sigma_field",
+                         "sigma_smooth")
 SW_UNITS = ("sigma_sw", "sigma_sw_tiled", "sigma_sw_chain", "sigma_sw_correlator")
 
 
@@ -67,6 +68,26 @@ def test_the_cluster_samplers_share_the_embedding_and_nothing_of_each_other():
         assert "sigma_cluster.hip" not in deps, (unit, sorted(deps))
 
 
+def test_the_smoothers_share_the_field_and_the_driver_and_nothing_of_each_other():
+    """Cooling (sigma_cooling) and the gradient flow (sigma_flow) meet in the field of unit vectors (sigma_field_device.hpp, whose
+    kernels and launches sigma_field.hip owns) and in the smoothing driver (sigma_smooth_host.hpp, sigma_smooth.hip): neither sees
+    the other, and neither the field nor the driver sees a smoother."""
+    build = os.path.join(CSRC, "build")
+    if not os.path.isdir(build):
+        pytest.skip("no built tree")
+    smoothers = {"sigma_cooling.hip", "sigma_flow.hip"}
+    for unit in ("sigma_cooling", "sigma_flow"):
+        deps = _deps(build, unit)
+        assert {"sigma_field_device.hpp", "sigma_smooth_host.hpp"} <= deps, (unit, sorted(deps))
+        assert deps & smoothers == {unit + ".hip"}, (unit, sorted(deps))
+    for unit in ("sigma_field", "sigma_smooth"):
+        deps = _deps(build, unit)
+        assert "sigma_field_device.hpp" in deps and not deps & smoothers, (unit, sorted(deps))
+    with open(os.path.join(CSRC, "sigma_field_device.hpp")) as f:
+        shared = f.read()
+    assert "cool_" not in shared and "flow_" not in shared
+
+
 def test_fillin_and_sigma_device_meet_in_test_math_only():
     """sigma_device.hpp switches fp contraction off for the rest of the file that includes it, fillin.hpp's callers are compiled
     with it on: the one unit that needs the primitives of both is test_math, whose kernel only calls functions compiled where
@@ -76,6 +97,6 @@ def test_fillin_and_sigma_device_meet_in_test_math_only():
         pytest.skip("no built tree")
     with open(os.path.join(CSRC, "Makefile")) as f:
         units = [w[:-4] for w in re.search(r"^SRCS := (.*)$", f.read(), re.M).group(1).split()]
-    assert len(units) >= 33 and "test_math" in units and "runtime" in units
+    assert len(units) >= 35 and "test_math" in units and "runtime" in units
     both = [u for u in units if {"fillin.hpp", "sigma_device.hpp"} <= _deps(build, u)]
     assert both == ["test_math"], both

@@ -31,6 +31,14 @@ KNOBS = {
     "MLMCPI_SIGMA_LEVEL_PLAN": (["", "32x32x512x2", "1x1x256x1", "128x1x1024x1", "26x26x256x16", "64x32x512x1"],
                                 ["32x32x512x2z", "32x32x512x2 ", "32x32x512", "0x32x512x2", "32x0x512x2", "129x1x256x1", "1x129x256x1",
                                  "32x32x100x2", "32x32x512x0", "32x32x512x17", "27x26x256x16", "128x128x256x1", "auto"]),
+    # the spellings of test_sigma_cooling_gpu.py / test_sigma_flow_gpu.py (their plans and test_the_knob_refuses_what_does_not_fit),
+    # and the trailing-character and field-count cases of _LEVEL_PLAN
+    "MLMCPI_SIGMA_COOL_PLAN": (["", "32x32x512x2", "1x1x256x1", "8x4x256x4", "48x48x1024x1", "7x5x512x3", "16x16x512x16", "128x1x1024x1"],
+                               ["0x4x256x1", "4x4x128x1", "4x4x256x0", "4x4x256x17", "64x64x256x1x", "20x20x256x16", "129x1x256x1",
+                                "1x129x256x1", "32x32x512x2z", "32x32x512x2 ", "32x32x512", "32x32x512x2x1", "auto"]),
+    "MLMCPI_SIGMA_FLOW_PLAN": (["", "16x16x512x1", "2x2x256x5", "27x27x512x1", "128x1x1024x1", "1x1x256x1", "8x4x256x2", "7x5x512x3"],
+                               ["0x4x256x1", "4x4x128x1", "4x4x256x0", "4x4x256x17", "16x16x256x1x", "2x2x256x6", "32x32x512x1",
+                                "129x1x256x1", "1x129x256x1", "16x16x512x1z", "16x16x512x1 ", "16x16x512", "16x16x512x1x1", "auto"]),
     "MLMCPI_SIGMA_TWOLEVEL_GROUPS": (["", "1", "7", "64"], ["0", "65", "7x", "7 ", "abc", "-1", "auto"]),
 }
 
@@ -48,8 +56,8 @@ def refused(name, value):
     return rc == INVALID and msg == "unknown option or value: %s=%s" % (show(name), show(value)), (name, value, rc, msg)
 
 
-def test_the_table_covers_the_eleven_knobs():
-    assert len(KNOBS) == 11
+def test_the_table_covers_the_thirteen_knobs():
+    assert len(KNOBS) == 13
     for name, (good, bad) in KNOBS.items():
         assert "" in good and len(good) >= 3 and len(bad) >= 5 and not set(good) & set(bad), name
 
